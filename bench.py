@@ -2,7 +2,7 @@
 """bench.py -- user-sequences/s of the TLSAN train step (forward + backward + update) on the
 Electronics-scale synthetic workload (BASELINE.json configs[2] shapes; SURVEY.md 8d inputs).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   (N > 1: one process per GPU.  Under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`
    the ranks come from the launcher's environment; started plainly, bench.py launches its N rank processes
    itself -- before this process touches the GPU -- and relays rank 0's JSON line.)
@@ -66,7 +66,49 @@ def parse():
     ap.add_argument("--accuracy-steps", type=int, default=2000,
                     help="accuracy leg (rank 0, N=1): train steps of the reference protocol on the real Digital-Music samples, "
                          "HIP path and fp64 oracle side by side, then AUC / P@20 / R@20 of both (0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR/<name>.npy (float32; sampled row ids float64): "
+                         "loss, gnorm and, on the single-GPU path, every parameter as get_params() would give it "
+                         "(a fixed, seeded row sample of the tables if all of it would exceed 64 MB)")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 60 << 20      # (bytes of array data: under 64 MB with the .npy headers)
+
+
+def dump_outputs(d, stepper, sharded):
+    """The outputs of the last timed step, without changing the model's state: get_params() would fold the lazy-L2
+    scale P into the stored tables, so the tables are read as stored and multiplied by P here (in fp32, the same one
+    multiply as k_scale_table).  Row samples (seed 0, sorted) keep their row ids in <name>_rows.npy (float64)."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    if sharded:
+        arrays = {"loss": stepper.last_loss, "gnorm": stepper.last_gnorm}
+        arrays = {k: v.detach().float().cpu().numpy().reshape(1) for k, v in arrays.items()}
+    else:
+        from tlsan_amd import _lib as L
+        from tlsan_amd.model import TABLE_KEYS
+        o = stepper._out.detach().cpu().numpy()
+        arrays = {"loss": o[0:1].copy(), "gnorm": o[1:2].copy()}
+        P = np.float32(stepper.state[:4].view(torch.float32).item()) if stepper.l2_mode == L.L2_LAZY else np.float32(1.0)
+        for k in TABLE_KEYS:
+            w = getattr(stepper, k).detach().float().cpu().numpy()
+            arrays[k] = w if k == "item_b" else w * P
+        arrays.update({k: np.asarray(v, np.float32) for k, v in stepper.unpack_dense(stepper.dense.detach().cpu().numpy()).items()})
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        small = sum(a.nbytes for a in arrays.values() if a.nbytes <= 1 << 20)
+        big = {k: a for k, a in arrays.items() if a.nbytes > 1 << 20}
+        keep = (DUMP_BUDGET - small) / sum(a.nbytes + 8 * a.shape[0] for a in big.values())   # (8 bytes: the row id)
+        rng = np.random.default_rng(0)
+        for k in sorted(big):
+            a = big[k]
+            rows = np.sort(rng.choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False))
+            arrays[k] = a[rows]
+            arrays[k + "_rows"] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": d, "arrays": sorted(arrays), "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def self_launch(args):
@@ -350,6 +392,8 @@ def main():
     run(args.steps, fence_warm, timed=False, clock=True)
     fence()
     dt = time.perf_counter() - t0
+    # (before the kernel-timing pass below, which trains on: what the last TIMED step left)
+    dumped = dump_outputs(args.dump_outputs, stepper, sharded) if args.dump_outputs and rank == 0 else None
     starts = np.asarray(getattr(stepper, "started_at", None) or [], np.float64)
     if hasattr(stepper, "started_at"):
         stepper.started_at = None
@@ -500,6 +544,8 @@ def main():
             "library": lib_id(L.LIB_PATH),
             "final_loss": round(loss, 6),
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if also is not None:
             out["bf16_tables"] = also
         if also_mm is not None:
