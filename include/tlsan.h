@@ -41,7 +41,7 @@ typedef struct {
   int32_t d;          /* hidden_units = d_item + d_cate = d_user + d_cate (model.py:100-109,135) */
   int32_t d_item;     /* itemid_embedding_size (== userid_embedding_size)                        */
   int32_t d_cate;     /* cateid_embedding_size                                                  */
-  int32_t num_heads;  /* 8 in every config; d/num_heads in {8,16,32}                             */
+  int32_t num_heads;  /* (d, num_heads) in {64/4, 64/8, 128/4, 128/8, 128/16, 256/8}; else UNSUPPORTED */
   int32_t Ls;         /* long-term window (columns of hist_i / usert_emb), <= 96 (reference max_length = 90) */
 } tlsan_dims;
 

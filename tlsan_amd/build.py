@@ -1,7 +1,7 @@
-"""Build libtlsan_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: six translation
+"""Build libtlsan_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: twelve translation
 units (the C ABI with every kernel but the fused one; k_fwd_bwd for d = 64 / 128 / 128 as 8-sample workgroups / 256 with
-the window in registers / 256 streamed)
-compiled in parallel, one link.  `python -m tlsan_amd.build` or `build()`."""
+the window in registers / 256 streamed, all with 8 heads; k_fwd_bwd and the dense finalize kernels for each of the
+pairs 64/4, 128/16 and 128/4) compiled in parallel, one link.  `python -m tlsan_amd.build` or `build()`."""
 from __future__ import annotations
 
 import os
@@ -13,7 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libtlsan_hip.so")
-SOURCES = ["tlsan_api.hip", "tlsan_attn_d64.hip", "tlsan_attn_d128.hip", "tlsan_attn_d128w4.hip", "tlsan_attn_d256.hip", "tlsan_attn_d256s.hip"]
+SOURCES = ["tlsan_api.hip", "tlsan_attn_d64.hip", "tlsan_attn_d128.hip", "tlsan_attn_d128w4.hip", "tlsan_attn_d256.hip", "tlsan_attn_d256s.hip",
+           "tlsan_attn_d64h4.hip", "tlsan_attn_d128h16.hip", "tlsan_attn_d128h4.hip",
+           "tlsan_update_d64h4.hip", "tlsan_update_d128h16.hip", "tlsan_update_d128h4.hip"]
 # per-source extra flags (see the source's header comment)
 # -fno-honor-nans on the d <= 128 units: fmaxf on an MFMA result otherwise gets a canonicalising v_max x, x, x in front of it
 # (cdna_hip_programming.md, pitfalls): 78 vector instructions of the bf16-operand kernel, 18 of the fp32 one; same results on
@@ -23,6 +25,7 @@ SOURCES = ["tlsan_api.hip", "tlsan_attn_d64.hip", "tlsan_attn_d128.hip", "tlsan_
 # gains no more and reassociates
 _NONAN = ["-fno-honor-nans", "-fno-signed-zeros"]   # (no canonicalising v_max before fmaxf; x + 0 / 0 - x folds: the sign of a zero is never looked at)
 SOURCE_FLAGS = {"tlsan_attn_d64.hip": _NONAN, "tlsan_attn_d128.hip": _NONAN, "tlsan_attn_d128w4.hip": _NONAN,
+                "tlsan_attn_d64h4.hip": _NONAN, "tlsan_attn_d128h16.hip": _NONAN, "tlsan_attn_d128h4.hip": _NONAN,
                 "tlsan_attn_d256.hip": ["-mllvm", "-sink-insts-to-avoid-spills"],
                 # (the two FP switches on the streamed d = 256 unit: C5 305-307 -> 302-304 us/step, three interleaved rounds,
                 #  profiles/r05_ab_fpflags_d256.txt; nothing on the Ls = 10 unit, which keeps its flags)
@@ -30,9 +33,12 @@ SOURCE_FLAGS = {"tlsan_attn_d64.hip": _NONAN, "tlsan_attn_d128.hip": _NONAN, "tl
 if os.environ.get("TLSAN_SOURCE_FLAGS"):   # (experiments: JSON {source: [flags]}, replaces the entries it names)
     import json
     SOURCE_FLAGS.update(json.loads(os.environ["TLSAN_SOURCE_FLAGS"]))
-HEADERS = ["tlsan_common.h", "tlsan_attn.h", "tlsan_attn_inst.h", "tlsan_update.h", "tlsan_eval.h", "tlsan_rows.h", "tlsan_shard.h"]
+HEADERS = ["tlsan_common.h", "tlsan_attn.h", "tlsan_attn_inst.h", "tlsan_update.h", "tlsan_update_inst.h", "tlsan_eval.h", "tlsan_rows.h", "tlsan_shard.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC] + \
         os.environ.get("TLSAN_HIPCC_EXTRA", "").split()   # (experiments: extra compiler flags)
+
+
+MAX_JOBS = 16   # compiler processes at once (a build must not take more CPUs than that on a shared machine)
 
 
 def _hipcc():
@@ -71,7 +77,7 @@ def build(force=False, verbose=False):
             raise RuntimeError("hipcc failed for %s:\n%s" % (s, r.stderr[-4000:]))
         return o
 
-    with ThreadPoolExecutor(max_workers=6) as ex:
+    with ThreadPoolExecutor(max_workers=max(1, min(MAX_JOBS, len(jobs)))) as ex:
         list(ex.map(run, jobs))
     objs = [os.path.join(objdir, s.replace(".hip", ".o")) for s in SOURCES]
     if force or jobs or _stale(LIB, objs):

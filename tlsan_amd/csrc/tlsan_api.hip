@@ -15,6 +15,7 @@
 #include "tlsan_common.h"
 #include "tlsan_eval.h"
 #include "tlsan_update.h"
+#include "tlsan_update_inst.h"
 #include "tlsan_shard.h"
 
 struct LaunchEvents { hipEvent_t start, stop; };   // optional time stamps of the dispatch (tlsan_attn_inst.h)
@@ -22,6 +23,13 @@ hipError_t tlsan_launch_fwd_bwd_d64(bool train, bool lstream, const FwdArgs& a, 
 hipError_t tlsan_launch_fwd_bwd_d128(bool train, bool lstream, const FwdArgs& a, int grid, hipStream_t st, LaunchEvents ev);
 hipError_t tlsan_launch_fwd_bwd_d256(bool train, bool lstream, const FwdArgs& a, int grid, hipStream_t st, LaunchEvents ev);
 hipError_t tlsan_launch_fwd_bwd_d128w4(const FwdArgs& a, int grid, hipStream_t st, LaunchEvents ev);   // training, 8-sample workgroups
+// the pairs of fewer or more than 8 heads: k_fwd_bwd and the dense finalize in units of their own
+hipError_t tlsan_launch_fwd_bwd_d64h4(bool train, bool lstream, const FwdArgs& a, int grid, hipStream_t st, LaunchEvents ev);
+hipError_t tlsan_launch_fwd_bwd_d128h16(bool train, bool lstream, const FwdArgs& a, int grid, hipStream_t st, LaunchEvents ev);
+hipError_t tlsan_launch_fwd_bwd_d128h4(bool train, bool lstream, const FwdArgs& a, int grid, hipStream_t st, LaunchEvents ev);
+void tlsan_launch_finalize_d64h4(const FinLaunch& L, hipStream_t hs);
+void tlsan_launch_finalize_d128h16(const FinLaunch& L, hipStream_t hs);
+void tlsan_launch_finalize_d128h4(const FinLaunch& L, hipStream_t hs);
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, ...) {
@@ -89,10 +97,16 @@ static int shape_of(const tlsan_dims* d, Shape* s) {
   if (d->user_count < 1 || d->item_count < 1 || d->cate_count < 1) return fail(TLSAN_E_BADARG, "empty table");
   s->D = D;
   s->DH = DH;
+  // (a pair is built when dh is 8, 16 or 32 and a sample spans 4 or 8 columns of max(dh, 16) channels: a sample's 4 * CPS
+  //  lanes cover its Ls + 3 use slots, and a pass of 16 samples is one workgroup of CPS wavefronts -- Geo)
   if (D == 64 && DH == 8) { using G = Geo<64, 8>; s->NSB = G::NSB; s->NPB = G::NPB; s->CW = G::CW; }
+  else if (D == 64 && DH == 16) { using G = Geo<64, 16>; s->NSB = G::NSB; s->NPB = G::NPB; s->CW = G::CW; }
+  else if (D == 128 && DH == 8) { using G = Geo<128, 8>; s->NSB = G::NSB; s->NPB = G::NPB; s->CW = G::CW; }
   else if (D == 128 && DH == 16) { using G = Geo<128, 16>; s->NSB = G::NSB; s->NPB = G::NPB; s->CW = G::CW; }
+  else if (D == 128 && DH == 32) { using G = Geo<128, 32>; s->NSB = G::NSB; s->NPB = G::NPB; s->CW = G::CW; }
   else if (D == 256 && DH == 32) { using G = Geo<256, 32>; s->NSB = G::NSB; s->NPB = G::NPB; s->CW = G::CW; }
-  else return fail(TLSAN_E_UNSUPPORTED, "unsupported (hidden_units=%d, num_heads=%d): this build has 64/8, 128/8, 256/8", D, d->num_heads);
+  else return fail(TLSAN_E_UNSUPPORTED, "unsupported (hidden_units=%d, num_heads=%d): this build has (hidden_units, num_heads) = "
+                   "64/4, 64/8, 128/4, 128/8, 128/16, 256/8", D, d->num_heads);
   return TLSAN_OK;
 }
 
@@ -123,13 +137,13 @@ static int cseg_min_cates() {
 }
 static bool fused_dk(int D, int ngroups) { return D <= 128 && ngroups <= FUSED_DK_MAX_GROUPS; }
 // Samples per workgroup pass of a TRAINING launch of the fused kernel (= per partial record): the width's NSB, or 8 at
-// d = 128 (4-wavefront workgroups: Geo<128, 16, 4>) with the window in registers and no dropout, when the batch is so
+// d = 128 with 8 heads (4-wavefront workgroups: Geo<128, 16, 4>) with the window in registers and no dropout, when the batch is so
 // small that 16-sample workgroups would leave three quarters of the CUs idle -- a wavefront then runs alone on its SIMD
 // (profiles/r04_nw4_ab.md; at larger batches the 16-sample workgroups are faster).
 // TLSAN_NW4 (A/B measurements; read once): 0 never, 1 as described, 2 always.
 static int train_group(const Shape& s, const tlsan_dims* d, const tlsan_batch* b, const tlsan_hparams* hp) {
   static const int mode = [] { const char* e = getenv("TLSAN_NW4"); return e ? atoi(e) : 1; }();
-  if (s.D != 128 || d->Ls > TLSAN_LS_MAX || (hp && hp->dropout != 0.0f) || mode == 0) return s.NSB;
+  if (s.D != 128 || s.DH != 16 || d->Ls > TLSAN_LS_MAX || (hp && hp->dropout != 0.0f) || mode == 0) return s.NSB;
   if (mode == 1 && (b->B + s.NSB - 1) / s.NSB > 64) return s.NSB;
   return 8;
 }
@@ -161,14 +175,15 @@ static void carve(const tlsan_dims* d, const Shape& s, int B, int Sn, char* base
   w->Gc = (float*)take(sizeof(float) * (size_t)(B + 1 + (d->cate_count >= cseg_min_cates() ? NI : 0)) * d->d_cate);
   w->gLong = (float*)take(sizeof(float) * B * D);
   w->gDB = (float*)take(sizeof(float) * B * D);
-  // streamed windows at d = 256: per-sample softmax statistics of the long block (k_fwd_bwd, FLATG: no room in the LDS)
-  w->gStat = (float*)take((D > 128 && streamed(d->Ls)) ? sizeof(float) * (size_t)B * 2 * D : 0);
+  // streamed windows with two 16-channel blocks per column (d = 256, and d = 128 with 4 heads): per-sample softmax
+  // statistics of the long block (k_fwd_bwd, FLATG: no room in the LDS)
+  w->gStat = (float*)take((s.CW > 16 && streamed(d->Ls)) ? sizeof(float) * (size_t)B * 2 * D : 0);
   w->partials = (float*)take(sizeof(float) * w->ngroups * s.NPB);
   // (sized so that the workspace of a batch also holds every smaller batch: the fused form of a smaller batch can
   //  need more partials than the split form of a larger one)
   int kp_slots = dk_nsplit(B, s.D);
   if (s.D <= 128) {
-    const int ng8 = s.D == 128 ? (B + 7) / 8 : ngroups;    // (8-sample workgroups: twice the groups)
+    const int ng8 = (s.D == 128 && s.DH == 16) ? (B + 7) / 8 : ngroups;    // (8-sample workgroups: twice the groups)
     const int fmax = ng8 < FUSED_DK_MAX_GROUPS ? ng8 : FUSED_DK_MAX_GROUPS;
     if (fmax > kp_slots) kp_slots = fmax;
   }
@@ -712,6 +727,16 @@ int tlsan_state_recategorize(const tlsan_dims* d, const tlsan_params* p, void* s
   return build_cate_csr(d, p, st, (hipStream_t)stream);
 }
 
+// the dense finalize of the shape's (d, heads) pair (shape_of has refused every other pair)
+static void launch_finalize_of(const Shape& s, const FinLaunch& L, hipStream_t hs) {
+  if (s.D == 64 && s.DH == 8) launch_finalize<64, 8>(L, hs);
+  else if (s.D == 64) tlsan_launch_finalize_d64h4(L, hs);
+  else if (s.D == 128 && s.DH == 16) launch_finalize<128, 16>(L, hs);
+  else if (s.D == 128 && s.DH == 8) tlsan_launch_finalize_d128h16(L, hs);
+  else if (s.D == 128) tlsan_launch_finalize_d128h4(L, hs);
+  else launch_finalize<256, 32>(L, hs);
+}
+
 static int launch_fwd(const Shape& s, bool train, const FwdArgs& a, hipStream_t hs, int grp = 0) {
   int grid = a.ngroups < 4096 ? a.ngroups : 4096;
   if (train && a.fuse_dk) grid = fwd_train_grid(a.ngroups);
@@ -719,9 +744,12 @@ static int launch_fwd(const Shape& s, bool train, const FwdArgs& a, hipStream_t 
   const bool lstream = streamed(a.Ls);  // long windows are streamed, short ones stay in registers
   LaunchEvents ev = {nullptr, nullptr};
   if (train) ev = prof_kernel_events();
-  if (train && s.D == 128 && grp == 8) e = tlsan_launch_fwd_bwd_d128w4(a, grid, hs, ev);
-  else if (s.D == 64) e = tlsan_launch_fwd_bwd_d64(train, lstream, a, grid, hs, ev);
-  else if (s.D == 128) e = tlsan_launch_fwd_bwd_d128(train, lstream, a, grid, hs, ev);
+  if (train && s.D == 128 && s.DH == 16 && grp == 8) e = tlsan_launch_fwd_bwd_d128w4(a, grid, hs, ev);
+  else if (s.D == 64 && s.DH == 8) e = tlsan_launch_fwd_bwd_d64(train, lstream, a, grid, hs, ev);
+  else if (s.D == 64) e = tlsan_launch_fwd_bwd_d64h4(train, lstream, a, grid, hs, ev);
+  else if (s.D == 128 && s.DH == 16) e = tlsan_launch_fwd_bwd_d128(train, lstream, a, grid, hs, ev);
+  else if (s.D == 128 && s.DH == 8) e = tlsan_launch_fwd_bwd_d128h16(train, lstream, a, grid, hs, ev);
+  else if (s.D == 128) e = tlsan_launch_fwd_bwd_d128h4(train, lstream, a, grid, hs, ev);
   else e = tlsan_launch_fwd_bwd_d256(train, lstream, a, grid, hs, ev);
   if (e == hipErrorNotSupported)
     return fail(TLSAN_E_UNSUPPORTED, "dropout > 0 is built for train steps only (and not for the 8-sample workgroup form)");
@@ -952,31 +980,11 @@ static int run_backward(const tlsan_dims* d, const Shape& s, const tlsan_params*
     const dim3 grid(w.nfin + 1 + A.nbH + (shared ? A.C * A.csplit : A.nbC) + (A.nbI_l > 0 ? A.nbI_l : A.nbI) + A.nbU);
     static const int low_env = [] { const char* e = getenv("TLSAN_SPEC_LOWOCC"); return e ? atoi(e) : -1; }();   // (A/B: 0 / 1 force it)
     const bool wide = apply_wide(A) && !shared, bf16 = A.p.table_dtype == TLSAN_TABLE_BF16, low = low_env < 0 ? tables_in_hbm(d) : low_env != 0;
-#define FU_LAUNCH(DD, HH)                                                                                                            \
-  do {                                                                                                                               \
-    if (shared) {                                                                                                                    \
-      if (bf16) {                                                                                                                    \
-        if (low) hipLaunchKernelGGL((k_finalize_update<DD, HH, false, TLSAN_TABLE_BF16, true, true>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A);  \
-        else hipLaunchKernelGGL((k_finalize_update<DD, HH, false, TLSAN_TABLE_BF16, false, true>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A);     \
-      } else {                                                                                                                       \
-        if (low) hipLaunchKernelGGL((k_finalize_update<DD, HH, false, TLSAN_TABLE_F32, true, true>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A);   \
-        else hipLaunchKernelGGL((k_finalize_update<DD, HH, false, TLSAN_TABLE_F32, false, true>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A);      \
-      }                                                                                                                              \
-    } else if (bf16) {                                                                                                                      \
-      if (wide) hipLaunchKernelGGL((k_finalize_update<DD, HH, true, TLSAN_TABLE_BF16>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A);  \
-      else if (low) hipLaunchKernelGGL((k_finalize_update<DD, HH, false, TLSAN_TABLE_BF16, true>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A); \
-      else hipLaunchKernelGGL((k_finalize_update<DD, HH, false, TLSAN_TABLE_BF16>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A);      \
-    } else {                                                                                                                         \
-      if (wide) hipLaunchKernelGGL((k_finalize_update<DD, HH, true, TLSAN_TABLE_F32>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A);   \
-      else if (low) hipLaunchKernelGGL((k_finalize_update<DD, HH, false, TLSAN_TABLE_F32, true>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A); \
-      else hipLaunchKernelGGL((k_finalize_update<DD, HH, false, TLSAN_TABLE_F32>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A);       \
-    }                                                                                                                                \
-  } while (0)
     if (shared && s.D > 128) return fail(TLSAN_E_UNSUPPORTED, "shared categories in the one-pass update: d <= 128");   // (lazy_one_pass never asks)
-    if (s.D == 64) FU_LAUNCH(64, 8);
-    else if (s.D == 128) FU_LAUNCH(128, 16);
-    else FU_LAUNCH(256, 32);
-#undef FU_LAUNCH
+    FinLaunch fl;
+    fl.f = f; fl.A = A; fl.grid = grid; fl.nbK = w.nbK; fl.nbS = w.nbS; fl.kind = FinLaunch::UPDATE;
+    fl.shared = shared; fl.bf16 = bf16; fl.wide = wide; fl.low = low; fl.csplit = false;
+    launch_finalize_of(s, fl, hs);
     CHECK_LAUNCH("k_finalize_update");
     prof_mark(4, hs);
     return TLSAN_OK;
@@ -992,25 +1000,21 @@ static int run_backward(const tlsan_dims* d, const Shape& s, const tlsan_params*
     //  workgroups per CU, instead of 135 and three; the sharded step's fused rows keep the wide form.  d = 128 with 90-entry
     //  windows: Movies-TV shape 106.6 -> 104.3 us/step, with 673 categories 116.2 -> 106.2: profiles/r04_presum_narrow_ab.md)
     const bool wide = A.di > 64 || A.dc > 64 || (A.WU > 128 && A.presum_rows != 0);
-#define FP_LAUNCH(DD, HH)                                                                                         \
-  do {                                                                                                            \
-    if (A.csplit > 1) {                                                                                           \
-      if (wide) hipLaunchKernelGGL((k_finalize_presum<DD, HH, true, true>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A);  \
-      else hipLaunchKernelGGL((k_finalize_presum<DD, HH, false, true>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A);      \
-    } else if (wide) hipLaunchKernelGGL((k_finalize_presum<DD, HH, true>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A);   \
-    else hipLaunchKernelGGL((k_finalize_presum<DD, HH, false>), grid, dim3(256), 0, hs, f, w.nbK, w.nbS, A);       \
-  } while (0)
-    if (s.D == 64) FP_LAUNCH(64, 8);
-    else if (s.D == 128) FP_LAUNCH(128, 16);
-    else FP_LAUNCH(256, 32);
-#undef FP_LAUNCH
+    FinLaunch fl;
+    fl.f = f; fl.A = A; fl.grid = grid; fl.nbK = w.nbK; fl.nbS = w.nbS; fl.kind = FinLaunch::PRESUM;
+    fl.shared = false; fl.bf16 = false; fl.wide = wide; fl.low = false; fl.csplit = A.csplit > 1;
+    launch_finalize_of(s, fl, hs);
     CHECK_LAUNCH("k_finalize_presum");
     prof_mark(4, hs);
     return TLSAN_OK;
   }
-  if (s.D == 64) hipLaunchKernelGGL((k_dense_finalize<64, 8>), dim3(w.nfin + 1), dim3(256), 0, hs, f, w.nbK, w.nbS);
-  else if (s.D == 128) hipLaunchKernelGGL((k_dense_finalize<128, 16>), dim3(w.nfin + 1), dim3(256), 0, hs, f, w.nbK, w.nbS);
-  else hipLaunchKernelGGL((k_dense_finalize<256, 32>), dim3(w.nfin + 1), dim3(256), 0, hs, f, w.nbK, w.nbS);
+  {
+    FinLaunch fl;
+    memset(&fl.A, 0, sizeof(fl.A));
+    fl.f = f; fl.grid = dim3(w.nfin + 1); fl.nbK = w.nbK; fl.nbS = w.nbS; fl.kind = FinLaunch::DENSE;
+    fl.shared = fl.bf16 = fl.wide = fl.low = fl.csplit = false;
+    launch_finalize_of(s, fl, hs);
+  }
   CHECK_LAUNCH("k_dense_finalize");
   prof_mark(4, hs);
   return TLSAN_OK;

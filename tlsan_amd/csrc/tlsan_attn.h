@@ -1248,8 +1248,9 @@ __global__ __launch_bounds__(512) void k_fwd_bwd(FwdArgs a) {
     for (int kb = 0; kb < NB; ++kb) {
       *(f32x4*)(sA + srow * LSTR + chb[kb]) = long4[kb];
       if constexpr (TRAIN && G::FUSE_DK) {
-        if (FUSE_RT || FLAT) *(f32x4*)(sL + srow * LSTR + chb[kb]) = long4[kb];
-        if (!FUSE_RT && vs) *(f32x4*)(a.gLong + (size_t)bidx_t * D + chb[kb]) = long4[kb];
+        // (FLATG, d = 128 with 32 channels per head: the streamed backward reads `long` from gLong, not from sL)
+        if (FUSE_RT || (FLAT && !FLATG)) *(f32x4*)(sL + srow * LSTR + chb[kb]) = long4[kb];
+        if ((!FUSE_RT || FLATG) && vs) *(f32x4*)(a.gLong + (size_t)bidx_t * D + chb[kb]) = long4[kb];
       } else if (TRAIN && vs) {
         *(f32x4*)(a.gLong + (size_t)bidx_t * D + chb[kb]) = long4[kb];
       }

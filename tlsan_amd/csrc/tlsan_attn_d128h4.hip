@@ -1,0 +1,5 @@
+// k_fwd_bwd instantiations for hidden_units = 128 with 4 heads (32 channels per head)
+#include "tlsan_attn_inst.h"
+hipError_t tlsan_launch_fwd_bwd_d128h4(bool train, bool lstream, const FwdArgs& a, int grid, hipStream_t st, LaunchEvents ev) {
+  return launch_fwd_bwd_impl<128, 32>(train, lstream, a, grid, st, ev);
+}

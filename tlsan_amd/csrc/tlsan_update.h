@@ -11,6 +11,11 @@
 #pragma once
 #include "tlsan_common.h"
 #include <type_traits>
+// TLSAN_ONCE: the kernels that are not templates belong to the unit that launches them (tlsan_api.hip); a unit that
+// includes this header only for the templates of the dense finalize (tlsan_update_*.hip) defines it as `static`
+#ifndef TLSAN_ONCE
+#define TLSAN_ONCE
+#endif
 
 // index slots of the state: the batch being trained and up to two announced successors (tlsan_batch_index)
 #define TLSAN_INDEX_SLOTS 3
@@ -102,7 +107,7 @@ __device__ __forceinline__ void count_samples_block(const CountArgs& a, int* his
   }
 }
 
-__global__ __launch_bounds__(256) void k_count(CountArgs a) {
+TLSAN_ONCE __global__ __launch_bounds__(256) void k_count(CountArgs a) {
   __shared__ int hist[COUNT_LDS_CATES];
   const int B = a.b.B, Ls = a.Ls, Sn = a.b.Sn, S = Ls + Sn + 1;
   const int nbs = (B + 255) / 256;
@@ -144,7 +149,7 @@ __global__ __launch_bounds__(256) void k_count(CountArgs a) {
 // few categories (15 in Movies-TV) 4096 returning atomics on 15 addresses cost it 20 us.
 // (the cursor draws of a block's 256 samples go through the LDS as well when the table is small: one returning atomic
 //  per block and category instead of one per sample -- 13 -> 4 us with 15 categories)
-__global__ __launch_bounds__(256) void k_uc_fill(const int32_t* __restrict__ u_cate, int B, int ncate, int32_t* cur_uc, int32_t* uc_list) {
+TLSAN_ONCE __global__ __launch_bounds__(256) void k_uc_fill(const int32_t* __restrict__ u_cate, int B, int ncate, int32_t* cur_uc, int32_t* uc_list) {
   __shared__ int hist[COUNT_LDS_CATES];
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (ncate > COUNT_LDS_CATES) {
@@ -171,7 +176,7 @@ struct PackArgs {
   tlsan_batch out;
 };
 
-__global__ void k_batch_pack(PackArgs a) {
+TLSAN_ONCE __global__ void k_batch_pack(PackArgs a) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int B = a.out.B, Sn = a.out.Sn, Ls = a.Ls, S = Ls + Sn + 1;
   if (t >= B * S) return;
@@ -480,7 +485,7 @@ __device__ __forceinline__ int isort_slot_id(const IsortArgs& a, int t) {
 }
 #define IS_PT (IS_BLK_SLOTS / 1024)   // slots per thread
 
-__global__ __launch_bounds__(1024) void k_isort_hist(IsortArgs a, CountArgs ca) {
+TLSAN_ONCE __global__ __launch_bounds__(1024) void k_isort_hist(IsortArgs a, CountArgs ca) {
   __shared__ int h[COUNT_LDS_CATES > IS_MAXB ? COUNT_LDS_CATES : IS_MAXB];
   const int tid = threadIdx.x;
   if ((int)blockIdx.x < a.nbu) {     // the samples' single uses (u_cate row; user row unless sorted)
@@ -501,7 +506,7 @@ __global__ __launch_bounds__(1024) void k_isort_hist(IsortArgs a, CountArgs ca) 
   for (int c = tid; c < a.nb; c += 1024) a.bh[(size_t)blk * a.nb + c] = h[c];
 }
 
-__global__ __launch_bounds__(1024) void k_isort_scatter(IsortArgs a) {
+TLSAN_ONCE __global__ __launch_bounds__(1024) void k_isort_scatter(IsortArgs a) {
   __shared__ int base[IS_MAXB];
   __shared__ int wsum[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, blk = blockIdx.x;
@@ -556,7 +561,7 @@ __global__ __launch_bounds__(1024) void k_isort_scatter(IsortArgs a) {
 
 // (its FIRST block, when us.u is set, is the user side's sort: independent of everything here and the longest block of
 //  the launch -- dispatched first it runs beside the bucket blocks; inside k_index_scan's launch it was the long pole)
-__global__ __launch_bounds__(1024) void k_isort_bucket(IsortArgs a, UsortArgs us) {
+TLSAN_ONCE __global__ __launch_bounds__(1024) void k_isort_bucket(IsortArgs a, UsortArgs us) {
   const int ub = us.u != nullptr ? 1 : 0;
   if (ub && blockIdx.x == 0) {
     usort_block(us);
@@ -685,7 +690,7 @@ struct ScanArgs {
 // The re-read is quadratic in the number of chunks, so for large tables (millions of rows) a
 // first launch leaves one packed sum per chunk (k_scan_block_sums) and the blocks add up the
 // preceding CHUNK sums instead (ScanArgs.bsum).
-__global__ __launch_bounds__(1024) void k_scan_block_sums(ScanArgs a) {
+TLSAN_ONCE __global__ __launch_bounds__(1024) void k_scan_block_sums(ScanArgs a) {
   __shared__ long long wsum[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int which = 0;
@@ -859,7 +864,7 @@ __device__ __forceinline__ void index_scan_block(const ScanArgs& a, int blk) {
   if (a.flag[which] != nullptr && marked && lane == 0 && i0 < n) a.flag[which][i0 >> 8] = 0;   // zero at rest
 }
 
-__global__ __launch_bounds__(1024) void k_index_scan(ScanArgs a) {
+TLSAN_ONCE __global__ __launch_bounds__(1024) void k_index_scan(ScanArgs a) {
   if (a.bal.perm != nullptr && (int)blockIdx.x == a.bal.blk) {
     balance_block<16>(a.bal);
     return;
@@ -1087,7 +1092,7 @@ __device__ __forceinline__ void fold_delta(const DeltaRec* __restrict__ recs, in
 }
 
 // (tlsan_state_renorm: the sum of squares must be complete before it is rescaled)
-__global__ __launch_bounds__(256) void k_fold_delta(const DeltaRec* recs, int n_spart, StateHdr* hdr, double* S_total) {
+TLSAN_ONCE __global__ __launch_bounds__(256) void k_fold_delta(const DeltaRec* recs, int n_spart, StateHdr* hdr, double* S_total) {
   __shared__ double shd[256];
   fold_delta(recs, n_spart, hdr, S_total, shd);
 }
@@ -1304,7 +1309,7 @@ __global__ __launch_bounds__(256) void k_dense_finalize(FinArgs a, int nbK, int 
 
 // dedup-norm mode: norm^2 = sum over destination rows of |summed row gradient|^2 (ROWNORM pass)
 // + dense gradients; overrides the coefficient / norm of the step summary
-__global__ __launch_bounds__(256) void k_clip_dedup(const double* rown_part, int nrow, const float* sqd, int nsqd,
+TLSAN_ONCE __global__ __launch_bounds__(256) void k_clip_dedup(const double* rown_part, int nrow, const float* sqd, int nsqd,
                                                     StateHdr* hdr, float clip, float* out_gnorm) {
   __shared__ double shd[256];
   const int tid = threadIdx.x;
@@ -1324,13 +1329,13 @@ __global__ __launch_bounds__(256) void k_clip_dedup(const double* rown_part, int
   }
 }
 
-__global__ __launch_bounds__(256) void k_reduce_double(const double* v, int n, double* out) {
+TLSAN_ONCE __global__ __launch_bounds__(256) void k_reduce_double(const double* v, int n, double* out) {
   __shared__ double shd[256];
   const double s = block_sum_double(v, n, shd);
   if (threadIdx.x == 0) *out = s;
 }
 
-__global__ void k_transpose_K(const float* __restrict__ K, float* __restrict__ KT, int D) {
+TLSAN_ONCE __global__ void k_transpose_K(const float* __restrict__ K, float* __restrict__ KT, int D) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < D * D) KT[(size_t)(t % D) * D + t / D] = K[t];
 }
@@ -2659,7 +2664,7 @@ __global__ __launch_bounds__(256) void k_spec_commit(ApplyArgs a) {
 }
 
 // split category sums (Rc64, exact doubles) -> float output, and back to zero at rest (tlsan_grads)
-__global__ void k_rc64_to_float(double* __restrict__ r64, float* __restrict__ out, int n) {
+TLSAN_ONCE __global__ void k_rc64_to_float(double* __restrict__ r64, float* __restrict__ out, int n) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n) {
     out[t] = (float)r64[t];
@@ -2769,7 +2774,7 @@ __global__ __launch_bounds__(256) void k_update_lazy(ApplyArgs a, int nbC16) {
 
 // stored *= P for one table (tlsan_state_renorm)
 // (dt: storage type of the table; width % 4 == 0 for bf16 tables; bf16 values are rounded stochastically)
-__global__ void k_scale_table(float* W, int rows, int width, int ld, const StateHdr* hdr, int dt, uint32_t salt) {
+TLSAN_ONCE __global__ void k_scale_table(float* W, int rows, int width, int ld, const StateHdr* hdr, int dt, uint32_t salt) {
   const float P = hdr->P;
   if (dt == TLSAN_TABLE_F32) {
     const size_t n = (size_t)rows * width;
@@ -2787,7 +2792,7 @@ __global__ void k_scale_table(float* W, int rows, int width, int ld, const State
   }
 }
 
-__global__ void k_renorm_commit(StateHdr* hdr) {
+TLSAN_ONCE __global__ void k_renorm_commit(StateHdr* hdr) {
   const double P = hdr->P;
   hdr->St *= P * P;
   hdr->P = 1.0f;

@@ -1,0 +1,55 @@
+// tlsan_update_inst.h -- launchers of the dense finalize kernels (k_dense_finalize, k_finalize_presum,
+// k_finalize_update), one template per (hidden_units, channels per head).  The three (d, heads) pairs of 8 heads are
+// instantiated in tlsan_api.hip; the other pairs in units of their own (tlsan_update_d*.hip), so that they compile
+// beside it.
+#pragma once
+#include "tlsan_update.h"
+
+struct FinLaunch {   // one launch of the dense finalize, in any of its three forms
+  enum Kind { DENSE = 0, PRESUM = 1, UPDATE = 2 };
+  FinArgs f;
+  ApplyArgs A;       // PRESUM, UPDATE: the row workgroups of the launch
+  dim3 grid;
+  int nbK, nbS;
+  int kind;
+  bool shared;       // UPDATE: shared categories (lazy_one_pass form 2)
+  bool bf16;         // UPDATE: bf16 tables
+  bool wide;         // PRESUM, UPDATE: the wide row form
+  bool low;          // UPDATE: the low-occupancy form (tables in HBM)
+  bool csplit;       // PRESUM: categories split over several workgroups
+};
+
+template <int D, int DH>
+static void launch_finalize(const FinLaunch& L, hipStream_t hs) {
+  const FinArgs& f = L.f;
+  const ApplyArgs& A = L.A;
+  const dim3 grid = L.grid, blk(256);
+  const int nbK = L.nbK, nbS = L.nbS;
+  if (L.kind == FinLaunch::UPDATE) {
+    if (L.shared) {
+      if (L.bf16) {
+        if (L.low) hipLaunchKernelGGL((k_finalize_update<D, DH, false, TLSAN_TABLE_BF16, true, true>), grid, blk, 0, hs, f, nbK, nbS, A);
+        else hipLaunchKernelGGL((k_finalize_update<D, DH, false, TLSAN_TABLE_BF16, false, true>), grid, blk, 0, hs, f, nbK, nbS, A);
+      } else {
+        if (L.low) hipLaunchKernelGGL((k_finalize_update<D, DH, false, TLSAN_TABLE_F32, true, true>), grid, blk, 0, hs, f, nbK, nbS, A);
+        else hipLaunchKernelGGL((k_finalize_update<D, DH, false, TLSAN_TABLE_F32, false, true>), grid, blk, 0, hs, f, nbK, nbS, A);
+      }
+    } else if (L.bf16) {
+      if (L.wide) hipLaunchKernelGGL((k_finalize_update<D, DH, true, TLSAN_TABLE_BF16>), grid, blk, 0, hs, f, nbK, nbS, A);
+      else if (L.low) hipLaunchKernelGGL((k_finalize_update<D, DH, false, TLSAN_TABLE_BF16, true>), grid, blk, 0, hs, f, nbK, nbS, A);
+      else hipLaunchKernelGGL((k_finalize_update<D, DH, false, TLSAN_TABLE_BF16>), grid, blk, 0, hs, f, nbK, nbS, A);
+    } else {
+      if (L.wide) hipLaunchKernelGGL((k_finalize_update<D, DH, true, TLSAN_TABLE_F32>), grid, blk, 0, hs, f, nbK, nbS, A);
+      else if (L.low) hipLaunchKernelGGL((k_finalize_update<D, DH, false, TLSAN_TABLE_F32, true>), grid, blk, 0, hs, f, nbK, nbS, A);
+      else hipLaunchKernelGGL((k_finalize_update<D, DH, false, TLSAN_TABLE_F32>), grid, blk, 0, hs, f, nbK, nbS, A);
+    }
+  } else if (L.kind == FinLaunch::PRESUM) {
+    if (L.csplit) {
+      if (L.wide) hipLaunchKernelGGL((k_finalize_presum<D, DH, true, true>), grid, blk, 0, hs, f, nbK, nbS, A);
+      else hipLaunchKernelGGL((k_finalize_presum<D, DH, false, true>), grid, blk, 0, hs, f, nbK, nbS, A);
+    } else if (L.wide) hipLaunchKernelGGL((k_finalize_presum<D, DH, true>), grid, blk, 0, hs, f, nbK, nbS, A);
+    else hipLaunchKernelGGL((k_finalize_presum<D, DH, false>), grid, blk, 0, hs, f, nbK, nbS, A);
+  } else {
+    hipLaunchKernelGGL((k_dense_finalize<D, DH>), grid, blk, 0, hs, f, nbK, nbS);
+  }
+}
