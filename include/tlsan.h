@@ -347,6 +347,29 @@ int tlsan_eval_counts_shard(const tlsan_dims* dims, const tlsan_params* p, const
                             const int32_t* labels_global, int32_t B, int32_t id_mul, int32_t id_add, int32_t* counts,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* Top-K recommendation over all items -- what the reference gets with tf.nn.top_k(eval_logits, K)
+ * (model.py:140), without materialising the [B, I] scores: for each row b of u_t [B, d], the K items
+ * of highest score  u_t[b] . [item_emb || cate_emb[item_cate]][n] + item_b[n]  (the scores of
+ * tlsan_eval_ranks / tlsan_eval_label_scores, bit for bit), in tf.nn.top_k's order: higher score first,
+ * equal scores -> lower GLOBAL id first; +0.0 == -0.0 (a zero score is returned as +0.0); a NaN score
+ * ranks after every other score.  1 <= K <= 256.
+ *   ids [B, K] int32, scores [B, K] float32; rows with fewer than K eligible items end in id -1, score -inf.
+ *   excl_off [B + 1] / excl_ids (both NULL: no exclusion): row b's list excl_ids[excl_off[b] .. excl_off[b+1])
+ *     of global ids, ascending; those items never appear in the row (ids outside the table or repeated are
+ *     ignored).
+ *   Item-sharded form: local item n is global id n * id_mul + id_add (1 and 0 for a whole table), as in
+ *     tlsan_eval_counts_shard; the ranks' lists of a row merge with tlsan_topk_merge.
+ * The result does not depend on B, on the other rows of the launch or on the launch geometry.
+ * Workspace: tlsan_topk_workspace_bytes (0, with tlsan_last_error set, for bad dims / K / B). */
+size_t tlsan_topk_workspace_bytes(const tlsan_dims* dims, int32_t B, int32_t K);
+int tlsan_eval_topk(const tlsan_dims* dims, const tlsan_params* p, const float* u_t, int32_t B, int32_t K,
+                    const int32_t* excl_off, const int32_t* excl_ids, int32_t id_mul, int32_t id_add,
+                    int32_t* ids, float* scores, void* ws, size_t ws_bytes, void* stream);
+/* [B, n_lists, K] lists, each sorted in that order and holding disjoint items (padded with id -1) -> the
+ * [B, K] best of each row.  The merge tlsan_eval_topk runs on its item slices. */
+int tlsan_topk_merge(const int32_t* cand_ids, const float* cand_scores, int32_t B, int32_t n_lists, int32_t K,
+                     int32_t* ids, float* scores, void* stream);
+
 /* Deterministic scatter-apply on one row table (the owner-side half of the multi-GPU step, and
  * the stand-alone form of the embedding update of model.py:198-205):
  *   for every row r < nrows:  g = gscale * sum_{k: dest[k]==r} grows[k] (+ reg * W[r] on the

@@ -14,6 +14,7 @@
 
 #include "tlsan_common.h"
 #include "tlsan_eval.h"
+#include "tlsan_topk.h"
 #include "tlsan_update.h"
 #include "tlsan_update_inst.h"
 #include "tlsan_shard.h"
@@ -30,6 +31,10 @@ hipError_t tlsan_launch_fwd_bwd_d128h4(bool train, bool lstream, const FwdArgs& 
 void tlsan_launch_finalize_d64h4(const FinLaunch& L, hipStream_t hs);
 void tlsan_launch_finalize_d128h16(const FinLaunch& L, hipStream_t hs);
 void tlsan_launch_finalize_d128h4(const FinLaunch& L, hipStream_t hs);
+// top-K selection over all items (tlsan_topk.hip)
+hipError_t tlsan_launch_topk(const TopkArgs& a, int D, int nslices, hipStream_t hs);
+hipError_t tlsan_launch_topk_merge(const int32_t* cid, const float* csc, int B, int nl, int K, int32_t* ids, float* scores,
+                                   hipStream_t hs);
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, ...) {
@@ -1281,6 +1286,92 @@ static int eval_ranks_impl(const tlsan_dims* d, const tlsan_params* p, const flo
   else EVAL_LAUNCH(256);
 #undef EVAL_LAUNCH
   CHECK_LAUNCH("k_eval");
+  return TLSAN_OK;
+}
+
+// ---- top-K items over all items (tlsan_topk.h) ----
+struct TopkWs {
+  float* all_emb;      // dense [I, D] item matrix when it fits EVAL_DENSE_MAX (as the rank path), else NULL
+  int32_t* ids;        // [B, nsl, K] the slices' lists (nsl > 1)
+  float* scores;
+  size_t bytes;
+  int nsl;
+};
+
+static void carve_topk(const tlsan_dims* d, int D, int B, int K, char* base, TopkWs* w) {
+  size_t o = 0;
+  auto take = [&](size_t n) { char* p = base ? base + o : nullptr; o += al(n); return p; };
+  const int ut = (B + 15) / 16;
+  const int want = (2048 + ut - 1) / ut;  // enough workgroups to fill the chip (the rank path's slicing)
+  int nsl = ((d->item_count + 63) / 64 + 3) / 4;
+  if (nsl > want) nsl = want;
+  if (nsl < 1) nsl = 1;
+  w->nsl = nsl;
+  const size_t ae = sizeof(float) * (size_t)d->item_count * D;
+  w->all_emb = ae <= EVAL_DENSE_MAX ? (float*)take(ae) : nullptr;
+  const size_t nc = nsl > 1 ? (size_t)B * nsl * K : 0;
+  w->ids = (int32_t*)take(4 * nc);
+  w->scores = (float*)take(4 * nc);
+  w->bytes = o;
+}
+
+size_t tlsan_topk_workspace_bytes(const tlsan_dims* d, int32_t B, int32_t K) {
+  Shape s;
+  if (shape_of(d, &s) != TLSAN_OK) return 0;
+  if (K < 1 || K > TOPK_MAX) { fail(TLSAN_E_BADARG, "top-K: K must be in 1..%d (got %d)", TOPK_MAX, K); return 0; }
+  if (B < 1) { fail(TLSAN_E_BADARG, "top-K: B must be >= 1 (got %d)", B); return 0; }
+  TopkWs w;
+  carve_topk(d, s.D, B, K, nullptr, &w);
+  return w.bytes;
+}
+
+int tlsan_eval_topk(const tlsan_dims* d, const tlsan_params* p, const float* u_t, int32_t B, int32_t K,
+                    const int32_t* excl_off, const int32_t* excl_ids, int32_t id_mul, int32_t id_add, int32_t* ids,
+                    float* scores, void* ws, size_t ws_bytes, void* stream) {
+  Shape s;
+  int rc = shape_of(d, &s);
+  if (rc) return rc;
+  if ((rc = check_params(p))) return rc;
+  if (!u_t || !ids || !scores || B < 1) return fail(TLSAN_E_BADARG, "tlsan_eval_topk: bad arguments");
+  if (K < 1 || K > TOPK_MAX) return fail(TLSAN_E_BADARG, "tlsan_eval_topk: K must be in 1..%d (got %d)", TOPK_MAX, K);
+  if (!excl_off != !excl_ids) return fail(TLSAN_E_BADARG, "tlsan_eval_topk: excl_off and excl_ids go together");
+  if (id_mul < 1 || id_add < 0 || (long long)(d->item_count - 1) * id_mul + id_add >= (1LL << 31))
+    return fail(TLSAN_E_BADARG, "tlsan_eval_topk: global ids n * id_mul + id_add must be non-negative int32");
+  if (!ws) return fail(TLSAN_E_WORKSPACE, "ws is NULL");
+  TopkWs w;
+  carve_topk(d, s.D, B, K, (char*)ws, &w);
+  if (w.bytes > ws_bytes) return fail(TLSAN_E_WORKSPACE, "workspace too small: need %zu have %zu", w.bytes, ws_bytes);
+  hipStream_t hs = (hipStream_t)stream;
+  TopkArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  EvalArgs& e = ta.e;
+  e.p = norm_params(p, d); e.u_t = u_t; e.B = B; e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate;
+  e.all_emb = w.all_emb; e.id_mul = id_mul; e.id_add = id_add;
+  ta.K = K; ta.excl_off = excl_off; ta.excl_ids = excl_ids;
+  ta.ids = w.nsl > 1 ? w.ids : ids;
+  ta.scores = w.nsl > 1 ? w.scores : scores;
+  if (e.all_emb) {
+    const int nae = (d->item_count * (s.D / 4) + 255) / 256;
+    if (s.D == 64) hipLaunchKernelGGL(k_all_emb<64>, dim3(nae), dim3(256), 0, hs, e);
+    else if (s.D == 128) hipLaunchKernelGGL(k_all_emb<128>, dim3(nae), dim3(256), 0, hs, e);
+    else hipLaunchKernelGGL(k_all_emb<256>, dim3(nae), dim3(256), 0, hs, e);
+    CHECK_LAUNCH("k_all_emb");
+  }
+  hipError_t err = tlsan_launch_topk(ta, s.D, w.nsl, hs);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_eval_topk: %s", hipGetErrorString(err));
+  if (w.nsl > 1 && (err = tlsan_launch_topk_merge(w.ids, w.scores, B, w.nsl, K, ids, scores, hs)) != hipSuccess)
+    return fail(TLSAN_E_LAUNCH, "k_topk_merge: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+int tlsan_topk_merge(const int32_t* cand_ids, const float* cand_scores, int32_t B, int32_t n_lists, int32_t K,
+                     int32_t* ids, float* scores, void* stream) {
+  if (!cand_ids || !cand_scores || !ids || !scores || B < 1 || n_lists < 1)
+    return fail(TLSAN_E_BADARG, "tlsan_topk_merge: bad arguments");
+  if (K < 1 || K > TOPK_MAX) return fail(TLSAN_E_BADARG, "tlsan_topk_merge: K must be in 1..%d (got %d)", TOPK_MAX, K);
+  if ((long long)n_lists * K >= (1LL << 30)) return fail(TLSAN_E_UNSUPPORTED, "tlsan_topk_merge: n_lists * K too large");
+  const hipError_t err = tlsan_launch_topk_merge(cand_ids, cand_scores, B, n_lists, K, ids, scores, (hipStream_t)stream);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_topk_merge: %s", hipGetErrorString(err));
   return TLSAN_OK;
 }
 

@@ -1325,12 +1325,7 @@ class ShardedModel:
                                                  self._ws.data_ptr(), self._ws.numel(), st), "tlsan_eval_label_scores")
         ut_all, s_all, lab_all = allgather_rows(ut, self.group), allgather_rows(s_lab, self.group), allgather_rows(db.i, self.group)
         Bt = int(ut_all.shape[0])
-        nloc = ModPartition(self.I, self.world).local_count(self.rank)
-        ldims = L.Dims(self.U, max(nloc, 1), self.C, self.d, self.di, self.dc, self.H, self.Ls)
-        base = self.shard.data_ptr()
-        lp = L.Params(base, base + 4 * self.di, base, base + 4 * self.di, self.cate_emb.data_ptr(), self.dense.data_ptr(),
-                      self.dense_KT.data_ptr(), self._icl_local.data_ptr(), self.W, self.W, self.W, self.W,
-                      self._P.data_ptr() if self.lazy else None)
+        nloc, ldims, lp = self._item_shard()
         nws = self.lib.tlsan_workspace_bytes(C.byref(ldims), Bt, 0)
         if self._ews is None or self._ews.numel() < nws:
             self._ews = torch.empty(int(nws * 1.25), dtype=torch.uint8, device=self.device)
@@ -1342,6 +1337,63 @@ class ShardedModel:
         if self.world > 1:
             allreduce_sum(counts, self.group)
         return counts[self.rank * B:(self.rank + 1) * B]
+
+    def _item_shard(self):
+        """This rank's items as a table of their own (local item n = global item n * world + rank): (local count,
+        dims, params) for the all-items scoring."""
+        nloc = ModPartition(self.I, self.world).local_count(self.rank)
+        ldims = L.Dims(self.U, max(nloc, 1), self.C, self.d, self.di, self.dc, self.H, self.Ls)
+        base = self.shard.data_ptr()
+        lp = L.Params(base, base + 4 * self.di, base, base + 4 * self.di, self.cate_emb.data_ptr(), self.dense.data_ptr(),
+                      self.dense_KT.data_ptr(), self._icl_local.data_ptr(), self.W, self.W, self.W, self.W,
+                      self._P.data_ptr() if self.lazy else None)
+        return nloc, ldims, lp
+
+    def recommend(self, batch, k, exclude=None):
+        """Model.recommend for this rank's rows (every rank calls it, with the same k and exclusion mode): u_t and
+        the exclusion lists are all-gathered, every rank selects the k best of ITS item shard for all rows
+        (tlsan_eval_topk, global ids n * world + rank), each row's lists go to the rank that owns the row (one
+        all-to-all) and are merged there (tlsan_topk_merge).  Same ids and scores as Model.recommend."""
+        from .model import eval_topk, exclusion_csr, topk_merge
+        db = self.device_batch(batch, is_test=True)
+        sl = self._plan_eval(db)
+        table = self._fetch(sl)
+        dims, cp, cb = self._compact(db, sl, table)
+        B, k, st = db.B, int(k), self._stream()
+        li = torch.empty(B, dtype=torch.float32, device=self.device)
+        ut = torch.empty(B, self.d, dtype=torch.float32, device=self.device)
+        L.check(self.lib.tlsan_forward(C.byref(dims), C.byref(cp), C.byref(cb), li.data_ptr(), None, ut.data_ptr(),
+                                       None, 0, st), "tlsan_forward")
+        off, xid = exclusion_csr(db, exclude, self.I)
+        ut_all = allgather_rows(ut, self.group)
+        Bt = int(ut_all.shape[0])
+        if off is not None and self.world > 1:
+            # every rank's rows: slots of one width (exclusion_csr), padded to the widest rank's with ignored ids
+            w = int(off[1].item())
+            width = int(allgather_rows(torch.tensor([w], device=self.device), self.group).max().item())
+            rows = torch.full((B, width), np.iinfo(np.int32).max, dtype=torch.int32, device=self.device)
+            rows[:, :w] = xid.view(B, w)
+            xid = allgather_rows(rows, self.group).view(-1)
+            off = torch.arange(0, (Bt + 1) * width, width, dtype=torch.int32, device=self.device)
+        nloc, ldims, lp = self._item_shard()
+        if nloc > 0:
+            def workspace(nbytes):
+                if getattr(self, "_tws", None) is None or self._tws.numel() < nbytes:
+                    self._tws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                return self._tws
+            cid, csc = eval_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), self.world, self.rank, workspace, st)
+        else:
+            cid = torch.full((Bt, k), -1, dtype=torch.int32, device=self.device)
+            csc = torch.full((Bt, k), float("-inf"), dtype=torch.float32, device=self.device)
+        if self.world > 1:
+            # rows [r B, (r + 1) B) belong to rank r: block s of what arrives is rank s's list of this rank's rows
+            rid, rsc = torch.empty_like(cid), torch.empty_like(csc)
+            a2a(rid, cid, None, None, self.group)
+            a2a(rsc, csc, None, None, self.group)
+            cid, csc = topk_merge(self.lib, rid.view(self.world, B, k).transpose(0, 1).contiguous(),
+                                  rsc.view(self.world, B, k).transpose(0, 1).contiguous(), st)
+        torch.cuda.current_stream(self.device).synchronize()   # `table` stays alive until done
+        return cid, csc
 
     def _hits(self, batch, n_valid=None):
         from .model import KS

@@ -139,6 +139,69 @@ def concurrent_streams(device, want=1, pool=6, **stream_kw):
     return chosen
 
 
+def exclusion_csr(db, exclude, n_items):
+    """Per-row item lists to keep out of a recommendation, as the CSR tlsan_eval_topk takes: (excl_off [B + 1],
+    excl_ids) int32 device tensors.  exclude: None -> (None, None); "history" -> the items the row's input holds,
+    hist_i[b, :sl[b]] and hist_i_new[b, :sl_new[b]] (the padding past the lengths is item 0, a real item, so the
+    lengths decide); or a sequence of B arrays of item ids.  Built on the device without a host round trip: every row
+    is a slot of the same width, sorted, its repeats and its unused slots set to INT32_MAX (ids outside the table are
+    ignored by the kernel, so they sort to the end of the row and cost nothing)."""
+    if exclude is None:
+        return None, None
+    B, dev, pad = db.B, db.i.device, np.iinfo(np.int32).max
+    if isinstance(exclude, str):
+        if exclude != "history":
+            raise ValueError("exclude must be None, 'history' or a sequence of per-row id arrays")
+        ar = torch.arange(db.hist_i.shape[1], device=dev)[None, :]
+        vals = [torch.where(ar < db.sl.long()[:, None], db.hist_i, pad)]
+        if db.Sn > 0:
+            ar = torch.arange(db.Sn, device=dev)[None, :]
+            vals.append(torch.where(ar < db.sl_new.long()[:, None], db.hist_i_new.reshape(B, db.Sn), pad))
+        vals = torch.cat(vals, 1).to(torch.int32)
+    else:
+        if len(exclude) != B:
+            raise ValueError("exclude: %d lists for %d rows" % (len(exclude), B))
+        lists = [np.asarray(x, np.int64).reshape(-1) for x in exclude]
+        host = np.full((B, max([len(x) for x in lists] + [1])), pad, np.int64)
+        for r, x in enumerate(lists):
+            host[r, :len(x)] = x
+        host[(host < 0) | (host >= n_items)] = pad
+        vals = torch.as_tensor(host.astype(np.int32)).to(dev)
+    vals = torch.sort(vals, 1).values
+    vals[:, 1:] = torch.where(vals[:, 1:] == vals[:, :-1], pad, vals[:, 1:])    # repeats
+    vals = torch.sort(vals, 1).values.contiguous()
+    off = torch.arange(0, (B + 1) * vals.shape[1], vals.shape[1], dtype=torch.int32, device=dev)
+    return off, vals.view(-1)
+
+
+def eval_topk(lib, dims, cparams, ut, B, k, excl, id_mul, id_add, workspace, stream):
+    """tlsan_eval_topk on u_t [B, d] -> (ids [B, k] int32, scores [B, k] float32) device tensors.
+    workspace(nbytes) returns a uint8 device tensor of at least nbytes."""
+    k = int(k)
+    nws = lib.tlsan_topk_workspace_bytes(C.byref(dims), B, k)
+    if nws == 0:
+        raise L.TlsanError("tlsan_topk_workspace_bytes: %s" % lib.tlsan_last_error().decode())
+    ws = workspace(nws)
+    ids = torch.empty(B, k, dtype=torch.int32, device=ut.device)
+    scores = torch.empty(B, k, dtype=torch.float32, device=ut.device)
+    off, xid = excl
+    L.check(lib.tlsan_eval_topk(C.byref(dims), C.byref(cparams), ut.data_ptr(), B, k,
+                                None if off is None else off.data_ptr(), None if xid is None else xid.data_ptr(),
+                                id_mul, id_add, ids.data_ptr(), scores.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+            "tlsan_eval_topk")
+    return ids, scores
+
+
+def topk_merge(lib, cand_ids, cand_scores, stream):
+    """tlsan_topk_merge: [B, n_lists, k] sorted lists of disjoint items -> (ids [B, k], scores [B, k])."""
+    B, n, k = cand_ids.shape
+    ids = torch.empty(B, k, dtype=torch.int32, device=cand_ids.device)
+    scores = torch.empty(B, k, dtype=torch.float32, device=cand_ids.device)
+    L.check(lib.tlsan_topk_merge(cand_ids.contiguous().data_ptr(), cand_scores.contiguous().data_ptr(), B, n, k,
+                                 ids.data_ptr(), scores.data_ptr(), stream), "tlsan_topk_merge")
+    return ids, scores
+
+
 class DeviceBatch:
     """The placeholders of model.py:27-53 as int32 / fp32 device tensors + the C struct."""
 
@@ -745,6 +808,22 @@ class Model(object):
                                           db.B, ranks.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
                 "tlsan_eval_ranks")
         return ranks
+
+    def recommend(self, batch, k, exclude=None):
+        """The k best items over ALL items for each row -- what tf.nn.top_k(eval_logits, k) gives the reference
+        (model.py:140) -- without materialising the [B, I] scores.  Takes label_ranks' batches (the label and the
+        negative are not used).  -> (ids [B, k] int32, scores [B, k] float32) device tensors, in tf.nn.top_k's
+        order (higher score first, ties -> lower id); rows with fewer than k eligible items end in -1 / -inf.
+        exclude: None; "history" -- the items the row's input holds (the last Ls items and the current session);
+        or a sequence of B arrays of item ids.  Scores equal label_ranks' / eval_label_scores' bit for bit."""
+        _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
+        return eval_topk(self.lib, self.dims, self.cparams, ut, db.B, k, exclusion_csr(db, exclude, self.config["item_count"]),
+                         1, 0, self._topk_workspace, self._stream())
+
+    def _topk_workspace(self, nbytes):
+        if getattr(self, "_tws", None) is None or self._tws.numel() < nbytes:
+            self._tws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._tws
 
     def _hits(self, batch, ranks=None):
         r = self.label_ranks(batch).cpu().numpy() if ranks is None else np.asarray(ranks)

@@ -67,7 +67,23 @@ def parse(argv=None):
     ap.add_argument("--device_input", type=int, default=1,
                     help="1: keep the sample sets in HBM and assemble batches on the device (tlsan_amd.device_input); "
                          "0: the host batcher (tlsan_amd.input), one upload per batch")
+    ap.add_argument("--recommend_k", type=int, default=0,
+                    help="at the end of training, write <model_dir>/recommend_top<K>.npz: the K best items over all items "
+                         "for every test row (arrays user, ids, scores); 0 = off")
+    ap.add_argument("--recommend_exclude", default="history", choices=["history", "none"],
+                    help="items kept out of the recommendations: 'history' = the items the test row's input holds (its "
+                         "last Ls items and its current session -- what the batch carries), 'none' = nothing")
     return ap.parse_args(argv)
+
+
+def recommend_path(model_dir, k):
+    return os.path.join(model_dir, "recommend_top%d.npz" % k)
+
+
+def write_recommendations(model_dir, k, user, ids, scores):
+    path = recommend_path(model_dir, k)
+    np.savez(path, user=np.asarray(user, np.int64), ids=np.asarray(ids, np.int32), scores=np.asarray(scores, np.float32))
+    return path
 
 
 def load_dataset(path):
@@ -169,6 +185,20 @@ def eval_prec_recall(model, test_set, config):
     return prec, recall
 
 
+def recommend_test_set(model, test_set, config, k, exclude):
+    """Model.recommend over every test row, in launches of EVAL_CHUNK rows -> (user, ids, scores) host arrays."""
+    import torch
+    chunk = max(EVAL_CHUNK, config["test_batch_size"]) // config["test_batch_size"] * config["test_batch_size"]
+    users, ids, scores = [], [], []
+    for _, batch in _test_batches(test_set, config, chunk):
+        db = model.device_batch(batch, is_test=True)
+        i, s = model.recommend(db, k, exclude=None if exclude == "none" else exclude)
+        users.append(db.u)
+        ids.append(i)
+        scores.append(s)
+    return tuple(torch.cat(x).cpu().numpy() for x in (users, ids, scores))
+
+
 def train(args, data=None):
     """data (optional): (train PackedSet, test PackedSet, (U, I, C), item_cate_list) already in memory
     (tlsan_amd.build_dataset.build_packed) instead of --dataset."""
@@ -245,6 +275,10 @@ def train(args, data=None):
     final_auc = eval_auc(model, test_set, config)
     best_auc = max(best_auc, final_auc)
     model.save(None)                                           # train.py:239
+    if args.recommend_k:
+        path = write_recommendations(args.model_dir, args.recommend_k,
+                                     *recommend_test_set(model, test_set, config, args.recommend_k, args.recommend_exclude))
+        say("Recommendations: %s" % path)
     model.train_writer.flush()
     model.eval_writer.flush()
     say("Best test_auc:", best_auc)
@@ -412,6 +446,23 @@ def train_sharded(args):
     final_auc = eval_auc_()
     best_auc = max(best_auc, final_auc)
     model.save(None)
+    if args.recommend_k:
+        # every rank takes its share of each test batch; rank 0 gathers the shares (in rank order: the batch's order)
+        from .dist import allgather_rows
+        k, parts = args.recommend_k, []
+        for _, batch in DataInputTest(test_set, config["test_batch_size"], config["Ls"]):
+            part, real = _equal_share(batch, rank, world)
+            ids, scores = model.recommend(part, k, exclude=None if args.recommend_exclude == "none" else "history")
+            user = torch.as_tensor(np.asarray(part[0]), dtype=torch.int64, device=dev)
+            got = [allgather_rows(t, model.group) for t in (user, ids, scores)]
+            n_real = allgather_rows(torch.tensor([real], dtype=torch.int64, device=dev), model.group).cpu().tolist()
+            if rank == 0:
+                w = len(part[0])
+                parts.append([np.concatenate([g.cpu().numpy()[r * w:r * w + n_real[r]] for r in range(world)])
+                              for g in got])
+        if rank == 0:
+            path = write_recommendations(args.model_dir, k, *(np.concatenate(x) for x in zip(*parts)))
+            say("Recommendations: %s" % path)
     model.train_writer.flush()
     model.eval_writer.flush()
     say("Best test_auc:", best_auc)
