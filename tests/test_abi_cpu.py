@@ -74,3 +74,22 @@ def test_model_needs_gpu():
     cfg = make_config()
     with pytest.raises(RuntimeError):
         Model(cfg, np.zeros(cfg["item_count"], np.int32))
+
+
+def test_environment_switches_are_listed():
+    """INTEGRATION.md's table of environment switches names exactly the TLSAN_* variables the library and the package read."""
+    read = set()
+    csrc = os.path.join(ROOT, "tlsan_amd", "csrc")
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".h")):
+            read |= set(re.findall(r'getenv\("(TLSAN_\w+)"', open(os.path.join(csrc, f)).read()))
+    pkg = os.path.join(ROOT, "tlsan_amd")
+    for f in os.listdir(pkg):
+        if f.endswith(".py"):
+            read |= set(re.findall(r'os\.environ(?:\.get\(|\[)\s*"(TLSAN_\w+)"', open(os.path.join(pkg, f)).read()))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    rows = doc[doc.index("| switch | read by | what |"):].split("\n\n")[0].splitlines()[2:]
+    listed = set()
+    for row in rows:
+        listed |= set(re.findall(r"\b(TLSAN_\w+?)(?:=|`)", row.split("|")[1]))
+    assert read == listed, (sorted(read - listed), sorted(listed - read))

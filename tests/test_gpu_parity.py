@@ -1314,7 +1314,7 @@ def test_shared_categories_in_the_one_pass_form(d, Ls, C, clip):
 
 def test_shared_categories_one_pass_equals_the_split_form():
     """Unclipped steps of the form above leave the SAME BITS as the split form (row sums beside the finalize, then
-    k_update_lazy; TLSAN_LAZY_CSPL=0, read once per process): four steps announced two ahead on four table shapes, fp32 and
+    k_update_lazy; TLSAN_LAZY_ONE_PASS=0, read once per process): four steps announced two ahead on four table shapes, fp32 and
     bf16 tables (TLSAN_LAZY_ONE_PASS=3 sends cache-resident bf16 tables through the one-pass form too), losses and every
     parameter -- and as the same form with fewer workgroups per category (TLSAN_CSPLIT_FINE=0)."""
     import subprocess, sys
@@ -1323,8 +1323,8 @@ def test_shared_categories_one_pass_equals_the_split_form():
     # (third run: round 5's rule for how many workgroups share a category -- 27 instead of 64 here; the sums are exact, so
     #  the number of workgroups that share a category must not change a bit either)
     # (fourth run: the sharers deal a category's uses out by item instead of by position)
-    for cspl, fine, pos in (("1", "1", "1"), ("0", "1", "1"), ("1", "0", "1"), ("1", "1", "0")):
-        env = dict(os.environ, TLSAN_LAZY_ONE_PASS="3", TLSAN_LAZY_CSPL=cspl, TLSAN_CSPLIT_FINE=fine, TLSAN_CSPLIT_POS=pos)
+    for one_pass, fine, pos in (("3", "1", "1"), ("0", "1", "1"), ("3", "0", "1"), ("3", "1", "0")):
+        env = dict(os.environ, TLSAN_LAZY_ONE_PASS=one_pass, TLSAN_CSPLIT_FINE=fine, TLSAN_CSPLIT_POS=pos)
         r = subprocess.run([sys.executable, "-c", _CSPL_DIGEST % root], cwd=root, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
         digests.append([l for l in r.stdout.splitlines() if l.startswith("DIGEST")][-1])
@@ -1337,8 +1337,8 @@ def test_speculative_one_pass_lazy_update():
     after a clipped step only -- corrects the rows (k_finalize_update / k_spec_commit, tlsan_update.h).
     TLSAN_LAZY_ONE_PASS=2 with TLSAN_CSEG_MIN=1 (both read once per process) sends every table that way: the oracle tests of
     lazy train steps must hold -- clip inactive AND active (test_lazy_l2_matches_dense_oracle[0.02]: the correcting pass),
-    bf16 tables, hipGraph replay, a diverged step -- and unclipped steps must leave the SAME BITS as the one-pass form that
-    waits for the finalize (TLSAN_LAZY_SPEC=0)."""
+    bf16 tables, hipGraph replay, a diverged step -- and unclipped steps must leave the SAME BITS as the split form (row sums
+    beside the finalize, then k_update_lazy; TLSAN_LAZY_ONE_PASS=0)."""
     import re, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sel = ("test_lazy_l2_matches_dense_oracle or test_lazy_is_deterministic or test_category_segments_match_oracle "
@@ -1365,8 +1365,8 @@ def test_speculative_one_pass_lazy_update():
     mt = re.search(r"(\d+) passed", r.stdout)
     assert mt and int(mt.group(1)) >= 25, r.stdout[-2000:]
     digests = []
-    for spec in ("1", "0"):
-        env = dict(os.environ, TLSAN_LAZY_ONE_PASS="2", TLSAN_CSEG_MIN="1", TLSAN_LAZY_SPEC=spec)
+    for one_pass in ("2", "0"):
+        env = dict(os.environ, TLSAN_LAZY_ONE_PASS=one_pass, TLSAN_CSEG_MIN="1")
         r = subprocess.run([sys.executable, "-c", _ISORT_DIGEST % root], cwd=root, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
         digests.append([l for l in r.stdout.splitlines() if l.startswith("DIGEST")][-1])

@@ -427,7 +427,7 @@ static void fill_apply(ApplyArgs& A, const tlsan_dims* d, const Shape& s, const 
   A.cseg = (b && cate_seg(d, b)) ? 1 : 0;
   A.Rc64 = st.Rc64;
   A.csplit = 1; A.cpass = 256; A.cpos = 0;
-  A.hot_n = st.hdr ? &st.hdr->n_hot[k] : nullptr; A.hot_list = st.hot_list[k]; A.nbH = 0;
+  A.hot_n = st.hdr ? &st.hdr->n_hot[k] : nullptr; A.hot_list = st.hot_list[k];
   A.gd = w.gd;
   A.Rc = w.Rc; A.Ri = w.Ri; A.Rb = w.Rb; A.Ru = w.Ru;
   A.part_out = st.S_part; A.delta_out = st.S_delta; A.hdr = st.hdr;
@@ -471,11 +471,9 @@ static void category_split(ApplyArgs& A, const tlsan_dims* d, const tlsan_batch*
   //  bound by slots pays for it 1:1 -- 673 categories of 620 uses (Ls = 90) as four shares each: 2 692 workgroups of 8.8 us,
   //  24 of the launch's 32 k slot-us; unshared: d = 256 239 -> 224 us/step, d = 128 103.5 -> 97.4.  Movies-TV's 15
   //  categories run best as ~46 shares each at Ls = 10 AND at Ls = 90 (64: 97.7, 46: 94.4, 30: 94.9, 11: 104), i.e. ~700
-  //  category workgroups beside the rows' on 1 280 slots.  TLSAN_CSPLIT_PER / TLSAN_CSPLIT_BUDGET for A/B.)
-  static const int per_share = [] { const char* e = getenv("TLSAN_CSPLIT_PER"); return e && atoi(e) > 0 ? atoi(e) : 128; }();
-  static const int budget = [] { const char* e = getenv("TLSAN_CSPLIT_BUDGET"); return e && atoi(e) > 0 ? atoi(e) : 700; }();
-  long n = uses > 512 ? (uses / per_share < 64 ? uses / per_share : 64) : 1;
-  if (n > budget / d->cate_count) n = budget / d->cate_count;
+  //  category workgroups beside the rows' on 1 280 slots.)
+  long n = uses > 512 ? (uses / 128 < 64 ? uses / 128 : 64) : 1;
+  if (n > 700 / d->cate_count) n = 700 / d->cate_count;
   if (n < 1) n = 1;
   if (fine && uses > 96) {
     // the launch's other workgroups: the finalize's and the hot rows' (~206), 16 used item / user rows each (lazy_blocks)
@@ -498,6 +496,26 @@ static void category_split(ApplyArgs& A, const tlsan_dims* d, const tlsan_batch*
   }
 }
 
+// The training step's tail: the launches after the fused forward / backward kernel (run_backward), planned ONCE per step by
+// plan_tail and issued by launch_tail.  The finalize launch and the second launch take the same ApplyArgs (TailPlan::fin.A):
+// k_finalize_update writes per-workgroup S_delta records and hdr->spart_n laid out by nbH, nbC, nbI and nbU, and
+// k_spec_commit walks its blocks by the same four counts.
+enum TailForm {
+  TAIL_APPLY,        // k_dense_finalize, then k_apply over every row (dense L2, tlsan_grads with full gradients)
+  TAIL_SPLIT,        // row sums beside the finalize (k_finalize_presum), then k_update_lazy (sparse tlsan_grads: k_rc64_to_float)
+  TAIL_SPEC,         // the speculative one pass: k_finalize_update, then k_spec_commit
+  TAIL_SPEC_SHARED,  // the same, the shared categories summed beside it and updated by the commit (k_*<.., CSPL>)
+};
+struct TailPlan {
+  TailForm form;
+  bool update;         // a train step (not tlsan_grads)
+  bool sparse_index;   // the tail walks the index's used-row records (build_index)
+  FinLaunch fin;       // the finalize launch; run_backward fills the front half's fields of fin.f
+  dim3 grid;           // the second launch's (TAIL_APPLY: launch_apply's own)
+  bool wide;           // TAIL_SPLIT / TAIL_SPEC*: the second launch's wide row form
+  int nbC16;           // TAIL_SPLIT update: k_update_lazy's blocks of 16 category rows
+};
+
 // The lazy update as ONE pass over the used rows (round 6; k_finalize_update / k_spec_commit, tlsan_update.h).  The split
 // form (row sums in the finalize's launch, then k_update_lazy) sends every summed row through memory -- written by one
 // launch, read by the next beside the parameter row's read-modify-write -- and ends in a launch of its own; in the one-pass
@@ -505,73 +523,126 @@ static void category_split(ApplyArgs& A, const tlsan_dims* d, const tlsan_batch*
 static bool tables_in_hbm(const tlsan_dims* d) {      // (well beyond the 256 MiB Infinity Cache)
   return 4.0 * ((double)d->item_count * d->d_item + (double)d->user_count * (d->d_item + d->Ls)) > 512e6;
 }
-// Where the one-pass form was measured to win (profiles/r06_lazy_one_pass.md): rows of up to 64 floats per table half
-// (d <= 128) at any table size -- bench shape 56.9 -> 55.4 us/step, 8192 sequences 106.5 -> 103.6, Amazon session lengths
-// 59.9 -> 57.8, 10 M / 5 M tables 97 -> 80 --; wider rows (d = 256) only where the tables live in HBM (C5 300 -> 267; with
-// cache-resident tables it loses 2.5 us to the split form).  TLSAN_LAZY_ONE_PASS: 0 never, 1 (default) as described,
-// 2 whenever the tables take category segments, 3 wherever the form is built.
-// Returns 0 (the split form), 1 (one pass), or 2: one pass over the item and user rows while the category rows -- few, large
-// categories (Movies-TV: 15) that several row-sum workgroups share, adding exact doubles with atomics (category_split) -- are
-// summed beside them and updated by the commit launch (k_finalize_update / k_spec_commit<.., CSPL>; TLSAN_LAZY_CSPL=0: off).
-static int lazy_one_pass(const tlsan_dims* d, const tlsan_batch* b, const ApplyArgs& A) {
-  static const int mode = [] { const char* e = getenv("TLSAN_LAZY_ONE_PASS"); return e ? atoi(e) : 1; }();
-  static const int cspl = [] { const char* e = getenv("TLSAN_LAZY_CSPL"); return e ? atoi(e) : 1; }();
-  if (mode == 0) return 0;
-  ApplyArgs T = A;
-  category_split(T, d, b);
-  if (T.csplit > 1) {
-    if (!cspl || mode == 2 || A.di > 64 || A.dc > 64 || A.WU > 256) return 0;   // (built in the narrow form: d <= 128)
-    if (mode == 1 && A.p.table_dtype == TLSAN_TABLE_BF16 && !tables_in_hbm(d)) return 0;   // (as below)
-    return 2;
+
+// A: fill_apply's (+ tlsan_grads' outputs, the optimizer's slots).  update: a train step; otherwise tlsan_grads.
+static int plan_tail(const tlsan_dims* d, const Shape& s, const tlsan_batch* b, const tlsan_hparams* hp, const Ws& w,
+                     const ApplyArgs& A0, bool update, TailPlan* P) {
+  ApplyArgs A = A0;
+  *P = TailPlan{};
+  FinLaunch& fl = P->fin;
+  FinArgs& f = fl.f;
+  f.gd = w.gd; f.count_step = update ? 1 : 0;
+  fl.nbK = w.nbK; fl.nbS = w.nbS;
+  P->update = update;
+  const bool lazy = update && hp->l2_mode == TLSAN_L2_LAZY;
+  // tlsan_grads' pure per-row sums of the used rows (what the sharded step asks for): they ride with the dense finalize as in
+  // the lazy train step, written straight to the output rows -- no apply launch (sparse == 2: the four outputs are views of
+  // ONE fused row table, see tlsan_grads_out)
+  const bool sparse_grads = !update && A.go.sparse && hp->reg == 0.0f && hp->norm_mode == TLSAN_NORM_TF18;
+  P->sparse_index = lazy || sparse_grads;
+  if (!P->sparse_index) {
+    P->form = TAIL_APPLY;
+    fl.kind = FinLaunch::DENSE; fl.grid = dim3(w.nfin + 1); fl.A = A;
+    return TLSAN_OK;
   }
-  if (apply_wide(A) && !A.cseg) return 0;      // (the wide form is built for category segments only)
-  if (mode >= 2) return mode == 2 ? A.cseg != 0 : 1;
-  // bf16 tables: a clipped step rounds twice in this form -- the speculative write at the magnitude of w - lr g, the
+  if (sparse_grads) { A.presum_rows = A.go.sparse == 2 ? 2 : 1; A.Rc = A.go.cate_emb; f.gd = A.go.dense; }
+  category_split(A, d, b);
+  lazy_blocks(A, b->B, b->Sn);
+  A.nbH = AP_HOT_CAP;   // hot item rows: a workgroup each, leading the row workgroups (they return at once where there are none)
+  const bool bf16 = A.p.table_dtype == TLSAN_TABLE_BF16;
+  // Where the one-pass form was measured to win (profiles/r06_lazy_one_pass.md): rows of up to 64 floats per table half
+  // (d <= 128) at any table size -- bench shape 56.9 -> 55.4 us/step, 8192 sequences 106.5 -> 103.6, Amazon session lengths
+  // 59.9 -> 57.8, 10 M / 5 M tables 97 -> 80 --; wider rows (d = 256) only where the tables live in HBM (C5 300 -> 267; with
+  // cache-resident tables it loses 2.5 us to the split form).  TLSAN_LAZY_ONE_PASS: 0 never, 1 (default) as described,
+  // 2 whenever the tables take category segments, 3 wherever the form is built.
+  // TAIL_SPEC_SHARED: one pass over the item and user rows while the category rows -- few, large categories (Movies-TV: 15)
+  // that several row-sum workgroups share, adding exact doubles with atomics (category_split) -- are summed beside them and
+  // updated by the commit launch (k_finalize_update / k_spec_commit<.., CSPL>).
+  static const int mode = [] { const char* e = getenv("TLSAN_LAZY_ONE_PASS"); return e ? atoi(e) : 1; }();
+  // bf16 tables: a clipped step rounds twice in the one-pass form -- the speculative write at the magnitude of w - lr g, the
   // correction at that of the result -- so its stored elements can be off by one ulp of the SPECULATIVE value (unbiased,
   // and only in clipped steps; fp32 tables: 2^-24 of it, far inside every bound).  Taken where it pays for that (tables in
   // HBM: C5 in bf16 227 -> 202 us/step); with cache-resident bf16 tables (0.4-1.0 us) the split form and its
   // one-rounding guarantee stay.
-  if (A.p.table_dtype == TLSAN_TABLE_BF16 && !tables_in_hbm(d)) return 0;
-  if (!apply_wide(A)) return 1;
-  return A.cseg && tables_in_hbm(d) ? 1 : 0;
-}
-
-// second half of the split lazy update (the first half rides with the dense finalize, run_backward)
-static int launch_update_lazy(ApplyArgs A, int B, int Sn, hipStream_t hs) {
-  lazy_blocks(A, B, Sn);
-  const int nbC16 = (A.C + 15) / 16;
-  const dim3 g1(nbC16 + A.nbI + A.nbU + A.nbD), blk(256);
-  const bool wide = apply_wide(A);
-  if (A.p.table_dtype == TLSAN_TABLE_BF16) {
-    if (wide) hipLaunchKernelGGL((k_update_lazy<true, TLSAN_TABLE_BF16>), g1, blk, 0, hs, A, nbC16);
-    else hipLaunchKernelGGL((k_update_lazy<false, TLSAN_TABLE_BF16>), g1, blk, 0, hs, A, nbC16);
-  } else {
-    if (wide) hipLaunchKernelGGL((k_update_lazy<true, TLSAN_TABLE_F32>), g1, blk, 0, hs, A, nbC16);
-    else hipLaunchKernelGGL((k_update_lazy<false, TLSAN_TABLE_F32>), g1, blk, 0, hs, A, nbC16);
+  const bool cache_bf16 = bf16 && !tables_in_hbm(d);
+  TailForm form = TAIL_SPLIT;
+  if (lazy && mode != 0) {
+    if (A.csplit > 1) {   // (built in the narrow form: d <= 128)
+      if (mode != 2 && A.di <= 64 && A.dc <= 64 && A.WU <= 256 && !(mode == 1 && cache_bf16)) form = TAIL_SPEC_SHARED;
+    } else if (A.cseg || !apply_wide(A)) {   // (the wide form is built for category segments only)
+      if (mode >= 2) form = (mode != 2 || A.cseg) ? TAIL_SPEC : TAIL_SPLIT;
+      else if (!cache_bf16 && (!apply_wide(A) || tables_in_hbm(d))) form = TAIL_SPEC;
+    }
   }
-  CHECK_LAUNCH("k_update_lazy");
+  P->form = form;
+
+  if (form == TAIL_SPLIT) {
+    // the exact row sums of the apply pass share the finalize's launch (they wait for nothing it produces)
+    A.nbC = A.cseg ? (A.C + AP_ROWS_PB - 1) / AP_ROWS_PB : A.C * A.csplit;
+    fl.kind = FinLaunch::PRESUM;
+    fl.grid = dim3(w.nfin + 1 + A.nbH + A.nbC + A.nbI + A.nbU);
+    // (the row-sum launch covers user rows of up to 256 floats in two passes of its narrow form -- 92 registers, five
+    //  workgroups per CU, instead of 135 and three; the sharded step's fused rows keep the wide form.  d = 128 with 90-entry
+    //  windows: Movies-TV shape 106.6 -> 104.3 us/step, with 673 categories 116.2 -> 106.2: profiles/r04_presum_narrow_ab.md)
+    fl.wide = A.di > 64 || A.dc > 64 || (A.WU > 128 && A.presum_rows != 0);
+    fl.csplit = A.csplit > 1;
+    f.commit = lazy ? 1 : 0;
+    if (lazy) {   // k_update_lazy: ceil(C / 16) blocks of category rows, the used item / user rows, the dense parameters
+      P->nbC16 = (A.C + 15) / 16;
+      P->grid = dim3(P->nbC16 + A.nbI + A.nbU + A.nbD);
+      P->wide = apply_wide(A);
+    } else {      // k_rc64_to_float (split categories only)
+      P->grid = dim3((A.C * A.dc + 255) / 256);
+    }
+  } else {
+    // the row workgroups UPDATE beside the finalize, with clip coefficient 1 (k_finalize_update); the commit and -- after a
+    // clipped step -- the correction follow in k_spec_commit
+    const bool shared = form == TAIL_SPEC_SHARED;
+    if (shared && s.D > 128) return fail(TLSAN_E_UNSUPPORTED, "shared categories in the one-pass update: d <= 128");
+    // (shared: A.nbC = the commit launch's blocks of 16 category rows; the finalize's launch carries C * csplit)
+    if (shared) A.nbC = (A.C + 15) / 16;
+    // (item-row workgroups launched: at most SPEC_ITEM_BLOCKS -- ApplyArgs.nbI_l; TLSAN_SPEC_ITEM_BLOCKS=<n>, 0: all.  The
+    //  shared-category form keeps SPEC_ITEM_BLOCKS -- Movies-TV's 1787 blocks stay below it; fewer, 1024 / 640 / 384,
+    //  measured a loss there: profiles/r06_ab_hot_cate.txt)
+    static const int item_cap = [] { const char* e = getenv("TLSAN_SPEC_ITEM_BLOCKS"); return e ? atoi(e) : SPEC_ITEM_BLOCKS; }();
+    const int cap = shared ? SPEC_ITEM_BLOCKS : item_cap;
+    A.nbI_l = (cap > 0 && A.nbI > cap) ? cap : 0;
+    // user-row workgroups ahead of the item rows in the wide form (profiles/r06_ab_c5_tail.txt).  Shared categories:
+    // k_finalize_update<.., CSPL> orders them itself, by a.WU > 128, and does not read ufirst.
+    A.ufirst = (apply_wide(A) && !shared) ? 1 : 0;
+    fl.kind = FinLaunch::UPDATE;
+    fl.grid = dim3(w.nfin + 1 + A.nbH + (shared ? A.C * A.csplit : A.nbC) + (A.nbI_l > 0 ? A.nbI_l : A.nbI) + A.nbU);
+    fl.shared = shared; fl.bf16 = bf16; fl.wide = apply_wide(A) && !shared;
+    fl.low = tables_in_hbm(d);   // (the low-occupancy form: see SPEC_WPE, tlsan_update.h)
+    f.count_step = 0; f.spec = 1;
+    // k_spec_commit: the dense parameters, (shared: the category-row blocks,) then at most SPEC_FIX_BLOCKS correcting workgroups
+    const int nrow = A.nbH + (shared ? 0 : A.nbC) + A.nbI + A.nbU;
+    P->grid = dim3(A.nbD + (shared ? A.nbC : 0) + (nrow < SPEC_FIX_BLOCKS ? nrow : SPEC_FIX_BLOCKS));
+    P->wide = fl.wide;
+  }
+  fl.A = A;
   return TLSAN_OK;
 }
 
-static int launch_apply(int mode, ApplyArgs A, bool with_dense, hipStream_t hs, bool lazy = false) {
+static int launch_apply(int mode, ApplyArgs A, bool with_dense, hipStream_t hs) {
   const dim3 g1(A.nbC + A.nbI + A.nbU + (with_dense ? A.nbD : 0)), blk(256);
   const bool wide = apply_wide(A);
   const bool bf16 = A.p.table_dtype == TLSAN_TABLE_BF16;
-#define AP_LAUNCH(M, LZ)                                                                                     \
+#define AP_LAUNCH(M)                                                                                         \
   do {                                                                                                       \
     if (bf16) {                                                                                              \
-      if (wide) hipLaunchKernelGGL((k_apply<M, LZ, true, TLSAN_TABLE_BF16>), g1, blk, 0, hs, A);             \
-      else hipLaunchKernelGGL((k_apply<M, LZ, false, TLSAN_TABLE_BF16>), g1, blk, 0, hs, A);                 \
+      if (wide) hipLaunchKernelGGL((k_apply<M, true, TLSAN_TABLE_BF16>), g1, blk, 0, hs, A);                 \
+      else hipLaunchKernelGGL((k_apply<M, false, TLSAN_TABLE_BF16>), g1, blk, 0, hs, A);                     \
     } else {                                                                                                 \
-      if (wide) hipLaunchKernelGGL((k_apply<M, LZ, true>), g1, blk, 0, hs, A);                               \
-      else hipLaunchKernelGGL((k_apply<M, LZ, false>), g1, blk, 0, hs, A);                                   \
+      if (wide) hipLaunchKernelGGL((k_apply<M, true>), g1, blk, 0, hs, A);                                   \
+      else hipLaunchKernelGGL((k_apply<M, false>), g1, blk, 0, hs, A);                                       \
     }                                                                                                        \
   } while (0)
   switch (mode) {
-    case AP_UPDATE: if (lazy) AP_LAUNCH(AP_UPDATE, true); else AP_LAUNCH(AP_UPDATE, false); break;
-    case AP_GRADS: AP_LAUNCH(AP_GRADS, false); break;
-    case AP_SUMSQ: AP_LAUNCH(AP_SUMSQ, false); break;
-    default: AP_LAUNCH(AP_ROWNORM, false); break;
+    case AP_UPDATE: AP_LAUNCH(AP_UPDATE); break;
+    case AP_GRADS: AP_LAUNCH(AP_GRADS); break;
+    case AP_SUMSQ: AP_LAUNCH(AP_SUMSQ); break;
+    default: AP_LAUNCH(AP_ROWNORM); break;
   }
 #undef AP_LAUNCH
   CHECK_LAUNCH("k_apply");
@@ -901,16 +972,14 @@ static int build_index(const tlsan_dims* d, const tlsan_batch* b, const int32_t*
   return TLSAN_OK;
 }
 
-// shared front half of train_step / grads: index build, fused fwd+bwd, dense-grad reduction
+// shared front half of train_step / grads: index build, fused fwd+bwd, dK partials; fills f but for plan_tail's fields
 static int run_backward(const tlsan_dims* d, const Shape& s, const tlsan_params* p, const tlsan_batch* b,
-                        const tlsan_hparams* hp, bool update, const tlsan_step_out* out, const Ws& w, const St& st,
-                        const tlsan_dense_layout& L, hipStream_t hs, const ApplyArgs* presum = nullptr,
-                        float* gd_out = nullptr, bool sparse_index = false, bool spec = false) {
-  const bool commit = update && hp->l2_mode == TLSAN_L2_LAZY && !spec;
+                        const tlsan_hparams* hp, const tlsan_step_out* out, const Ws& w, const St& st,
+                        const tlsan_dense_layout& L, hipStream_t hs, bool sparse_index, FinArgs* f) {
   const int k = hp->index_slot;
   int rc;
   prof_mark(0, hs);
-  if (!hp->index_prebuilt && (rc = build_index(d, b, p->item_cate, st, k, hs, presum != nullptr || sparse_index))) return rc;
+  if (!hp->index_prebuilt && (rc = build_index(d, b, p->item_cate, st, k, hs, sparse_index))) return rc;
   // --- fused forward + backward
   FwdArgs a;
   fill_fwd(a, d, s, p, b, w, L);
@@ -955,73 +1024,14 @@ static int run_backward(const tlsan_dims* d, const Shape& s, const tlsan_params*
   }
   CHECK_LAUNCH("k_dk_partial");
   prof_mark(3, hs);
-  FinArgs f;
-  memset(&f, 0, sizeof(f));
-  f.lay = L; f.partials = w.partials; f.nrec = (b->B + grp - 1) / grp; f.Kp = w.Kp; f.nsplit = nsplit;
-  f.gd = gd_out ? gd_out : w.gd; f.sqd = w.sqd; f.scal = w.scal;
-  f.S_delta = st.S_delta; f.n_spart = st.nbI + st.nbU + st.nbC + AP_HOT_CAP; f.S_total = st.S_total;
-  f.hdr = st.hdr; f.lr = hp->lr; f.reg = hp->reg; f.clip = hp->clip; f.inv_B = 1.0f / (float)b->B;
-  f.norm_mode = hp->norm_mode; f.commit = commit ? 1 : 0; f.count_step = update ? 1 : 0;
-  f.out_loss = out ? out->loss : nullptr;
-  f.out_gnorm = out ? out->gnorm : nullptr;
-  f.out_sq = out ? out->sq_rows : nullptr;
-  if (presum && spec) {
-    // the one-pass form: the row workgroups UPDATE beside the finalize, with clip coefficient 1 (k_finalize_update; the commit
-    // and -- after a clipped step -- the correction follow in k_spec_commit, tlsan_train_step_opt)
-    ApplyArgs A = *presum;
-    lazy_blocks(A, b->B, b->Sn);
-    A.nbH = AP_HOT_CAP;      // hot item rows: a workgroup each, leading the row workgroups (they return at once where there are none)
-    f.count_step = 0; f.spec = 1;
-    const bool shared = A.csplit > 1;   // (lazy_one_pass form 2: A.nbC = the commit launch's category blocks; this launch carries C * csplit)
-    // (item-row workgroups launched: at most SPEC_ITEM_BLOCKS -- ApplyArgs.nbI_l; TLSAN_SPEC_ITEM_BLOCKS=<n>, 0: all, for A/B)
-    static const int item_cap = [] { const char* e = getenv("TLSAN_SPEC_ITEM_BLOCKS"); return e ? atoi(e) : SPEC_ITEM_BLOCKS; }();
-    // (the shared-category form: the same cap -- Movies-TV's 1787 blocks stay below it; fewer, 1024 / 640 / 384, measured a
-    //  loss there: profiles/r06_ab_hot_cate.txt; TLSAN_SPEC_ITEM_BLOCKS_SHARED=<n> for A/B)
-    static const int item_cap_sh = [] { const char* e = getenv("TLSAN_SPEC_ITEM_BLOCKS_SHARED"); return e ? atoi(e) : SPEC_ITEM_BLOCKS; }();
-    const int cap_here = shared ? item_cap_sh : item_cap;
-    A.nbI_l = (cap_here > 0 && A.nbI > cap_here) ? cap_here : 0;
-    static const int ufirst = [] { const char* e = getenv("TLSAN_SPEC_UFIRST"); return e ? atoi(e) : 1; }();
-    A.ufirst = (ufirst && apply_wide(A) && !shared) ? 1 : 0;
-    const dim3 grid(w.nfin + 1 + A.nbH + (shared ? A.C * A.csplit : A.nbC) + (A.nbI_l > 0 ? A.nbI_l : A.nbI) + A.nbU);
-    static const int low_env = [] { const char* e = getenv("TLSAN_SPEC_LOWOCC"); return e ? atoi(e) : -1; }();   // (A/B: 0 / 1 force it)
-    const bool wide = apply_wide(A) && !shared, bf16 = A.p.table_dtype == TLSAN_TABLE_BF16, low = low_env < 0 ? tables_in_hbm(d) : low_env != 0;
-    if (shared && s.D > 128) return fail(TLSAN_E_UNSUPPORTED, "shared categories in the one-pass update: d <= 128");   // (lazy_one_pass never asks)
-    FinLaunch fl;
-    fl.f = f; fl.A = A; fl.grid = grid; fl.nbK = w.nbK; fl.nbS = w.nbS; fl.kind = FinLaunch::UPDATE;
-    fl.shared = shared; fl.bf16 = bf16; fl.wide = wide; fl.low = low; fl.csplit = false;
-    launch_finalize_of(s, fl, hs);
-    CHECK_LAUNCH("k_finalize_update");
-    prof_mark(4, hs);
-    return TLSAN_OK;
-  }
-  if (presum) {
-    // lazy update: the exact row sums of the apply pass share the launch (they wait for nothing it produces)
-    ApplyArgs A = *presum;
-    lazy_blocks(A, b->B, b->Sn);
-    A.nbC = A.cseg ? (A.C + AP_ROWS_PB - 1) / AP_ROWS_PB : A.C * A.csplit;
-    A.nbH = AP_HOT_CAP;   // hot item rows: a workgroup each, leading the grid
-    const dim3 grid(w.nfin + 1 + A.nbH + A.nbC + A.nbI + A.nbU);
-    // (the row-sum launch covers user rows of up to 256 floats in two passes of its narrow form -- 92 registers, five
-    //  workgroups per CU, instead of 135 and three; the sharded step's fused rows keep the wide form.  d = 128 with 90-entry
-    //  windows: Movies-TV shape 106.6 -> 104.3 us/step, with 673 categories 116.2 -> 106.2: profiles/r04_presum_narrow_ab.md)
-    const bool wide = A.di > 64 || A.dc > 64 || (A.WU > 128 && A.presum_rows != 0);
-    FinLaunch fl;
-    fl.f = f; fl.A = A; fl.grid = grid; fl.nbK = w.nbK; fl.nbS = w.nbS; fl.kind = FinLaunch::PRESUM;
-    fl.shared = false; fl.bf16 = false; fl.wide = wide; fl.low = false; fl.csplit = A.csplit > 1;
-    launch_finalize_of(s, fl, hs);
-    CHECK_LAUNCH("k_finalize_presum");
-    prof_mark(4, hs);
-    return TLSAN_OK;
-  }
-  {
-    FinLaunch fl;
-    memset(&fl.A, 0, sizeof(fl.A));
-    fl.f = f; fl.grid = dim3(w.nfin + 1); fl.nbK = w.nbK; fl.nbS = w.nbS; fl.kind = FinLaunch::DENSE;
-    fl.shared = fl.bf16 = fl.wide = fl.low = fl.csplit = false;
-    launch_finalize_of(s, fl, hs);
-  }
-  CHECK_LAUNCH("k_dense_finalize");
-  prof_mark(4, hs);
+  f->lay = L; f->partials = w.partials; f->nrec = (b->B + grp - 1) / grp; f->Kp = w.Kp; f->nsplit = nsplit;
+  f->sqd = w.sqd; f->scal = w.scal;
+  f->S_delta = st.S_delta; f->n_spart = st.nbI + st.nbU + st.nbC + AP_HOT_CAP; f->S_total = st.S_total;
+  f->hdr = st.hdr; f->lr = hp->lr; f->reg = hp->reg; f->clip = hp->clip; f->inv_B = 1.0f / (float)b->B;
+  f->norm_mode = hp->norm_mode;
+  f->out_loss = out ? out->loss : nullptr;
+  f->out_gnorm = out ? out->gnorm : nullptr;
+  f->out_sq = out ? out->sq_rows : nullptr;
   return TLSAN_OK;
 }
 
@@ -1048,7 +1058,7 @@ static int prep_step(const tlsan_dims* d, Shape* s, const tlsan_params* p, const
 
 // dedup-norm mode: per-row squared norms of the SUMMED gradients (ROWNORM pass), then the coefficient
 static int clip_dedup(const ApplyArgs& A, const tlsan_hparams* hp, const tlsan_step_out* out, const Ws& w,
-                      const St& st, const tlsan_batch* b, hipStream_t hs) {
+                      const St& st, hipStream_t hs) {
   ApplyArgs R = A;
   R.part_out = w.rownorm_part;
   int rc = launch_apply(AP_ROWNORM, R, false, hs);
@@ -1056,6 +1066,52 @@ static int clip_dedup(const ApplyArgs& A, const tlsan_hparams* hp, const tlsan_s
   hipLaunchKernelGGL(k_clip_dedup, dim3(1), dim3(256), 0, hs, w.rownorm_part, st.nbI + st.nbU + st.nbC, w.sqd, w.nfin,
                      st.hdr, hp->clip, out ? out->gnorm : nullptr);
   CHECK_LAUNCH("k_clip_dedup");
+  return TLSAN_OK;
+}
+
+// the plan's launches: the finalize (run_backward filled the front half of its arguments), then the second launch
+static int launch_tail(const Shape& s, const TailPlan& P, const tlsan_hparams* hp, const tlsan_step_out* out, const Ws& w,
+                       const St& st, hipStream_t hs) {
+  static const char* const fin_name[] = {"k_dense_finalize", "k_finalize_presum", "k_finalize_update"};
+  const ApplyArgs& A = P.fin.A;
+  const bool bf16 = A.p.table_dtype == TLSAN_TABLE_BF16;
+  const dim3 blk(256);
+  int rc;
+  launch_finalize_of(s, P.fin, hs);
+  CHECK_LAUNCH(fin_name[P.fin.kind]);
+  prof_mark(4, hs);
+  switch (P.form) {
+    case TAIL_APPLY:
+      if (hp->norm_mode == TLSAN_NORM_DEDUP && (rc = clip_dedup(A, hp, out, w, st, hs))) return rc;
+      if ((rc = launch_apply(P.update ? AP_UPDATE : AP_GRADS, A, true, hs))) return rc;
+      break;
+    case TAIL_SPLIT:
+      if (P.update) {   // the short elementwise update of the summed rows
+        if (bf16 && P.wide) hipLaunchKernelGGL((k_update_lazy<true, TLSAN_TABLE_BF16>), P.grid, blk, 0, hs, A, P.nbC16);
+        else if (bf16) hipLaunchKernelGGL((k_update_lazy<false, TLSAN_TABLE_BF16>), P.grid, blk, 0, hs, A, P.nbC16);
+        else if (P.wide) hipLaunchKernelGGL((k_update_lazy<true, TLSAN_TABLE_F32>), P.grid, blk, 0, hs, A, P.nbC16);
+        else hipLaunchKernelGGL((k_update_lazy<false, TLSAN_TABLE_F32>), P.grid, blk, 0, hs, A, P.nbC16);
+        CHECK_LAUNCH("k_update_lazy");
+      } else if (A.csplit > 1) {   // the split workgroups left exact double sums: round them into the output
+        hipLaunchKernelGGL(k_rc64_to_float, P.grid, blk, 0, hs, A.Rc64, A.Rc, A.C * A.dc);
+        CHECK_LAUNCH("k_rc64_to_float");
+      }
+      break;
+    case TAIL_SPEC_SHARED:
+      if (bf16) hipLaunchKernelGGL((k_spec_commit<false, TLSAN_TABLE_BF16, true>), P.grid, blk, 0, hs, A);
+      else hipLaunchKernelGGL((k_spec_commit<false, TLSAN_TABLE_F32, true>), P.grid, blk, 0, hs, A);
+      CHECK_LAUNCH("k_spec_commit");
+      break;
+    case TAIL_SPEC:
+      if (bf16 && P.wide) hipLaunchKernelGGL((k_spec_commit<true, TLSAN_TABLE_BF16>), P.grid, blk, 0, hs, A);
+      else if (bf16) hipLaunchKernelGGL((k_spec_commit<false, TLSAN_TABLE_BF16>), P.grid, blk, 0, hs, A);
+      else if (P.wide) hipLaunchKernelGGL((k_spec_commit<true, TLSAN_TABLE_F32>), P.grid, blk, 0, hs, A);
+      else hipLaunchKernelGGL((k_spec_commit<false, TLSAN_TABLE_F32>), P.grid, blk, 0, hs, A);
+      CHECK_LAUNCH("k_spec_commit");
+      break;
+  }
+  prof_mark(5, hs);
+  prof_step_done();
   return TLSAN_OK;
 }
 
@@ -1129,51 +1185,10 @@ int tlsan_train_step_opt(const tlsan_dims* d, const tlsan_params* p, const tlsan
     if (opt->kind == TLSAN_OPT_ADAM)  // adam.py: lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t)
       A.oalpha = (float)((double)hp->lr * sqrt(1.0 - pow((double)opt->beta2, opt->step)) / (1.0 - pow((double)opt->beta1, opt->step)));
   }
-  static const int spec_on = [] { const char* e = getenv("TLSAN_LAZY_SPEC"); return e ? atoi(e) : 1; }();
-  int form = hp->l2_mode == TLSAN_L2_LAZY ? lazy_one_pass(d, b, A) : 0;
-  if (form == 2 && !spec_on) form = 0;     // (shared categories: built in the speculative form only)
-  if (form != 0) {
-    // ONE pass over the used rows (segment sums and the update of a row by the same lanes) instead of row sums beside the
-    // finalize + an elementwise update: the summed rows make no round trip through memory (lazy_one_pass says where)
-    if (form == 2) {   // shared categories: summed in the first launch (C * csplit workgroups), updated by 16-row blocks of the commit
-      category_split(A, d, b);
-      A.nbC = (A.C + 15) / 16;
-    }
-    ApplyArgs A1 = A;
-    lazy_blocks(A1, b->B, b->Sn);
-    if (spec_on) {   // the row update beside the finalize, with coefficient 1; then the commit (+ the correction of a clipped step)
-      if ((rc = run_backward(d, s, p, b, hp, true, out, w, st, L, hs, &A, nullptr, true, true))) return rc;
-      A1.nbH = AP_HOT_CAP;
-      const int nrow = A1.nbH + (form == 2 ? 0 : A1.nbC) + A1.nbI + A1.nbU;
-      const dim3 grid(A1.nbD + (form == 2 ? A1.nbC : 0) + (nrow < SPEC_FIX_BLOCKS ? nrow : SPEC_FIX_BLOCKS));
-      const bool wide = apply_wide(A1) && form != 2;
-      if (form == 2) {
-        if (A1.p.table_dtype == TLSAN_TABLE_BF16) hipLaunchKernelGGL((k_spec_commit<false, TLSAN_TABLE_BF16, true>), grid, dim3(256), 0, hs, A1);
-        else hipLaunchKernelGGL((k_spec_commit<false, TLSAN_TABLE_F32, true>), grid, dim3(256), 0, hs, A1);
-      } else if (A1.p.table_dtype == TLSAN_TABLE_BF16) {
-        if (wide) hipLaunchKernelGGL((k_spec_commit<true, TLSAN_TABLE_BF16>), grid, dim3(256), 0, hs, A1);
-        else hipLaunchKernelGGL((k_spec_commit<false, TLSAN_TABLE_BF16>), grid, dim3(256), 0, hs, A1);
-      } else {
-        if (wide) hipLaunchKernelGGL((k_spec_commit<true, TLSAN_TABLE_F32>), grid, dim3(256), 0, hs, A1);
-        else hipLaunchKernelGGL((k_spec_commit<false, TLSAN_TABLE_F32>), grid, dim3(256), 0, hs, A1);
-      }
-      CHECK_LAUNCH("k_spec_commit");
-    } else {         // (A/B: the finalize's whole chain, then one pass over the rows)
-      if ((rc = run_backward(d, s, p, b, hp, true, out, w, st, L, hs, nullptr, nullptr, true))) return rc;
-      if ((rc = launch_apply(AP_UPDATE, A1, true, hs, true))) return rc;
-    }
-  } else if (hp->l2_mode == TLSAN_L2_LAZY) {   // row sums beside the finalize, then the short elementwise update
-    category_split(A, d, b);
-    if ((rc = run_backward(d, s, p, b, hp, true, out, w, st, L, hs, &A))) return rc;
-    if ((rc = launch_update_lazy(A, b->B, b->Sn, hs))) return rc;
-  } else {
-    if ((rc = run_backward(d, s, p, b, hp, true, out, w, st, L, hs))) return rc;
-    if (hp->norm_mode == TLSAN_NORM_DEDUP && (rc = clip_dedup(A, hp, out, w, st, b, hs))) return rc;
-    if ((rc = launch_apply(AP_UPDATE, A, true, hs))) return rc;
-  }
-  prof_mark(5, hs);
-  prof_step_done();
-  return TLSAN_OK;
+  TailPlan P;
+  if ((rc = plan_tail(d, s, b, hp, w, A, true, &P))) return rc;
+  if ((rc = run_backward(d, s, p, b, hp, out, w, st, L, hs, P.sparse_index, &P.fin.f))) return rc;
+  return launch_tail(s, P, hp, out, w, st, hs);
 }
 
 int tlsan_grads(const tlsan_dims* d, const tlsan_params* p, const tlsan_batch* b, const tlsan_hparams* hp,
@@ -1194,29 +1209,10 @@ int tlsan_grads(const tlsan_dims* d, const tlsan_params* p, const tlsan_batch* b
   if (A.go.ld_user == 0) A.go.ld_user = d->d_item;
   if (A.go.ld_usert == 0) A.go.ld_usert = d->Ls;
   if (A.go.ld_item % 4 || A.go.ld_user % 4) return fail(TLSAN_E_UNSUPPORTED, "gradient row strides must be multiples of 4 floats");
-  if (hp->reg == 0.0f && g->sparse && hp->norm_mode == TLSAN_NORM_TF18) {
-    // pure per-row sums of the used rows (what the sharded step asks for): they ride with the dense
-    // finalize as in the lazy train step, written straight to the output rows -- no apply launch
-    // (sparse == 2: the four outputs are views of ONE fused row table, see tlsan_grads_out)
-    A.presum_rows = g->sparse == 2 ? 2 : 1;
-    A.Rc = g->cate_emb;
-    category_split(A, d, b);
-    if ((rc = run_backward(d, s, p, b, hp, false, out, w, st, L, hs, &A, g->dense))) return rc;
-    if (A.csplit > 1) {  // the split workgroups left exact double sums: round them into the output
-      const int n = d->cate_count * d->d_cate;
-      hipLaunchKernelGGL(k_rc64_to_float, dim3((n + 255) / 256), dim3(256), 0, hs, st.Rc64, g->cate_emb, n);
-      CHECK_LAUNCH("k_rc64_to_float");
-    }
-    prof_mark(5, hs);
-    prof_step_done();
-    return TLSAN_OK;
-  }
-  if ((rc = run_backward(d, s, p, b, hp, false, out, w, st, L, hs))) return rc;
-  if (hp->norm_mode == TLSAN_NORM_DEDUP && (rc = clip_dedup(A, hp, out, w, st, b, hs))) return rc;
-  if ((rc = launch_apply(AP_GRADS, A, true, hs))) return rc;
-  prof_mark(5, hs);
-  prof_step_done();
-  return TLSAN_OK;
+  TailPlan P;
+  if ((rc = plan_tail(d, s, b, hp, w, A, false, &P))) return rc;
+  if ((rc = run_backward(d, s, p, b, hp, out, w, st, L, hs, P.sparse_index, &P.fin.f))) return rc;
+  return launch_tail(s, P, hp, out, w, st, hs);
 }
 
 static int eval_ranks_impl(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const int32_t* labels, int32_t B,

@@ -1521,7 +1521,7 @@ __device__ __forceinline__ void opt_elem(const OptCtx& o, float& w, float g, flo
 // on another is issued up front: used-row records, clip-norm partials, the parameter row, and
 // the first AP_OWN gradient rows of a segment in one batch (clamped addresses instead of
 // branches, which the compiler would serialise).
-// LAZY: the row blocks walk the compacted records of used rows (k_index_scan) instead of every row.
+// LAZY (apply_*_block): the row blocks walk the compacted records of used rows (k_index_scan) instead of every row.
 // NCH = float4 chunks per lane: 16 lanes x NCH x 4 floats >= the widest row (d_item, WU, d_cate).
 #define AP_CAP 2048  // LDS list of use positions of one category pass
 
@@ -2272,7 +2272,7 @@ __device__ __forceinline__ void presum_hot_block(const ApplyArgs& a, int h, doub
 }
 
 // WIDE: d_item / d_cate above 64 or d_item + Ls above 128 columns (more float4 chunks per lane)
-template <int MODE, bool LAZY, bool WIDE, int DT = TLSAN_TABLE_F32>
+template <int MODE, bool WIDE, int DT = TLSAN_TABLE_F32>
 __global__ __launch_bounds__(256) void k_apply(ApplyArgs a) {
   constexpr int NC = WIDE ? 2 : 1, NI = WIDE ? 2 : 1, NU = WIDE ? 4 : 2;
   __shared__ double shd[4 * 16 * NC * 4];
@@ -2286,8 +2286,7 @@ __global__ __launch_bounds__(256) void k_apply(ApplyArgs a) {
   x.blk = blockIdx.x;
   AP_STAMP(0);
   if (a.stamps != nullptr && x.tid == 0) a.stamps[(size_t)x.blk * 8 + 4] = __builtin_amdgcn_s_memrealtime();
-  // (the step summary of k_dense_finalize already advanced hdr->P for a lazy update)
-  x.P = (MODE == AP_UPDATE && LAZY) ? a.hdr->P_prev : a.hdr->P;
+  x.P = a.hdr->P;
   x.invP = 1.0f / x.P;
   x.step = MODE == AP_UPDATE ? a.lr * a.hdr->coef : 0.0f;
   x.lazy_scale = x.step / (x.P * (1.0f - x.step * a.reg));
@@ -2297,12 +2296,12 @@ __global__ __launch_bounds__(256) void k_apply(ApplyArgs a) {
   x.oc.opt = a.opt; x.oc.lr = a.lr; x.oc.b1 = a.ob1; x.oc.b2 = a.ob2; x.oc.eps = a.oeps; x.oc.alpha = a.oalpha;
   const int blk = x.blk;
   if (blk < a.nbC) {
-    if (a.cseg) apply_cseg_block<MODE, LAZY, NC, AP_OWN, DT>(a, x, blk * AP_ROWS_PB, shp);   // (nbC = ceil(C / 16) then)
-    else apply_cate_block<MODE, LAZY, NC, DT>(a, x, shd, shp, sh_pos, sh_lo, sh_n, sh_wtot);
+    if (a.cseg) apply_cseg_block<MODE, false, NC, AP_OWN, DT>(a, x, blk * AP_ROWS_PB, shp);   // (nbC = ceil(C / 16) then)
+    else apply_cate_block<MODE, false, NC, DT>(a, x, shd, shp, sh_pos, sh_lo, sh_n, sh_wtot);
   } else if (blk < a.nbC + a.nbI) {
-    apply_rows_block<MODE, LAZY, true, NI, AP_OWN, DT>(a, x, (blk - a.nbC) * AP_ROWS_PB, shp);
+    apply_rows_block<MODE, false, true, NI, AP_OWN, DT>(a, x, (blk - a.nbC) * AP_ROWS_PB, shp);
   } else if (blk < a.nbC + a.nbI + a.nbU) {
-    apply_rows_block<MODE, LAZY, false, NU, AP_OWN / 2, DT>(a, x, (blk - a.nbC - a.nbI) * AP_ROWS_PB, shp);
+    apply_rows_block<MODE, false, false, NU, AP_OWN / 2, DT>(a, x, (blk - a.nbC - a.nbI) * AP_ROWS_PB, shp);
   } else {
     // ================= 256 dense parameters =================
     const int nd = (blk - a.nbC - a.nbI - a.nbU) * 256 + x.tid;
@@ -2315,13 +2314,11 @@ __global__ __launch_bounds__(256) void k_apply(ApplyArgs a) {
           a.go.dense[nd] = g;
         } else {
           float wn = w0 - x.step * g;
-          if constexpr (!LAZY) {
-            if (a.opt != TLSAN_OPT_SGD) {
-              float a1 = a.s1.dense[nd], a2 = a.s2.dense[nd];
-              wn = w0;
-              opt_elem(x.oc, wn, x.coef * g, a1, a2);
-              a.s1.dense[nd] = a1; a.s2.dense[nd] = a2;
-            }
+          if (a.opt != TLSAN_OPT_SGD) {
+            float a1 = a.s1.dense[nd], a2 = a.s2.dense[nd];
+            wn = w0;
+            opt_elem(x.oc, wn, x.coef * g, a1, a2);
+            a.s1.dense[nd] = a1; a.s2.dense[nd] = a2;
           }
           a.p.dense[nd] = wn;
           if (nd >= a.lay.K && nd < a.lay.k0) {
@@ -2344,7 +2341,7 @@ __global__ __launch_bounds__(256) void k_apply(ApplyArgs a) {
 //   k_finalize_presum : workgroups [0, nbK+nbS] are k_dense_finalize's, the rest are k_apply's in
 //                       PRESUM mode (exact per-row sums -> Rc / Ri / Rb / Ru, counters reset)
 //   k_update_lazy     : elementwise w -= scale * sum for the used rows + the dense parameters
-// Same arithmetic per element as k_apply<AP_UPDATE, lazy> (the sums are rounded to float there too).
+// Same arithmetic per element as apply_*_block<AP_UPDATE, lazy> (the sums are rounded to float there too).
 // (the narrow form is held to 96 registers -- five workgroups per CU: left alone, the compiler takes 124 for the 64 loads the
 //  dK entry blocks keep in flight and costs the launch a fifth of its residency; held, it needs 91 and spills nothing)
 #ifndef PRESUM_WPE_WIDE
@@ -2433,7 +2430,7 @@ __device__ __forceinline__ double update_cate_rows(const ApplyArgs& a, int c, in
 // The lazy-L2 step for tables that live in HBM (round 6): the SPECULATIVE one-pass update.
 // The split form above sends every summed row through memory (written by the row-sum launch, read by k_update_lazy beside
 // the parameter row's read-modify-write): at 10 M users / 5 M items that round trip is a third of the tail's traffic.  One
-// pass over the used rows (segment sums and the row's update by the same lanes, k_apply<AP_UPDATE, lazy>) avoids it but
+// pass over the used rows (segment sums and the row's update by the same lanes, apply_*_block<AP_UPDATE, lazy>) avoids it but
 // needs the clip coefficient first, i.e. the finalize's whole chain in front of it (C5: 26 us).  clip_by_global_norm's
 // coefficient is 1 unless the global norm exceeds the clip (model.py:201) -- so:
 //   k_finalize_update : the finalize's workgroups lead the grid; the row workgroups update with coefficient 1 beside them.
@@ -2540,7 +2537,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? SPEC
   } else {
     const int blk = x.blk;
     if (blk < a.nbC) {
-      // (the wide form takes category segments only -- lazy_one_pass, tlsan_api.hip: the item-walk category workgroups in its
+      // (the wide form takes category segments only -- plan_tail, tlsan_api.hip: the item-walk category workgroups in its
       //  kernel cost the row roles 44 more spilled bytes per lane)
       if (WIDE || a.cseg) apply_cseg_block<AP_UPDATE, true, NC, OWN, DT>(a, x, blk * AP_ROWS_PB, shp);
       else apply_cate_block<AP_UPDATE, true, NC, DT>(a, x, shd, shp, sh_pos, sh_lo, sh_n, sh_wtot);

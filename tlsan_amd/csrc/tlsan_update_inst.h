@@ -12,7 +12,7 @@ struct FinLaunch {   // one launch of the dense finalize, in any of its three fo
   dim3 grid;
   int nbK, nbS;
   int kind;
-  bool shared;       // UPDATE: shared categories (lazy_one_pass form 2)
+  bool shared;       // UPDATE: shared categories (plan_tail: TAIL_SPEC_SHARED)
   bool bf16;         // UPDATE: bf16 tables
   bool wide;         // PRESUM, UPDATE: the wide row form
   bool low;          // UPDATE: the low-occupancy form (tables in HBM)
