@@ -1331,6 +1331,47 @@ def test_shared_categories_one_pass_equals_the_split_form():
     assert len(set(digests)) == 1, digests
 
 
+@pytest.mark.parametrize("table_dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("d", [64, 128])
+def test_lazy_sum_of_squares_tracks_the_tables(d, table_dtype):
+    """Lazy L2 keeps the stored tables' sum of squares (StateHdr::St, state bytes 32..40) from per-workgroup records of its
+    changes, which the next step folds in (DeltaRec, tlsan_update.h): after any sequence of updates it equals the tables'
+    own.  Batches of varying B and Sn make the records an update leaves shrink and grow; a large L2 rate at lr = 1 makes
+    one workgroup's change a visible part of the sum; the first steps clip (the correcting pass adds to its records); the
+    scale is folded into the tables every third step.  The tables are large enough that fp32 rounding in that fold stays far
+    below the tolerance.  A second run that takes gradients after every step (a fold without an update) ends bit-equal."""
+    import torch
+    clip = {64: 13.5, 128: 17.0}[d]     # (above the norm of the later steps, below that of the first: profiled with the oracle)
+    cfg = make_config(U=3000, I=4000, C=40, d=d, regulation_rate=0.05, max_gradient_norm=clip)
+    p = _p32(random_params(cfg, seed=1301))
+    if table_dtype == "bf16":
+        for k in BF16_TABLES:
+            p[k] = _bf16_round(p[k]).astype(np.float64)
+    _, cat = random_batch(cfg, B=8, Sn=2, seed=1300)
+    shapes = [(64, 1), (5, 3), (40, 5), (1, 2), (64, 4), (17, 1)]
+    batches = [_tuple(random_batch(cfg, B=B, Sn=Sn, seed=1310 + k)[0]) for k, (B, Sn) in enumerate(shapes)]
+    probe = _tuple(random_batch(cfg, B=9, Sn=2, seed=1320)[0])
+    runs = []
+    for every_step in (False, True):
+        m = _model(cfg, cat, p, l2_mode="lazy", table_dtype=table_dtype)
+        m.renorm_every = 3
+        losses, gnorms = [], []
+        for b in batches:
+            losses.append(m.train(None, b, 1.0))
+            gnorms.append(m.last_gnorm())
+            if every_step:
+                m.grads(probe)
+        m.grads(probe)                     # (folds the last step's records)
+        St = float(m.state[32:40].view(torch.float64).item())
+        ref = sum(float(getattr(m, k).double().pow(2).sum().item()) for k in orc.REG_TABLES)
+        assert abs(St - ref) <= 1e-9 * ref, (St, ref)
+        assert gnorms[0] > clip and min(gnorms) < clip, gnorms
+        runs.append((St, losses, m.get_params()))
+    assert runs[0][0] == runs[1][0] and runs[0][1] == runs[1][1], (runs[0][:2], runs[1][:2])
+    for k in runs[0][2]:
+        assert np.array_equal(runs[0][2][k], runs[1][2][k]), k
+
+
 def test_speculative_one_pass_lazy_update():
     """Tables that live in HBM (more than 512 MB of user / item rows, category segments) take the lazy-L2 step as ONE pass
     over the used rows BESIDE the finalize, with clip coefficient 1, and a second launch that commits the table scale and --
@@ -1344,7 +1385,7 @@ def test_speculative_one_pass_lazy_update():
     sel = ("test_lazy_l2_matches_dense_oracle or test_lazy_is_deterministic or test_category_segments_match_oracle "
            "or test_full_size_batch_matches_oracle or test_one_hot_row_takes_every_use or test_multi_step_tracks_oracle "
            "or test_prefetched_index_equals_inline or test_periodic_scale_fold or test_bf16_tables or test_graph_replay_equals_eager "
-           "or test_nonfinite_inputs_give_nonfinite_loss or test_real_fixture_batches")
+           "or test_nonfinite_inputs_give_nonfinite_loss or test_real_fixture_batches or test_lazy_sum_of_squares")
     # (3: every table shape the one-pass form takes -- the item-walk category workgroups and the hot-row workgroups of
     #  tables with few categories, which TLSAN_CSEG_MIN=1 would hide)
     r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_parity.py", "-m", "gpu", "-q", "-x", "-k", sel],
@@ -1359,11 +1400,17 @@ def test_speculative_one_pass_lazy_update():
                         "test_lazy_l2_matches_dense_oracle or test_lazy_is_deterministic or test_category_segments_match_oracle "
                         "or test_full_size_batch_matches_oracle or test_one_hot_row_takes_every_use or test_multi_step_tracks_oracle "
                         "or test_prefetched_index_equals_inline or test_periodic_scale_fold or test_bf16_tables or test_graph_replay_equals_eager "
-                        "or test_nonfinite_inputs_give_nonfinite_loss or test_real_fixture_batches"],
+                        "or test_nonfinite_inputs_give_nonfinite_loss or test_real_fixture_batches or test_lazy_sum_of_squares"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=1800)
     assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
     mt = re.search(r"(\d+) passed", r.stdout)
     assert mt and int(mt.group(1)) >= 25, r.stdout[-2000:]
+    # (the split form: the row sums beside the finalize, then k_update_lazy)
+    r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_parity.py", "-m", "gpu", "-q", "-x", "-k", "test_lazy_sum_of_squares"],
+                       cwd=root, env=dict(os.environ, TLSAN_LAZY_ONE_PASS="0"), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
+    mt = re.search(r"(\d+) passed", r.stdout)
+    assert mt and int(mt.group(1)) == 4, r.stdout[-2000:]
     digests = []
     for one_pass in ("2", "0"):
         env = dict(os.environ, TLSAN_LAZY_ONE_PASS=one_pass, TLSAN_CSEG_MIN="1")

@@ -288,6 +288,7 @@ struct St {  // persistent state
   int4* is_tmp[TLSAN_INDEX_SLOTS];
   size_t bytes;
   int nbI, nbU, nbC;
+  int nrec;   // records per step-parity array of S_delta: a workgroup each of the row blocks and the hot-row workgroups
 };
 
 static void carve_state(const tlsan_dims* d, char* base, St* s) {
@@ -315,7 +316,8 @@ static void carve_state(const tlsan_dims* d, char* base, St* s) {
   s->cate_cur = (int32_t*)take(4 * (size_t)d->cate_count);
   s->cate_items = (int32_t*)take(4 * (size_t)d->item_count);
   s->S_part = (double*)take(8 * (size_t)(s->nbI + s->nbU + s->nbC));
-  s->S_delta = (DeltaRec*)take(sizeof(DeltaRec) * ((size_t)(s->nbI + s->nbU + s->nbC) + AP_HOT_CAP));   // (+ the hot-row workgroups of a one-pass update)
+  s->nrec = s->nbI + s->nbU + s->nbC + AP_HOT_CAP;
+  s->S_delta = (DeltaRec*)take(sizeof(DeltaRec) * 2 * (size_t)s->nrec);   // (two arrays, by step parity: DeltaRec)
   for (int k = 0; k < TLSAN_INDEX_SLOTS; ++k) s->uc_list[k] = (int32_t*)take(4 * (size_t)UC_LIST_CAP);
   s->Rc64 = (double*)take(8 * (size_t)d->cate_count * d->d_cate);
   for (int k = 0; k < TLSAN_INDEX_SLOTS; ++k) s->hot_list[k] = (int32_t*)take(4 * (size_t)AP_HOT_CAP);
@@ -430,7 +432,7 @@ static void fill_apply(ApplyArgs& A, const tlsan_dims* d, const Shape& s, const 
   A.hot_n = st.hdr ? &st.hdr->n_hot[k] : nullptr; A.hot_list = st.hot_list[k];
   A.gd = w.gd;
   A.Rc = w.Rc; A.Ri = w.Ri; A.Rb = w.Rb; A.Ru = w.Ru;
-  A.part_out = st.S_part; A.delta_out = st.S_delta; A.hdr = st.hdr;
+  A.part_out = st.S_part; A.delta_out = st.S_delta; A.delta_nrec = st.nrec; A.hdr = st.hdr;
   A.urec_item = st.urec_item[k]; A.urec_user = st.urec_user[k];
   if (hp) { A.lr = hp->lr; A.reg = hp->reg; }
   A.nbI = st.nbI; A.nbU = st.nbU; A.nbC = st.nbC; A.nbD = (L.n_dense + 255) / 256;
@@ -607,9 +609,9 @@ static int plan_tail(const tlsan_dims* d, const Shape& s, const tlsan_batch* b, 
     static const int item_cap = [] { const char* e = getenv("TLSAN_SPEC_ITEM_BLOCKS"); return e ? atoi(e) : SPEC_ITEM_BLOCKS; }();
     const int cap = shared ? SPEC_ITEM_BLOCKS : item_cap;
     A.nbI_l = (cap > 0 && A.nbI > cap) ? cap : 0;
-    // user-row workgroups ahead of the item rows in the wide form (profiles/r06_ab_c5_tail.txt).  Shared categories:
-    // k_finalize_update<.., CSPL> orders them itself, by a.WU > 128, and does not read ufirst.
-    A.ufirst = (apply_wide(A) && !shared) ? 1 : 0;
+    // user-row workgroups ahead of the item rows in the wide form (profiles/r06_ab_c5_tail.txt); shared categories: where the
+    // user rows take two passes of the narrow form (k_finalize_update<.., CSPL>)
+    A.ufirst = (shared ? A.WU > 128 : apply_wide(A)) ? 1 : 0;
     fl.kind = FinLaunch::UPDATE;
     fl.grid = dim3(w.nfin + 1 + A.nbH + (shared ? A.C * A.csplit : A.nbC) + (A.nbI_l > 0 ? A.nbI_l : A.nbI) + A.nbU);
     fl.shared = shared; fl.bf16 = bf16; fl.wide = apply_wide(A) && !shared;
@@ -754,7 +756,7 @@ int tlsan_state_renorm(const tlsan_dims* d, const tlsan_params* p, void* state, 
   hipStream_t hs = (hipStream_t)stream;
   const int dt = q.table_dtype;
   // (changes of the sum of squares the last update left as records: part of St before St is rescaled)
-  hipLaunchKernelGGL(k_fold_delta, dim3(1), dim3(256), 0, hs, st.S_delta, st.nbI + st.nbU + st.nbC + AP_HOT_CAP, st.hdr, st.S_total);
+  hipLaunchKernelGGL(k_fold_delta, dim3(1), dim3(256), 0, hs, st.S_delta, st.nrec, st.hdr, st.S_total);
   hipLaunchKernelGGL(k_scale_table, dim3(1024), dim3(256), 0, hs, q.item_emb, d->item_count, d->d_item, q.ld_item, st.hdr, dt, 0x1b873593u);
   hipLaunchKernelGGL(k_scale_table, dim3(1024), dim3(256), 0, hs, q.user_emb, d->user_count, d->d_item, q.ld_user, st.hdr, dt, 0xcc9e2d51u);
   hipLaunchKernelGGL(k_scale_table, dim3(256), dim3(256), 0, hs, q.usert_emb, d->user_count, d->Ls, q.ld_usert, st.hdr, TLSAN_TABLE_F32, 0u);
@@ -1026,7 +1028,7 @@ static int run_backward(const tlsan_dims* d, const Shape& s, const tlsan_params*
   prof_mark(3, hs);
   f->lay = L; f->partials = w.partials; f->nrec = (b->B + grp - 1) / grp; f->Kp = w.Kp; f->nsplit = nsplit;
   f->sqd = w.sqd; f->scal = w.scal;
-  f->S_delta = st.S_delta; f->n_spart = st.nbI + st.nbU + st.nbC + AP_HOT_CAP; f->S_total = st.S_total;
+  f->S_delta = st.S_delta; f->delta_nrec = st.nrec; f->S_total = st.S_total;
   f->hdr = st.hdr; f->lr = hp->lr; f->reg = hp->reg; f->clip = hp->clip; f->inv_B = 1.0f / (float)b->B;
   f->norm_mode = hp->norm_mode;
   f->out_loss = out ? out->loss : nullptr;

@@ -10,6 +10,7 @@
 // sums are order-independent (exact_term) or in a fixed order, so two runs are bitwise equal.
 #pragma once
 #include "tlsan_common.h"
+#include <cstddef>
 #include <type_traits>
 // TLSAN_ONCE: the kernels that are not templates belong to the unit that launches them (tlsan_api.hip); a unit that
 // includes this header only for the templates of the dense finalize (tlsan_update_*.hip) defines it as `static`
@@ -28,7 +29,7 @@ struct StateHdr {
   double St;               // sum of squares of the four STORED tables (true value: P^2 * St)
   float coef;              // global-norm clip coefficient of the current step (model.py:201)
   uint32_t nstep;          // update steps taken (salt of the stochastic rounding of bf16 tables)
-  int32_t spart_n;         // leading records of S_delta the last update may have written
+  int32_t spart_n[2];      // [step & 1]: leading records of that step's S_delta array (DeltaRec) its update may have written
   int32_t n_hot[TLSAN_INDEX_SLOTS];        // [index slot] item rows with more than AP_HOT uses (k_index_scan; listed in the state)
   uint32_t folded;         // the step (nstep) whose S_delta records are already part of St (a step is folded once)
   // the speculative one-pass lazy update (k_finalize_update / k_spec_commit): the step summary leaves the table scale
@@ -36,21 +37,27 @@ struct StateHdr {
   // stay put while the first launch's row workgroups read them
   float P_next;
   uint32_t spec_salt;
-  float pad0[13];
+  float pad0[12];
   // ---- its own 128-B line: hammered by atomics, must not share a line with anything that is read
   int32_t ticket;          // arrival counter of k_dense_finalize: the last workgroup writes the step summary
   int32_t pad1[31];
 };
 static_assert(sizeof(StateHdr) == 256, "StateHdr layout");
+static_assert(offsetof(StateHdr, St) == 32, "StateHdr layout: St is read at byte 32 (tests/test_gpu_parity.py)");
 
 // A workgroup's change of the stored tables' sum of squares, tagged with the step that made it (StateHdr::nstep after
 // that step).  The next step's finalize adds up the records of the previous step, once (StateHdr::folded), and ignores
 // older ones: nothing is ever cleared.  (Round 2 kept plain doubles that the finalize cleared as it consumed them;
 // tlsan_state_renorm then rescaled a sum that lacked the last step's changes.)
+// S_delta holds two arrays of nrec records (St::nrec), one per step parity: a record tagged t lives in array t & 1
+// (delta_recs).  The fold of step t reads array t & 1 while the writers of step t + 1 -- in k_finalize_update, the same
+// launch -- fill the other one, so no writer can overwrite a record before it is folded.
 struct DeltaRec {
   double v;
   unsigned long long tag;
 };
+template <class R>
+__device__ __forceinline__ R* delta_recs(R* base, int nrec, unsigned long long tag) { return base + (tag & 1) * (size_t)nrec; }
 
 #ifndef TLSAN_KCH
 #define TLSAN_KCH 64     // dK partials a finalize thread has in flight (dense_finalize_block)
@@ -968,7 +975,7 @@ struct FinArgs {
   float* sqd;             // [nbK + nbS] per-block sum of gd^2
   float* scal;            // [0] = sum of per-sample BCE, [1] = sum of squares of per-use rows
   const DeltaRec* S_delta; // per-workgroup changes of the regularised tables' sum of squares, tagged by step
-  int32_t n_spart;
+  int32_t delta_nrec;      // records per step-parity array of S_delta (DeltaRec)
   double* S_total;
   // step summary (written by the last workgroup to arrive)
   StateHdr* hdr;
@@ -1065,12 +1072,14 @@ __device__ __forceinline__ double block_sum_double(const double* __restrict__ v,
 }
 
 // The apply kernels leave per-workgroup CHANGES of the tables' sum of squares (DeltaRec, tagged by step): add the records
-// of the last update to the running sum, once (StateHdr::folded).  One 256-thread workgroup, fixed order.
-__device__ __forceinline__ void fold_delta(const DeltaRec* __restrict__ recs, int n_spart, StateHdr* hdr, double* S_total, double* shd) {
+// of the last update to the running sum, once (StateHdr::folded).  One 256-thread workgroup, fixed order.  The records and
+// their count are the last update's step-parity array and spart_n entry: this step's writers fill the other ones.
+__device__ __forceinline__ void fold_delta(const DeltaRec* S_delta, int nrec, StateHdr* hdr, double* S_total, double* shd) {
   const int tid = threadIdx.x;
   const unsigned long long tag = hdr->nstep;     // (the records of the last update; this step's summary has not run yet)
+  const DeltaRec* __restrict__ recs = delta_recs(S_delta, nrec, tag);
   // (a step's records are added once: a gradient-only call between two updates finds them folded)
-  const int np = hdr->folded == (uint32_t)tag ? 0 : min(n_spart, hdr->spart_n);
+  const int np = hdr->folded == (uint32_t)tag ? 0 : min(nrec, hdr->spart_n[tag & 1]);
   double s = 0.0;
   for (int k0 = tid; k0 < np; k0 += 256 * 8) {     // 8 records in flight (clamped addresses, masked sum), fixed order
     DeltaRec t[8];
@@ -1092,9 +1101,9 @@ __device__ __forceinline__ void fold_delta(const DeltaRec* __restrict__ recs, in
 }
 
 // (tlsan_state_renorm: the sum of squares must be complete before it is rescaled)
-TLSAN_ONCE __global__ __launch_bounds__(256) void k_fold_delta(const DeltaRec* recs, int n_spart, StateHdr* hdr, double* S_total) {
+TLSAN_ONCE __global__ __launch_bounds__(256) void k_fold_delta(const DeltaRec* S_delta, int nrec, StateHdr* hdr, double* S_total) {
   __shared__ double shd[256];
-  fold_delta(recs, n_spart, hdr, S_total, shd);
+  fold_delta(S_delta, nrec, hdr, S_total, shd);
 }
 
 // Grid: [0, nbK) blocks reduce the D*D kernel gradient over the batch splits (one thread per
@@ -1108,11 +1117,11 @@ __device__ __forceinline__ void dense_finalize_block(const FinArgs& a, int nbK, 
   const int tid = threadIdx.x;
   const tlsan_dense_layout& L = a.lay;
   if (blk == nbK + nbS) {
-    // the apply kernels leave per-workgroup CHANGES of the tables' sum of squares: fold them in
-    // and clear them (consumed exactly once)
+    // the apply kernels leave per-workgroup CHANGES of the tables' sum of squares: fold the last
+    // update's in (once)
     // (only the entries the last update can have written: a lazy update of a 10^7-row table leaves
     //  a few thousand, not rows / 16)
-    fold_delta(a.S_delta, a.n_spart, a.hdr, a.S_total, shd);
+    fold_delta(a.S_delta, a.delta_nrec, a.hdr, a.S_total, shd);
     __syncthreads();  // shd is reused below
   }
   float g = 0.0f;
@@ -1374,9 +1383,10 @@ struct ApplyArgs {
   // hot item rows (more than AP_HOT uses) get a workgroup each in the row-sum pass: nbH = AP_HOT_CAP such
   // workgroups lead the grid, the item-row workgroups leave those rows to them (when the list did not overflow)
   const int32_t* hot_n; const int32_t* hot_list; int32_t nbH;
+  int32_t delta_nrec;      // UPDATE: records per step-parity array of delta_out (DeltaRec)
   double* Rc64;            // [C][dc], zero at rest (state)
   double* part_out;        // SUMSQ: sum of squares per workgroup; ROWNORM: sum g^2
-  DeltaRec* delta_out;     // UPDATE: change of the stored tables' sum of squares per workgroup, tagged with the step
+  DeltaRec* delta_out;     // UPDATE: change of the stored tables' sum of squares per workgroup, tagged with the step (S_delta)
   StateHdr* hdr;           // P, P_prev, coef (read); spart_n (written by an update)
   const int32_t* n_uniq_item; const int32_t* n_uniq_user;   // used-row counts of this step's index slot
   float lr, reg;
@@ -1438,14 +1448,16 @@ __device__ __forceinline__ void combine_groups(double (&acc)[NCH][4]) {
     }
 }
 
-// accum: add to the record this step's first launch left (the correcting pass of a speculative update, k_spec_commit)
-__device__ __forceinline__ void block_delta_store(double part, double* shd, DeltaRec* dst, unsigned long long tag, bool accum = false) {
+// record i of step `tag` (in that step's parity array of a.delta_out).  accum: add to the record this step's first launch
+// left (the correcting pass of a speculative update, k_spec_commit)
+__device__ __forceinline__ void block_delta_store(double part, double* shd, const ApplyArgs& a, int i, unsigned long long tag, bool accum = false) {
   __syncthreads();
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) part += __shfl_xor(part, o);
   if ((threadIdx.x & 63) == 0) shd[threadIdx.x >> 6] = part;
   __syncthreads();
   if (threadIdx.x == 0) {
+    DeltaRec* dst = delta_recs(a.delta_out, a.delta_nrec, tag) + i;
     const double v = shd[0] + shd[1] + shd[2] + shd[3];
     dst->v = (accum && dst->tag == tag) ? dst->v + v : v;
     dst->tag = tag;
@@ -1769,7 +1781,7 @@ __device__ __forceinline__ void apply_cate_block(const ApplyArgs& a, const ApCtx
   if constexpr (RESET) {
     if (tid == 0 && nu > 0) a.cnt_uc[c] = 0;
   }
-  if constexpr (MODE == AP_UPDATE) block_delta_store(part, shp, &a.delta_out[x.blk], x.salt, x.accum);
+  if constexpr (MODE == AP_UPDATE) block_delta_store(part, shp, a, x.blk, x.salt, x.accum);
   else if constexpr (MODE != AP_GRADS) block_part_store(part, shp, &a.part_out[x.blk]);
 }
 
@@ -2023,7 +2035,7 @@ __device__ __forceinline__ void apply_rows_block(const ApplyArgs& a, const ApCtx
       if (n > 0 && l16 == 0) (IS_ITEM ? a.cnt_item : a.cnt_user)[row] = 0;
     }
   }
-  if constexpr (MODE == AP_UPDATE) block_delta_store(part, shp, &a.delta_out[x.blk], x.salt, x.accum);
+  if constexpr (MODE == AP_UPDATE) block_delta_store(part, shp, a, x.blk, x.salt, x.accum);
   else if constexpr (MODE != AP_GRADS) block_part_store(part, shp, &a.part_out[x.blk]);
 }
 
@@ -2152,7 +2164,7 @@ __device__ __forceinline__ void apply_cseg_block(const ApplyArgs& a, const ApCtx
       if (l16 == 0 && n > 0) a.cnt_uc[c] = 0;
     }
   }
-  if constexpr (MODE == AP_UPDATE) block_delta_store(part, shp, &a.delta_out[x.blk], x.salt, x.accum);
+  if constexpr (MODE == AP_UPDATE) block_delta_store(part, shp, a, x.blk, x.salt, x.accum);
   else if constexpr (MODE != AP_GRADS) block_part_store(part, shp, &a.part_out[x.blk]);
 }
 
@@ -2241,7 +2253,7 @@ __device__ __forceinline__ void presum_hot_block(const ApplyArgs& a, int h, doub
         a.cnt_item[row] = 0;
       }
     }
-    block_delta_store(part, shp, &a.delta_out[a.nbC + a.nbI + a.nbU + h], x.salt, x.accum);
+    block_delta_store(part, shp, a, a.nbC + a.nbI + a.nbU + h, x.salt, x.accum);
     return;
   }
   if (wave == 0 && grp == 0) {
@@ -2292,7 +2304,7 @@ __global__ __launch_bounds__(256) void k_apply(ApplyArgs a) {
   x.lazy_scale = x.step / (x.P * (1.0f - x.step * a.reg));
   x.salt = a.hdr->nstep;
   x.coef = MODE == AP_UPDATE ? a.hdr->coef : 0.0f;
-  if (MODE == AP_UPDATE && x.blk == 0 && x.tid == 0) a.hdr->spart_n = a.nbC + a.nbI + a.nbU;
+  if (MODE == AP_UPDATE && x.blk == 0 && x.tid == 0) a.hdr->spart_n[x.salt & 1] = a.nbC + a.nbI + a.nbU;
   x.oc.opt = a.opt; x.oc.lr = a.lr; x.oc.b1 = a.ob1; x.oc.b2 = a.ob2; x.oc.eps = a.oeps; x.oc.alpha = a.oalpha;
   const int blk = x.blk;
   if (blk < a.nbC) {
@@ -2497,7 +2509,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? SPEC
   x.lazy_scale = x.step / (x.P * (1.0f - x.step * a.reg));
   x.salt = a.hdr->nstep + 1;    // what the step's salt and record tag will be (hdr->spec_salt)
   x.coef = 1.0f;
-  if (x.blk == 0 && x.tid == 0) a.hdr->spart_n = a.nbC + a.nbI + a.nbU + a.nbH;
+  if (x.blk == 0 && x.tid == 0) a.hdr->spart_n[x.salt & 1] = a.nbC + a.nbI + a.nbU + a.nbH;
   if (x.blk < a.nbH) {          // hot item rows lead the row workgroups
     presum_hot_block<NI, true, DT>(a, x.blk, shd, shp, &x);
     return;
@@ -2511,12 +2523,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? SPEC
       apply_cate_block<AP_PRESUM, true, NC, DT, true>(a, x, shd, shp, sh_pos, sh_lo, sh_n, sh_wtot);
     } else {
       // (the row blocks' records follow the commit launch's category blocks': [nbC | nbI | nbU].  Two-pass user blocks are the
-      //  longer ones and lead the item blocks -- the launch ends when its last-placed blocks do)
+      //  longer ones and lead the item blocks (a.ufirst) -- the launch ends when its last-placed blocks do)
       int rb = x.blk - nbCg;
       const int nbIl = a.nbI_l > 0 ? a.nbI_l : a.nbI;     // item-row workgroups launched (ApplyArgs.nbI_l)
-      const bool ufirst = a.WU > 128;
-      const bool is_user = ufirst ? rb < a.nbU : rb >= nbIl;
-      if (is_user) rb -= ufirst ? 0 : nbIl; else rb -= ufirst ? a.nbU : 0;
+      const bool uf = a.ufirst != 0;
+      const bool is_user = uf ? rb < a.nbU : rb >= nbIl;
+      if (is_user) rb -= uf ? 0 : nbIl; else rb -= uf ? a.nbU : 0;
       x.blk = a.nbC + (is_user ? a.nbI : 0) + rb;
       if (!is_user) {
         const int nuq = *a.n_uniq_item;
@@ -2527,7 +2539,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? SPEC
         }
       } else {
         apply_rows_block<AP_UPDATE, true, false, NU, AP_OWN / 2, DT>(a, x, rb * AP_ROWS_PB, shp);
-        if (ufirst) {                        // the second half of a wide user row (its change of the sum of squares: added to the record)
+        if (a.WU > 128) {                    // the second half of a wide user row (its change of the sum of squares: added to the record)
           __syncthreads();
           x.accum = true;
           apply_rows_block<AP_UPDATE, true, false, NU, AP_OWN / 2, DT, NU>(a, x, rb * AP_ROWS_PB, shp);
@@ -2605,7 +2617,7 @@ __global__ __launch_bounds__(256) void k_spec_commit(ApplyArgs a) {
       const float Pp = a.hdr->P_prev;
       const int cb = (int)blockIdx.x - a.nbD;
       const double part = update_cate_rows<NC, DT>(a, cb * 16 + (tid >> 4), tid & 15, st_true / (Pp * (1.0f - st_true * a.reg)), a.hdr->spec_salt);
-      block_delta_store(part, shp, &a.delta_out[cb], a.hdr->spec_salt);
+      block_delta_store(part, shp, a, cb, a.hdr->spec_salt);
       return;
     }
   }
@@ -2680,7 +2692,7 @@ __global__ __launch_bounds__(256) void k_update_lazy(ApplyArgs a, int nbC16) {
   const float step = a.lr * a.hdr->coef;
   const float lazy_scale = step / (P * (1.0f - step * a.reg));
   const uint32_t salt = a.hdr->nstep;
-  if (blk == 0 && tid == 0) a.hdr->spart_n = nbC16 + a.nbI + a.nbU;
+  if (blk == 0 && tid == 0) a.hdr->spart_n[salt & 1] = nbC16 + a.nbI + a.nbU;
   double part = 0.0;
   if (blk < nbC16) {
     part = update_cate_rows<NC, DT>(a, blk * 16 + gid, l16, lazy_scale, salt);
@@ -2765,7 +2777,7 @@ __global__ __launch_bounds__(256) void k_update_lazy(ApplyArgs a, int nbC16) {
     }
     return;
   }
-  block_delta_store(part, shp, &a.delta_out[blk], salt);
+  block_delta_store(part, shp, a, blk, salt);
 }
 
 
