@@ -370,6 +370,31 @@ int tlsan_eval_topk(const tlsan_dims* dims, const tlsan_params* p, const float* 
 int tlsan_topk_merge(const int32_t* cand_ids, const float* cand_scores, int32_t B, int32_t n_lists, int32_t K,
                      int32_t* ids, float* scores, void* stream);
 
+/* Scores of caller-given candidates (a re-ranking of a retrieval stage's items, or a sampled evaluation):
+ *   scores[b, c] = u_t[b] . [item_emb || cate_emb[item_cate]][g] + item_b[g],  g = cand[b, c] (global id),
+ * for u_t [B, d], cand [B, C] int32, scores [B, C] float32.  Each score equals tlsan_eval_label_scores' for the
+ * same (row, item) bit for bit -- and so a tlsan_eval_topk list entry's -- with lazy L2 (P != 1) and bf16 tables.
+ *   Whole table (id_mul == 1, id_add == 0): ids outside 0 .. item_count-1 (the padding -1 among them) score -inf.
+ *   Item-sharded form: local item n is global id n * id_mul + id_add, as in tlsan_eval_counts_shard; a candidate
+ *     this table does not hold is skipped and its score left untouched (each rank scores its own ids).
+ * The result does not depend on B, C, on the other rows of the launch or on the launch geometry.  B, C >= 1. */
+int tlsan_score_candidates(const tlsan_dims* dims, const tlsan_params* p, const float* u_t, int32_t B, int32_t C,
+                           const int32_t* cand, int32_t id_mul, int32_t id_add, float* scores, void* stream);
+/* ranks[b] = how many candidates c >= 1 of row b come ahead of candidate 0 (the label) in tf.nn.top_k's order, as
+ * tlsan_eval_topk orders: higher score first, equal scores -> lower global id first; +0.0 == -0.0; a NaN score
+ * comes after every other score.  Candidates with a negative id (padding) and repeats of candidate 0's id are not
+ * counted.  With every other item as a candidate this is tlsan_eval_ranks' rank.  cand, scores [B, C]. */
+int tlsan_candidate_ranks(const int32_t* cand, const float* scores, int32_t B, int32_t C, int32_t* ranks, void* stream);
+/* N distinct negatives per row, 1 <= N <= 1024, reproducible from their definition alone.  Row b is the global row
+ * row = row0 + b; with splitmix64 the standard finaliser (uint64 arithmetic, wrapping), draw t = 0, 1, 2, ... of the
+ * row is the item  ((key >> 32) * item_count) >> 32,  key = splitmix64(splitmix64(seed ^ row) ^ t).
+ * out[b] holds the first N distinct items of that sequence that are eligible -- not labels[b], not in the row's
+ * exclusion list (excl_off [B + 1] / excl_ids, both NULL for none: as tlsan_eval_topk's) -- among the first 64 N
+ * draws; slots left unfilled hold -1.  The result depends on (seed, row, label, exclusion list, item_count, N) only:
+ * not on B, the chunking of the rows, the launch geometry or the number of ranks.  out [B, N] int32. */
+int tlsan_sample_negatives(int32_t item_count, const int32_t* labels, int32_t B, int32_t N, uint64_t seed, int64_t row0,
+                           const int32_t* excl_off, const int32_t* excl_ids, int32_t* out, void* stream);
+
 /* Deterministic scatter-apply on one row table (the owner-side half of the multi-GPU step, and
  * the stand-alone form of the embedding update of model.py:198-205):
  *   for every row r < nrows:  g = gscale * sum_{k: dest[k]==r} grows[k] (+ reg * W[r] on the

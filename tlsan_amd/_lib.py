@@ -18,13 +18,15 @@ INDEX_FOR_LAZY_SGD = 0x100   # TLSAN_INDEX_FOR_LAZY_SGD (include/tlsan.h)
 INDEX_SLOTS = 3   # TLSAN_INDEX_SLOTS (csrc/tlsan_update.h): destination-index slots of the state
 SN_CAP = 96     # TLSAN_SN_CAP (csrc/tlsan_common.h): longest session of a training batch
 TOPK_MAX = 256  # TOPK_MAX (csrc/tlsan_topk.h): largest K of tlsan_eval_topk
+NEG_MAX = 1024  # NEG_MAX (csrc/tlsan_cand.h): largest N of tlsan_sample_negatives
 
 EXPORTS = [
     "tlsan_abi_version", "tlsan_last_error", "tlsan_dense_layout_of", "tlsan_workspace_bytes",
     "tlsan_state_bytes", "tlsan_state_init", "tlsan_state_reindex", "tlsan_state_recategorize", "tlsan_state_scale",
     "tlsan_state_renorm", "tlsan_sync_derived", "tlsan_forward", "tlsan_forward_att",
     "tlsan_train_step", "tlsan_train_step_opt", "tlsan_batch_pack", "tlsan_batch_index", "tlsan_grads", "tlsan_eval_ranks", "tlsan_eval_label_scores", "tlsan_eval_counts_shard",
-    "tlsan_topk_workspace_bytes", "tlsan_eval_topk", "tlsan_topk_merge", "tlsan_profile_enable", "tlsan_profile_stride",
+    "tlsan_topk_workspace_bytes", "tlsan_eval_topk", "tlsan_topk_merge",
+    "tlsan_score_candidates", "tlsan_candidate_ranks", "tlsan_sample_negatives", "tlsan_profile_enable", "tlsan_profile_stride",
     "tlsan_profile_collect", "tlsan_debug_stamps", "tlsan_rows_apply_workspace", "tlsan_rows_apply", "tlsan_scan_compact",
     "tlsan_route_plan", "tlsan_shard_gather", "tlsan_shard_summary", "tlsan_shard_apply_workspace", "tlsan_shard_apply",
     "tlsan_shard_summary_opt", "tlsan_shard_apply_opt", "tlsan_shard_apply_lazy_workspace", "tlsan_shard_apply_lazy",
@@ -186,6 +188,14 @@ def load():
     lib.tlsan_topk_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p]
     lib.tlsan_topk_merge.restype = C.c_int
+    lib.tlsan_score_candidates.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                           C.c_int32, C.c_void_p, C.c_void_p]
+    lib.tlsan_score_candidates.restype = C.c_int
+    lib.tlsan_candidate_ranks.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.tlsan_candidate_ranks.restype = C.c_int
+    lib.tlsan_sample_negatives.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.tlsan_sample_negatives.restype = C.c_int
     lib.tlsan_profile_enable.argtypes = [C.c_int]
     lib.tlsan_profile_enable.restype = C.c_int
     lib.tlsan_profile_stride.argtypes = [C.c_int]

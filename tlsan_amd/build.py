@@ -1,5 +1,6 @@
-"""Build libtlsan_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: thirteen translation
-units (the C ABI with every kernel but the fused one and the top-K selection; the top-K selection; k_fwd_bwd for d = 64 / 128 / 128 as 8-sample workgroups / 256 with
+"""Build libtlsan_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: fourteen translation
+units (the C ABI with every kernel but the fused one, the top-K selection and the candidate kernels; the top-K selection;
+the candidate scoring, ranks and negative sampling; k_fwd_bwd for d = 64 / 128 / 128 as 8-sample workgroups / 256 with
 the window in registers / 256 streamed, all with 8 heads; k_fwd_bwd and the dense finalize kernels for each of the
 pairs 64/4, 128/16 and 128/4) compiled in parallel, one link.  `python -m tlsan_amd.build` or `build()`."""
 from __future__ import annotations
@@ -13,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libtlsan_hip.so")
-SOURCES = ["tlsan_api.hip", "tlsan_topk.hip", "tlsan_attn_d64.hip", "tlsan_attn_d128.hip", "tlsan_attn_d128w4.hip", "tlsan_attn_d256.hip", "tlsan_attn_d256s.hip",
+SOURCES = ["tlsan_api.hip", "tlsan_topk.hip", "tlsan_cand.hip", "tlsan_attn_d64.hip", "tlsan_attn_d128.hip", "tlsan_attn_d128w4.hip", "tlsan_attn_d256.hip", "tlsan_attn_d256s.hip",
            "tlsan_attn_d64h4.hip", "tlsan_attn_d128h16.hip", "tlsan_attn_d128h4.hip",
            "tlsan_update_d64h4.hip", "tlsan_update_d128h16.hip", "tlsan_update_d128h4.hip"]
 # per-source extra flags (see the source's header comment)
@@ -34,7 +35,8 @@ if os.environ.get("TLSAN_SOURCE_FLAGS"):   # (experiments: JSON {source: [flags]
     import json
     SOURCE_FLAGS.update(json.loads(os.environ["TLSAN_SOURCE_FLAGS"]))
 # headers only some units include (the others do not rebuild when they change)
-SOURCE_HEADERS = {"tlsan_api.hip": ["tlsan_topk.h"], "tlsan_topk.hip": ["tlsan_topk.h"]}
+SOURCE_HEADERS = {"tlsan_api.hip": ["tlsan_topk.h", "tlsan_cand.h"], "tlsan_topk.hip": ["tlsan_topk.h"],
+                  "tlsan_cand.hip": ["tlsan_topk.h", "tlsan_cand.h"]}
 HEADERS = ["tlsan_common.h", "tlsan_attn.h", "tlsan_attn_inst.h", "tlsan_update.h", "tlsan_update_inst.h", "tlsan_eval.h", "tlsan_rows.h", "tlsan_shard.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC] + \
         os.environ.get("TLSAN_HIPCC_EXTRA", "").split()   # (experiments: extra compiler flags)

@@ -15,6 +15,7 @@
 #include "tlsan_common.h"
 #include "tlsan_eval.h"
 #include "tlsan_topk.h"
+#include "tlsan_cand.h"
 #include "tlsan_update.h"
 #include "tlsan_update_inst.h"
 #include "tlsan_shard.h"
@@ -35,6 +36,10 @@ void tlsan_launch_finalize_d128h4(const FinLaunch& L, hipStream_t hs);
 hipError_t tlsan_launch_topk(const TopkArgs& a, int D, int nslices, hipStream_t hs);
 hipError_t tlsan_launch_topk_merge(const int32_t* cid, const float* csc, int B, int nl, int K, int32_t* ids, float* scores,
                                    hipStream_t hs);
+// candidate scoring, candidate ranks, negative sampling (tlsan_cand.hip)
+hipError_t tlsan_launch_score_cand(const CandArgs& a, int D, hipStream_t hs);
+hipError_t tlsan_launch_cand_ranks(const int32_t* cand, const float* scores, int B, int C, int32_t* ranks, hipStream_t hs);
+hipError_t tlsan_launch_sample_neg(const NegArgs& a, hipStream_t hs);
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, ...) {
@@ -1370,6 +1375,52 @@ int tlsan_topk_merge(const int32_t* cand_ids, const float* cand_scores, int32_t 
   if ((long long)n_lists * K >= (1LL << 30)) return fail(TLSAN_E_UNSUPPORTED, "tlsan_topk_merge: n_lists * K too large");
   const hipError_t err = tlsan_launch_topk_merge(cand_ids, cand_scores, B, n_lists, K, ids, scores, (hipStream_t)stream);
   if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_topk_merge: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+// ---- caller-given candidates (tlsan_cand.h) ----
+int tlsan_score_candidates(const tlsan_dims* d, const tlsan_params* p, const float* u_t, int32_t B, int32_t C,
+                           const int32_t* cand, int32_t id_mul, int32_t id_add, float* scores, void* stream) {
+  Shape s;
+  int rc = shape_of(d, &s);
+  if (rc) return rc;
+  if ((rc = check_params(p))) return rc;
+  if (!u_t || !cand || !scores) return fail(TLSAN_E_BADARG, "tlsan_score_candidates: NULL argument");
+  if (B < 1 || C < 1) return fail(TLSAN_E_BADARG, "tlsan_score_candidates: B and C must be >= 1 (got %d, %d)", B, C);
+  if ((long long)B * C >= (1LL << 31)) return fail(TLSAN_E_UNSUPPORTED, "tlsan_score_candidates: B * C overflows int32");
+  if (id_mul < 1 || id_add < 0 || (long long)(d->item_count - 1) * id_mul + id_add >= (1LL << 31))
+    return fail(TLSAN_E_BADARG, "tlsan_score_candidates: global ids n * id_mul + id_add must be non-negative int32");
+  CandArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  EvalArgs& e = ca.e;
+  e.p = norm_params(p, d); e.u_t = u_t; e.B = B; e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate;
+  e.id_mul = id_mul; e.id_add = id_add;
+  ca.C = C; ca.cand = cand; ca.scores = scores;
+  const hipError_t err = tlsan_launch_score_cand(ca, s.D, (hipStream_t)stream);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_score_cand: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+int tlsan_candidate_ranks(const int32_t* cand, const float* scores, int32_t B, int32_t C, int32_t* ranks, void* stream) {
+  if (!cand || !scores || !ranks) return fail(TLSAN_E_BADARG, "tlsan_candidate_ranks: NULL argument");
+  if (B < 1 || C < 1) return fail(TLSAN_E_BADARG, "tlsan_candidate_ranks: B and C must be >= 1 (got %d, %d)", B, C);
+  const hipError_t err = tlsan_launch_cand_ranks(cand, scores, B, C, ranks, (hipStream_t)stream);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_cand_ranks: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+int tlsan_sample_negatives(int32_t item_count, const int32_t* labels, int32_t B, int32_t N, uint64_t seed, int64_t row0,
+                           const int32_t* excl_off, const int32_t* excl_ids, int32_t* out, void* stream) {
+  if (!labels || !out) return fail(TLSAN_E_BADARG, "tlsan_sample_negatives: NULL argument");
+  if (item_count < 1 || B < 1) return fail(TLSAN_E_BADARG, "tlsan_sample_negatives: item_count and B must be >= 1");
+  if (N < 1 || N > NEG_MAX) return fail(TLSAN_E_BADARG, "tlsan_sample_negatives: N must be in 1..%d (got %d)", NEG_MAX, N);
+  if (!excl_off != !excl_ids) return fail(TLSAN_E_BADARG, "tlsan_sample_negatives: excl_off and excl_ids go together");
+  NegArgs na;
+  memset(&na, 0, sizeof(na));
+  na.item_count = item_count; na.B = B; na.N = N; na.seed = seed; na.row0 = row0;
+  na.labels = labels; na.excl_off = excl_off; na.excl_ids = excl_ids; na.out = out;
+  const hipError_t err = tlsan_launch_sample_neg(na, (hipStream_t)stream);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_sample_neg: %s", hipGetErrorString(err));
   return TLSAN_OK;
 }
 

@@ -1,0 +1,93 @@
+// tlsan_cand.h -- scores of caller-given candidate items, their ranks, and the sampled-negatives evaluation.
+//
+// k_score_cand: scores[b, c] = u_t[b] . [item_emb || cate_emb[item_cate]][g] * P + item_b[g] for g = cand[b, c], in the
+// form of k_eval_label: a wavefront holds the A fragments of 16 rows (load_user_frag) and, for each candidate column
+// c, scores one 16x16 tile whose lane column r is row r's candidate (score_tile) and keeps the diagonal.  The diagonal
+// element is the same MFMA chain on the same operands as the label's own score, and the two roundings (* P, + bias)
+// are kept apart, so a candidate's score equals tlsan_eval_label_scores' (and a tlsan_eval_topk list entry's) bit for
+// bit.  One MFMA column in 16 is kept; the kernel is bound by the row gathers, not by the matrix pipe.
+//
+// k_cand_ranks (tlsan_cand.hip): how many candidates c >= 1 of a row come ahead of candidate 0, in tf.nn.top_k's
+// order (topk_key).
+//
+// k_sample_neg (tlsan_cand.hip): the first N distinct eligible items of the row's draw sequence (cand_draw); the
+// definition is in include/tlsan.h.
+#pragma once
+#include "tlsan_eval.h"
+#include "tlsan_topk.h"
+
+#define NEG_MAX 1024
+
+struct CandArgs {
+  EvalArgs e;               // scoring: p, u_t, B, I, di, dc, id_mul, id_add (labels, s_label, ranks, all_emb unused)
+  int32_t C;
+  const int32_t* cand;      // [B, C] global item ids
+  float* scores;            // [B, C]
+};
+
+// Local item of global id g, or -1 when this table does not hold it.
+__device__ __forceinline__ int cand_local(int g, int I, int id_mul, int id_add) {
+  if (g < id_add) return -1;
+  const int o = g - id_add;
+  const int n = id_mul == 1 ? o : o / id_mul;
+  return (n * id_mul == o && n < I) ? n : -1;
+}
+
+// grid (ceil(B/16), slices); wavefront w of slice y scores columns c = (y * 4 + w) + k * 4 * slices.
+template <int D>
+__global__ __launch_bounds__(256) void k_score_cand(CandArgs ca) {
+  // (score = (acc * P) + bias in two roundings, as k_eval_label forms the label's score)
+#pragma clang fp contract(off)
+  const EvalArgs& a = ca.e;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
+  const int u0 = blockIdx.x * 16, u = u0 + r;
+  const bool uv = u < a.B;
+  const bool whole = a.id_mul == 1 && a.id_add == 0;   // whole table: ids outside it score -inf (else: not ours, skipped)
+  f32x4 af[D / 16];
+  load_user_frag<D>(a, u0, q, r, af);
+  const float P = a.p.scale ? *a.p.scale : 1.0f;
+  const int32_t* crow = ca.cand + (size_t)(uv ? u : 0) * ca.C;
+  float* srow = ca.scores + (size_t)(uv ? u : 0) * ca.C;
+  for (int c = blockIdx.y * 4 + wave; c < ca.C; c += gridDim.y * 4) {
+    const int n = uv ? cand_local(crow[c], a.I, a.id_mul, a.id_add) : -1;
+    const int item = n >= 0 ? n : 0;
+    const f32x4 acc = score_tile<D>(a, af, item, q) * P;
+    const float bias = a.p.item_b[(size_t)item * a.p.ld_itemb];
+    // diagonal: row (4q+i) == column r
+    if (uv && q == (r >> 2)) {
+      float v = acc[0];
+      if ((r & 3) == 1) v = acc[1];
+      if ((r & 3) == 2) v = acc[2];
+      if ((r & 3) == 3) v = acc[3];
+      if (n >= 0) srow[c] = v + bias;
+      else if (whole) srow[c] = -__builtin_inff();
+    }
+  }
+}
+
+__device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
+  z += 0x9e3779b97f4a7c15ull;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+
+// item of draw t of a row whose stream is h = splitmix64(seed ^ row)
+__device__ __forceinline__ int cand_draw(uint64_t h, uint64_t t, int item_count) {
+  const uint64_t key = splitmix64(h ^ t);
+  return (int)(((key >> 32) * (uint64_t)item_count) >> 32);
+}
+
+#define NEG_HASH (2 * NEG_MAX)   // LDS open-addressing set of the row's accepted items (load <= 1/2)
+
+struct NegArgs {
+  int32_t item_count, B, N;
+  uint64_t seed;
+  int64_t row0;
+  const int32_t* labels;    // [B]
+  const int32_t* excl_off;  // [B + 1] or NULL
+  const int32_t* excl_ids;
+  int32_t* out;             // [B, N]
+};
+
+__device__ __forceinline__ unsigned neg_slot(int item) { return ((unsigned)item * 2654435761u) >> 21; }  // 11 bits

@@ -1395,6 +1395,68 @@ class ShardedModel:
         torch.cuda.current_stream(self.device).synchronize()   # `table` stays alive until done
         return cid, csc
 
+    def _forward_ut(self, db):
+        """u_t [B, d] of this rank's rows (the forward on the compact table) and the fetched table, which must stay alive
+        until the work that follows has run."""
+        sl = self._plan_eval(db)
+        table = self._fetch(sl)
+        dims, cp, cb = self._compact(db, sl, table)
+        li = torch.empty(db.B, dtype=torch.float32, device=self.device)
+        ut = torch.empty(db.B, self.d, dtype=torch.float32, device=self.device)
+        L.check(self.lib.tlsan_forward(C.byref(dims), C.byref(cp), C.byref(cb), li.data_ptr(), None, ut.data_ptr(),
+                                       None, 0, self._stream()), "tlsan_forward")
+        return ut, table
+
+    def _score_owned(self, ut, cand):
+        """Scores of this rank's rows' candidates (u_t [B, d], cand [B, C] global ids; every rank calls it with the same
+        C): u_t and the ids are all-gathered, every rank scores the ids of ITS item shard (global id n * world + rank)
+        for all rows, one all-to-all returns each row's scores to its owner, which SELECTS each candidate's score from
+        the rank that holds the id (a sum would turn -0 into +0).  Padding and ids outside the table score -inf."""
+        from .model import score_candidates
+        B, Cn = cand.shape
+        ut_all, cand_all = allgather_rows(ut, self.group), allgather_rows(cand, self.group)
+        sc = torch.full((int(ut_all.shape[0]), Cn), float("-inf"), dtype=torch.float32, device=self.device)
+        nloc, ldims, lp = self._item_shard()
+        if nloc > 0:
+            score_candidates(self.lib, ldims, lp, ut_all, cand_all, self.world, self.rank, self._stream(), scores=sc)
+        if self.world == 1:
+            return sc
+        # rows [r B, (r + 1) B) belong to rank r: block s of what arrives is rank s's scores of this rank's rows
+        got = torch.empty_like(sc)
+        a2a(got, sc, None, None, self.group)
+        owner = torch.where(cand >= 0, cand % self.world, torch.zeros_like(cand)).long()
+        return torch.gather(got.view(self.world, B, Cn), 0, owner[None]).view(B, Cn)
+
+    def score_candidates(self, batch, candidates):
+        """Model.score_candidates for this rank's rows (every rank calls it, with the same C).  Same scores, bit for
+        bit."""
+        from .model import candidate_tensor
+        db = self.device_batch(batch, is_test=True)
+        ut, table = self._forward_ut(db)
+        sc = self._score_owned(ut, candidate_tensor(candidates, db.B, self.device))
+        torch.cuda.current_stream(self.device).synchronize()   # `table` stays alive until done
+        return sc
+
+    def sample_negatives(self, batch, n, seed=1234, row0=0, exclude="history"):
+        """Model.sample_negatives for this rank's rows; row0 is the GLOBAL index of this rank's first row.  No
+        collective: a row's negatives depend on (seed, row, label, exclusion, n) only."""
+        from .model import exclusion_csr, sample_negatives
+        db = self.device_batch(batch, is_test=True)
+        return sample_negatives(self.lib, self.I, db.i, n, seed, row0, exclusion_csr(db, exclude, self.I), self._stream())
+
+    def sampled_ranks(self, batch, n, seed=1234, row0=0, exclude="history"):
+        """Model.sampled_ranks for this rank's rows (every rank calls it, with the same n); row0 is the GLOBAL index of
+        this rank's first row.  Same ranks as Model.sampled_ranks."""
+        from .model import candidate_ranks, exclusion_csr, sample_negatives
+        db = self.device_batch(batch, is_test=True)
+        ut, table = self._forward_ut(db)
+        st = self._stream()
+        neg = sample_negatives(self.lib, self.I, db.i, n, seed, row0, exclusion_csr(db, exclude, self.I), st)
+        cand = torch.cat([db.i.view(-1, 1).to(torch.int32), neg], 1).contiguous()
+        ranks = candidate_ranks(self.lib, cand, self._score_owned(ut, cand), st)
+        torch.cuda.current_stream(self.device).synchronize()   # `table` stays alive until done
+        return ranks
+
     def _hits(self, batch, n_valid=None):
         from .model import KS
         r = self.label_ranks(batch)

@@ -202,6 +202,84 @@ def topk_merge(lib, cand_ids, cand_scores, stream):
     return ids, scores
 
 
+def candidate_tensor(candidates, B, device):
+    """[B, C] global item ids (array or tensor, -1 = padding) -> contiguous int32 device tensor."""
+    if isinstance(candidates, torch.Tensor):
+        cand = candidates.to(device=device, dtype=torch.int32)
+    else:
+        cand = torch.as_tensor(np.asarray(candidates, np.int64).astype(np.int32)).to(device)
+    if cand.dim() != 2 or cand.shape[0] != B or cand.shape[1] < 1:
+        raise ValueError("candidates: want a [%d, C] array of item ids, got shape %s" % (B, tuple(cand.shape)))
+    return cand.contiguous()
+
+
+def score_candidates(lib, dims, cparams, ut, cand, id_mul, id_add, stream, scores=None):
+    """tlsan_score_candidates on u_t [B, d] and cand [B, C] int32 -> scores [B, C] float32 (written into `scores` when
+    given: the item-sharded form leaves the ids it does not hold untouched)."""
+    B, Cn = cand.shape
+    if scores is None:
+        scores = torch.empty(B, Cn, dtype=torch.float32, device=cand.device)
+    L.check(lib.tlsan_score_candidates(C.byref(dims), C.byref(cparams), ut.data_ptr(), B, Cn, cand.data_ptr(), id_mul,
+                                       id_add, scores.data_ptr(), stream), "tlsan_score_candidates")
+    return scores
+
+
+def candidate_ranks(lib, cand, scores, stream):
+    """tlsan_candidate_ranks: how many of each row's candidates 1.. come ahead of candidate 0 -> [B] int32."""
+    B, Cn = cand.shape
+    ranks = torch.empty(B, dtype=torch.int32, device=cand.device)
+    L.check(lib.tlsan_candidate_ranks(cand.data_ptr(), scores.contiguous().data_ptr(), B, Cn, ranks.data_ptr(), stream),
+            "tlsan_candidate_ranks")
+    return ranks
+
+
+def sample_negatives(lib, item_count, labels, n, seed, row0, excl, stream):
+    """tlsan_sample_negatives for the rows of labels [B] int32 (global row row0 + b) -> [B, n] int32."""
+    B = int(labels.shape[0])
+    out = torch.empty(B, int(n), dtype=torch.int32, device=labels.device)
+    off, xid = excl
+    L.check(lib.tlsan_sample_negatives(int(item_count), labels.contiguous().data_ptr(), B, int(n),
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(row0), None if off is None else off.data_ptr(),
+                                       None if xid is None else xid.data_ptr(), out.data_ptr(), stream),
+            "tlsan_sample_negatives")
+    return out
+
+
+SAMPLED_KS = (1, 5, 10, 20)
+
+
+def rank_histogram(ranks, n):
+    """[n + 1] int64 counts of the sampled ranks 0 .. n (what sampled_metrics needs: sums of counts are exact, so the
+    metrics do not depend on how the rows were split into launches or ranks)."""
+    r = np.asarray(ranks.cpu().numpy() if isinstance(ranks, torch.Tensor) else ranks, np.int64).reshape(-1)
+    if r.size and (r.min() < 0 or r.max() > n):
+        raise ValueError("sampled ranks must lie in 0..%d" % n)
+    return np.bincount(r, minlength=n + 1).astype(np.int64)
+
+
+def metrics_from_histogram(hist, n, ks=SAMPLED_KS):
+    """The sampled-evaluation metrics of a rank histogram (rank_histogram), summed in float64:
+    HR@k = mean(rank < k), NDCG@k = mean([rank < k] / log2(rank + 2)), MRR = mean(1 / (rank + 1)),
+    AUC_N = mean(1 - rank / n)."""
+    hist = np.asarray(hist, np.int64)
+    rows = int(hist.sum())
+    r = np.arange(len(hist), dtype=np.float64)
+    h = hist.astype(np.float64)
+    out = {}
+    for k in ks:
+        out["HR@%d" % k] = float(hist[:k].sum()) / rows
+    for k in ks:
+        out["NDCG@%d" % k] = float((h[:k] / np.log2(r[:k] + 2.0)).sum()) / rows
+    out["MRR"] = float((h / (r + 1.0)).sum()) / rows
+    out["AUC_N"] = 1.0 - float(int((hist * np.arange(len(hist), dtype=np.int64)).sum())) / (float(n) * rows)
+    return out
+
+
+def sampled_metrics(ranks, n, ks=SAMPLED_KS):
+    """HR@k, NDCG@k, MRR and AUC_N of the ranks of the labels among n sampled negatives (Model.sampled_ranks)."""
+    return metrics_from_histogram(rank_histogram(ranks, n), n, ks)
+
+
 class DeviceBatch:
     """The placeholders of model.py:27-53 as int32 / fp32 device tensors + the C struct."""
 
@@ -819,6 +897,33 @@ class Model(object):
         _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
         return eval_topk(self.lib, self.dims, self.cparams, ut, db.B, k, exclusion_csr(db, exclude, self.config["item_count"]),
                          1, 0, self._topk_workspace, self._stream())
+
+    def score_candidates(self, batch, candidates):
+        """Scores of caller-given items: candidates [B, C] global item ids (array or tensor; -1 = padding, which scores
+        -inf) -> [B, C] float32 device tensor, u_t[b] . [item_emb || cate_emb[item_cate]][g] + item_b[g].  A score
+        equals label_ranks' / recommend's for the same (row, item) bit for bit."""
+        _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
+        cand = candidate_tensor(candidates, db.B, self.device)
+        return score_candidates(self.lib, self.dims, self.cparams, ut, cand, 1, 0, self._stream())
+
+    def sample_negatives(self, batch, n, seed=1234, row0=0, exclude="history"):
+        """n distinct negatives per row -> [B, n] int32 device tensor (-1 where fewer are found): the first n eligible
+        items of row (row0 + b)'s draw sequence under `seed` (tlsan_sample_negatives; never the label, never an item
+        of `exclude`, which takes recommend's forms).  Depends on (seed, row0 + b, label, exclusion, n) only."""
+        db = self.device_batch(batch, is_test=True)
+        return sample_negatives(self.lib, self.config["item_count"], db.i, n, seed, row0,
+                                exclusion_csr(db, exclude, self.config["item_count"]), self._stream())
+
+    def sampled_ranks(self, batch, n, seed=1234, row0=0, exclude="history"):
+        """Rank of each row's label among its n sampled negatives (sample_negatives) -> [B] int32 device tensor: one
+        forward, one sampling, one scoring of [label | negatives], one ranking; no host round trip."""
+        _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
+        st = self._stream()
+        neg = sample_negatives(self.lib, self.config["item_count"], db.i, n, seed, row0,
+                               exclusion_csr(db, exclude, self.config["item_count"]), st)
+        cand = torch.cat([db.i.view(-1, 1).to(torch.int32), neg], 1).contiguous()
+        scores = score_candidates(self.lib, self.dims, self.cparams, ut, cand, 1, 0, st)
+        return candidate_ranks(self.lib, cand, scores, st)
 
     def _topk_workspace(self, nbytes):
         if getattr(self, "_tws", None) is None or self._tws.numel() < nbytes:

@@ -23,7 +23,7 @@ import time
 import numpy as np
 
 from .input import DataInput, DataInputTest, PackedSet, load_packed
-from .model import KS, Model
+from .model import KS, Model, metrics_from_histogram
 
 FLAGS = [  # (name, type, default)  -- train.py:26-54
     ("hidden_units", int, 64), ("num_blocks", int, 1), ("num_heads", int, 8), ("Ls", int, 10),
@@ -73,7 +73,20 @@ def parse(argv=None):
     ap.add_argument("--recommend_exclude", default="history", choices=["history", "none"],
                     help="items kept out of the recommendations: 'history' = the items the test row's input holds (its "
                          "last Ls items and its current session -- what the batch carries), 'none' = nothing")
+    ap.add_argument("--eval_negatives", type=int, default=0,
+                    help="sampled evaluation at every evaluation point: rank each test label among N sampled negatives "
+                         "and report HR@k, NDCG@k (k = 1, 5, 10, 20), MRR and AUC_N; 0 = off")
+    ap.add_argument("--eval_neg_seed", type=int, default=1234,
+                    help="seed of the negatives (a test row's negatives depend on the seed and its position in the test set)")
+    ap.add_argument("--eval_neg_exclude", default="history", choices=["history", "none"],
+                    help="items never drawn as a row's negatives besides its label: 'history' = the items the test row's "
+                         "input holds, 'none' = nothing")
     return ap.parse_args(argv)
+
+
+def sampled_line(n, res):
+    """The driver's line of sampled metrics (metrics_from_histogram's dict)."""
+    return "Sampled N=%d: " % n + " ".join("%s = %.4f" % (k, v) for k, v in res.items())
 
 
 def recommend_path(model_dir, k):
@@ -199,6 +212,22 @@ def recommend_test_set(model, test_set, config, k, exclude):
     return tuple(torch.cat(x).cpu().numpy() for x in (users, ids, scores))
 
 
+def eval_sampled(model, test_set, config, n, seed, exclude):
+    """HR@k / NDCG@k / MRR / AUC_N of every test label among n sampled negatives (Model.sampled_ranks), in launches of
+    EVAL_CHUNK rows.  A row's negatives depend on its position in the test set (row0), so the result does not depend on
+    the chunking; the ranks are counted on the device (exact sums) and read once."""
+    import torch
+    chunk = max(EVAL_CHUNK, config["test_batch_size"]) // config["test_batch_size"] * config["test_batch_size"]
+    hist = None
+    for bi, batch in _test_batches(test_set, config, chunk):
+        r = model.sampled_ranks(batch, n, seed=seed, row0=(bi - 1) * chunk, exclude=None if exclude == "none" else exclude)
+        h = torch.bincount(r.long(), minlength=n + 1)
+        hist = h if hist is None else hist + h
+    res = metrics_from_histogram(hist.cpu().numpy(), n)
+    model.eval_writer.add_summary(list(res.items()), global_step=model.global_step.eval())
+    return res
+
+
 def train(args, data=None):
     """data (optional): (train PackedSet, test PackedSet, (U, I, C), item_cate_list) already in memory
     (tlsan_amd.build_dataset.build_packed) instead of --dataset."""
@@ -224,6 +253,9 @@ def train(args, data=None):
     t0 = time.time()
     init_auc = eval_auc(model, test_set, config)
     say("Init AUC: %.4f" % init_auc)
+    sampled = lambda: eval_sampled(model, test_set, config, args.eval_negatives, args.eval_neg_seed, args.eval_neg_exclude)
+    if args.eval_negatives:
+        say(sampled_line(args.eval_negatives, sampled()))
     lr = args.learning_rate
     rng = epoch_rng(args.shuffle_seed)  # train.py:15,191
     best_auc, history = 0.0, []
@@ -250,6 +282,8 @@ def train(args, data=None):
                 say("Epoch %d Global_step %d\tTrain_loss: %.4f\tEval_auc: %.4f" %
                     (model.global_epoch_step.eval(), step, float(loss_sum.item()) / args.eval_freq, auc), flush=True)
                 loss_sum.zero_()
+                if args.eval_negatives:
+                    say(sampled_line(args.eval_negatives, sampled()))
                 if args.eval_topk:                             # train.py:209-218: P@k / R@k at every evaluation
                     prec, recall = eval_prec_recall(model, test_set, config)
                     say("Precision:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, prec)))
@@ -274,6 +308,7 @@ def train(args, data=None):
         prec, recall = eval_prec_recall(model, test_set, config)
     final_auc = eval_auc(model, test_set, config)
     best_auc = max(best_auc, final_auc)
+    final_sampled = sampled() if args.eval_negatives else None
     model.save(None)                                           # train.py:239
     if args.recommend_k:
         path = write_recommendations(args.model_dir, args.recommend_k,
@@ -284,10 +319,15 @@ def train(args, data=None):
     say("Best test_auc:", best_auc)
     say("Best precision:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, best_prec)))   # :241-248
     say("Best recall:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, best_recall)))
+    if final_sampled is not None:
+        say(sampled_line(args.eval_negatives, final_sampled))
     say("Finished", flush=True)
-    return dict(init_auc=init_auc, best_auc=best_auc, final_auc=final_auc, steps=model.global_step.eval(),
-                seconds=time.time() - t0, history=history, prec=prec, recall=recall,
-                best_prec=best_prec, best_recall=best_recall)
+    res = dict(init_auc=init_auc, best_auc=best_auc, final_auc=final_auc, steps=model.global_step.eval(),
+               seconds=time.time() - t0, history=history, prec=prec, recall=recall,
+               best_prec=best_prec, best_recall=best_recall)
+    if final_sampled is not None:
+        res["sampled"] = final_sampled
+    return res
 
 
 def _lookahead2(it):
@@ -395,9 +435,26 @@ def train_sharded(args):
             recall = model.eval_recall(None, part, n_valid=real)
         return [float(x) for x in prec], [float(x) for x in recall]
 
+    def eval_sampled_():
+        # a rank's rows of a test batch start at the batch's first row + _share's lo; the padding of _equal_share past
+        # the real rows is not counted, and the rank histograms sum exactly over the ranks
+        n, bs = args.eval_negatives, config["test_batch_size"]
+        hist = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        for bi, batch in DataInputTest(test_set, bs, config["Ls"]):
+            part, real = _equal_share(batch, rank, world)
+            row0 = (bi - 1) * bs + len(batch[0]) * rank // world
+            r = model.sampled_ranks(part, n, seed=args.eval_neg_seed, row0=row0,
+                                    exclude=None if args.eval_neg_exclude == "none" else "history")
+            hist += torch.bincount(r[:real].long(), minlength=n + 1)
+        res = metrics_from_histogram(np.asarray(reduce_sum(hist.tolist()), np.int64), n)
+        model.eval_writer.add_summary(list(res.items()), global_step=model.global_step.eval())
+        return res
+
     t0 = time.time()
     init_auc = eval_auc_()
     say("Init AUC: %.4f" % init_auc)
+    if args.eval_negatives:
+        say(sampled_line(args.eval_negatives, eval_sampled_()))
     lr = args.learning_rate
     rng = epoch_rng(args.shuffle_seed)             # train.py:15,191; the same shuffle on every rank
     best_auc, history = 0.0, []
@@ -421,6 +478,8 @@ def train_sharded(args):
                 say("Epoch %d Global_step %d\tTrain_loss: %.4f\tEval_auc: %.4f" %
                     (model.global_epoch_step.eval(), step, float(loss_sum.item()) / args.eval_freq, auc), flush=True)
                 loss_sum.zero_()
+                if args.eval_negatives:
+                    say(sampled_line(args.eval_negatives, eval_sampled_()))
                 if args.eval_topk:
                     prec, recall = eval_pr_()
                     say("Precision:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, prec)))
@@ -445,6 +504,7 @@ def train_sharded(args):
         prec, recall = eval_pr_()
     final_auc = eval_auc_()
     best_auc = max(best_auc, final_auc)
+    final_sampled = eval_sampled_() if args.eval_negatives else None
     model.save(None)
     if args.recommend_k:
         # every rank takes its share of each test batch; rank 0 gathers the shares (in rank order: the batch's order)
@@ -466,10 +526,15 @@ def train_sharded(args):
     model.train_writer.flush()
     model.eval_writer.flush()
     say("Best test_auc:", best_auc)
+    if final_sampled is not None:
+        say(sampled_line(args.eval_negatives, final_sampled))
     say("Finished", flush=True)
-    return dict(init_auc=init_auc, best_auc=best_auc, final_auc=final_auc, steps=model.global_step.eval(),
-                seconds=time.time() - t0, history=history, prec=prec, recall=recall,
-                best_prec=best_prec, best_recall=best_recall, world=world)
+    res = dict(init_auc=init_auc, best_auc=best_auc, final_auc=final_auc, steps=model.global_step.eval(),
+               seconds=time.time() - t0, history=history, prec=prec, recall=recall,
+               best_prec=best_prec, best_recall=best_recall, world=world)
+    if final_sampled is not None:
+        res["sampled"] = final_sampled
+    return res
 
 
 def main(argv=None):
