@@ -1579,10 +1579,36 @@ struct ApCtx {
   bool accum = false; // UPDATE: add the block's change of the sum of squares to its record of this step (k_spec_commit)
 };
 
+// A row workgroup's context: its lanes' roles, its record (blk0: the workgroups that lead the grid) and the step's scalars
+// (lazy_scale: the lazy-L2 step's scale of the exact sum, apply_elem)
+__device__ __forceinline__ ApCtx ap_ctx(const ApplyArgs& a, int blk0, float P, float step, uint32_t salt, float coef) {
+  ApCtx x;
+  x.tid = threadIdx.x; x.wave = x.tid >> 6; x.lane = x.tid & 63; x.grp = x.lane >> 4; x.l16 = x.lane & 15;
+  x.gid = x.wave * 4 + x.grp;  // 16 groups
+  x.blk = blockIdx.x - blk0;
+  x.P = P;
+  x.invP = 1.0f / P;
+  x.step = step;
+  x.lazy_scale = step / (P * (1.0f - step * a.reg));
+  x.salt = salt;
+  x.coef = coef;
+  x.oc.opt = a.opt; x.oc.lr = a.lr; x.oc.b1 = a.ob1; x.oc.b2 = a.ob2; x.oc.eps = a.oeps; x.oc.alpha = a.oalpha;
+  return x;
+}
+
 #define AP_STAMP(k)                                                                      \
   do {                                                                                   \
     if (a.stamps != nullptr && x.tid == 0) a.stamps[(size_t)x.blk * 8 + (k)] = __builtin_amdgcn_s_memtime(); \
   } while (0)
+
+// A dense parameter's new value, and its copy in dense_KT (K transposed) when it is one of K's
+__device__ __forceinline__ void dense_store(const ApplyArgs& a, int nd, float wn) {
+  a.p.dense[nd] = wn;
+  if (nd >= a.lay.K && nd < a.lay.k0) {
+    const int idx = nd - a.lay.K;
+    a.p.dense_KT[(size_t)(idx % a.D) * a.D + idx / a.D] = wn;
+  }
+}
 
 // ================= one category row per workgroup =================
 template <int MODE, bool LAZY, int NCH, int DT, bool CSPLIT = false>
@@ -2332,11 +2358,7 @@ __global__ __launch_bounds__(256) void k_apply(ApplyArgs a) {
             opt_elem(x.oc, wn, x.coef * g, a1, a2);
             a.s1.dense[nd] = a1; a.s2.dense[nd] = a2;
           }
-          a.p.dense[nd] = wn;
-          if (nd >= a.lay.K && nd < a.lay.k0) {
-            const int idx = nd - a.lay.K;
-            a.p.dense_KT[(size_t)(idx % a.D) * a.D + idx / a.D] = wn;
-          }
+          dense_store(a, nd, wn);
         }
       }
     }
@@ -2377,11 +2399,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? PRES
     if (stp && threadIdx.x == 0) { stp[6] = __builtin_amdgcn_s_memtime(); stp[5] = __builtin_amdgcn_s_memrealtime(); }
     return;
   }
-  ApCtx x;
-  x.tid = threadIdx.x; x.wave = x.tid >> 6; x.lane = x.tid & 63; x.grp = x.lane >> 4; x.l16 = x.lane & 15;
-  x.gid = x.wave * 4 + x.grp;
-  x.blk = blockIdx.x - nfin;
-  x.P = 1.0f; x.invP = 1.0f; x.step = 0.0f; x.lazy_scale = 0.0f; x.salt = 0u;
+  ApCtx x = ap_ctx(a, nfin, 1.0f, 0.0f, 0u, 0.0f);
   if (x.blk < a.nbH) {   // hot item rows lead the grid (no debug stamps)
     presum_hot_block<NI>(a, x.blk, shd, shp);
     return;
@@ -2499,16 +2517,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? SPEC
     if (stp && threadIdx.x == 0) { stp[6] = __builtin_amdgcn_s_memtime(); stp[5] = __builtin_amdgcn_s_memrealtime(); }
     return;
   }
-  ApCtx x;
-  x.tid = threadIdx.x; x.wave = x.tid >> 6; x.lane = x.tid & 63; x.grp = x.lane >> 4; x.l16 = x.lane & 15;
-  x.gid = x.wave * 4 + x.grp;
-  x.blk = blockIdx.x - nfin;
-  x.P = a.hdr->P;               // (stable: this launch's summary does not commit)
-  x.invP = 1.0f / x.P;
-  x.step = a.lr;                // coefficient 1
-  x.lazy_scale = x.step / (x.P * (1.0f - x.step * a.reg));
-  x.salt = a.hdr->nstep + 1;    // what the step's salt and record tag will be (hdr->spec_salt)
-  x.coef = 1.0f;
+  // P: stable (this launch's summary does not commit); step: coefficient 1; salt: what the step's salt and record tag
+  // will be (hdr->spec_salt)
+  ApCtx x = ap_ctx(a, nfin, a.hdr->P, a.lr, a.hdr->nstep + 1, 1.0f);
   if (x.blk == 0 && x.tid == 0) a.hdr->spart_n[x.salt & 1] = a.nbC + a.nbI + a.nbU + a.nbH;
   if (x.blk < a.nbH) {          // hot item rows lead the row workgroups
     presum_hot_block<NI, true, DT>(a, x.blk, shd, shp, &x);
@@ -2599,14 +2610,7 @@ __global__ __launch_bounds__(256) void k_spec_commit(ApplyArgs a) {
     }
     const float step = a.lr * coef;
     const int nd = blockIdx.x * 256 + tid;
-    if (nd < a.lay.n_dense) {
-      const float wn = a.p.dense[nd] - step * a.gd[nd];
-      a.p.dense[nd] = wn;
-      if (nd >= a.lay.K && nd < a.lay.k0) {
-        const int idx = nd - a.lay.K;
-        a.p.dense_KT[(size_t)(idx % a.D) * a.D + idx / a.D] = wn;
-      }
-    }
+    if (nd < a.lay.n_dense) dense_store(a, nd, a.p.dense[nd] - step * a.gd[nd]);
     return;
   }
   const float st_true = a.lr * coef;
@@ -2767,14 +2771,7 @@ __global__ __launch_bounds__(256) void k_update_lazy(ApplyArgs a, int nbC16) {
     }
   } else {
     const int nd = (blk - nbC16 - a.nbI - a.nbU) * 256 + tid;
-    if (nd < a.lay.n_dense) {
-      const float wn = a.p.dense[nd] - step * a.gd[nd];
-      a.p.dense[nd] = wn;
-      if (nd >= a.lay.K && nd < a.lay.k0) {
-        const int idx = nd - a.lay.K;
-        a.p.dense_KT[(size_t)(idx % a.D) * a.D + idx / a.D] = wn;
-      }
-    }
+    if (nd < a.lay.n_dense) dense_store(a, nd, a.p.dense[nd] - step * a.gd[nd]);
     return;
   }
   block_delta_store(part, shp, a, blk, salt);
