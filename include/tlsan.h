@@ -253,9 +253,35 @@ int tlsan_train_step(const tlsan_dims* dims, const tlsan_params* p, const tlsan_
  * IndexedSlices covering every row (gathers + the dense L2 term), so every row of the four
  * regularised tables is updated every step; item_b (not regularised) is updated where used
  * (RMSProp, Adadelta) or everywhere (Adam, whose sparse form decays m and v of all rows).
- * Needs hp->l2_mode == TLSAN_L2_DENSE and fp32 tables.  kind == TLSAN_OPT_SGD (or opt == NULL) is
- * tlsan_train_step. */
+ * Needs hp->l2_mode == TLSAN_L2_DENSE; fp32 slots (the tables may be bf16).  kind == TLSAN_OPT_SGD (or opt == NULL) is
+ * tlsan_train_step.
+ *
+ * kind | TLSAN_OPT_LAZY (ADAM, RMSPROP or ADADELTA; the "lazy" / sparse optimizers of TF's LazyAdamOptimizer and
+ * torch.optim.SparseAdam): the dense step of the same optimizer, from the same parameters and slots, RESTRICTED to the
+ * rows the batch used.  Same constructor defaults, slots and slot initialisation as the dense kind.
+ *   - loss and clip norm: the dense optimizer's (L2 term over the whole tables, TF18 norm, formed as the lazy-L2 SGD step
+ *     forms them): the clip coefficient c is the dense one up to summation order;
+ *   - a used row gets the dense update with its slots, g = c * (sum of its uses' gradients + reg * W), as a whole row
+ *     (usert_emb: all Ls columns).  Used: user rows of b->u; item rows of the candidates b->i and of the valid positions of
+ *     hist_i (< sl) and hist_i_new (< sl_new); category rows of a u_cate, or of the item at a used position -- a category
+ *     row moves when the index counts a u_cate use of it (with category segments: any use) or when its summed gradient has
+ *     a non-zero element; padding is not a use;
+ *   - item_b (not regularised) moves where its summed gradient is non-zero: the candidates (a candidate whose sigmoid
+ *     saturates to exactly y has gradient 0 and keeps its slots, as under the dense RMSProp / Adadelta);
+ *   - EVERY OTHER ROW keeps W and both slots bit for bit: the L2 term of unused rows counts in the loss and the norm but
+ *     does not reach the update.  This is the intended deviation from the dense forms;
+ *   - the dense weights move every step, as under the dense optimizer;
+ *   - the step does not change the table scale P.  On a fresh state P is 1 and stays exactly 1 (the stored tables are
+ *     the parameters; St stays their sum of squares).  If lazy-L2 SGD steps ran on the same state before (P != 1), the
+ *     step acts on the true values P * stored, as the forward pass and the loss do, and stores (P * w)' / P.
+ * Needs hp->l2_mode == TLSAN_L2_LAZY, norm_mode TLSAN_NORM_TF18 and params->scale == tlsan_state_scale(state)
+ * (TLSAN_E_UNSUPPORTED / TLSAN_E_BADARG otherwise, before any launch); bf16 tables, dropout and matrix_dtype as usual.
+ * TLSAN_OPT_LAZY alone (or with SGD) is TLSAN_E_BADARG.  An index prebuilt with TLSAN_INDEX_FOR_LAZY_SGD serves these
+ * steps too.  The row launch reads the summed gradient, W, m and v of the used rows and writes W, m and v: seven row
+ * widths per used row, where the lazy SGD update moves three (category rows: every row's summed gradient is read, W, m
+ * and v of the used ones only). */
 enum { TLSAN_OPT_SGD = 0, TLSAN_OPT_ADAM = 1, TLSAN_OPT_RMSPROP = 2, TLSAN_OPT_ADADELTA = 3 };
+#define TLSAN_OPT_LAZY 0x100
 typedef struct {
   int32_t kind;
   int32_t step;
@@ -296,7 +322,8 @@ int tlsan_batch_pack(const tlsan_packed* set, const int32_t* order, int32_t lo, 
  * it after the last step that used the same slot and before the step that consumes it.
  * slot | TLSAN_INDEX_FOR_LAZY_SGD: the index will be consumed by a lazy-L2 SGD train step only, which reaches the
  * user table's offsets through the batch's ids and the used-row records -- they are then written for the used rows
- * only (10 M users: 80 MB less per step).  An index built that way must not feed tlsan_grads or a dense-L2 step.
+ * only (10 M users: 80 MB less per step).  An index built that way must not feed tlsan_grads or a dense-L2 step; it does
+ * serve a lazy optimizer's step (tlsan_optimizer, TLSAN_OPT_LAZY), which walks the same records.
  * item_cate: params->item_cate of the tables the step will run on (tables with thousands of categories count item
  * uses per category as well; may be NULL below TLSAN_CSEG_MIN categories -- the only parameter-side input, and it is
  * not a trainable). */

@@ -75,6 +75,7 @@ class Optimizer(C.Structure):
 
 
 OPT_SGD, OPT_ADAM, OPT_RMSPROP, OPT_ADADELTA = 0, 1, 2, 3
+OPT_LAZY = 0x100   # TLSAN_OPT_LAZY (include/tlsan.h): OR-ed into ADAM / RMSPROP / ADADELTA, the used rows only
 
 
 class ShardOptimizer(C.Structure):

@@ -542,6 +542,9 @@ static int plan_tail(const tlsan_dims* d, const Shape& s, const tlsan_batch* b, 
   fl.nbK = w.nbK; fl.nbS = w.nbS;
   P->update = update;
   const bool lazy = update && hp->l2_mode == TLSAN_L2_LAZY;
+  // lazy Adam / RMSProp / Adadelta (TLSAN_OPT_LAZY): always the split form -- the one-pass forms speculate on the clip
+  // coefficient and correct linearly, which a non-linear update cannot -- and the table scale stays 1 (no commit)
+  const bool lazy_opt = lazy && A.opt != TLSAN_OPT_SGD;
   // tlsan_grads' pure per-row sums of the used rows (what the sharded step asks for): they ride with the dense finalize as in
   // the lazy train step, written straight to the output rows -- no apply launch (sparse == 2: the four outputs are views of
   // ONE fused row table, see tlsan_grads_out)
@@ -573,7 +576,7 @@ static int plan_tail(const tlsan_dims* d, const Shape& s, const tlsan_batch* b, 
   // one-rounding guarantee stay.
   const bool cache_bf16 = bf16 && !tables_in_hbm(d);
   TailForm form = TAIL_SPLIT;
-  if (lazy && mode != 0) {
+  if (lazy && !lazy_opt && mode != 0) {
     if (A.csplit > 1) {   // (built in the narrow form: d <= 128)
       if (mode != 2 && A.di <= 64 && A.dc <= 64 && A.WU <= 256 && !(mode == 1 && cache_bf16)) form = TAIL_SPEC_SHARED;
     } else if (A.cseg || !apply_wide(A)) {   // (the wide form is built for category segments only)
@@ -593,8 +596,8 @@ static int plan_tail(const tlsan_dims* d, const Shape& s, const tlsan_batch* b, 
     //  windows: Movies-TV shape 106.6 -> 104.3 us/step, with 673 categories 116.2 -> 106.2: profiles/r04_presum_narrow_ab.md)
     fl.wide = A.di > 64 || A.dc > 64 || (A.WU > 128 && A.presum_rows != 0);
     fl.csplit = A.csplit > 1;
-    f.commit = lazy ? 1 : 0;
-    if (lazy) {   // k_update_lazy: ceil(C / 16) blocks of category rows, the used item / user rows, the dense parameters
+    f.commit = lazy && !lazy_opt ? 1 : 0;
+    if (lazy) {   // k_update_lazy (_opt): ceil(C / 16) blocks of category rows, the used item / user rows, the dense parameters
       P->nbC16 = (A.C + 15) / 16;
       P->grid = dim3(P->nbC16 + A.nbI + A.nbU + A.nbD);
       P->wide = apply_wide(A);
@@ -1093,7 +1096,13 @@ static int launch_tail(const Shape& s, const TailPlan& P, const tlsan_hparams* h
       if ((rc = launch_apply(P.update ? AP_UPDATE : AP_GRADS, A, true, hs))) return rc;
       break;
     case TAIL_SPLIT:
-      if (P.update) {   // the short elementwise update of the summed rows
+      if (P.update && A.opt != TLSAN_OPT_SGD) {   // lazy Adam / RMSProp / Adadelta: the used rows and their slots
+        if (bf16 && P.wide) hipLaunchKernelGGL((k_update_lazy_opt<true, TLSAN_TABLE_BF16>), P.grid, blk, 0, hs, A, P.nbC16);
+        else if (bf16) hipLaunchKernelGGL((k_update_lazy_opt<false, TLSAN_TABLE_BF16>), P.grid, blk, 0, hs, A, P.nbC16);
+        else if (P.wide) hipLaunchKernelGGL((k_update_lazy_opt<true, TLSAN_TABLE_F32>), P.grid, blk, 0, hs, A, P.nbC16);
+        else hipLaunchKernelGGL((k_update_lazy_opt<false, TLSAN_TABLE_F32>), P.grid, blk, 0, hs, A, P.nbC16);
+        CHECK_LAUNCH("k_update_lazy_opt");
+      } else if (P.update) {   // the short elementwise update of the summed rows
         if (bf16 && P.wide) hipLaunchKernelGGL((k_update_lazy<true, TLSAN_TABLE_BF16>), P.grid, blk, 0, hs, A, P.nbC16);
         else if (bf16) hipLaunchKernelGGL((k_update_lazy<false, TLSAN_TABLE_BF16>), P.grid, blk, 0, hs, A, P.nbC16);
         else if (P.wide) hipLaunchKernelGGL((k_update_lazy<true, TLSAN_TABLE_F32>), P.grid, blk, 0, hs, A, P.nbC16);
@@ -1173,12 +1182,17 @@ int tlsan_train_step_opt(const tlsan_dims* d, const tlsan_params* p, const tlsan
   int rc = prep_step(d, &s, p, b, hp, state, ws, ws_bytes, &w, &st);
   if (rc) return rc;
   const bool other = opt && opt->kind != TLSAN_OPT_SGD;
+  const int kind = other ? opt->kind & ~TLSAN_OPT_LAZY : TLSAN_OPT_SGD;
   if (other) {
-    if (opt->kind != TLSAN_OPT_ADAM && opt->kind != TLSAN_OPT_RMSPROP && opt->kind != TLSAN_OPT_ADADELTA)
-      return fail(TLSAN_E_BADARG, "tlsan_optimizer: kind %d", opt->kind);
-    if (hp->l2_mode != TLSAN_L2_DENSE) return fail(TLSAN_E_UNSUPPORTED, "optimizers other than sgd update every row: l2_mode must be TLSAN_L2_DENSE");
+    if (kind != TLSAN_OPT_ADAM && kind != TLSAN_OPT_RMSPROP && kind != TLSAN_OPT_ADADELTA)
+      return fail(TLSAN_E_BADARG, "tlsan_optimizer: kind %d (TLSAN_OPT_LAZY goes with ADAM, RMSPROP or ADADELTA)", opt->kind);
+    if (opt->kind & TLSAN_OPT_LAZY) {   // (prep_step checked the rest of the lazy-L2 contract: TF18 norm, params->scale)
+      if (hp->l2_mode != TLSAN_L2_LAZY) return fail(TLSAN_E_UNSUPPORTED, "TLSAN_OPT_LAZY updates the used rows only: l2_mode must be TLSAN_L2_LAZY");
+    } else if (hp->l2_mode != TLSAN_L2_DENSE) {
+      return fail(TLSAN_E_UNSUPPORTED, "optimizers other than sgd update every row: l2_mode must be TLSAN_L2_DENSE");
+    }
     if ((rc = check_slot(opt->slot1, "slot1")) || (rc = check_slot(opt->slot2, "slot2"))) return rc;
-    if (opt->kind == TLSAN_OPT_ADAM && opt->step < 1) return fail(TLSAN_E_BADARG, "tlsan_optimizer: Adam's step counts from 1");
+    if (kind == TLSAN_OPT_ADAM && opt->step < 1) return fail(TLSAN_E_BADARG, "tlsan_optimizer: Adam's step counts from 1");
   }
   hipStream_t hs = (hipStream_t)stream;
   tlsan_dense_layout L;
@@ -1186,10 +1200,10 @@ int tlsan_train_step_opt(const tlsan_dims* d, const tlsan_params* p, const tlsan
   ApplyArgs A;
   fill_apply(A, d, s, p, b, hp, w, st, L);
   if (other) {
-    A.opt = opt->kind;
+    A.opt = kind;
     A.s1 = norm_params(opt->slot1, d); A.s2 = norm_params(opt->slot2, d);
     A.ob1 = opt->beta1; A.ob2 = opt->beta2; A.oeps = opt->epsilon;
-    if (opt->kind == TLSAN_OPT_ADAM)  // adam.py: lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t)
+    if (kind == TLSAN_OPT_ADAM)  // adam.py: lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t)
       A.oalpha = (float)((double)hp->lr * sqrt(1.0 - pow((double)opt->beta2, opt->step)) / (1.0 - pow((double)opt->beta1, opt->step)));
   }
   TailPlan P;

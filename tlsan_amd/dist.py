@@ -313,12 +313,15 @@ class ShardedModel:
             raise RuntimeError("ShardedModel needs torch.distributed to be initialised (one process per GPU)")
         if self.coalesce and not static_rows:
             raise NotImplementedError("coalesce=True is the static-shape step's option")
-        from .model import OPTIMIZERS
+        from .model import LAZY_OPTIMIZERS, OPTIMIZERS
         if config.get("num_blocks", 1) != 1:
             raise NotImplementedError("num_blocks != 1 (see tlsan_amd.model.Model)")
         self.optimizer = config.get("optimizer", "sgd")
         if self.optimizer not in OPTIMIZERS:
             raise ValueError("optimizer must be one of %s" % (sorted(OPTIMIZERS),))
+        if self.optimizer in LAZY_OPTIMIZERS:
+            raise NotImplementedError("optimizer=%r: the sharded step has no lazy optimizers (tlsan_amd.model.Model has)"
+                                      % self.optimizer)
         self.dropout = float(config.get("dropout", 0.0))
         if not 0.0 <= self.dropout < 1.0:
             raise ValueError("dropout must be in [0, 1)")

@@ -84,6 +84,11 @@ TABLE_KEYS = ("item_emb", "item_b", "user_emb", "usert_emb", "cate_emb")
 # defaults, which model.py:188-193 keeps (only learning_rate is passed)
 OPTIMIZERS = {"sgd": (L.OPT_SGD, 0.0, 0.0, 0.0), "adam": (L.OPT_ADAM, 0.9, 0.999, 1e-8),
               "rmsprop": (L.OPT_RMSPROP, 0.9, 0.0, 1e-10), "adadelta": (L.OPT_ADADELTA, 0.95, 0.0, 1e-8)}
+# the lazy ("sparse") forms: the same optimizers restricted to the rows a batch used (TLSAN_OPT_LAZY, include/tlsan.h)
+LAZY_OPTIMIZERS = ("lazy_adam", "lazy_rmsprop", "lazy_adadelta")
+OPTIMIZERS.update({"lazy_adam": (L.OPT_ADAM | L.OPT_LAZY, 0.9, 0.999, 1e-8),
+                   "lazy_rmsprop": (L.OPT_RMSPROP | L.OPT_LAZY, 0.9, 0.0, 1e-10),
+                   "lazy_adadelta": (L.OPT_ADADELTA | L.OPT_LAZY, 0.95, 0.0, 1e-8)})
 
 
 _STREAM_CACHE = {}
@@ -348,7 +353,11 @@ class Model(object):
         deterministic stochastic rounding; usert_emb, item_b and the dense weights stay fp32.
         init: "numpy" -- the variables' initial values drawn on the host (init_params; reproducible across
         devices); "device" -- the same distributions drawn in HBM (tables of 10^7 rows: BASELINE.json
-        configs[4]; no host copy of the tables is ever made)."""
+        configs[4]; no host copy of the tables is ever made).
+        config["optimizer"]: "sgd", "adam", "rmsprop", "adadelta" (the reference's), or "lazy_adam", "lazy_rmsprop",
+        "lazy_adadelta": the same optimizers restricted to the rows each batch used (unused rows keep their values and
+        slots bit for bit; include/tlsan.h, TLSAN_OPT_LAZY).  A lazy optimizer runs the lazy tail whatever l2_mode
+        says: "dense" and "lazy" are both accepted, with the same result; norm_mode must be "tf18"."""
         if init not in ("numpy", "device"):
             raise ValueError("init must be 'numpy' or 'device'")
         # matrix_dtype: arithmetic of the fused kernel's matrix products -- "f32": exact fp32 MFMA (the reference's
@@ -375,7 +384,16 @@ class Model(object):
         self.optimizer = config.get("optimizer", "sgd")           # model.py:188-195
         if self.optimizer not in OPTIMIZERS:
             raise ValueError("optimizer must be one of %s" % (sorted(OPTIMIZERS),))
-        if self.optimizer != "sgd":
+        # lazy_adam / lazy_rmsprop / lazy_adadelta update only the rows a batch used (include/tlsan.h, TLSAN_OPT_LAZY): they
+        # always run the lazy tail, whatever l2_mode says -- "dense" and "lazy" are both accepted and give the same result
+        self.lazy_opt = self.optimizer in LAZY_OPTIMIZERS
+        if self.lazy_opt:
+            if l2_mode not in ("dense", "lazy"):
+                raise ValueError("l2_mode must be 'dense' or 'lazy'")
+            if norm_mode != "tf18":
+                raise NotImplementedError("optimizer=%r supports norm_mode='tf18' only" % self.optimizer)
+            l2_mode = "lazy"
+        elif self.optimizer != "sgd":
             # adam / rmsprop / adadelta see every row of the regularised tables every step (the L2 term
             # makes the reference's gradients dense), so the lazy-L2 form does not apply
             if l2_mode != "dense":
@@ -516,7 +534,7 @@ class Model(object):
             return
         self.slots, self._cslots = [], []
         for which in range(2):
-            fill = 1.0 if (self.optimizer == "rmsprop" and which == 0) else 0.0
+            fill = 1.0 if (self.optimizer in ("rmsprop", "lazy_rmsprop") and which == 0) else 0.0
             t = {k: torch.full_like(getattr(self, k), fill, dtype=torch.float32) for k in TABLE_KEYS}
             t["dense"] = torch.full_like(self.dense, fill)
             self.slots.append(t)
@@ -594,8 +612,9 @@ class Model(object):
             self._sync_state()
 
     def fold_scale(self):
-        """lazy L2: fold the table scale P into the stored tables (P = 1 afterwards)."""
-        if self.l2_mode == L.L2_LAZY:
+        """lazy L2: fold the table scale P into the stored tables (P = 1 afterwards).  The lazy optimizers keep P = 1:
+        nothing to fold."""
+        if self.l2_mode == L.L2_LAZY and not self.lazy_opt:
             L.check(self.lib.tlsan_state_renorm(C.byref(self.dims), C.byref(self.cparams), self.state.data_ptr(),
                                                 self._stream()), "tlsan_state_renorm")
 
@@ -675,13 +694,14 @@ class Model(object):
         if torch.cuda.is_current_stream_capturing():   # hipGraph capture: one self-contained step
             if self.dropout > 0.0:
                 raise NotImplementedError("the dropout seed is a launch argument: capture is not supported")
-            if self.optimizer == "adam":
+            if self.optimizer in ("adam", "lazy_adam"):
                 raise NotImplementedError("Adam's step count is a launch argument: capture is not supported")
             hp = self.hparams(lr)
             self._train_call(db, hp, out, ws)
             self._step += 1
             return db
-        if self.l2_mode == L.L2_LAZY and self.renorm_every and self._step and self._step % self.renorm_every == 0:
+        if self.l2_mode == L.L2_LAZY and not self.lazy_opt and self.renorm_every and self._step and \
+                self._step % self.renorm_every == 0:
             # keep the table scale P = prod(1 - lr c reg) away from fp32 underflow in very long runs
             # (a fixed schedule, so runs stay bitwise reproducible); one sweep of the tables
             self.fold_scale()
@@ -753,7 +773,7 @@ class Model(object):
                 if self.started_at is not None:  # (when the host SAW this step's first kernel start: bench.py's spread of step times)
                     self.started_at.append(tq)
             for ndb, kk in ahead:
-                flag = L.INDEX_FOR_LAZY_SGD if (self.l2_mode == L.L2_LAZY and self.optimizer == "sgd") else 0
+                flag = L.INDEX_FOR_LAZY_SGD if (self.l2_mode == L.L2_LAZY and (self.optimizer == "sgd" or self.lazy_opt)) else 0
                 L.check(self.lib.tlsan_batch_index(C.byref(self.dims), C.byref(ndb.c), self.cparams.item_cate, self.state.data_ptr(), kk | flag,
                                                    C.c_void_p(self._side.cuda_stream)), "tlsan_batch_index")
                 self._idx_event[kk].record(self._side)

@@ -394,6 +394,8 @@ def train_sharded(args):
         raise NotImplementedError("--norm_mode %s: the sharded step forms the clip norm as TF 1.8 does (tf18)" % args.norm_mode)
     if args.matrix_dtype != "f32":
         raise NotImplementedError("--matrix_dtype %s: the sharded step computes in fp32" % args.matrix_dtype)
+    if args.optimizer.startswith("lazy_"):
+        raise NotImplementedError("--optimizer %s: the sharded step has no lazy optimizers" % args.optimizer)
     resume = prepare_model_dir(args.model_dir, args.from_scratch, rank,
                                (lambda: dist.barrier()) if world > 1 else None)     # train.py:124-127
     l2_mode = args.l2_mode if args.optimizer == "sgd" else "dense"
