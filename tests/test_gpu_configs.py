@@ -455,7 +455,7 @@ def _c5_sharded_oracle_worker(rank, world, port, ret):
                 us[np.searchsorted(cp["users"], ui)] = ur
             q = dict(item_emb=it[:, :di].copy(), item_b=it[:, di].copy(), user_emb=us[:, :di].copy(), usert_emb=us[:, di:di + Ls].copy(),
                      cate_emb=m.cate_emb[torch.as_tensor(cp["cates"], device=dev)].double().cpu().numpy())
-            q.update({k: np.asarray(v, np.float64) for k, v in m._unpack_dense(m.dense.cpu().numpy()).items()})
+            q.update({k: np.asarray(v, np.float64) for k, v in m.unpack_dense(m.dense.cpu().numpy()).items()})
             return q
 
         q0 = collect()

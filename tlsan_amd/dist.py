@@ -47,7 +47,9 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
-from .model import DENSE_KEYS, TABLE_KEYS, DeviceBatch, Model, _Var, _Writer, concurrent_streams
+from .model import (_STARTED_WORDS, KS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer,
+                    candidate_tensor, concurrent_streams, eval_topk, exclusion_csr, pack_dense, read_checkpoint,
+                    sample_negatives, sampled_ranks, score_candidates, topk_merge, unpack_dense, write_checkpoint)
 
 
 _STATE_HDR_BYTES = 256   # sizeof(StateHdr), csrc/tlsan_update.h: what tlsan_state_reindex keeps
@@ -313,7 +315,6 @@ class ShardedModel:
             raise RuntimeError("ShardedModel needs torch.distributed to be initialised (one process per GPU)")
         if self.coalesce and not static_rows:
             raise NotImplementedError("coalesce=True is the static-shape step's option")
-        from .model import LAZY_OPTIMIZERS, OPTIMIZERS
         if config.get("num_blocks", 1) != 1:
             raise NotImplementedError("num_blocks != 1 (see tlsan_amd.model.Model)")
         self.optimizer = config.get("optimizer", "sgd")
@@ -394,9 +395,7 @@ class ShardedModel:
         self._side = None
         self._sizes = {}      # (compact rows, categories, B, Sn) -> (state bytes, workspace bytes)
         self._ews = None
-        self._hits_p = np.zeros(6, np.int64)
-        self._hits_r = np.zeros(6, np.int64)
-        self._n_p = self._n_r = 0
+        self._topk = TopKCounters()
         loc = np.arange(self.rank, I, self.world)
         self._icl_local = torch.as_tensor(np.concatenate([icl[loc], np.zeros(1, np.int32)])).to(dev)   # category of local item n
         self._slots = [None, None, None]    # routing plans: current / prefetched / forward-only (evaluation)
@@ -407,6 +406,7 @@ class ShardedModel:
         self._epoch = 0
         self.global_step = _Var(lambda: self._step)
         self.global_epoch_step = _Var(lambda: self._epoch)
+        self.global_epoch_step_op = _Var(self._inc_epoch)
         self.train_writer = _Writer(os.path.join(config.get("model_dir", "."), "train"))
         self.eval_writer = _Writer(os.path.join(config.get("model_dir", "."), "eval"))
         if init == "device":
@@ -433,15 +433,26 @@ class ShardedModel:
         p = Model.init_params(small, seed)          # cate_emb and the dense weights: the host stream, the same on every rank
         self.cate_emb.copy_(torch.as_tensor(np.asarray(p["cate_emb"], np.float32)))
         self._P.fill_(1.0)
-        self._pack_dense(p)
+        self._load_dense_and_KT(p)
         self._refresh_squares()
         self._reset_step_state()
 
     # ------------------------------------------------------------------ helpers
-    def _pack_dense(self, p):
+    def pack_dense(self, p):
+        return pack_dense(self.lay, self.d, self.H, p)
+
+    def unpack_dense(self, flat):
+        return unpack_dense(self.lay, self.d, self.H, flat)
+
+    def _load_dense_and_KT(self, p):
+        """The dense weights of p into `dense`, and dense_K's transpose into dense_KT."""
         d, lay = self.d, self.lay
-        self.dense.copy_(torch.as_tensor(self._dense_flat(p)))
+        self.dense.copy_(torch.as_tensor(self.pack_dense(p)))
         self.dense_KT.copy_(self.dense[lay.K:lay.K + d * d].view(d, d).t())
+
+    def _inc_epoch(self):
+        self._epoch += 1
+        return self._epoch
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -760,23 +771,18 @@ class ShardedModel:
                                                     1.0 / G, self._step_dev.data_ptr(), self.cate_emb.data_ptr(), Cc, self.dc,
                                                     fp + 4 * n_dense, self._sq.data_ptr(), tail + 8, self._P.data_ptr(),
                                                     self._lws.data_ptr(), self._lws.numel(), st), "tlsan_shard_apply_lazy")
-            self._step += 1
-            self._keep = (table, gf, vals, sl["recv_rows"])
-            if self.renorm_every and self._step % self.renorm_every == 0:
-                self.fold_scale()
-            if ndb is not None:
-                nsl = self._plan_stage2(self._slots[self._next_slot])
-                self._prepare_side(ndb, nsl)
-            return db
-        L.check(self.lib.tlsan_shard_apply_opt(self.shard.data_ptr(), W, self.cI, self.router.R, W, di, di + Ls,
-                                               vals.data_ptr(), W, sl["recv_rows"].data_ptr(), sl["n_recv"], sl["src_off"],
-                                               G, self._slots_buf.data_ptr(), 1.0 / G, self._step_dev.data_ptr(), self.reg,
-                                               self.cate_emb.data_ptr(), Cc, self.dc, fp + 4 * n_dense,
-                                               self._sq.data_ptr(), tail + 8, sopt, float(lr),
-                                               self._aws.data_ptr(), self._aws.numel(), st),
-                "tlsan_shard_apply")
+        else:
+            L.check(self.lib.tlsan_shard_apply_opt(self.shard.data_ptr(), W, self.cI, self.router.R, W, di, di + Ls,
+                                                   vals.data_ptr(), W, sl["recv_rows"].data_ptr(), sl["n_recv"], sl["src_off"],
+                                                   G, self._slots_buf.data_ptr(), 1.0 / G, self._step_dev.data_ptr(), self.reg,
+                                                   self.cate_emb.data_ptr(), Cc, self.dc, fp + 4 * n_dense,
+                                                   self._sq.data_ptr(), tail + 8, sopt, float(lr),
+                                                   self._aws.data_ptr(), self._aws.numel(), st),
+                    "tlsan_shard_apply")
         self._step += 1
         self._keep = (table, gf, vals, sl["recv_rows"])
+        if self.renorm_every and self._step % self.renorm_every == 0:
+            self.fold_scale()          # (lazy L2; nothing to fold otherwise)
         if ndb is not None:
             nsl = self._plan_stage2(self._slots[self._next_slot])   # its counts arrived long ago
             self._prepare_side(ndb, nsl)
@@ -807,7 +813,9 @@ class ShardedModel:
         side, side2 = concurrent_streams(self.device, 2)     # on hardware queues of their own (see there)
         st = dict(cap=cap, n=n, kcap=kcap, B=db.B,
                   status=torch.zeros(1, dtype=torch.int32, device=dev),
-                  status_host=torch.zeros(1, dtype=torch.int32).pin_memory(), status_step=0,   # mirror of `status`, copied behind every plan
+                  # status_host: a pinned word the plan's kernel writes itself, and only on overflow (the count of the
+                  # overflowing owner); it is not a copy of `status`
+                  status_host=torch.zeros(1, dtype=torch.int32).pin_memory(), status_step=0,
                   stamp=torch.ones(1, dtype=torch.int32, device=dev),           # uint32 on the device side; never 0
                   gf=torch.zeros(n, W, dtype=torch.float32, device=dev),
                   vals=torch.zeros(n, W, dtype=torch.float32, device=dev) if G > 1 else None,
@@ -816,7 +824,6 @@ class ShardedModel:
                   fork=torch.cuda.Event(),
                   side_group=None, checked=0, graphs=0, warm=False)
         st["fork"].record()
-        from .model import _STARTED_WORDS
         st["started"] = torch.zeros(16, dtype=torch.int32).pin_memory()
         _STARTED_WORDS.append(st["started"])          # (a queued step writes it when it starts: it outlives the model)
         st["started_word"] = C.c_uint32.from_address(st["started"].data_ptr())
@@ -1357,7 +1364,6 @@ class ShardedModel:
         the exclusion lists are all-gathered, every rank selects the k best of ITS item shard for all rows
         (tlsan_eval_topk, global ids n * world + rank), each row's lists go to the rank that owns the row (one
         all-to-all) and are merged there (tlsan_topk_merge).  Same ids and scores as Model.recommend."""
-        from .model import eval_topk, exclusion_csr, topk_merge
         db = self.device_batch(batch, is_test=True)
         sl = self._plan_eval(db)
         table = self._fetch(sl)
@@ -1415,7 +1421,6 @@ class ShardedModel:
         C): u_t and the ids are all-gathered, every rank scores the ids of ITS item shard (global id n * world + rank)
         for all rows, one all-to-all returns each row's scores to its owner, which SELECTS each candidate's score from
         the rank that holds the id (a sum would turn -0 into +0).  Padding and ids outside the table score -inf."""
-        from .model import score_candidates
         B, Cn = cand.shape
         ut_all, cand_all = allgather_rows(ut, self.group), allgather_rows(cand, self.group)
         sc = torch.full((int(ut_all.shape[0]), Cn), float("-inf"), dtype=torch.float32, device=self.device)
@@ -1433,7 +1438,6 @@ class ShardedModel:
     def score_candidates(self, batch, candidates):
         """Model.score_candidates for this rank's rows (every rank calls it, with the same C).  Same scores, bit for
         bit."""
-        from .model import candidate_tensor
         db = self.device_batch(batch, is_test=True)
         ut, table = self._forward_ut(db)
         sc = self._score_owned(ut, candidate_tensor(candidates, db.B, self.device))
@@ -1443,25 +1447,19 @@ class ShardedModel:
     def sample_negatives(self, batch, n, seed=1234, row0=0, exclude="history"):
         """Model.sample_negatives for this rank's rows; row0 is the GLOBAL index of this rank's first row.  No
         collective: a row's negatives depend on (seed, row, label, exclusion, n) only."""
-        from .model import exclusion_csr, sample_negatives
         db = self.device_batch(batch, is_test=True)
         return sample_negatives(self.lib, self.I, db.i, n, seed, row0, exclusion_csr(db, exclude, self.I), self._stream())
 
     def sampled_ranks(self, batch, n, seed=1234, row0=0, exclude="history"):
         """Model.sampled_ranks for this rank's rows (every rank calls it, with the same n); row0 is the GLOBAL index of
         this rank's first row.  Same ranks as Model.sampled_ranks."""
-        from .model import candidate_ranks, exclusion_csr, sample_negatives
         db = self.device_batch(batch, is_test=True)
         ut, table = self._forward_ut(db)
-        st = self._stream()
-        neg = sample_negatives(self.lib, self.I, db.i, n, seed, row0, exclusion_csr(db, exclude, self.I), st)
-        cand = torch.cat([db.i.view(-1, 1).to(torch.int32), neg], 1).contiguous()
-        ranks = candidate_ranks(self.lib, cand, self._score_owned(ut, cand), st)
+        ranks = sampled_ranks(self.lib, self.I, db, ut, n, seed, row0, exclude, self._score_owned, self._stream())
         torch.cuda.current_stream(self.device).synchronize()   # `table` stays alive until done
         return ranks
 
     def _hits(self, batch, n_valid=None):
-        from .model import KS
         r = self.label_ranks(batch)
         if n_valid is not None:        # rows past n_valid only pad this rank's share to the common size
             r = r[:n_valid]
@@ -1475,18 +1473,10 @@ class ShardedModel:
         """Streaming precision_at_k over the global batch (model.py:265-281); cumulative like the reference's
         never-reset local variables (train.py:75-76,82).  Identical on every rank.  Every rank must pass
         the same number of rows (the all-gather is equal-sized); n_valid marks how many of them count."""
-        from .model import KS
-        h, n = self._hits(batch, n_valid)
-        self._hits_p += h
-        self._n_p += n
-        return [self._hits_p[i] / (k * self._n_p) for i, k in enumerate(KS)]
+        return self._topk.add_prec(*self._hits(batch, n_valid))
 
     def eval_recall(self, sess, batch, n_valid=None):
-        from .model import KS
-        h, n = self._hits(batch, n_valid)
-        self._hits_r += h
-        self._n_r += n
-        return [self._hits_r[i] / self._n_r for i in range(len(KS))]
+        return self._topk.add_recall(*self._hits(batch, n_valid))
 
     def label_ranks(self, batch):
         """rank of the positive item among ALL items for each test row of this rank's batch (model.py:140-156)"""
@@ -1535,24 +1525,12 @@ class ShardedModel:
         return dict(item_emb=item[:, :di].copy(), item_b=item[:, di].copy(),
                     user_emb=user[:, :di].copy(), usert_emb=user[:, di:di + Ls].copy())
 
-    def _unpack_dense(self, flat):
-        d, dh, lay = self.d, self.d // self.H, self.lay
-        out = {}
-        for k, off, shape in (("fwa1_W1", lay.f1_W1, (dh, dh)), ("fwa1_b1", lay.f1_b1, (dh,)),
-                              ("fwa1_W2", lay.f1_W2, (dh, dh)), ("fwa1_b2", lay.f1_b2, (dh,)),
-                              ("dense_K", lay.K, (d, d)), ("dense_b", lay.k0, (d,)),
-                              ("fwa2_W1", lay.f2_W1, (dh, dh)), ("fwa2_b1", lay.f2_b1, (dh,)),
-                              ("fwa2_W2", lay.f2_W2, (dh, dh)), ("fwa2_b2", lay.f2_b2, (dh,)), ("gamma", lay.gamma, ())):
-            n = int(np.prod(shape)) if shape else 1
-            out[k] = flat[off:off + n].reshape(shape).copy()
-        return out
-
     def gather_params(self):
         """Full (un-sharded) parameters on every rank, as numpy (tests / checkpoints)."""
         self.fold_scale()
         out = self._gather_tables(self.shard)
         out["cate_emb"] = self.cate_emb.cpu().numpy()
-        out.update(self._unpack_dense(self.dense.cpu().numpy()))
+        out.update(self.unpack_dense(self.dense.cpu().numpy()))
         return out
 
     # ------------------------------------------------------------------ checkpoints (model.py:302-313)
@@ -1569,10 +1547,9 @@ class ShardedModel:
         base = os.path.join(self.config["model_dir"], "TLSAN-%d" % self._step)
         if not sharded:
             full = self.gather_params()                      # (a collective: every rank takes part)
-            slots = self.gather_slots()                      # tf.train.Saver keeps the optimizer's slot variables too
-            extra = {} if slots is None else {"slot%d/%s" % (n, k): v for n, sl_ in enumerate(slots, 1) for k, v in sl_.items()}
+            slots = self.gather_slots()
             if self.rank == 0:
-                np.savez(base + ".npz", global_step=self._step, global_epoch_step=self._epoch, **full, **extra)
+                write_checkpoint(base + ".npz", self._step, self._epoch, full, slots)
         else:
             sl = {} if self._sopt is None else {k: v.cpu().numpy() for k, v in self.slots.items()}
             np.savez("%s.shard%dof%d.npz" % (base, self.rank, self.world), shard=self.shard.cpu().numpy(),
@@ -1592,10 +1569,10 @@ class ShardedModel:
         """`path`: the prefix save() returned (sharded checkpoint of the SAME world size), or a
         single-file .npz checkpoint of Model.save / save(sharded=False) -- then every rank keeps its rows."""
         if path.endswith(".npz"):
-            z = np.load(path)
-            self.set_params({k: z[k] for k in TABLE_KEYS + DENSE_KEYS})
-            if self._sopt is not None and "slot1/item_emb" in z.files:   # the optimizer's accumulators (Model.save)
-                self._set_slots([{k: z["slot%d/%s" % (n, k)] for k in TABLE_KEYS + DENSE_KEYS} for n in (1, 2)])
+            step, epoch, params, slots = read_checkpoint(path, want_slots=self._sopt is not None)
+            self.set_params(params)
+            if slots is not None:                                        # the optimizer's accumulators (Model.save)
+                self._set_slots(slots)
         else:
             rep_ = np.load(path + ".replicated.npz")
             if int(rep_["world"]) != self.world:
@@ -1614,9 +1591,8 @@ class ShardedModel:
             if self._sopt is not None and "shard_s1" in zs.files:      # the optimizer's accumulators
                 for k in self.slots:
                     self.slots[k].copy_(torch.as_tensor((zs if k.startswith("shard_") else rep_)[k]))
-            z = rep_
-        self._step = int(z["global_step"])
-        self._epoch = int(z["global_epoch_step"])
+            step, epoch = int(rep_["global_step"]), int(rep_["global_epoch_step"])
+        self._step, self._epoch = step, epoch
         self._reset_step_state()
 
     def _reset_step_state(self):
@@ -1651,22 +1627,12 @@ class ShardedModel:
         t[self.cI:self.cI + len(gu), di:di + Ls] = np.asarray(p["usert_emb"], np.float32)[gu]
         return t
 
-    def _dense_flat(self, p):
-        lay = self.lay
-        flat = np.zeros(lay.n_dense, np.float32)
-        for k, off in (("fwa1_W1", lay.f1_W1), ("fwa1_b1", lay.f1_b1), ("fwa1_W2", lay.f1_W2), ("fwa1_b2", lay.f1_b2),
-                       ("dense_K", lay.K), ("dense_b", lay.k0), ("fwa2_W1", lay.f2_W1), ("fwa2_b1", lay.f2_b1),
-                       ("fwa2_W2", lay.f2_W2), ("fwa2_b2", lay.f2_b2), ("gamma", lay.gamma)):
-            a = np.asarray(p[k], np.float32).reshape(-1)
-            flat[off:off + a.size] = a
-        return flat
-
     def _set_slots(self, slots):
         """The two accumulator sets of adam / rmsprop / adadelta from full tables (Model.get_slots' format)."""
         for n, src in enumerate(slots, 1):
             self.slots["shard_s%d" % n].copy_(torch.as_tensor(self._shard_layout(src)))
             self.slots["cate_s%d" % n].copy_(torch.as_tensor(np.asarray(src["cate_emb"], np.float32)))
-            self.slots["dense_s%d" % n].copy_(torch.as_tensor(self._dense_flat(src)))
+            self.slots["dense_s%d" % n].copy_(torch.as_tensor(self.pack_dense(src)))
 
     def gather_slots(self):
         """Full (un-sharded) optimizer accumulators on every rank, in Model.get_slots' format (None for sgd)."""
@@ -1676,7 +1642,7 @@ class ShardedModel:
         for n in (1, 2):
             full = self._gather_tables(self.slots["shard_s%d" % n])
             full["cate_emb"] = self.slots["cate_s%d" % n].cpu().numpy()
-            full.update(self._unpack_dense(self.slots["dense_s%d" % n].cpu().numpy()))
+            full.update(self.unpack_dense(self.slots["dense_s%d" % n].cpu().numpy()))
             out.append(full)
         return out
 
@@ -1693,6 +1659,6 @@ class ShardedModel:
         self.shard.copy_(torch.as_tensor(self._shard_layout(p)))
         self.cate_emb.copy_(torch.as_tensor(np.asarray(p["cate_emb"], np.float32)))
         self._P.fill_(1.0)
-        self._pack_dense(p)
+        self._load_dense_and_KT(p)
         self._refresh_squares()
         self._reset_step_state()

@@ -80,6 +80,58 @@ def glorot_uniform(rng, shape):
 DENSE_KEYS = ("fwa1_W1", "fwa1_b1", "fwa1_W2", "fwa1_b2", "dense_K", "dense_b",
               "fwa2_W1", "fwa2_b1", "fwa2_W2", "fwa2_b2", "gamma")
 TABLE_KEYS = ("item_emb", "item_b", "user_emb", "usert_emb", "cate_emb")
+
+
+def dense_slices(lay, d, heads):
+    """The layout of the flat `dense` vector, stated once: (name, offset, shape) of every DENSE_KEYS weight under the
+    library's DenseLayout `lay` (tlsan_dense_layout_of) for hidden_units d and `heads` heads."""
+    dh = d // heads
+    return (("fwa1_W1", lay.f1_W1, (dh, dh)), ("fwa1_b1", lay.f1_b1, (dh,)),
+            ("fwa1_W2", lay.f1_W2, (dh, dh)), ("fwa1_b2", lay.f1_b2, (dh,)),
+            ("dense_K", lay.K, (d, d)), ("dense_b", lay.k0, (d,)),
+            ("fwa2_W1", lay.f2_W1, (dh, dh)), ("fwa2_b1", lay.f2_b1, (dh,)),
+            ("fwa2_W2", lay.f2_W2, (dh, dh)), ("fwa2_b2", lay.f2_b2, (dh,)),
+            ("gamma", lay.gamma, ()))
+
+
+def pack_dense(lay, d, heads, p):
+    """Dict of dense weights (numpy, names as DENSE_KEYS) -> the flat [lay.n_dense] float32 vector (padding zero)."""
+    out = np.zeros(lay.n_dense, np.float32)
+    for k, off, shape in dense_slices(lay, d, heads):
+        n = int(np.prod(shape)) if shape else 1
+        out[off:off + n] = np.asarray(p[k], np.float32).reshape(-1)
+    return out
+
+
+def unpack_dense(lay, d, heads, flat):
+    """The flat dense vector (numpy) -> dict of copies of its weights, shaped as the parameters."""
+    flat = np.asarray(flat)
+    out = {}
+    for k, off, shape in dense_slices(lay, d, heads):
+        n = int(np.prod(shape)) if shape else 1
+        out[k] = flat[off:off + n].reshape(shape).copy()
+    return out
+
+
+def write_checkpoint(path, step, epoch, params, slots=None):
+    """The single-file checkpoint TLSAN-<step>.npz: the two counters, every parameter under its name and, when the
+    optimizer has accumulators (two dicts named like the parameters), those as slot1/<name> and slot2/<name> --
+    tf.train.Saver keeps the optimizer's slot variables too."""
+    extra = {}
+    for n, sl in enumerate(slots or (), 1):
+        extra.update({"slot%d/%s" % (n, k): v for k, v in sl.items()})
+    np.savez(path, global_step=step, global_epoch_step=epoch, **params, **extra)
+
+
+def read_checkpoint(path, want_slots=True):
+    """write_checkpoint's file -> (step, epoch, params, slots); slots is None when the file holds none (an sgd run)
+    or want_slots is false."""
+    z = np.load(path)
+    keys = TABLE_KEYS + DENSE_KEYS
+    slots = None
+    if want_slots and "slot1/item_emb" in z.files:
+        slots = [{k: z["slot%d/%s" % (n, k)] for k in keys} for n in (1, 2)]
+    return int(z["global_step"]), int(z["global_epoch_step"]), {k: z[k] for k in keys}, slots
 # optimizer -> (TLSAN_OPT_*, beta1 | decay | rho, beta2 | momentum, epsilon): TF 1.8's constructor
 # defaults, which model.py:188-193 keeps (only learning_rate is passed)
 OPTIMIZERS = {"sgd": (L.OPT_SGD, 0.0, 0.0, 0.0), "adam": (L.OPT_ADAM, 0.9, 0.999, 1e-8),
@@ -248,6 +300,39 @@ def sample_negatives(lib, item_count, labels, n, seed, row0, excl, stream):
                                        None if xid is None else xid.data_ptr(), out.data_ptr(), stream),
             "tlsan_sample_negatives")
     return out
+
+
+def sampled_ranks(lib, item_count, db, ut, n, seed, row0, exclude, score, stream):
+    """Rank of each row's label among its n sampled negatives -> [B] int32 device tensor: one sampling, one scoring of
+    [label | negatives] by score(u_t, cand) -> [B, 1 + n] scores, one ranking; no host round trip."""
+    neg = sample_negatives(lib, item_count, db.i, n, seed, row0, exclusion_csr(db, exclude, item_count), stream)
+    cand = torch.cat([db.i.view(-1, 1).to(torch.int32), neg], 1).contiguous()
+    return candidate_ranks(lib, cand, score(ut, cand), stream)
+
+
+class TopKCounters:
+    """The streaming precision_at_k / recall_at_k state (model.py:265-299): hits per k of KS and rows counted, one
+    pair for each metric, cumulative over every update like the reference's never-reset local variables
+    (train.py:75-76,82)."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.hits_p = np.zeros(len(KS), np.int64)
+        self.hits_r = np.zeros(len(KS), np.int64)
+        self.n_p = self.n_r = 0
+
+    def add_prec(self, hits, n):
+        """Count a batch (hits [len(KS)]: rows whose label ranks below k; n rows) -> P@k so far."""
+        self.hits_p += hits
+        self.n_p += n
+        return [self.hits_p[i] / (k * self.n_p) for i, k in enumerate(KS)]
+
+    def add_recall(self, hits, n):
+        self.hits_r += hits
+        self.n_r += n
+        return [self.hits_r[i] / self.n_r for i in range(len(KS))]
 
 
 SAMPLED_KS = (1, 5, 10, 20)
@@ -456,13 +541,10 @@ class Model(object):
         self.global_epoch_step = _Var(lambda: self._epoch)
         self.global_epoch_step_op = _Var(self._inc_epoch)
         self._out = torch.zeros(4, dtype=torch.float32, device=self.device)  # loss, gnorm, sq_rows
-        self._hits_p = np.zeros(len(KS), np.int64)
-        self._hits_r = np.zeros(len(KS), np.int64)
-        self._n_p = 0
-        self._n_r = 0
-        for idx, k in enumerate(KS):
-            setattr(self, "prec_%d" % k, _Var(lambda idx=idx, k=k: self._hits_p[idx] / max(1, k * self._n_p)))
-            setattr(self, "recall_%d" % k, _Var(lambda idx=idx: self._hits_r[idx] / max(1, self._n_r)))
+        self._topk = c = TopKCounters()
+        for idx, k in enumerate(KS):            # (0 before any batch was counted)
+            setattr(self, "prec_%d" % k, _Var(lambda idx=idx, k=k: c.hits_p[idx] / max(1, k * c.n_p)))
+            setattr(self, "recall_%d" % k, _Var(lambda idx=idx: c.hits_r[idx] / max(1, c.n_r)))
         self._sync_state()
 
     # ------------------------------------------------------------------ parameters
@@ -572,32 +654,11 @@ class Model(object):
                 t[k].copy_(torch.as_tensor(np.asarray(src[k], np.float32)))
             t["dense"].copy_(torch.as_tensor(self.pack_dense(src)))
 
-    def _dense_slices(self):
-        lay, d = self.lay, self.config["hidden_units"]
-        dh = d // self.config["num_heads"]
-        return {
-            "fwa1_W1": (lay.f1_W1, (dh, dh)), "fwa1_b1": (lay.f1_b1, (dh,)),
-            "fwa1_W2": (lay.f1_W2, (dh, dh)), "fwa1_b2": (lay.f1_b2, (dh,)),
-            "dense_K": (lay.K, (d, d)), "dense_b": (lay.k0, (d,)),
-            "fwa2_W1": (lay.f2_W1, (dh, dh)), "fwa2_b1": (lay.f2_b1, (dh,)),
-            "fwa2_W2": (lay.f2_W2, (dh, dh)), "fwa2_b2": (lay.f2_b2, (dh,)),
-            "gamma": (lay.gamma, ()),
-        }
-
     def pack_dense(self, p):
-        out = np.zeros(self.lay.n_dense, np.float32)
-        for k, (off, shape) in self._dense_slices().items():
-            n = int(np.prod(shape)) if shape else 1
-            out[off:off + n] = np.asarray(p[k], np.float32).reshape(-1)
-        return out
+        return pack_dense(self.lay, self.config["hidden_units"], self.config["num_heads"], p)
 
     def unpack_dense(self, flat):
-        flat = np.asarray(flat)
-        out = {}
-        for k, (off, shape) in self._dense_slices().items():
-            n = int(np.prod(shape)) if shape else 1
-            out[k] = flat[off:off + n].reshape(shape).copy()
-        return out
+        return unpack_dense(self.lay, self.config["hidden_units"], self.config["num_heads"], flat)
 
     def set_params(self, p):
         """Load a dict of numpy arrays (names as in oracle / checkpoint) into device memory."""
@@ -939,11 +1000,8 @@ class Model(object):
         forward, one sampling, one scoring of [label | negatives], one ranking; no host round trip."""
         _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
         st = self._stream()
-        neg = sample_negatives(self.lib, self.config["item_count"], db.i, n, seed, row0,
-                               exclusion_csr(db, exclude, self.config["item_count"]), st)
-        cand = torch.cat([db.i.view(-1, 1).to(torch.int32), neg], 1).contiguous()
-        scores = score_candidates(self.lib, self.dims, self.cparams, ut, cand, 1, 0, st)
-        return candidate_ranks(self.lib, cand, scores, st)
+        score = lambda ut, cand: score_candidates(self.lib, self.dims, self.cparams, ut, cand, 1, 0, st)
+        return sampled_ranks(self.lib, self.config["item_count"], db, ut, n, seed, row0, exclude, score, st)
 
     def _topk_workspace(self, nbytes):
         if getattr(self, "_tws", None) is None or self._tws.numel() < nbytes:
@@ -958,22 +1016,14 @@ class Model(object):
         """Streaming precision_at_k update ops (model.py:265-281); counters are cumulative over
         every call, like the reference's never-reset local variables (train.py:75-76,82).
         ranks (optional): the label ranks of this batch's rows, already computed (label_ranks on a larger launch)."""
-        h, n = self._hits(batch, ranks)
-        self._hits_p += h
-        self._n_p += n
-        return [self._hits_p[i] / (k * self._n_p) for i, k in enumerate(KS)]
+        return self._topk.add_prec(*self._hits(batch, ranks))
 
     def eval_recall(self, sess, batch, ranks=None):
-        h, n = self._hits(batch, ranks)
-        self._hits_r += h
-        self._n_r += n
-        return [self._hits_r[i] / self._n_r for i in range(len(KS))]
+        return self._topk.add_recall(*self._hits(batch, ranks))
 
     def reset_metrics(self):
         """Not in the reference (its counters are never reset); provided for per-round metrics."""
-        self._hits_p[:] = 0
-        self._hits_r[:] = 0
-        self._n_p = self._n_r = 0
+        self._topk.reset()
 
     # ------------------------------------------------------------------ checkpoint
     def save(self, sess=None):
@@ -981,11 +1031,7 @@ class Model(object):
         os.makedirs(self.config["model_dir"], exist_ok=True)
         base = os.path.join(self.config["model_dir"], "TLSAN")
         path = "%s-%d.npz" % (base, self._step)
-        extra = {}
-        if self.slots is not None:        # tf.train.Saver keeps the optimizer's slot variables too
-            for n, sl in enumerate(self.get_slots()):
-                extra.update({"slot%d/%s" % (n + 1, k): v for k, v in sl.items()})
-        np.savez(path, global_step=self._step, global_epoch_step=self._epoch, **self.get_params(), **extra)
+        write_checkpoint(path, self._step, self._epoch, self.get_params(), self.get_slots())
         json.dump(self.config, open("%s-%d.json" % (base, self._step), "w"), indent=2)
         if not self.config.get("quiet"):
             print("model saved at %s" % path, flush=True)
@@ -993,11 +1039,10 @@ class Model(object):
 
     def restore(self, sess, path):
         """model.py:310-313."""
-        z = np.load(path)
-        self.set_params({k: z[k] for k in TABLE_KEYS + DENSE_KEYS})
-        self._step = int(z["global_step"])
-        self._epoch = int(z["global_epoch_step"])
-        if self.slots is not None and "slot1/item_emb" in z:
-            self.set_slots([{k: z["slot%d/%s" % (n, k)] for k in TABLE_KEYS + DENSE_KEYS} for n in (1, 2)])
+        step, epoch, params, slots = read_checkpoint(path, want_slots=self.slots is not None)
+        self.set_params(params)
+        self._step, self._epoch = step, epoch
+        if slots is not None:
+            self.set_slots(slots)
         if not self.config.get("quiet"):
             print("model restored from %s" % path, flush=True)

@@ -228,6 +228,90 @@ def eval_sampled(model, test_set, config, n, seed, exclude):
     return res
 
 
+def _run(args, say, model, train_set, triples, issue, eval_auc, eval_pr, eval_sampled, recommend, say_best, **extra):
+    """The flow of the reference's train.py:185-249, written once for train() and train_sharded(), which pass in what
+    differs between them:
+      triples()                     one epoch of the (shuffled) train_set as (batch, next, after_next) triples (_lookahead2)
+      issue(batch, lr, nxt, nxt2)   issues one step, with the batches to announce ahead (None: none) -> the device scalar
+                                    that holds the step's loss
+      eval_auc() -> AUC, eval_pr() -> (P@k, R@k over KS), eval_sampled() -> the sampled metrics (--eval_negatives)
+      recommend()                   writes the recommendation file (--recommend_k) -> its path, None on a rank that wrote none
+      say_best(best P@k, best R@k)  the driver's own closing lines about them
+      extra                         further entries of the result dict."""
+    import torch
+    t0 = time.time()
+    init_auc = eval_auc()
+    say("Init AUC: %.4f" % init_auc)
+    if args.eval_negatives:
+        say(sampled_line(args.eval_negatives, eval_sampled()))
+    lr = args.learning_rate
+    rng = epoch_rng(args.shuffle_seed)  # train.py:15,191 (sharded: the same shuffle on every rank)
+    best_auc, history = 0.0, []
+    best_prec, best_recall = [0.0] * 6, [0.0] * 6              # train.py:187-188
+    prec, recall = [0.0] * 6, [0.0] * 6
+    loss_sum = torch.zeros((), dtype=torch.float32, device=model.device)
+    done = False
+    for _ in range(args.max_epochs):
+        train_set.shuffle(rng)  # train.py:191
+        for batch, nxt, nxt2 in triples():
+            # the reference reads the loss back every step (model.py:229-234); the sum is all the driver
+            # uses, so it is accumulated on the device and read at the evaluation points only
+            left = (args.max_steps - model.global_step.eval() - 1) if args.max_steps else 2     # steps after this one
+            loss_sum += issue(batch, lr, nxt if left >= 1 else None, nxt2 if left >= 2 else None)
+            step = model.global_step.eval()
+            if step % args.eval_freq == 0:
+                auc = eval_auc()
+                history.append((step, time.time() - t0, auc))
+                say("Epoch %d Global_step %d\tTrain_loss: %.4f\tEval_auc: %.4f" %
+                    (model.global_epoch_step.eval(), step, float(loss_sum.item()) / args.eval_freq, auc), flush=True)
+                loss_sum.zero_()
+                if args.eval_negatives:
+                    say(sampled_line(args.eval_negatives, eval_sampled()))
+                if args.eval_topk:                             # train.py:209-218: P@k / R@k at every evaluation
+                    prec, recall = eval_pr()
+                    say("Precision:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, prec)))
+                    say("Recall:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, recall)))
+                    if step > 20000:                        # :222-227
+                        best_prec = [max(a_, b_) for a_, b_ in zip(best_prec, prec)]
+                        best_recall = [max(a_, b_) for a_, b_ in zip(best_recall, recall)]
+                if auc > 0.8 and auc > best_auc:  # train.py:228-230
+                    best_auc = auc
+                    model.save(None)
+                best_auc = max(best_auc, auc)
+            if step == 150000:  # train.py:232-233
+                lr = 0.1
+            if args.max_steps and step >= args.max_steps:
+                done = True
+                break
+        say("Epoch %d DONE\tCost time: %.2f" % (model.global_epoch_step.eval(), time.time() - t0), flush=True)  # :235-237
+        model.global_epoch_step_op.eval()
+        if done:
+            break
+    if not args.eval_topk or not history:   # (the reference reports what its evaluations saw; make sure there is one)
+        prec, recall = eval_pr()
+    final_auc = eval_auc()
+    best_auc = max(best_auc, final_auc)
+    final_sampled = eval_sampled() if args.eval_negatives else None
+    model.save(None)                                           # train.py:239
+    if args.recommend_k:
+        path = recommend()
+        if path is not None:
+            say("Recommendations: %s" % path)
+    model.train_writer.flush()
+    model.eval_writer.flush()
+    say("Best test_auc:", best_auc)
+    say_best(best_prec, best_recall)
+    if final_sampled is not None:
+        say(sampled_line(args.eval_negatives, final_sampled))
+    say("Finished", flush=True)
+    res = dict(init_auc=init_auc, best_auc=best_auc, final_auc=final_auc, steps=model.global_step.eval(),
+               seconds=time.time() - t0, history=history, prec=prec, recall=recall,
+               best_prec=best_prec, best_recall=best_recall, **extra)
+    if final_sampled is not None:
+        res["sampled"] = final_sampled
+    return res
+
+
 def train(args, data=None):
     """data (optional): (train PackedSet, test PackedSet, (U, I, C), item_cate_list) already in memory
     (tlsan_amd.build_dataset.build_packed) instead of --dataset."""
@@ -250,84 +334,28 @@ def train(args, data=None):
         train_batches = lambda: DeviceDataInput(train_set, args.train_batch_size, config["Ls"])
     else:
         train_batches = lambda: DataInput(train_set, args.train_batch_size, config["Ls"])
-    t0 = time.time()
-    init_auc = eval_auc(model, test_set, config)
-    say("Init AUC: %.4f" % init_auc)
-    sampled = lambda: eval_sampled(model, test_set, config, args.eval_negatives, args.eval_neg_seed, args.eval_neg_exclude)
-    if args.eval_negatives:
-        say(sampled_line(args.eval_negatives, sampled()))
-    lr = args.learning_rate
-    rng = epoch_rng(args.shuffle_seed)  # train.py:15,191
-    best_auc, history = 0.0, []
-    best_prec, best_recall = [0.0] * 6, [0.0] * 6              # train.py:187-188
-    prec, recall = [0.0] * 6, [0.0] * 6
-    import torch
-    loss_sum = torch.zeros((), dtype=torch.float32, device=args.device)
-    done = False
-    for _ in range(args.max_epochs):
-        train_set.shuffle(rng)  # train.py:191
-        for batch, nxt, nxt2 in _lookahead2(model.device_batch(b) for _, b in train_batches()):
-            # the reference reads the loss back every step (model.py:229-234); the sum is all the driver
-            # uses, so it is accumulated on the device and read at the evaluation points only
-            left = (args.max_steps - model.global_step.eval() - 1) if args.max_steps else 2     # steps after this one
-            model.train_async(batch, lr, next_batch=nxt if (nxt is not None and left >= 1) else None,
-                              after_next=nxt2 if (nxt2 is not None and left >= 2) else None)
-            loss_sum += model._out[0]
-            step = model.global_step.eval()
-            if args.display_freq and step % args.display_freq == 0:    # train.py:194-195 (add_summary)
-                model.train_writer.add_summary(model.train_summary(), global_step=step)
-            if step % args.eval_freq == 0:
-                auc = eval_auc(model, test_set, config)
-                history.append((step, time.time() - t0, auc))
-                say("Epoch %d Global_step %d\tTrain_loss: %.4f\tEval_auc: %.4f" %
-                    (model.global_epoch_step.eval(), step, float(loss_sum.item()) / args.eval_freq, auc), flush=True)
-                loss_sum.zero_()
-                if args.eval_negatives:
-                    say(sampled_line(args.eval_negatives, sampled()))
-                if args.eval_topk:                             # train.py:209-218: P@k / R@k at every evaluation
-                    prec, recall = eval_prec_recall(model, test_set, config)
-                    say("Precision:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, prec)))
-                    say("Recall:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, recall)))
-                    if step > 20000:                           # :222-227
-                        best_prec = [max(a_, b_) for a_, b_ in zip(best_prec, prec)]
-                        best_recall = [max(a_, b_) for a_, b_ in zip(best_recall, recall)]
-                if auc > 0.8 and auc > best_auc:  # train.py:228-230
-                    best_auc = auc
-                    model.save(None)
-                best_auc = max(best_auc, auc)
-            if step == 150000:  # train.py:232-233
-                lr = 0.1
-            if args.max_steps and step >= args.max_steps:
-                done = True
-                break
-        say("Epoch %d DONE\tCost time: %.2f" % (model.global_epoch_step.eval(), time.time() - t0), flush=True)  # :235-237
-        model.global_epoch_step_op.eval()
-        if done:
-            break
-    if not args.eval_topk or not history:   # (the reference reports what its evaluations saw; make sure there is one)
-        prec, recall = eval_prec_recall(model, test_set, config)
-    final_auc = eval_auc(model, test_set, config)
-    best_auc = max(best_auc, final_auc)
-    final_sampled = sampled() if args.eval_negatives else None
-    model.save(None)                                           # train.py:239
-    if args.recommend_k:
-        path = write_recommendations(args.model_dir, args.recommend_k,
-                                     *recommend_test_set(model, test_set, config, args.recommend_k, args.recommend_exclude))
-        say("Recommendations: %s" % path)
-    model.train_writer.flush()
-    model.eval_writer.flush()
-    say("Best test_auc:", best_auc)
-    say("Best precision:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, best_prec)))   # :241-248
-    say("Best recall:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, best_recall)))
-    if final_sampled is not None:
-        say(sampled_line(args.eval_negatives, final_sampled))
-    say("Finished", flush=True)
-    res = dict(init_auc=init_auc, best_auc=best_auc, final_auc=final_auc, steps=model.global_step.eval(),
-               seconds=time.time() - t0, history=history, prec=prec, recall=recall,
-               best_prec=best_prec, best_recall=best_recall)
-    if final_sampled is not None:
-        res["sampled"] = final_sampled
-    return res
+
+    def issue(batch, lr, nxt, nxt2):
+        model.train_async(batch, lr, next_batch=nxt, after_next=nxt2)
+        step = model.global_step.eval()
+        if args.display_freq and step % args.display_freq == 0:    # train.py:194-195 (add_summary)
+            model.train_writer.add_summary(model.train_summary(), global_step=step)
+        return model._out[0]
+
+    def say_best(best_prec, best_recall):                              # train.py:241-248
+        say("Best precision:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, best_prec)))
+        say("Best recall:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, best_recall)))
+
+    return _run(args, say, model, train_set,
+                triples=lambda: _lookahead2(model.device_batch(b) for _, b in train_batches()), issue=issue,
+                eval_auc=lambda: eval_auc(model, test_set, config),
+                eval_pr=lambda: eval_prec_recall(model, test_set, config),
+                eval_sampled=lambda: eval_sampled(model, test_set, config, args.eval_negatives, args.eval_neg_seed,
+                                                  args.eval_neg_exclude),
+                recommend=lambda: write_recommendations(
+                    args.model_dir, args.recommend_k,
+                    *recommend_test_set(model, test_set, config, args.recommend_k, args.recommend_exclude)),
+                say_best=say_best)
 
 
 def _lookahead2(it):
@@ -452,63 +480,7 @@ def train_sharded(args):
         model.eval_writer.add_summary(list(res.items()), global_step=model.global_step.eval())
         return res
 
-    t0 = time.time()
-    init_auc = eval_auc_()
-    say("Init AUC: %.4f" % init_auc)
-    if args.eval_negatives:
-        say(sampled_line(args.eval_negatives, eval_sampled_()))
-    lr = args.learning_rate
-    rng = epoch_rng(args.shuffle_seed)             # train.py:15,191; the same shuffle on every rank
-    best_auc, history = 0.0, []
-    best_prec, best_recall = [0.0] * 6, [0.0] * 6
-    prec, recall = [0.0] * 6, [0.0] * 6
-    loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
-    done = False
-    for _ in range(args.max_epochs):
-        train_set.shuffle(rng)
-        shares = (_share(b, rank, world) + (len(b[0]),) for _, b in DataInput(train_set, args.train_batch_size, config["Ls"]))
-        for (part, real, n_glob), nxt, nxt2 in _lookahead2((model.device_batch(p_), r_, n_) for p_, r_, n_ in shares):
-            left = (args.max_steps - model.global_step.eval() - 1) if args.max_steps else 2     # steps after this one
-            model.train_async(part, lr, next_batch=nxt[0] if (nxt is not None and left >= 1) else None,
-                              after_next=nxt2[0] if (nxt2 is not None and left >= 2 and args.static_rows) else None,
-                              weight=real * world / n_glob, sample0=n_glob * rank // world)
-            loss_sum += model.last_loss[0]
-            step = model.global_step.eval()
-            if step % args.eval_freq == 0:
-                auc = eval_auc_()
-                history.append((step, time.time() - t0, auc))
-                say("Epoch %d Global_step %d\tTrain_loss: %.4f\tEval_auc: %.4f" %
-                    (model.global_epoch_step.eval(), step, float(loss_sum.item()) / args.eval_freq, auc), flush=True)
-                loss_sum.zero_()
-                if args.eval_negatives:
-                    say(sampled_line(args.eval_negatives, eval_sampled_()))
-                if args.eval_topk:
-                    prec, recall = eval_pr_()
-                    say("Precision:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, prec)))
-                    say("Recall:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, recall)))
-                    if step > 20000:
-                        best_prec = [max(a_, b_) for a_, b_ in zip(best_prec, prec)]
-                        best_recall = [max(a_, b_) for a_, b_ in zip(best_recall, recall)]
-                if auc > 0.8 and auc > best_auc:
-                    best_auc = auc
-                    model.save(None)
-                best_auc = max(best_auc, auc)
-            if step == 150000:
-                lr = 0.1
-            if args.max_steps and step >= args.max_steps:
-                done = True
-                break
-        say("Epoch %d DONE\tCost time: %.2f" % (model.global_epoch_step.eval(), time.time() - t0), flush=True)
-        model._epoch += 1
-        if done:
-            break
-    if not args.eval_topk or not history:
-        prec, recall = eval_pr_()
-    final_auc = eval_auc_()
-    best_auc = max(best_auc, final_auc)
-    final_sampled = eval_sampled_() if args.eval_negatives else None
-    model.save(None)
-    if args.recommend_k:
+    def recommend_():
         # every rank takes its share of each test batch; rank 0 gathers the shares (in rank order: the batch's order)
         from .dist import allgather_rows
         k, parts = args.recommend_k, []
@@ -523,20 +495,21 @@ def train_sharded(args):
                 parts.append([np.concatenate([g.cpu().numpy()[r * w:r * w + n_real[r]] for r in range(world)])
                               for g in got])
         if rank == 0:
-            path = write_recommendations(args.model_dir, k, *(np.concatenate(x) for x in zip(*parts)))
-            say("Recommendations: %s" % path)
-    model.train_writer.flush()
-    model.eval_writer.flush()
-    say("Best test_auc:", best_auc)
-    if final_sampled is not None:
-        say(sampled_line(args.eval_negatives, final_sampled))
-    say("Finished", flush=True)
-    res = dict(init_auc=init_auc, best_auc=best_auc, final_auc=final_auc, steps=model.global_step.eval(),
-               seconds=time.time() - t0, history=history, prec=prec, recall=recall,
-               best_prec=best_prec, best_recall=best_recall, world=world)
-    if final_sampled is not None:
-        res["sampled"] = final_sampled
-    return res
+            return write_recommendations(args.model_dir, k, *(np.concatenate(x) for x in zip(*parts)))
+
+    def triples():
+        shares = (_share(b, rank, world) + (len(b[0]),) for _, b in DataInput(train_set, args.train_batch_size, config["Ls"]))
+        return _lookahead2((model.device_batch(p_), r_, n_) for p_, r_, n_ in shares)
+
+    def issue(share, lr, nxt, nxt2):
+        part, real, n_glob = share
+        model.train_async(part, lr, next_batch=None if nxt is None else nxt[0],
+                          after_next=nxt2[0] if (nxt2 is not None and args.static_rows) else None,
+                          weight=real * world / n_glob, sample0=n_glob * rank // world)
+        return model.last_loss[0]
+
+    return _run(args, say, model, train_set, triples, issue, eval_auc_, eval_pr_, eval_sampled_, recommend_,
+                say_best=lambda best_prec, best_recall: None, world=world)
 
 
 def main(argv=None):
