@@ -374,6 +374,30 @@ int tlsan_eval_counts_shard(const tlsan_dims* dims, const tlsan_params* p, const
                             const int32_t* labels_global, int32_t B, int32_t id_mul, int32_t id_add, int32_t* counts,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* The all-items ranking with per-row exclusion lists: the rank of a label among the items its row has NOT seen (the
+ * leave-one-out protocol of a next-item recommender).  tlsan_eval_ranks_excl / tlsan_eval_counts_shard_excl do what
+ * tlsan_eval_ranks / tlsan_eval_counts_shard do -- ranks / counts are theirs, unfiltered, bit for bit -- and, in the same
+ * call (one dense item matrix, where the rank path builds one, for both), say what the lists change:
+ *   excl_off [B + 1] / excl_ids: row b's list excl_ids[excl_off[b] .. excl_off[b+1]) of global ids, ascending, as
+ *     tlsan_eval_topk's; repeats and ids outside the table are ignored.  THE LABEL IS NEVER EXCLUDED, even when its row
+ *     lists it (a test label can sit in its user's own history: SURVEY 8c).
+ *   held[b]:  the number of DISTINCT listed items, other than the label, that this table holds;
+ *   ahead[b]: how many of those the rank path counted ahead of the label: score > label's score, or equal and a lower
+ *     global id -- the decision of the counting kernel this call ran on this table, on the same operands, the same
+ *     MFMA chain and the same rounding of (acc * P) + bias (the kernel that reads the dense item matrix contracts the
+ *     two into one fused multiply-add, the gathering one does not; the count of the listed items follows whichever ran).
+ *   filtered rank = ranks[b] - ahead[b] (never negative);  eligible items = item_count - 1 - held[b].
+ * Item-sharded form: ids this table does not hold are skipped, so counts, ahead and held each sum exactly over the ranks.
+ * ranks / counts, ahead, held: [B] int32, all required.  A row's result does not depend on B, on the other rows or on
+ * the launch geometry.  Workspace: tlsan_workspace_bytes(dims, B, 0), as tlsan_eval_ranks. */
+int tlsan_eval_ranks_excl(const tlsan_dims* dims, const tlsan_params* p, const float* u_t, const int32_t* labels, int32_t B,
+                          const int32_t* excl_off, const int32_t* excl_ids, int32_t* ranks, int32_t* ahead, int32_t* held,
+                          void* ws, size_t ws_bytes, void* stream);
+int tlsan_eval_counts_shard_excl(const tlsan_dims* dims, const tlsan_params* p, const float* u_t, const float* label_scores,
+                                 const int32_t* labels_global, int32_t B, int32_t id_mul, int32_t id_add,
+                                 const int32_t* excl_off, const int32_t* excl_ids, int32_t* counts, int32_t* ahead,
+                                 int32_t* held, void* ws, size_t ws_bytes, void* stream);
+
 /* Top-K recommendation over all items -- what the reference gets with tf.nn.top_k(eval_logits, K)
  * (model.py:140), without materialising the [B, I] scores: for each row b of u_t [B, d], the K items
  * of highest score  u_t[b] . [item_emb || cate_emb[item_cate]][n] + item_b[n]  (the scores of

@@ -25,6 +25,7 @@ EXPORTS = [
     "tlsan_state_bytes", "tlsan_state_init", "tlsan_state_reindex", "tlsan_state_recategorize", "tlsan_state_scale",
     "tlsan_state_renorm", "tlsan_sync_derived", "tlsan_forward", "tlsan_forward_att",
     "tlsan_train_step", "tlsan_train_step_opt", "tlsan_batch_pack", "tlsan_batch_index", "tlsan_grads", "tlsan_eval_ranks", "tlsan_eval_label_scores", "tlsan_eval_counts_shard",
+    "tlsan_eval_ranks_excl", "tlsan_eval_counts_shard_excl",
     "tlsan_topk_workspace_bytes", "tlsan_eval_topk", "tlsan_topk_merge",
     "tlsan_score_candidates", "tlsan_candidate_ranks", "tlsan_sample_negatives", "tlsan_profile_enable", "tlsan_profile_stride",
     "tlsan_profile_collect", "tlsan_debug_stamps", "tlsan_rows_apply_workspace", "tlsan_rows_apply", "tlsan_scan_compact",
@@ -181,6 +182,13 @@ def load():
     lib.tlsan_eval_counts_shard.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.tlsan_eval_counts_shard.restype = C.c_int
+    lib.tlsan_eval_ranks_excl.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.tlsan_eval_ranks_excl.restype = C.c_int
+    lib.tlsan_eval_counts_shard_excl.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.tlsan_eval_counts_shard_excl.restype = C.c_int
     lib.tlsan_topk_workspace_bytes.argtypes = [P(Dims), C.c_int32, C.c_int32]
     lib.tlsan_topk_workspace_bytes.restype = C.c_size_t
     lib.tlsan_eval_topk.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,

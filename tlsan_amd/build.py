@@ -1,6 +1,6 @@
 """Build libtlsan_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: fourteen translation
 units (the C ABI with every kernel but the fused one, the top-K selection and the candidate kernels; the top-K selection;
-the candidate scoring, ranks and negative sampling; k_fwd_bwd for d = 64 / 128 / 128 as 8-sample workgroups / 256 with
+the candidate scoring, ranks, negative sampling and the exclusion-list count; k_fwd_bwd for d = 64 / 128 / 128 as 8-sample workgroups / 256 with
 the window in registers / 256 streamed, all with 8 heads; k_fwd_bwd and the dense finalize kernels for each of the
 pairs 64/4, 128/16 and 128/4) compiled in parallel, one link.  `python -m tlsan_amd.build` or `build()`."""
 from __future__ import annotations

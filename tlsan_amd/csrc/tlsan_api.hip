@@ -40,6 +40,7 @@ hipError_t tlsan_launch_topk_merge(const int32_t* cid, const float* csc, int B, 
 hipError_t tlsan_launch_score_cand(const CandArgs& a, int D, hipStream_t hs);
 hipError_t tlsan_launch_cand_ranks(const int32_t* cand, const float* scores, int B, int C, int32_t* ranks, hipStream_t hs);
 hipError_t tlsan_launch_sample_neg(const NegArgs& a, hipStream_t hs);
+hipError_t tlsan_launch_excl_ahead(const ExclArgs& a, int D, hipStream_t hs);
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, ...) {
@@ -1236,9 +1237,11 @@ int tlsan_grads(const tlsan_dims* d, const tlsan_params* p, const tlsan_batch* b
   return launch_tail(s, P, hp, out, w, st, hs);
 }
 
+// the exclusion lists of the _excl entry points and their two outputs (all NULL: none)
+struct ExclOut { const int32_t* off; const int32_t* ids; int32_t* ahead; int32_t* held; };
 static int eval_ranks_impl(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const int32_t* labels, int32_t B,
                            int32_t* ranks, void* ws, size_t ws_bytes, void* stream, const float* s_label_in, int id_mul,
-                           int id_add, float* s_label_out);
+                           int id_add, float* s_label_out, const ExclOut* xo = nullptr);
 
 int tlsan_eval_ranks(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const int32_t* labels, int32_t B,
                      int32_t* ranks, void* ws, size_t ws_bytes, void* stream) {
@@ -1258,10 +1261,34 @@ int tlsan_eval_counts_shard(const tlsan_dims* d, const tlsan_params* p, const fl
   return eval_ranks_impl(d, p, u_t, labels_global, B, counts, ws, ws_bytes, stream, label_scores, id_mul, id_add, nullptr);
 }
 
+int tlsan_eval_ranks_excl(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const int32_t* labels, int32_t B,
+                          const int32_t* excl_off, const int32_t* excl_ids, int32_t* ranks, int32_t* ahead, int32_t* held,
+                          void* ws, size_t ws_bytes, void* stream) {
+  if (!excl_off || !excl_ids || !ranks || !ahead || !held) return fail(TLSAN_E_BADARG, "tlsan_eval_ranks_excl: NULL argument");
+  const ExclOut xo = {excl_off, excl_ids, ahead, held};
+  return eval_ranks_impl(d, p, u_t, labels, B, ranks, ws, ws_bytes, stream, nullptr, 1, 0, nullptr, &xo);
+}
+
+int tlsan_eval_counts_shard_excl(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const float* label_scores,
+                                 const int32_t* labels_global, int32_t B, int32_t id_mul, int32_t id_add,
+                                 const int32_t* excl_off, const int32_t* excl_ids, int32_t* counts, int32_t* ahead,
+                                 int32_t* held, void* ws, size_t ws_bytes, void* stream) {
+  if (!label_scores || !counts || !excl_off || !excl_ids || !ahead || !held)
+    return fail(TLSAN_E_BADARG, "tlsan_eval_counts_shard_excl: NULL argument");
+  if (id_mul < 1 || id_add < 0 || (d && (long long)(d->item_count - 1) * id_mul + id_add >= (1LL << 31)))
+    return fail(TLSAN_E_BADARG, "tlsan_eval_counts_shard_excl: global ids n * id_mul + id_add must be non-negative int32");
+  const ExclOut xo = {excl_off, excl_ids, ahead, held};
+  return eval_ranks_impl(d, p, u_t, labels_global, B, counts, ws, ws_bytes, stream, label_scores, id_mul, id_add, nullptr, &xo);
+}
+
+// The one place that says which counting kernel ranks a table: the one that reads the dense item matrix when the
+// workspace holds one (carve: up to EVAL_DENSE_MAX bytes), else the gathering one.  k_excl_ahead follows it.
+static bool eval_rank_dense(const EvalArgs& e) { return e.all_emb != nullptr; }
+
 // s_label_in == NULL: the label's score is computed here (labels index THIS table); s_label_out != NULL: only that.
 static int eval_ranks_impl(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const int32_t* labels, int32_t B,
                            int32_t* ranks, void* ws, size_t ws_bytes, void* stream, const float* s_label_in, int id_mul,
-                           int id_add, float* s_label_out) {
+                           int id_add, float* s_label_out, const ExclOut* xo) {
   Shape s;
   int rc = shape_of(d, &s);
   if (rc) return rc;
@@ -1291,7 +1318,7 @@ static int eval_ranks_impl(const tlsan_dims* d, const tlsan_params* p, const flo
   do {                                                                                                   \
     if (!s_label_in) hipLaunchKernelGGL(k_eval_label<DD>, dim3(ut), dim3(64), 0, hs, e);                 \
     if (!ranks) break;                                                                                   \
-    if (e.all_emb) {                                                                                     \
+    if (eval_rank_dense(e)) {                                                                            \
       hipLaunchKernelGGL(k_all_emb<DD>, dim3(nae), dim3(256), 0, hs, e);                                 \
       hipLaunchKernelGGL(k_eval_rank_dense<DD>, dim3(ut, ngrp), dim3(256), 0, hs, e);                    \
     } else {                                                                                             \
@@ -1303,6 +1330,17 @@ static int eval_ranks_impl(const tlsan_dims* d, const tlsan_params* p, const flo
   else EVAL_LAUNCH(256);
 #undef EVAL_LAUNCH
   CHECK_LAUNCH("k_eval");
+  if (xo) {   // after the count: the dense item matrix of this call is there, and s_label holds the labels' scores
+    if (hipMemsetAsync(xo->ahead, 0, sizeof(int32_t) * (size_t)B, hs) != hipSuccess ||
+        hipMemsetAsync(xo->held, 0, sizeof(int32_t) * (size_t)B, hs) != hipSuccess)
+      return fail(TLSAN_E_LAUNCH, "memset ahead / held");
+    ExclArgs xa;
+    memset(&xa, 0, sizeof(xa));
+    xa.e = e; xa.excl_off = xo->off; xa.excl_ids = xo->ids; xa.ahead = xo->ahead; xa.held = xo->held;
+    xa.fused = eval_rank_dense(e) ? 1 : 0;
+    const hipError_t err = tlsan_launch_excl_ahead(xa, s.D, hs);
+    if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_excl_ahead: %s", hipGetErrorString(err));
+  }
   return TLSAN_OK;
 }
 

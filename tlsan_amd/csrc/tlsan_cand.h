@@ -12,6 +12,9 @@
 //
 // k_sample_neg (tlsan_cand.hip): the first N distinct eligible items of the row's draw sequence (cand_draw); the
 // definition is in include/tlsan.h.
+//
+// k_excl_ahead (tlsan_cand.hip): for the items of a row's exclusion list, the decision the all-items rank kernel took
+// for them (ExclArgs below) -- what a filtered rank subtracts from tlsan_eval_ranks' rank.
 #pragma once
 #include "tlsan_eval.h"
 #include "tlsan_topk.h"
@@ -23,6 +26,20 @@ struct CandArgs {
   int32_t C;
   const int32_t* cand;      // [B, C] global item ids
   float* scores;            // [B, C]
+};
+
+// k_excl_ahead: row b's list is excl_ids[excl_off[b] .. excl_off[b + 1]) (global ids, ascending).  An entry counts when
+// it is the first of its value, is not the row's label and is held by this table (cand_local); held[b] += 1 for it, and
+// ahead[b] += 1 when the rank kernel of this table counted it ahead of the label.  `fused` says which rank kernel that
+// was: k_eval_rank_dense (e.all_emb set) forms the score as ONE fused multiply-add fma(acc, P, bias), k_eval_rank as a
+// rounded product and a rounded sum (read off their ISA: v_fma_f32 / v_fmac_f32 against v_pk_mul_f32 + v_add_f32, every width).
+struct ExclArgs {
+  EvalArgs e;               // p, u_t, labels (global ids), s_label, B, I, di, dc, all_emb (dense form), id_mul, id_add
+  const int32_t* excl_off;  // [B + 1]
+  const int32_t* excl_ids;
+  int32_t* ahead;           // [B], zeroed before the launch
+  int32_t* held;            // [B], zeroed before the launch
+  int32_t fused;            // 1: fma(acc, P, bias) (k_eval_rank_dense); 0: (acc * P) + bias (k_eval_rank)
 };
 
 // Local item of global id g, or -1 when this table does not hold it.

@@ -1305,7 +1305,7 @@ class ShardedModel:
         return float(self.last_loss.item())
 
     # ------------------------------------------------------------------ evaluation
-    def forward(self, batch, is_test=True, want_ranks=False):
+    def forward(self, batch, is_test=True, want_ranks=False, exclude=None):
         db = self.device_batch(batch, is_test)
         sl = self._plan_eval(db)
         table = self._fetch(sl)
@@ -1316,16 +1316,32 @@ class ShardedModel:
         L.check(self.lib.tlsan_forward(C.byref(dims), C.byref(cp), C.byref(cb), li.data_ptr(),
                                        None if lj is None else lj.data_ptr(), None if ut is None else ut.data_ptr(),
                                        None, 0, self._stream()), "tlsan_forward")
-        ranks = self._ranks(db, dims, cp, cb, ut) if want_ranks else None
+        ranks = self._ranks(db, dims, cp, cb, ut, exclude) if want_ranks else None
         torch.cuda.current_stream(self.device).synchronize()   # `table` stays alive until done
         return (li, lj, ranks) if want_ranks else (li, lj)
 
-    def _ranks(self, db, dims, cp, cb, ut):
+    def _gather_excl(self, off, xid, B):
+        """The exclusion lists (exclusion_csr) of every rank's rows: slots of one width, padded to the widest rank's with
+        ignored ids -> (off, ids) over the world * B all-gathered rows."""
+        if off is None or self.world == 1:
+            return off, xid
+        w = int(off[1].item())
+        width = int(allgather_rows(torch.tensor([w], device=self.device), self.group).max().item())
+        rows = torch.full((B, width), np.iinfo(np.int32).max, dtype=torch.int32, device=self.device)
+        rows[:, :w] = xid.view(B, w)
+        xid = allgather_rows(rows, self.group).view(-1)
+        off = torch.arange(0, (self.world * B + 1) * width, width, dtype=torch.int32, device=self.device)
+        return off, xid
+
+    def _ranks(self, db, dims, cp, cb, ut, exclude=None):
         """All-items ranking with the items sharded: the label's own score comes from the
         compact table of the rank that holds the user; u_t, label scores and label ids are
         all-gathered; every rank counts the items of ITS shard that rank ahead of each label
         (ties -> lower global id, tf.nn.top_k's order); one all-reduce of the counts gives the
-        ranks.  Same kernels as the single-GPU tlsan_eval_ranks."""
+        ranks.  Same kernels as the single-GPU tlsan_eval_ranks.
+        exclude (Model.label_ranks' forms): the lists are all-gathered with u_t, every rank also counts the listed
+        items of ITS shard (tlsan_eval_counts_shard_excl: those it holds, and those of them it counted ahead of the
+        label), and the two counts ride in the same all-reduce -> (filtered ranks, eligible items) of this rank's rows."""
         B, st = db.B, self._stream()
         nws = self.lib.tlsan_workspace_bytes(C.byref(dims), B, 0)
         if self._ws is None or self._ws.numel() < nws:
@@ -1339,6 +1355,19 @@ class ShardedModel:
         nws = self.lib.tlsan_workspace_bytes(C.byref(ldims), Bt, 0)
         if self._ews is None or self._ews.numel() < nws:
             self._ews = torch.empty(int(nws * 1.25), dtype=torch.uint8, device=self.device)
+        if exclude is not None:
+            off, xid = self._gather_excl(*exclusion_csr(db, exclude, self.I), B)
+            cah = torch.zeros(3, Bt, dtype=torch.int32, device=self.device)     # counts, ahead, held
+            if nloc > 0:
+                L.check(self.lib.tlsan_eval_counts_shard_excl(C.byref(ldims), C.byref(lp), ut_all.data_ptr(), s_all.data_ptr(),
+                                                              lab_all.data_ptr(), Bt, self.world, self.rank, off.data_ptr(),
+                                                              xid.data_ptr(), cah[0].data_ptr(), cah[1].data_ptr(),
+                                                              cah[2].data_ptr(), self._ews.data_ptr(), self._ews.numel(), st),
+                        "tlsan_eval_counts_shard_excl")
+            if self.world > 1:
+                allreduce_sum(cah, self.group)
+            mine = cah[:, self.rank * B:(self.rank + 1) * B]
+            return mine[0] - mine[1], (self.I - 1) - mine[2]
         counts = torch.zeros(Bt, dtype=torch.int32, device=self.device)
         if nloc > 0:
             L.check(self.lib.tlsan_eval_counts_shard(C.byref(ldims), C.byref(lp), ut_all.data_ptr(), s_all.data_ptr(),
@@ -1373,17 +1402,9 @@ class ShardedModel:
         ut = torch.empty(B, self.d, dtype=torch.float32, device=self.device)
         L.check(self.lib.tlsan_forward(C.byref(dims), C.byref(cp), C.byref(cb), li.data_ptr(), None, ut.data_ptr(),
                                        None, 0, st), "tlsan_forward")
-        off, xid = exclusion_csr(db, exclude, self.I)
         ut_all = allgather_rows(ut, self.group)
         Bt = int(ut_all.shape[0])
-        if off is not None and self.world > 1:
-            # every rank's rows: slots of one width (exclusion_csr), padded to the widest rank's with ignored ids
-            w = int(off[1].item())
-            width = int(allgather_rows(torch.tensor([w], device=self.device), self.group).max().item())
-            rows = torch.full((B, width), np.iinfo(np.int32).max, dtype=torch.int32, device=self.device)
-            rows[:, :w] = xid.view(B, w)
-            xid = allgather_rows(rows, self.group).view(-1)
-            off = torch.arange(0, (Bt + 1) * width, width, dtype=torch.int32, device=self.device)
+        off, xid = self._gather_excl(*exclusion_csr(db, exclude, self.I), B)
         nloc, ldims, lp = self._item_shard()
         if nloc > 0:
             def workspace(nbytes):
@@ -1478,9 +1499,15 @@ class ShardedModel:
     def eval_recall(self, sess, batch, n_valid=None):
         return self._topk.add_recall(*self._hits(batch, n_valid))
 
-    def label_ranks(self, batch):
-        """rank of the positive item among ALL items for each test row of this rank's batch (model.py:140-156)"""
-        return self.forward(batch, is_test=True, want_ranks=True)[2]
+    def label_ranks(self, batch, exclude=None, return_eligible=False):
+        """rank of the positive item among ALL items for each test row of this rank's batch (model.py:140-156).
+        exclude / return_eligible: Model.label_ranks' -- the filtered rank among the items the row's list does not hold
+        (the label is never excluded) and the number of items the label competes with; every rank calls it with the
+        same exclusion mode.  Same integers as Model.label_ranks."""
+        r = self.forward(batch, is_test=True, want_ranks=True, exclude=exclude)[2]
+        if exclude is None:
+            return (r, torch.full_like(r, self.I - 1)) if return_eligible else r
+        return r if return_eligible else r[0]
 
     def eval_auc(self, sess, batch):
         li, lj = self.forward(batch, is_test=True)

@@ -162,6 +162,29 @@ class DataInputTest(_Input):
             raise ValueError("DataInputTest needs test tuples")
 
 
+def seen_items_csr(train_set, n_users):
+    """Every user's seen items from a training PackedSet, as a CSR (off [n_users + 1], ids), both int64: user u's list
+    ids[off[u]:off[u + 1]] is sorted and distinct and holds every item of the `hist` and `sess` of u's samples and every
+    `target` whose label is 1 (a target with label 0 is a sampled negative, not an interaction).  A user without
+    samples has an empty list.  Note that a TEST label is often inside its user's list (the reference's builder keeps
+    the held-out item in the training sessions), which is why the filtered ranking never excludes the label."""
+    if train_set.is_test:
+        raise ValueError("seen_items_csr needs train tuples")
+    u = train_set.u
+    pos = train_set.label == 1
+    users = np.concatenate([np.repeat(u, np.diff(train_set.hist_off)), np.repeat(u, np.diff(train_set.sess_off)), u[pos]])
+    items = np.concatenate([train_set.hist, train_set.sess, train_set.target[pos]])
+    if users.size and (users.min() < 0 or users.max() >= n_users):
+        raise ValueError("seen_items_csr: user id outside 0..%d" % (n_users - 1))
+    if items.size and items.min() < 0:
+        raise ValueError("seen_items_csr: negative item id")
+    span = int(items.max()) + 1 if items.size else 1
+    key = np.unique(users * span + items)          # (sorted by user, then item; repeats dropped)
+    off = np.zeros(n_users + 1, np.int64)
+    off[1:] = np.cumsum(np.bincount(key // span, minlength=n_users))
+    return off, key % span
+
+
 def load_packed(path):
     """Load a ``packed_<name>.npz`` export: (train PackedSet, test PackedSet, (U,I,C), item_cate_list)."""
     z = np.load(path)

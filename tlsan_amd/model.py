@@ -196,25 +196,70 @@ def concurrent_streams(device, want=1, pool=6, **stream_kw):
     return chosen
 
 
+class SeenItems:
+    """Every user's seen items (input.seen_items_csr) on the device: the fourth form of `exclude` that exclusion_csr
+    -- and so recommend, sample_negatives, sampled_ranks and label_ranks, single and sharded -- takes.  A row b then
+    keeps out the seen list of its user db.u[b] UNITED with the row's own input (what "history" gives: a test row's
+    input is not always inside its user's training list)."""
+
+    def __init__(self, off, ids, device):
+        off, ids = np.asarray(off, np.int64), np.asarray(ids, np.int64)
+        if off.ndim != 1 or len(off) < 2 or off[0] != 0 or off[-1] != len(ids) or (np.diff(off) < 0).any():
+            raise ValueError("SeenItems: off must be a CSR offset array [n_users + 1] over ids")
+        if len(ids) and (ids.min() < 0 or ids.max() > np.iinfo(np.int32).max):
+            raise ValueError("SeenItems: item ids must be non-negative int32")
+        self.n_users = len(off) - 1
+        self.max_len = int(np.diff(off).max())
+        self.off = torch.as_tensor(off).to(device)
+        self.ids = torch.as_tensor(np.concatenate([ids, [0]]).astype(np.int32)).to(device)   # (+1: never empty)
+
+    @classmethod
+    def from_train_set(cls, train_set, n_users, device):
+        from .input import seen_items_csr
+        return cls(*seen_items_csr(train_set, n_users), device=device)
+
+    def rows(self, u, pad):
+        """[B, max_len] int32: the list of each row's user, left-aligned, the rest `pad` (a user id outside
+        0 .. n_users - 1 has an empty list: checking it would be a host round trip per batch)."""
+        u = u.long()
+        known = (u >= 0) & (u < self.n_users)
+        u = torch.where(known, u, 0)
+        lo = self.off[u]
+        n = torch.where(known, self.off[u + 1] - lo, 0)
+        ar = torch.arange(max(self.max_len, 1), device=u.device)[None, :]
+        ok = ar < n[:, None]
+        return torch.where(ok, self.ids[torch.where(ok, lo[:, None] + ar, 0)], pad).to(torch.int32)
+
+
+def _input_items(db, pad):
+    """[B, Ls + Sn] int32: the items the row's input holds (hist_i[b, :sl[b]], hist_i_new[b, :sl_new[b]]), the rest
+    `pad` (the padding past the lengths is item 0, a real item, so the lengths decide)."""
+    B, dev = db.B, db.i.device
+    ar = torch.arange(db.hist_i.shape[1], device=dev)[None, :]
+    vals = [torch.where(ar < db.sl.long()[:, None], db.hist_i, pad)]
+    if db.Sn > 0:
+        ar = torch.arange(db.Sn, device=dev)[None, :]
+        vals.append(torch.where(ar < db.sl_new.long()[:, None], db.hist_i_new.reshape(B, db.Sn), pad))
+    return torch.cat(vals, 1).to(torch.int32)
+
+
 def exclusion_csr(db, exclude, n_items):
     """Per-row item lists to keep out of a recommendation, as the CSR tlsan_eval_topk takes: (excl_off [B + 1],
     excl_ids) int32 device tensors.  exclude: None -> (None, None); "history" -> the items the row's input holds,
     hist_i[b, :sl[b]] and hist_i_new[b, :sl_new[b]] (the padding past the lengths is item 0, a real item, so the
-    lengths decide); or a sequence of B arrays of item ids.  Built on the device without a host round trip: every row
+    lengths decide); a sequence of B arrays of item ids; or a SeenItems holder -> the seen list of the row's user
+    db.u[b] united with the row's own input.  Built on the device without a host round trip: every row
     is a slot of the same width, sorted, its repeats and its unused slots set to INT32_MAX (ids outside the table are
     ignored by the kernel, so they sort to the end of the row and cost nothing)."""
     if exclude is None:
         return None, None
     B, dev, pad = db.B, db.i.device, np.iinfo(np.int32).max
-    if isinstance(exclude, str):
+    if isinstance(exclude, SeenItems):
+        vals = torch.cat([exclude.rows(db.u, pad), _input_items(db, pad)], 1)
+    elif isinstance(exclude, str):
         if exclude != "history":
-            raise ValueError("exclude must be None, 'history' or a sequence of per-row id arrays")
-        ar = torch.arange(db.hist_i.shape[1], device=dev)[None, :]
-        vals = [torch.where(ar < db.sl.long()[:, None], db.hist_i, pad)]
-        if db.Sn > 0:
-            ar = torch.arange(db.Sn, device=dev)[None, :]
-            vals.append(torch.where(ar < db.sl_new.long()[:, None], db.hist_i_new.reshape(B, db.Sn), pad))
-        vals = torch.cat(vals, 1).to(torch.int32)
+            raise ValueError("exclude must be None, 'history', a SeenItems or a sequence of per-row id arrays")
+        vals = _input_items(db, pad)
     else:
         if len(exclude) != B:
             raise ValueError("exclude: %d lists for %d rows" % (len(exclude), B))
@@ -347,10 +392,9 @@ def rank_histogram(ranks, n):
     return np.bincount(r, minlength=n + 1).astype(np.int64)
 
 
-def metrics_from_histogram(hist, n, ks=SAMPLED_KS):
-    """The sampled-evaluation metrics of a rank histogram (rank_histogram), summed in float64:
-    HR@k = mean(rank < k), NDCG@k = mean([rank < k] / log2(rank + 2)), MRR = mean(1 / (rank + 1)),
-    AUC_N = mean(1 - rank / n)."""
+def _histogram_sums(hist, ks):
+    """HR@k, NDCG@k and MRR of a rank histogram (hist[r] rows of rank r), summed in float64 -- the one implementation,
+    for the sampled evaluation (metrics_from_histogram) and the full ranking (full_ranking_metrics)."""
     hist = np.asarray(hist, np.int64)
     rows = int(hist.sum())
     r = np.arange(len(hist), dtype=np.float64)
@@ -361,8 +405,26 @@ def metrics_from_histogram(hist, n, ks=SAMPLED_KS):
     for k in ks:
         out["NDCG@%d" % k] = float((h[:k] / np.log2(r[:k] + 2.0)).sum()) / rows
     out["MRR"] = float((h / (r + 1.0)).sum()) / rows
+    return out
+
+
+def metrics_from_histogram(hist, n, ks=SAMPLED_KS):
+    """The sampled-evaluation metrics of a rank histogram (rank_histogram), summed in float64:
+    HR@k = mean(rank < k), NDCG@k = mean([rank < k] / log2(rank + 2)), MRR = mean(1 / (rank + 1)),
+    AUC_N = mean(1 - rank / n)."""
+    hist = np.asarray(hist, np.int64)
+    rows = int(hist.sum())
+    out = _histogram_sums(hist, ks)
     out["AUC_N"] = 1.0 - float(int((hist * np.arange(len(hist), dtype=np.int64)).sum())) / (float(n) * rows)
     return out
+
+
+def full_ranking_metrics(hist, ks=SAMPLED_KS):
+    """HR@k, NDCG@k and MRR of the histogram of the (filtered) label ranks over all items (rank_histogram with
+    n = item_count - 1; Model.label_ranks(exclude=)).  Counts are exact integers, so histograms of launches and of ranks
+    add up and the result does not depend on the split.  AUC_N is not defined here: the number of eligible items
+    differs from row to row."""
+    return _histogram_sums(hist, ks)
 
 
 def sampled_metrics(ranks, n, ks=SAMPLED_KS):
@@ -958,15 +1020,33 @@ class Model(object):
         li, lj, _, _ = self.forward(batch, is_test=True)
         return (li - lj) > 0
 
-    def label_ranks(self, batch):
-        """rank of the positive item among all items for each test row (model.py:140-156)."""
+    def label_ranks(self, batch, exclude=None, return_eligible=False):
+        """rank of the positive item among all items for each test row (model.py:140-156) -> [B] int32 device tensor.
+        exclude=None: among ALL items (the reference's ranking).  Otherwise exclude takes recommend's forms ("history",
+        a sequence of B id arrays, a SeenItems holder) and the result is the FILTERED rank: the label's rank among the
+        items that are not excluded -- the all-items rank minus the listed items the rank kernel counted ahead of the
+        label (tlsan_eval_ranks_excl), so it is exact, never negative, and 0 when everything but the label is listed.
+        The label itself is never excluded, even when the list holds it (test labels often sit in their user's own
+        seen list).  return_eligible: also the number of items each row's label competes with,
+        item_count - 1 - |list \\ {label}| -> (ranks, eligible)."""
         li, lj, ut, db = self.forward(batch, is_test=True, want_u_t=True)
         ws = self._workspace(db.B, db.Sn)
         ranks = torch.empty(db.B, dtype=torch.int32, device=self.device)
-        L.check(self.lib.tlsan_eval_ranks(C.byref(self.dims), C.byref(self.cparams), ut.data_ptr(), db.i.data_ptr(),
-                                          db.B, ranks.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
-                "tlsan_eval_ranks")
-        return ranks
+        if exclude is None:
+            L.check(self.lib.tlsan_eval_ranks(C.byref(self.dims), C.byref(self.cparams), ut.data_ptr(), db.i.data_ptr(),
+                                              db.B, ranks.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                    "tlsan_eval_ranks")
+            if return_eligible:
+                return ranks, torch.full_like(ranks, self.config["item_count"] - 1)
+            return ranks
+        off, xid = exclusion_csr(db, exclude, self.config["item_count"])
+        ahead, held = torch.empty_like(ranks), torch.empty_like(ranks)
+        L.check(self.lib.tlsan_eval_ranks_excl(C.byref(self.dims), C.byref(self.cparams), ut.data_ptr(), db.i.data_ptr(),
+                                               db.B, off.data_ptr(), xid.data_ptr(), ranks.data_ptr(), ahead.data_ptr(),
+                                               held.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                "tlsan_eval_ranks_excl")
+        ranks = ranks - ahead
+        return (ranks, (self.config["item_count"] - 1) - held) if return_eligible else ranks
 
     def recommend(self, batch, k, exclude=None):
         """The k best items over ALL items for each row -- what tf.nn.top_k(eval_logits, k) gives the reference
@@ -974,7 +1054,7 @@ class Model(object):
         negative are not used).  -> (ids [B, k] int32, scores [B, k] float32) device tensors, in tf.nn.top_k's
         order (higher score first, ties -> lower id); rows with fewer than k eligible items end in -1 / -inf.
         exclude: None; "history" -- the items the row's input holds (the last Ls items and the current session);
-        or a sequence of B arrays of item ids.  Scores equal label_ranks' / eval_label_scores' bit for bit."""
+        a sequence of B arrays of item ids; or a SeenItems holder -- the user's seen items and the row's input.  Scores equal label_ranks' / eval_label_scores' bit for bit."""
         _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
         return eval_topk(self.lib, self.dims, self.cparams, ut, db.B, k, exclusion_csr(db, exclude, self.config["item_count"]),
                          1, 0, self._topk_workspace, self._stream())

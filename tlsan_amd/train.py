@@ -23,7 +23,7 @@ import time
 import numpy as np
 
 from .input import DataInput, DataInputTest, PackedSet, load_packed
-from .model import KS, Model, metrics_from_histogram
+from .model import KS, Model, SeenItems, full_ranking_metrics, metrics_from_histogram
 
 FLAGS = [  # (name, type, default)  -- train.py:26-54
     ("hidden_units", int, 64), ("num_blocks", int, 1), ("num_heads", int, 8), ("Ls", int, 10),
@@ -70,23 +70,46 @@ def parse(argv=None):
     ap.add_argument("--recommend_k", type=int, default=0,
                     help="at the end of training, write <model_dir>/recommend_top<K>.npz: the K best items over all items "
                          "for every test row (arrays user, ids, scores); 0 = off")
-    ap.add_argument("--recommend_exclude", default="history", choices=["history", "none"],
+    ap.add_argument("--recommend_exclude", default="history", choices=["history", "none", "seen"],
                     help="items kept out of the recommendations: 'history' = the items the test row's input holds (its "
-                         "last Ls items and its current session -- what the batch carries), 'none' = nothing")
+                         "last Ls items and its current session -- what the batch carries), 'none' = nothing, 'seen' = "
+                         "every item of the user's training samples and the row's input")
     ap.add_argument("--eval_negatives", type=int, default=0,
                     help="sampled evaluation at every evaluation point: rank each test label among N sampled negatives "
                          "and report HR@k, NDCG@k (k = 1, 5, 10, 20), MRR and AUC_N; 0 = off")
     ap.add_argument("--eval_neg_seed", type=int, default=1234,
                     help="seed of the negatives (a test row's negatives depend on the seed and its position in the test set)")
-    ap.add_argument("--eval_neg_exclude", default="history", choices=["history", "none"],
+    ap.add_argument("--eval_neg_exclude", default="history", choices=["history", "none", "seen"],
                     help="items never drawn as a row's negatives besides its label: 'history' = the items the test row's "
-                         "input holds, 'none' = nothing")
+                         "input holds, 'none' = nothing, 'seen' = every item of the user's training samples and the row's input")
+    ap.add_argument("--eval_rank_exclude", default="off", choices=["off", "none", "history", "seen"],
+                    help="full-ranking evaluation at every evaluation point: rank each test label among ALL items the row "
+                         "has not seen and report HR@k, NDCG@k (k = 1, 5, 10, 20) and MRR; what counts as seen: 'none' = "
+                         "nothing, 'history' = the row's input, 'seen' = every item of the user's training samples and the "
+                         "row's input (leave-one-out).  The label itself is never excluded.  'off' = no such evaluation")
     return ap.parse_args(argv)
 
 
 def sampled_line(n, res):
     """The driver's line of sampled metrics (metrics_from_histogram's dict)."""
     return "Sampled N=%d: " % n + " ".join("%s = %.4f" % (k, v) for k, v in res.items())
+
+
+def full_ranking_line(mode, res):
+    """The driver's line of full-ranking metrics (full_ranking_metrics' dict)."""
+    return "Full ranking (exclude=%s): " % mode + " ".join("%s = %.4f" % (k, v) for k, v in res.items())
+
+
+def exclude_arg(mode, seen):
+    """A flag's exclusion mode -> the `exclude` argument of recommend / sampled_ranks / label_ranks."""
+    return {"none": None, "history": "history", "seen": seen}[mode]
+
+
+def seen_items_for(args, train_set, n_users, device):
+    """The seen-items holder when one of the exclusion flags asks for it (built once, from the host train set)."""
+    if "seen" not in (args.recommend_exclude, args.eval_neg_exclude, args.eval_rank_exclude):
+        return None
+    return SeenItems.from_train_set(train_set, n_users, device)
 
 
 def recommend_path(model_dir, k):
@@ -205,7 +228,7 @@ def recommend_test_set(model, test_set, config, k, exclude):
     users, ids, scores = [], [], []
     for _, batch in _test_batches(test_set, config, chunk):
         db = model.device_batch(batch, is_test=True)
-        i, s = model.recommend(db, k, exclude=None if exclude == "none" else exclude)
+        i, s = model.recommend(db, k, exclude=exclude)
         users.append(db.u)
         ids.append(i)
         scores.append(s)
@@ -220,7 +243,7 @@ def eval_sampled(model, test_set, config, n, seed, exclude):
     chunk = max(EVAL_CHUNK, config["test_batch_size"]) // config["test_batch_size"] * config["test_batch_size"]
     hist = None
     for bi, batch in _test_batches(test_set, config, chunk):
-        r = model.sampled_ranks(batch, n, seed=seed, row0=(bi - 1) * chunk, exclude=None if exclude == "none" else exclude)
+        r = model.sampled_ranks(batch, n, seed=seed, row0=(bi - 1) * chunk, exclude=exclude)
         h = torch.bincount(r.long(), minlength=n + 1)
         hist = h if hist is None else hist + h
     res = metrics_from_histogram(hist.cpu().numpy(), n)
@@ -228,13 +251,30 @@ def eval_sampled(model, test_set, config, n, seed, exclude):
     return res
 
 
-def _run(args, say, model, train_set, triples, issue, eval_auc, eval_pr, eval_sampled, recommend, say_best, **extra):
+def eval_full_ranking(model, test_set, config, exclude):
+    """HR@k / NDCG@k / MRR of every test label among ALL items its row's exclusion list does not hold
+    (Model.label_ranks(exclude=); None: among all items), in launches of EVAL_CHUNK rows.  The filtered ranks are counted
+    on the device (exact sums) and read once, so the result does not depend on the chunking."""
+    import torch
+    chunk = max(EVAL_CHUNK, config["test_batch_size"]) // config["test_batch_size"] * config["test_batch_size"]
+    hist = None
+    for _, batch in _test_batches(test_set, config, chunk):
+        h = torch.bincount(model.label_ranks(batch, exclude=exclude).long(), minlength=config["item_count"])
+        hist = h if hist is None else hist + h
+    res = full_ranking_metrics(hist.cpu().numpy())
+    model.eval_writer.add_summary([("Full/" + k, v) for k, v in res.items()], global_step=model.global_step.eval())
+    return res
+
+
+def _run(args, say, model, train_set, triples, issue, eval_auc, eval_pr, eval_sampled, recommend, say_best, eval_full=None,
+         **extra):
     """The flow of the reference's train.py:185-249, written once for train() and train_sharded(), which pass in what
     differs between them:
       triples()                     one epoch of the (shuffled) train_set as (batch, next, after_next) triples (_lookahead2)
       issue(batch, lr, nxt, nxt2)   issues one step, with the batches to announce ahead (None: none) -> the device scalar
                                     that holds the step's loss
       eval_auc() -> AUC, eval_pr() -> (P@k, R@k over KS), eval_sampled() -> the sampled metrics (--eval_negatives)
+      eval_full() -> the full-ranking metrics (--eval_rank_exclude other than off)
       recommend()                   writes the recommendation file (--recommend_k) -> its path, None on a rank that wrote none
       say_best(best P@k, best R@k)  the driver's own closing lines about them
       extra                         further entries of the result dict."""
@@ -244,6 +284,9 @@ def _run(args, say, model, train_set, triples, issue, eval_auc, eval_pr, eval_sa
     say("Init AUC: %.4f" % init_auc)
     if args.eval_negatives:
         say(sampled_line(args.eval_negatives, eval_sampled()))
+    full_mode = args.eval_rank_exclude if args.eval_rank_exclude != "off" else None
+    if full_mode:
+        say(full_ranking_line(full_mode, eval_full()))
     lr = args.learning_rate
     rng = epoch_rng(args.shuffle_seed)  # train.py:15,191 (sharded: the same shuffle on every rank)
     best_auc, history = 0.0, []
@@ -267,6 +310,8 @@ def _run(args, say, model, train_set, triples, issue, eval_auc, eval_pr, eval_sa
                 loss_sum.zero_()
                 if args.eval_negatives:
                     say(sampled_line(args.eval_negatives, eval_sampled()))
+                if full_mode:
+                    say(full_ranking_line(full_mode, eval_full()))
                 if args.eval_topk:                             # train.py:209-218: P@k / R@k at every evaluation
                     prec, recall = eval_pr()
                     say("Precision:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, prec)))
@@ -292,6 +337,7 @@ def _run(args, say, model, train_set, triples, issue, eval_auc, eval_pr, eval_sa
     final_auc = eval_auc()
     best_auc = max(best_auc, final_auc)
     final_sampled = eval_sampled() if args.eval_negatives else None
+    final_full = eval_full() if full_mode else None
     model.save(None)                                           # train.py:239
     if args.recommend_k:
         path = recommend()
@@ -303,12 +349,16 @@ def _run(args, say, model, train_set, triples, issue, eval_auc, eval_pr, eval_sa
     say_best(best_prec, best_recall)
     if final_sampled is not None:
         say(sampled_line(args.eval_negatives, final_sampled))
+    if final_full is not None:
+        say(full_ranking_line(full_mode, final_full))
     say("Finished", flush=True)
     res = dict(init_auc=init_auc, best_auc=best_auc, final_auc=final_auc, steps=model.global_step.eval(),
                seconds=time.time() - t0, history=history, prec=prec, recall=recall,
                best_prec=best_prec, best_recall=best_recall, **extra)
     if final_sampled is not None:
         res["sampled"] = final_sampled
+    if final_full is not None:
+        res["full_ranking"] = final_full
     return res
 
 
@@ -328,6 +378,7 @@ def train(args, data=None):
         model.restore(None, resume)
     else:
         say("Created new model parameters..", flush=True)
+    seen = seen_items_for(args, train_set, U, model.device)
     if args.device_input:
         from .device_input import DeviceDataInput, DevicePackedSet
         train_set, test_set = DevicePackedSet(train_set, args.device), DevicePackedSet(test_set, args.device)
@@ -351,11 +402,12 @@ def train(args, data=None):
                 eval_auc=lambda: eval_auc(model, test_set, config),
                 eval_pr=lambda: eval_prec_recall(model, test_set, config),
                 eval_sampled=lambda: eval_sampled(model, test_set, config, args.eval_negatives, args.eval_neg_seed,
-                                                  args.eval_neg_exclude),
+                                                  exclude_arg(args.eval_neg_exclude, seen)),
                 recommend=lambda: write_recommendations(
                     args.model_dir, args.recommend_k,
-                    *recommend_test_set(model, test_set, config, args.recommend_k, args.recommend_exclude)),
-                say_best=say_best)
+                    *recommend_test_set(model, test_set, config, args.recommend_k, exclude_arg(args.recommend_exclude, seen))),
+                say_best=say_best,
+                eval_full=lambda: eval_full_ranking(model, test_set, config, exclude_arg(args.eval_rank_exclude, seen)))
 
 
 def _lookahead2(it):
@@ -435,6 +487,7 @@ def train_sharded(args):
         say("Reloading model parameters..", flush=True)
         model.restore(None, resume)
     dev = model.device
+    seen = seen_items_for(args, train_set, U, dev)
 
     def reduce_sum(vals):
         t = torch.tensor(vals, dtype=torch.float64, device=dev)
@@ -474,10 +527,21 @@ def train_sharded(args):
             part, real = _equal_share(batch, rank, world)
             row0 = (bi - 1) * bs + len(batch[0]) * rank // world
             r = model.sampled_ranks(part, n, seed=args.eval_neg_seed, row0=row0,
-                                    exclude=None if args.eval_neg_exclude == "none" else "history")
+                                    exclude=exclude_arg(args.eval_neg_exclude, seen))
             hist += torch.bincount(r[:real].long(), minlength=n + 1)
         res = metrics_from_histogram(np.asarray(reduce_sum(hist.tolist()), np.int64), n)
         model.eval_writer.add_summary(list(res.items()), global_step=model.global_step.eval())
+        return res
+
+    def eval_full_():
+        # as eval_sampled_: the padding of _equal_share is not counted, and the rank histograms sum exactly over the ranks
+        hist = torch.zeros(I, dtype=torch.int64, device=dev)
+        for _, batch in DataInputTest(test_set, config["test_batch_size"], config["Ls"]):
+            part, real = _equal_share(batch, rank, world)
+            r = model.label_ranks(part, exclude=exclude_arg(args.eval_rank_exclude, seen))
+            hist += torch.bincount(r[:real].long(), minlength=I)
+        res = full_ranking_metrics(np.asarray(reduce_sum(hist.tolist()), np.int64))
+        model.eval_writer.add_summary([("Full/" + k, v) for k, v in res.items()], global_step=model.global_step.eval())
         return res
 
     def recommend_():
@@ -486,7 +550,7 @@ def train_sharded(args):
         k, parts = args.recommend_k, []
         for _, batch in DataInputTest(test_set, config["test_batch_size"], config["Ls"]):
             part, real = _equal_share(batch, rank, world)
-            ids, scores = model.recommend(part, k, exclude=None if args.recommend_exclude == "none" else "history")
+            ids, scores = model.recommend(part, k, exclude=exclude_arg(args.recommend_exclude, seen))
             user = torch.as_tensor(np.asarray(part[0]), dtype=torch.int64, device=dev)
             got = [allgather_rows(t, model.group) for t in (user, ids, scores)]
             n_real = allgather_rows(torch.tensor([real], dtype=torch.int64, device=dev), model.group).cpu().tolist()
@@ -509,7 +573,7 @@ def train_sharded(args):
         return model.last_loss[0]
 
     return _run(args, say, model, train_set, triples, issue, eval_auc_, eval_pr_, eval_sampled_, recommend_,
-                say_best=lambda best_prec, best_recall: None, world=world)
+                say_best=lambda best_prec, best_recall: None, eval_full=eval_full_, world=world)
 
 
 def main(argv=None):
