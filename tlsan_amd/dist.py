@@ -38,6 +38,7 @@ CPU/gloo in the tests); all arithmetic on rows is in libtlsan_hip.so.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import time
@@ -47,9 +48,10 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
-from .model import (_STARTED_WORDS, KS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer,
-                    candidate_tensor, concurrent_streams, eval_topk, exclusion_csr, pack_dense, read_checkpoint,
-                    sample_negatives, sampled_ranks, score_candidates, topk_merge, unpack_dense, write_checkpoint)
+from .model import (_STARTED_WORDS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer,
+                    candidate_tensor, concurrent_streams, eval_topk, exclusion_csr, grow_workspace, hits_and_rows, pack_dense,
+                    read_checkpoint, sample_negatives, sampled_ranks, score_candidates, topk_merge, unpack_dense,
+                    write_checkpoint)
 
 
 _STATE_HDR_BYTES = 256   # sizeof(StateHdr), csrc/tlsan_update.h: what tlsan_state_reindex keeps
@@ -673,8 +675,7 @@ class ShardedModel:
         if fresh:
             sl["state"] = torch.zeros(int(nst * 1.5), dtype=torch.uint8, device=self.device)
             sl["state"][:4].view(torch.float32).fill_(1.0)   # table scale P = 1 (the owners apply the decay)
-        if self._ws is None or self._ws.numel() < nws:
-            self._ws = torch.empty(int(nws * 1.25), dtype=torch.uint8, device=self.device)
+        grow_workspace(self, "_ws", nws, 1.25)
         # the compact table's item -> category map changes every step: rebuild the category -> items
         # index for it; the use counters are zero between steps unless the (padded) shape changed
         key = (dims.item_count, dims.cate_count)
@@ -849,8 +850,7 @@ class ShardedModel:
         if nst == 0 or nws == 0:
             raise L.TlsanError(self.lib.tlsan_last_error().decode())
         st["dims"] = dims
-        if self._ws is None or self._ws.numel() < nws:
-            self._ws = torch.empty(int(nws), dtype=torch.uint8, device=dev)
+        grow_workspace(self, "_ws", nws)
         wire = self.wire_dtype == "bf16"
         di = self.di
         tail = max(1, self.Ls)                              # fp32 floats after the embedding: item_b / the position weights
@@ -1305,19 +1305,27 @@ class ShardedModel:
         return float(self.last_loss.item())
 
     # ------------------------------------------------------------------ evaluation
-    def forward(self, batch, is_test=True, want_ranks=False, exclude=None):
+    @contextlib.contextmanager
+    def _eval_forward(self, batch, is_test=True, lj=False, ut=True):
+        """The forward of a forward-only batch on its compact table (plan -> fetch -> compact views -> tlsan_forward):
+        yields (db, (dims, cp, cb), li, lj, u_t) -- lj when asked and the batch has a j, u_t [B, d] when asked, None
+        otherwise -- for the work the caller queues behind it, and waits for that work on the way out: the fetched
+        table must stay alive until it has run."""
         db = self.device_batch(batch, is_test)
         sl = self._plan_eval(db)
         table = self._fetch(sl)
-        dims, cp, cb = self._compact(db, sl, table)
-        li = torch.empty(db.B, dtype=torch.float32, device=self.device)
-        lj = torch.empty(db.B, dtype=torch.float32, device=self.device) if db.j is not None else None
-        ut = torch.empty(db.B, self.d, dtype=torch.float32, device=self.device) if want_ranks else None
-        L.check(self.lib.tlsan_forward(C.byref(dims), C.byref(cp), C.byref(cb), li.data_ptr(),
-                                       None if lj is None else lj.data_ptr(), None if ut is None else ut.data_ptr(),
-                                       None, 0, self._stream()), "tlsan_forward")
-        ranks = self._ranks(db, dims, cp, cb, ut, exclude) if want_ranks else None
-        torch.cuda.current_stream(self.device).synchronize()   # `table` stays alive until done
+        views = self._compact(db, sl, table)
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        li, lj, ut = new(db.B), new(db.B) if lj and db.j is not None else None, new(db.B, self.d) if ut else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        L.check(self.lib.tlsan_forward(*map(C.byref, views), li.data_ptr(), ptr(lj), ptr(ut), None, 0, self._stream()),
+                "tlsan_forward")
+        yield db, views, li, lj, ut
+        torch.cuda.current_stream(self.device).synchronize()
+
+    def forward(self, batch, is_test=True, want_ranks=False, exclude=None):
+        with self._eval_forward(batch, is_test, lj=True, ut=want_ranks) as (db, views, li, lj, ut):
+            ranks = self._ranks(db, *views, ut, exclude) if want_ranks else None
         return (li, lj, ranks) if want_ranks else (li, lj)
 
     def _gather_excl(self, off, xid, B):
@@ -1343,39 +1351,30 @@ class ShardedModel:
         items of ITS shard (tlsan_eval_counts_shard_excl: those it holds, and those of them it counted ahead of the
         label), and the two counts ride in the same all-reduce -> (filtered ranks, eligible items) of this rank's rows."""
         B, st = db.B, self._stream()
-        nws = self.lib.tlsan_workspace_bytes(C.byref(dims), B, 0)
-        if self._ws is None or self._ws.numel() < nws:
-            self._ws = torch.empty(int(nws * 1.25), dtype=torch.uint8, device=self.device)
+        ws = grow_workspace(self, "_ws", self.lib.tlsan_workspace_bytes(C.byref(dims), B, 0), 1.25)
         s_lab = torch.empty(B, dtype=torch.float32, device=self.device)
         L.check(self.lib.tlsan_eval_label_scores(C.byref(dims), C.byref(cp), ut.data_ptr(), cb.i, B, s_lab.data_ptr(),
-                                                 self._ws.data_ptr(), self._ws.numel(), st), "tlsan_eval_label_scores")
+                                                 ws.data_ptr(), ws.numel(), st), "tlsan_eval_label_scores")
         ut_all, s_all, lab_all = allgather_rows(ut, self.group), allgather_rows(s_lab, self.group), allgather_rows(db.i, self.group)
         Bt = int(ut_all.shape[0])
         nloc, ldims, lp = self._item_shard()
-        nws = self.lib.tlsan_workspace_bytes(C.byref(ldims), Bt, 0)
-        if self._ews is None or self._ews.numel() < nws:
-            self._ews = torch.empty(int(nws * 1.25), dtype=torch.uint8, device=self.device)
-        if exclude is not None:
-            off, xid = self._gather_excl(*exclusion_csr(db, exclude, self.I), B)
-            cah = torch.zeros(3, Bt, dtype=torch.int32, device=self.device)     # counts, ahead, held
+        ws = grow_workspace(self, "_ews", self.lib.tlsan_workspace_bytes(C.byref(ldims), Bt, 0), 1.25)
+        head = (C.byref(ldims), C.byref(lp), ut_all.data_ptr(), s_all.data_ptr(), lab_all.data_ptr(), Bt, self.world, self.rank)
+        tail = (ws.data_ptr(), ws.numel(), st)
+        cah = torch.zeros(1 if exclude is None else 3, Bt, dtype=torch.int32, device=self.device)     # counts (, ahead, held)
+        if exclude is None:
             if nloc > 0:
-                L.check(self.lib.tlsan_eval_counts_shard_excl(C.byref(ldims), C.byref(lp), ut_all.data_ptr(), s_all.data_ptr(),
-                                                              lab_all.data_ptr(), Bt, self.world, self.rank, off.data_ptr(),
-                                                              xid.data_ptr(), cah[0].data_ptr(), cah[1].data_ptr(),
-                                                              cah[2].data_ptr(), self._ews.data_ptr(), self._ews.numel(), st),
+                L.check(self.lib.tlsan_eval_counts_shard(*head, cah[0].data_ptr(), *tail), "tlsan_eval_counts_shard")
+        else:
+            off, xid = self._gather_excl(*exclusion_csr(db, exclude, self.I), B)
+            if nloc > 0:
+                L.check(self.lib.tlsan_eval_counts_shard_excl(*head, off.data_ptr(), xid.data_ptr(), cah[0].data_ptr(),
+                                                              cah[1].data_ptr(), cah[2].data_ptr(), *tail),
                         "tlsan_eval_counts_shard_excl")
-            if self.world > 1:
-                allreduce_sum(cah, self.group)
-            mine = cah[:, self.rank * B:(self.rank + 1) * B]
-            return mine[0] - mine[1], (self.I - 1) - mine[2]
-        counts = torch.zeros(Bt, dtype=torch.int32, device=self.device)
-        if nloc > 0:
-            L.check(self.lib.tlsan_eval_counts_shard(C.byref(ldims), C.byref(lp), ut_all.data_ptr(), s_all.data_ptr(),
-                                                     lab_all.data_ptr(), Bt, self.world, self.rank, counts.data_ptr(),
-                                                     self._ews.data_ptr(), self._ews.numel(), st), "tlsan_eval_counts_shard")
         if self.world > 1:
-            allreduce_sum(counts, self.group)
-        return counts[self.rank * B:(self.rank + 1) * B]
+            allreduce_sum(cah, self.group)
+        mine = cah[:, self.rank * B:(self.rank + 1) * B]
+        return mine[0] if exclude is None else (mine[0] - mine[1], (self.I - 1) - mine[2])
 
     def _item_shard(self):
         """This rank's items as a table of their own (local item n = global item n * world + rank): (local count,
@@ -1393,49 +1392,26 @@ class ShardedModel:
         the exclusion lists are all-gathered, every rank selects the k best of ITS item shard for all rows
         (tlsan_eval_topk, global ids n * world + rank), each row's lists go to the rank that owns the row (one
         all-to-all) and are merged there (tlsan_topk_merge).  Same ids and scores as Model.recommend."""
-        db = self.device_batch(batch, is_test=True)
-        sl = self._plan_eval(db)
-        table = self._fetch(sl)
-        dims, cp, cb = self._compact(db, sl, table)
-        B, k, st = db.B, int(k), self._stream()
-        li = torch.empty(B, dtype=torch.float32, device=self.device)
-        ut = torch.empty(B, self.d, dtype=torch.float32, device=self.device)
-        L.check(self.lib.tlsan_forward(C.byref(dims), C.byref(cp), C.byref(cb), li.data_ptr(), None, ut.data_ptr(),
-                                       None, 0, st), "tlsan_forward")
-        ut_all = allgather_rows(ut, self.group)
-        Bt = int(ut_all.shape[0])
-        off, xid = self._gather_excl(*exclusion_csr(db, exclude, self.I), B)
-        nloc, ldims, lp = self._item_shard()
-        if nloc > 0:
-            def workspace(nbytes):
-                if getattr(self, "_tws", None) is None or self._tws.numel() < nbytes:
-                    self._tws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                return self._tws
-            cid, csc = eval_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), self.world, self.rank, workspace, st)
-        else:
-            cid = torch.full((Bt, k), -1, dtype=torch.int32, device=self.device)
-            csc = torch.full((Bt, k), float("-inf"), dtype=torch.float32, device=self.device)
-        if self.world > 1:
-            # rows [r B, (r + 1) B) belong to rank r: block s of what arrives is rank s's list of this rank's rows
-            rid, rsc = torch.empty_like(cid), torch.empty_like(csc)
-            a2a(rid, cid, None, None, self.group)
-            a2a(rsc, csc, None, None, self.group)
-            cid, csc = topk_merge(self.lib, rid.view(self.world, B, k).transpose(0, 1).contiguous(),
-                                  rsc.view(self.world, B, k).transpose(0, 1).contiguous(), st)
-        torch.cuda.current_stream(self.device).synchronize()   # `table` stays alive until done
+        with self._eval_forward(batch) as (db, _, _, _, ut):
+            B, k, st = db.B, int(k), self._stream()
+            ut_all = allgather_rows(ut, self.group)
+            Bt = int(ut_all.shape[0])
+            off, xid = self._gather_excl(*exclusion_csr(db, exclude, self.I), B)
+            nloc, ldims, lp = self._item_shard()
+            if nloc > 0:
+                cid, csc = eval_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), self.world, self.rank,
+                                     lambda nbytes: grow_workspace(self, "_tws", nbytes), st)
+            else:
+                cid = torch.full((Bt, k), -1, dtype=torch.int32, device=self.device)
+                csc = torch.full((Bt, k), float("-inf"), dtype=torch.float32, device=self.device)
+            if self.world > 1:
+                # rows [r B, (r + 1) B) belong to rank r: block s of what arrives is rank s's list of this rank's rows
+                rid, rsc = torch.empty_like(cid), torch.empty_like(csc)
+                a2a(rid, cid, None, None, self.group)
+                a2a(rsc, csc, None, None, self.group)
+                cid, csc = topk_merge(self.lib, rid.view(self.world, B, k).transpose(0, 1).contiguous(),
+                                      rsc.view(self.world, B, k).transpose(0, 1).contiguous(), st)
         return cid, csc
-
-    def _forward_ut(self, db):
-        """u_t [B, d] of this rank's rows (the forward on the compact table) and the fetched table, which must stay alive
-        until the work that follows has run."""
-        sl = self._plan_eval(db)
-        table = self._fetch(sl)
-        dims, cp, cb = self._compact(db, sl, table)
-        li = torch.empty(db.B, dtype=torch.float32, device=self.device)
-        ut = torch.empty(db.B, self.d, dtype=torch.float32, device=self.device)
-        L.check(self.lib.tlsan_forward(C.byref(dims), C.byref(cp), C.byref(cb), li.data_ptr(), None, ut.data_ptr(),
-                                       None, 0, self._stream()), "tlsan_forward")
-        return ut, table
 
     def _score_owned(self, ut, cand):
         """Scores of this rank's rows' candidates (u_t [B, d], cand [B, C] global ids; every rank calls it with the same
@@ -1459,11 +1435,8 @@ class ShardedModel:
     def score_candidates(self, batch, candidates):
         """Model.score_candidates for this rank's rows (every rank calls it, with the same C).  Same scores, bit for
         bit."""
-        db = self.device_batch(batch, is_test=True)
-        ut, table = self._forward_ut(db)
-        sc = self._score_owned(ut, candidate_tensor(candidates, db.B, self.device))
-        torch.cuda.current_stream(self.device).synchronize()   # `table` stays alive until done
-        return sc
+        with self._eval_forward(batch) as (db, _, _, _, ut):
+            return self._score_owned(ut, candidate_tensor(candidates, db.B, self.device))
 
     def sample_negatives(self, batch, n, seed=1234, row0=0, exclude="history"):
         """Model.sample_negatives for this rank's rows; row0 is the GLOBAL index of this rank's first row.  No
@@ -1474,20 +1447,13 @@ class ShardedModel:
     def sampled_ranks(self, batch, n, seed=1234, row0=0, exclude="history"):
         """Model.sampled_ranks for this rank's rows (every rank calls it, with the same n); row0 is the GLOBAL index of
         this rank's first row.  Same ranks as Model.sampled_ranks."""
-        db = self.device_batch(batch, is_test=True)
-        ut, table = self._forward_ut(db)
-        ranks = sampled_ranks(self.lib, self.I, db, ut, n, seed, row0, exclude, self._score_owned, self._stream())
-        torch.cuda.current_stream(self.device).synchronize()   # `table` stays alive until done
-        return ranks
+        with self._eval_forward(batch) as (db, _, _, _, ut):
+            return sampled_ranks(self.lib, self.I, db, ut, n, seed, row0, exclude, self._score_owned, self._stream())
 
     def _hits(self, batch, n_valid=None):
-        r = self.label_ranks(batch)
-        if n_valid is not None:        # rows past n_valid only pad this rank's share to the common size
-            r = r[:n_valid]
-        h = torch.stack([(r < k).sum() for k in KS] + [torch.tensor(r.numel(), device=r.device)]).to(torch.int64)
-        if self.world > 1:
-            allreduce_sum(h, self.group)        # hits and rows of the GLOBAL test batch
-        h = h.cpu().numpy()
+        h = hits_and_rows(self.label_ranks(batch)[:n_valid])   # (rows past n_valid only pad this rank's share to the common size)
+        if self.world > 1:                                      # hits and rows of the GLOBAL test batch
+            h = allreduce_sum(torch.as_tensor(h, device=self.device), self.group).cpu().numpy()
         return h[:-1], int(h[-1])
 
     def eval_prec(self, sess, batch, n_valid=None):
@@ -1509,9 +1475,13 @@ class ShardedModel:
             return (r, torch.full_like(r, self.I - 1)) if return_eligible else r
         return r if return_eligible else r[0]
 
-    def eval_auc(self, sess, batch):
+    def pairs_ranked_right(self, batch):
+        """Model.pairs_ranked_right for this rank's rows."""
         li, lj = self.forward(batch, is_test=True)
-        return float(((li - lj) > 0).float().mean().item())
+        return (li - lj) > 0
+
+    def eval_auc(self, sess, batch):
+        return float(self.pairs_ranked_right(batch).float().mean().item())
 
     # ------------------------------------------------------------------ inspection
     def _table_views(self):

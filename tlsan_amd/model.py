@@ -276,6 +276,16 @@ def exclusion_csr(db, exclude, n_items):
     return off, vals.view(-1)
 
 
+def grow_workspace(owner, name, nbytes, factor=1.0):
+    """The grow-only uint8 device workspace kept as `owner.<name>`, with room for nbytes: allocated anew, nbytes * factor
+    large, only when there is none or it is too small."""
+    buf = getattr(owner, name, None)
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(int(nbytes * factor), dtype=torch.uint8, device=owner.device)
+        setattr(owner, name, buf)
+    return buf
+
+
 def eval_topk(lib, dims, cparams, ut, B, k, excl, id_mul, id_add, workspace, stream):
     """tlsan_eval_topk on u_t [B, d] -> (ids [B, k] int32, scores [B, k] float32) device tensors.
     workspace(nbytes) returns a uint8 device tensor of at least nbytes."""
@@ -378,6 +388,13 @@ class TopKCounters:
         self.hits_r += hits
         self.n_r += n
         return [self.hits_r[i] / self.n_r for i in range(len(KS))]
+
+
+def hits_and_rows(ranks):
+    """What TopKCounters counts of a batch's label ranks (array or tensor) -> [len(KS) + 1] int64 array: the rows whose
+    label ranks below k for the k of KS, then the row count -- integers, so the vectors of the ranks' shares add up."""
+    r = ranks.cpu().numpy() if isinstance(ranks, torch.Tensor) else np.asarray(ranks)
+    return np.array([(r < k).sum() for k in KS] + [len(r)], np.int64)
 
 
 SAMPLED_KS = (1, 5, 10, 20)
@@ -1010,8 +1027,7 @@ class Model(object):
 
     def eval_auc(self, sess, batch):
         """mean(logit(pos) - logit(neg) > 0), ties wrong (model.py:237-263)."""
-        li, lj, _, _ = self.forward(batch, is_test=True)
-        return float(((li - lj) > 0).float().mean().item())
+        return float(self.pairs_ranked_right(batch).float().mean().item())
 
     def pairs_ranked_right(self, batch):
         """Per test row: logit(pos) - logit(neg) > 0 (bool tensor on the device) -- what eval_auc averages.  A row's
@@ -1084,13 +1100,14 @@ class Model(object):
         return sampled_ranks(self.lib, self.config["item_count"], db, ut, n, seed, row0, exclude, score, st)
 
     def _topk_workspace(self, nbytes):
-        if getattr(self, "_tws", None) is None or self._tws.numel() < nbytes:
-            self._tws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._tws
+        return grow_workspace(self, "_tws", nbytes)
+
+    def check_static_overflow(self):
+        """ShardedModel's check of its fixed-size exchanges, which the driver makes before an evaluation: none here."""
 
     def _hits(self, batch, ranks=None):
-        r = self.label_ranks(batch).cpu().numpy() if ranks is None else np.asarray(ranks)
-        return np.array([(r < k).sum() for k in KS], np.int64), len(r)
+        h = hits_and_rows(self.label_ranks(batch) if ranks is None else ranks)
+        return h[:-1], int(h[-1])
 
     def eval_prec(self, sess, batch, ranks=None):
         """Streaming precision_at_k update ops (model.py:265-281); counters are cumulative over

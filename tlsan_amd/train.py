@@ -21,9 +21,10 @@ import shutil
 import time
 
 import numpy as np
+import torch
 
 from .input import DataInput, DataInputTest, PackedSet, load_packed
-from .model import KS, Model, SeenItems, full_ranking_metrics, metrics_from_histogram
+from .model import KS, Model, SeenItems, full_ranking_metrics, hits_and_rows, metrics_from_histogram
 
 FLAGS = [  # (name, type, default)  -- train.py:26-54
     ("hidden_units", int, 64), ("num_blocks", int, 1), ("num_heads", int, 8), ("Ls", int, 10),
@@ -183,110 +184,187 @@ def _test_batches(test_set, config, batch_size=None):
     return DeviceDataInputTest(test_set, bs, config["Ls"])
 
 
-def _per_row(model, test_set, config, fn):
-    """fn(batch) -> per-row device tensor, over the whole test set in chunks of EVAL_CHUNK rows; one host copy."""
-    import torch
-    chunk = max(EVAL_CHUNK, config["test_batch_size"]) // config["test_batch_size"] * config["test_batch_size"]
-    parts = [fn(batch) for _, batch in _test_batches(test_set, config, chunk)]
-    return torch.cat(parts).cpu().numpy()
+def _share(batch, rank, world):
+    """This rank's rows of a global batch (contiguous, as even as possible) and how many of them are
+    real: a rank without rows gets row 0 as a placeholder (0 real rows), so that every rank takes
+    part in every collective."""
+    n = len(batch[0])
+    lo, hi = n * rank // world, n * (rank + 1) // world
+    if hi == lo:
+        return tuple(np.asarray(a)[:1] for a in batch), 0
+    return tuple(np.asarray(a)[lo:hi] for a in batch), hi - lo
 
 
-def eval_auc(model, test_set, config):
-    """train.py:86-96: batch AUCs weighted by batch length."""
-    ok = _per_row(model, test_set, config, model.pairs_ranked_right)
-    s, bs = 0.0, config["test_batch_size"]
-    for lo in range(0, len(ok), bs):
-        part = ok[lo:lo + bs]
-        auc_b = float(np.float32(part.sum()) / np.float32(len(part)))      # model.py:263: a float32 mean of 0/1
-        s += auc_b * len(part)
-    res = s / len(test_set)
+def _equal_share(batch, rank, world):
+    """Like _share, padded (by repeating the last row) to ceil(n / world) rows: the evaluation's
+    all-gather is equal-sized.  -> (rows, real rows)"""
+    part, real = _share(batch, rank, world)
+    want = -(-len(batch[0]) // world)
+    have = len(part[0])
+    if have < want:
+        part = tuple(np.concatenate([a, np.repeat(a[-1:], want - have, axis=0)], 0) for a in part)
+    return part, real
+
+
+class EvalRows:
+    """All an evaluation knows about the process layout: which test rows this process hands to the model together, and
+    how the processes' results combine.  rank None (train()): the whole test set in launches of EVAL_CHUNK rows, a
+    multiple of test_batch_size.  Otherwise (train_sharded()): this rank's share of every reference test batch; the sums
+    go through an all-reduce on `device`, the gathered rows to rank 0."""
+
+    def __init__(self, test_set, config, rank=None, world=1, group=None, device="cpu"):
+        self.test_set, self.config, self.total = test_set, config, len(test_set)
+        self.rank, self.world, self.group, self.device = rank, world, group, device
+
+    def launches(self, pad):
+        """(rows, real, row0) of every launch of this process, in test-set order: the rows for the model, how many of
+        them count (those past `real` only pad a share to the size every rank launches -- what an evaluation that
+        all-gathers asks for with `pad` -- or stand in for a share without rows) and the test-set index of rows[0]."""
+        bs = self.config["test_batch_size"]
+        if self.rank is None:
+            chunk = max(EVAL_CHUNK, bs) // bs * bs
+            for bi, batch in _test_batches(self.test_set, self.config, chunk):
+                row0 = (bi - 1) * chunk
+                yield batch, min(chunk, self.total - row0), row0
+        else:
+            for bi, batch in DataInputTest(self.test_set, bs, self.config["Ls"]):
+                part, real = (_equal_share if pad else _share)(batch, self.rank, self.world)
+                yield part, real, (bi - 1) * bs + len(batch[0]) * self.rank // self.world
+
+    def units(self, real):
+        """The lengths of a launch's pieces that the reference aggregates per batch (train.py:86-118): its test batches
+        within a whole launch; a share is one piece, the rank's part of one test batch (possibly empty)."""
+        if self.rank is not None:
+            return [real]
+        bs = self.config["test_batch_size"]
+        return [min(bs, real - lo) for lo in range(0, real, bs)]
+
+    def sum(self, t):
+        """The exact sum of an int64 / float64 tensor over the processes."""
+        if self.world > 1:
+            from .dist import allreduce_sum
+            t = allreduce_sum(t.to(self.device), self.group)
+        return t
+
+    def gather(self, tensors, real):
+        """The real rows of every process's tensors, in rank order, on rank 0 (None on the others)."""
+        if self.world == 1:
+            return [t[:real] for t in tensors]
+        from .dist import allgather_rows
+        n = allgather_rows(torch.tensor([real], device=tensors[0].device), self.group).tolist()
+        got, w = [allgather_rows(t, self.group) for t in tensors], len(tensors[0])
+        if self.rank == 0:
+            return [torch.cat([g[r * w:r * w + n[r]] for r in range(self.world)]) for g in got]
+
+
+def _per_row(rows, pad, fn):
+    """fn(launch rows, row0) -> per-row device tensor, over this process's launches: the real rows' values as ONE host
+    array (one copy per pass) and the lengths of its units."""
+    parts, units = [], []
+    for batch, real, row0 in rows.launches(pad):
+        parts.append(fn(batch, row0)[:real])
+        units += rows.units(real)
+    return torch.cat(parts).cpu().numpy(), units
+
+
+def eval_auc(model, test_set, config, rows=None):
+    """train.py:86-96: batch AUCs weighted by batch length; a unit's AUC is the reference's float32 mean of 0/1
+    (model.py:263), formed on the host from the count, and a rank's sum and the ranks' sums are formed in double."""
+    rows = rows or EvalRows(test_set, config)
+    model.check_static_overflow()      # (static_rows: a step that did not fit its exchange is reported here at the latest)
+    ok, units = _per_row(rows, False, lambda batch, _: model.pairs_ranked_right(batch))
+    s, lo = 0.0, 0
+    for n in units:
+        if n:
+            s += float(np.float32(ok[lo:lo + n].sum()) / np.float32(n)) * n
+        lo += n
+    res = float(rows.sum(torch.tensor([s], dtype=torch.float64))[0]) / rows.total
     model.eval_writer.add_summary(("AUC", res), global_step=model.global_step.eval())     # train.py:91-94
     return res
 
 
-def eval_prec_recall(model, test_set, config):
-    """train.py:98-118: one pass for precision, one for recall (cumulative counters, as the reference); the label
-    ranks both passes need are computed once."""
-    ranks = _per_row(model, test_set, config, model.label_ranks)
-    bs = config["test_batch_size"]
-    for lo in range(0, len(ranks), bs):
-        model.eval_prec(None, None, ranks=ranks[lo:lo + bs])
-    prec = [getattr(model, "prec_%d" % k).eval() for k in KS]
-    for lo in range(0, len(ranks), bs):
-        model.eval_recall(None, None, ranks=ranks[lo:lo + bs])
-    recall = [getattr(model, "recall_%d" % k).eval() for k in KS]
-    step = model.global_step.eval()
-    model.eval_writer.add_summary([("P@%d" % k, v) for k, v in zip(KS, prec)] +                 # train.py:103-106
-                                  [("R@%d" % k, v) for k, v in zip(KS, recall)], global_step=step)   # :114-117
+def eval_prec_recall(model, test_set, config, rows=None, summary=True):
+    """train.py:98-118: one pass over the reference's batches for precision, one for recall (cumulative counters, as the
+    reference); the label ranks both need are computed once, and a batch's hits are summed over the ranks' shares.
+    summary: whether the values also go to the evaluation summary."""
+    rows = rows or EvalRows(test_set, config)
+    ranks, units = _per_row(rows, True, lambda batch, _: model.label_ranks(batch))
+    los = np.cumsum([0] + units)
+    hits = rows.sum(torch.from_numpy(np.stack([hits_and_rows(ranks[lo:lo + n]) for lo, n in zip(los, units)]))).cpu().numpy()
+    for h in hits:
+        prec = model._topk.add_prec(h[:-1], int(h[-1]))
+    for h in hits:
+        recall = model._topk.add_recall(h[:-1], int(h[-1]))
+    prec, recall = [float(x) for x in prec], [float(x) for x in recall]
+    if summary:
+        model.eval_writer.add_summary([("P@%d" % k, v) for k, v in zip(KS, prec)] +                 # train.py:103-106
+                                      [("R@%d" % k, v) for k, v in zip(KS, recall)],                  # :114-117
+                                      global_step=model.global_step.eval())
     return prec, recall
 
 
-def recommend_test_set(model, test_set, config, k, exclude):
-    """Model.recommend over every test row, in launches of EVAL_CHUNK rows -> (user, ids, scores) host arrays."""
-    import torch
-    chunk = max(EVAL_CHUNK, config["test_batch_size"]) // config["test_batch_size"] * config["test_batch_size"]
-    users, ids, scores = [], [], []
-    for _, batch in _test_batches(test_set, config, chunk):
+def recommend_test_set(model, rows, k, exclude):
+    """model.recommend over every test row -> (user, ids, scores) host arrays in test-set order; None but on rank 0."""
+    parts = []
+    for batch, real, _ in rows.launches(True):
         db = model.device_batch(batch, is_test=True)
-        i, s = model.recommend(db, k, exclude=exclude)
-        users.append(db.u)
-        ids.append(i)
-        scores.append(s)
-    return tuple(torch.cat(x).cpu().numpy() for x in (users, ids, scores))
+        parts.append(rows.gather((db.u,) + tuple(model.recommend(db, k, exclude=exclude)), real))
+    if parts[0] is not None:
+        return tuple(torch.cat(x).cpu().numpy() for x in zip(*parts))
 
 
-def eval_sampled(model, test_set, config, n, seed, exclude):
-    """HR@k / NDCG@k / MRR / AUC_N of every test label among n sampled negatives (Model.sampled_ranks), in launches of
-    EVAL_CHUNK rows.  A row's negatives depend on its position in the test set (row0), so the result does not depend on
-    the chunking; the ranks are counted on the device (exact sums) and read once."""
-    import torch
-    chunk = max(EVAL_CHUNK, config["test_batch_size"]) // config["test_batch_size"] * config["test_batch_size"]
+def _histogram(rows, size, fn):
+    """[size] exact counts of fn(launch rows, row0) -> per-row integer device tensor over every process's real rows:
+    counted on the device, summed over the launches and the processes, read once."""
     hist = None
-    for bi, batch in _test_batches(test_set, config, chunk):
-        r = model.sampled_ranks(batch, n, seed=seed, row0=(bi - 1) * chunk, exclude=exclude)
-        h = torch.bincount(r.long(), minlength=n + 1)
+    for batch, real, row0 in rows.launches(True):
+        h = torch.bincount(fn(batch, row0)[:real].long(), minlength=size)
         hist = h if hist is None else hist + h
-    res = metrics_from_histogram(hist.cpu().numpy(), n)
+    return rows.sum(hist).cpu().numpy()
+
+
+def eval_sampled(model, rows, n, seed, exclude):
+    """HR@k / NDCG@k / MRR / AUC_N of every test label among n sampled negatives (sampled_ranks).  A row's negatives
+    depend on its position in the test set (row0 + b), so the result does not depend on the launches."""
+    res = metrics_from_histogram(_histogram(rows, n + 1, lambda batch, row0: model.sampled_ranks(
+        batch, n, seed=seed, row0=row0, exclude=exclude)), n)
     model.eval_writer.add_summary(list(res.items()), global_step=model.global_step.eval())
     return res
 
 
-def eval_full_ranking(model, test_set, config, exclude):
+def eval_full_ranking(model, rows, exclude):
     """HR@k / NDCG@k / MRR of every test label among ALL items its row's exclusion list does not hold
-    (Model.label_ranks(exclude=); None: among all items), in launches of EVAL_CHUNK rows.  The filtered ranks are counted
-    on the device (exact sums) and read once, so the result does not depend on the chunking."""
-    import torch
-    chunk = max(EVAL_CHUNK, config["test_batch_size"]) // config["test_batch_size"] * config["test_batch_size"]
-    hist = None
-    for _, batch in _test_batches(test_set, config, chunk):
-        h = torch.bincount(model.label_ranks(batch, exclude=exclude).long(), minlength=config["item_count"])
-        hist = h if hist is None else hist + h
-    res = full_ranking_metrics(hist.cpu().numpy())
+    (label_ranks(exclude=); None: among all items)."""
+    res = full_ranking_metrics(_histogram(rows, rows.config["item_count"], lambda batch, _: model.label_ranks(
+        batch, exclude=exclude)))
     model.eval_writer.add_summary([("Full/" + k, v) for k, v in res.items()], global_step=model.global_step.eval())
     return res
 
 
-def _run(args, say, model, train_set, triples, issue, eval_auc, eval_pr, eval_sampled, recommend, say_best, eval_full=None,
-         **extra):
+def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, **extra):
     """The flow of the reference's train.py:185-249, written once for train() and train_sharded(), which pass in what
     differs between them:
+      rows                          the EvalRows of the test set: every evaluation runs over it
+      seen                          the SeenItems holder of the exclusion flags (None when none asks for it)
       triples()                     one epoch of the (shuffled) train_set as (batch, next, after_next) triples (_lookahead2)
       issue(batch, lr, nxt, nxt2)   issues one step, with the batches to announce ahead (None: none) -> the device scalar
                                     that holds the step's loss
-      eval_auc() -> AUC, eval_pr() -> (P@k, R@k over KS), eval_sampled() -> the sampled metrics (--eval_negatives)
-      eval_full() -> the full-ranking metrics (--eval_rank_exclude other than off)
-      recommend()                   writes the recommendation file (--recommend_k) -> its path, None on a rank that wrote none
-      say_best(best P@k, best R@k)  the driver's own closing lines about them
+      topk_report                   whether P@k / R@k also go to the evaluation summary and their best values into the
+                                    closing lines (train.py:103-117, 241-248: train() does, the sharded driver does not)
       extra                         further entries of the result dict."""
-    import torch
+    auc_now = lambda: eval_auc(model, rows.test_set, rows.config, rows)
+    prec_recall_now = lambda: eval_prec_recall(model, rows.test_set, rows.config, rows, summary=topk_report)
+    sampled_now = lambda: eval_sampled(model, rows, args.eval_negatives, args.eval_neg_seed,
+                                       exclude_arg(args.eval_neg_exclude, seen))
+    full_now = lambda: eval_full_ranking(model, rows, exclude_arg(args.eval_rank_exclude, seen))
     t0 = time.time()
-    init_auc = eval_auc()
+    init_auc = auc_now()
     say("Init AUC: %.4f" % init_auc)
     if args.eval_negatives:
-        say(sampled_line(args.eval_negatives, eval_sampled()))
+        say(sampled_line(args.eval_negatives, sampled_now()))
     full_mode = args.eval_rank_exclude if args.eval_rank_exclude != "off" else None
     if full_mode:
-        say(full_ranking_line(full_mode, eval_full()))
+        say(full_ranking_line(full_mode, full_now()))
     lr = args.learning_rate
     rng = epoch_rng(args.shuffle_seed)  # train.py:15,191 (sharded: the same shuffle on every rank)
     best_auc, history = 0.0, []
@@ -303,17 +381,17 @@ def _run(args, say, model, train_set, triples, issue, eval_auc, eval_pr, eval_sa
             loss_sum += issue(batch, lr, nxt if left >= 1 else None, nxt2 if left >= 2 else None)
             step = model.global_step.eval()
             if step % args.eval_freq == 0:
-                auc = eval_auc()
+                auc = auc_now()
                 history.append((step, time.time() - t0, auc))
                 say("Epoch %d Global_step %d\tTrain_loss: %.4f\tEval_auc: %.4f" %
                     (model.global_epoch_step.eval(), step, float(loss_sum.item()) / args.eval_freq, auc), flush=True)
                 loss_sum.zero_()
                 if args.eval_negatives:
-                    say(sampled_line(args.eval_negatives, eval_sampled()))
+                    say(sampled_line(args.eval_negatives, sampled_now()))
                 if full_mode:
-                    say(full_ranking_line(full_mode, eval_full()))
+                    say(full_ranking_line(full_mode, full_now()))
                 if args.eval_topk:                             # train.py:209-218: P@k / R@k at every evaluation
-                    prec, recall = eval_pr()
+                    prec, recall = prec_recall_now()
                     say("Precision:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, prec)))
                     say("Recall:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, recall)))
                     if step > 20000:                        # :222-227
@@ -333,20 +411,23 @@ def _run(args, say, model, train_set, triples, issue, eval_auc, eval_pr, eval_sa
         if done:
             break
     if not args.eval_topk or not history:   # (the reference reports what its evaluations saw; make sure there is one)
-        prec, recall = eval_pr()
-    final_auc = eval_auc()
+        prec, recall = prec_recall_now()
+    final_auc = auc_now()
     best_auc = max(best_auc, final_auc)
-    final_sampled = eval_sampled() if args.eval_negatives else None
-    final_full = eval_full() if full_mode else None
+    final_sampled = sampled_now() if args.eval_negatives else None
+    final_full = full_now() if full_mode else None
     model.save(None)                                           # train.py:239
     if args.recommend_k:
-        path = recommend()
-        if path is not None:
+        rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen))
+        if rec is not None:                                    # (rank 0 holds the rows)
+            path = write_recommendations(args.model_dir, args.recommend_k, *rec)
             say("Recommendations: %s" % path)
     model.train_writer.flush()
     model.eval_writer.flush()
     say("Best test_auc:", best_auc)
-    say_best(best_prec, best_recall)
+    if topk_report:                                            # train.py:241-248
+        say("Best precision:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, best_prec)))
+        say("Best recall:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, best_recall)))
     if final_sampled is not None:
         say(sampled_line(args.eval_negatives, final_sampled))
     if final_full is not None:
@@ -393,21 +474,9 @@ def train(args, data=None):
             model.train_writer.add_summary(model.train_summary(), global_step=step)
         return model._out[0]
 
-    def say_best(best_prec, best_recall):                              # train.py:241-248
-        say("Best precision:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, best_prec)))
-        say("Best recall:\n" + " ".join("@%d = %.4f" % (k, v) for k, v in zip(KS, best_recall)))
-
-    return _run(args, say, model, train_set,
+    return _run(args, say, model, train_set, EvalRows(test_set, config), seen,
                 triples=lambda: _lookahead2(model.device_batch(b) for _, b in train_batches()), issue=issue,
-                eval_auc=lambda: eval_auc(model, test_set, config),
-                eval_pr=lambda: eval_prec_recall(model, test_set, config),
-                eval_sampled=lambda: eval_sampled(model, test_set, config, args.eval_negatives, args.eval_neg_seed,
-                                                  exclude_arg(args.eval_neg_exclude, seen)),
-                recommend=lambda: write_recommendations(
-                    args.model_dir, args.recommend_k,
-                    *recommend_test_set(model, test_set, config, args.recommend_k, exclude_arg(args.recommend_exclude, seen))),
-                say_best=say_best,
-                eval_full=lambda: eval_full_ranking(model, test_set, config, exclude_arg(args.eval_rank_exclude, seen)))
+                topk_report=True)
 
 
 def _lookahead2(it):
@@ -423,38 +492,14 @@ def _lookahead2(it):
         buf.pop(0)
 
 
-def _share(batch, rank, world):
-    """This rank's rows of a global batch (contiguous, as even as possible) and how many of them are
-    real: a rank without rows gets row 0 as a placeholder (0 real rows), so that every rank takes
-    part in every collective."""
-    n = len(batch[0])
-    lo, hi = n * rank // world, n * (rank + 1) // world
-    if hi == lo:
-        return tuple(np.asarray(a)[:1] for a in batch), 0
-    return tuple(np.asarray(a)[lo:hi] for a in batch), hi - lo
-
-
-def _equal_share(batch, rank, world):
-    """Like _share, padded (by repeating the last row) to ceil(n / world) rows: the evaluation's
-    all-gather is equal-sized.  -> (rows, real rows)"""
-    part, real = _share(batch, rank, world)
-    want = -(-len(batch[0]) // world)
-    have = len(part[0])
-    if have < want:
-        part = tuple(np.concatenate([a, np.repeat(a[-1:], want - have, axis=0)], 0) for a in part)
-    return part, real
-
-
 def train_sharded(args):
     """The same flow on N GPUs (`python -m torch.distributed.run --nproc-per-node N -m tlsan_amd.train
     --sharded 1 ...`): tables row-sharded over the ranks (tlsan_amd.dist.ShardedModel), every global
     batch of train_batch_size samples split over the ranks -- one SGD step per global batch, exactly
     the single-GPU trajectory up to fp32 summation order -- evaluation over the split test batches."""
-    import torch
     import torch.distributed as dist
     from .dist import ShardedModel
     if not dist.is_initialized():
-        import os
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29517")
         rank_, world_ = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -489,78 +534,6 @@ def train_sharded(args):
     dev = model.device
     seen = seen_items_for(args, train_set, U, dev)
 
-    def reduce_sum(vals):
-        t = torch.tensor(vals, dtype=torch.float64, device=dev)
-        if world > 1:
-            from .dist import allreduce_sum
-            allreduce_sum(t)
-        return t.tolist()
-
-    def eval_auc_():
-        # train.py:86-96: sum_b auc_b * len_b / N == (pairs ranked right) / N, summed over the ranks' shares
-        model.check_static_overflow()      # (static_rows: a step that did not fit its exchange is reported here at the latest)
-        right = 0.0
-        for _, batch in DataInputTest(test_set, config["test_batch_size"], config["Ls"]):
-            part, real = _share(batch, rank, world)
-            a = model.eval_auc(None, part)            # (a collective inside: every rank calls it, placeholder or not)
-            right += a * real if real else 0.0
-        res = reduce_sum([right])[0] / len(test_set)
-        model.eval_writer.add_summary(("AUC", res), global_step=model.global_step.eval())
-        return res
-
-    def eval_pr_():
-        prec = recall = None
-        for _, batch in DataInputTest(test_set, config["test_batch_size"], config["Ls"]):
-            part, real = _equal_share(batch, rank, world)
-            prec = model.eval_prec(None, part, n_valid=real)
-        for _, batch in DataInputTest(test_set, config["test_batch_size"], config["Ls"]):
-            part, real = _equal_share(batch, rank, world)
-            recall = model.eval_recall(None, part, n_valid=real)
-        return [float(x) for x in prec], [float(x) for x in recall]
-
-    def eval_sampled_():
-        # a rank's rows of a test batch start at the batch's first row + _share's lo; the padding of _equal_share past
-        # the real rows is not counted, and the rank histograms sum exactly over the ranks
-        n, bs = args.eval_negatives, config["test_batch_size"]
-        hist = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        for bi, batch in DataInputTest(test_set, bs, config["Ls"]):
-            part, real = _equal_share(batch, rank, world)
-            row0 = (bi - 1) * bs + len(batch[0]) * rank // world
-            r = model.sampled_ranks(part, n, seed=args.eval_neg_seed, row0=row0,
-                                    exclude=exclude_arg(args.eval_neg_exclude, seen))
-            hist += torch.bincount(r[:real].long(), minlength=n + 1)
-        res = metrics_from_histogram(np.asarray(reduce_sum(hist.tolist()), np.int64), n)
-        model.eval_writer.add_summary(list(res.items()), global_step=model.global_step.eval())
-        return res
-
-    def eval_full_():
-        # as eval_sampled_: the padding of _equal_share is not counted, and the rank histograms sum exactly over the ranks
-        hist = torch.zeros(I, dtype=torch.int64, device=dev)
-        for _, batch in DataInputTest(test_set, config["test_batch_size"], config["Ls"]):
-            part, real = _equal_share(batch, rank, world)
-            r = model.label_ranks(part, exclude=exclude_arg(args.eval_rank_exclude, seen))
-            hist += torch.bincount(r[:real].long(), minlength=I)
-        res = full_ranking_metrics(np.asarray(reduce_sum(hist.tolist()), np.int64))
-        model.eval_writer.add_summary([("Full/" + k, v) for k, v in res.items()], global_step=model.global_step.eval())
-        return res
-
-    def recommend_():
-        # every rank takes its share of each test batch; rank 0 gathers the shares (in rank order: the batch's order)
-        from .dist import allgather_rows
-        k, parts = args.recommend_k, []
-        for _, batch in DataInputTest(test_set, config["test_batch_size"], config["Ls"]):
-            part, real = _equal_share(batch, rank, world)
-            ids, scores = model.recommend(part, k, exclude=exclude_arg(args.recommend_exclude, seen))
-            user = torch.as_tensor(np.asarray(part[0]), dtype=torch.int64, device=dev)
-            got = [allgather_rows(t, model.group) for t in (user, ids, scores)]
-            n_real = allgather_rows(torch.tensor([real], dtype=torch.int64, device=dev), model.group).cpu().tolist()
-            if rank == 0:
-                w = len(part[0])
-                parts.append([np.concatenate([g.cpu().numpy()[r * w:r * w + n_real[r]] for r in range(world)])
-                              for g in got])
-        if rank == 0:
-            return write_recommendations(args.model_dir, k, *(np.concatenate(x) for x in zip(*parts)))
-
     def triples():
         shares = (_share(b, rank, world) + (len(b[0]),) for _, b in DataInput(train_set, args.train_batch_size, config["Ls"]))
         return _lookahead2((model.device_batch(p_), r_, n_) for p_, r_, n_ in shares)
@@ -572,12 +545,11 @@ def train_sharded(args):
                           weight=real * world / n_glob, sample0=n_glob * rank // world)
         return model.last_loss[0]
 
-    return _run(args, say, model, train_set, triples, issue, eval_auc_, eval_pr_, eval_sampled_, recommend_,
-                say_best=lambda best_prec, best_recall: None, eval_full=eval_full_, world=world)
+    return _run(args, say, model, train_set, EvalRows(test_set, config, rank, world, model.group, dev), seen, triples, issue,
+                topk_report=False, world=world)
 
 
 def main(argv=None):
-    import os
     args = parse(argv)
     if args.dataset is None:
         raise SystemExit("--dataset is required")
