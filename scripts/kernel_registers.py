@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
 """Register / scratch report of every k_fwd_bwd instantiation: compiles the fused kernel's translation units for gfx950
 with -Rpass-analysis=kernel-resource-usage (no GPU needed) and prints one line per variant.
-  python scripts/kernel_registers.py [unit ...] > profiles/rNN_kernel_registers.txt"""
+  python scripts/kernel_registers.py [unit ...] > profiles/rNN_kernel_registers.txt
+  python scripts/kernel_registers.py --all [unit ...]   every kernel of every unit of the build (or of the units named), one
+                                              line each: the unit, the mangled name, VGPRs, AGPRs, SGPRs, scratch bytes per lane, LDS bytes, occupancy"""
 import os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "tlsan_amd", "csrc")
-UNITS = tuple(sys.argv[1:]) or ("tlsan_attn_d64", "tlsan_attn_d128", "tlsan_attn_d128w4", "tlsan_attn_d256", "tlsan_attn_d256s",
+ALL = "--all" in sys.argv
+UNITS = tuple(a for a in sys.argv[1:] if a != "--all") or ("tlsan_attn_d64", "tlsan_attn_d128", "tlsan_attn_d128w4", "tlsan_attn_d256", "tlsan_attn_d256s",
                                "tlsan_attn_d64h4", "tlsan_attn_d128h16", "tlsan_attn_d128h4")
 sys.path.insert(0, ROOT)
-from tlsan_amd.build import SOURCE_FLAGS   # (per-source compiler flags of the product build)
+from tlsan_amd.build import SOURCE_FLAGS, SOURCES   # (per-source compiler flags of the product build)
+if ALL and len(sys.argv) == 2:
+    UNITS = tuple(s[:-len(".hip")] for s in SOURCES)
 def run(u):
     with tempfile.TemporaryDirectory() as td:
         r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
@@ -18,6 +23,14 @@ def run(u):
         return r.stderr
 with ThreadPoolExecutor(4) as ex:
     texts = list(ex.map(run, UNITS))
+if ALL:
+    rows = []
+    for u, txt in zip(UNITS, texts):
+        for m in re.findall(r"Function Name: (\S+).*?SGPRs: (\d+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", txt, re.S):
+            n, sg, v, a, sc, occ, lds = m
+            rows.append("%s %s vgpr=%s agpr=%s sgpr=%s scratch=%s lds=%s occ=%s" % (u, n, v, a, sg, sc, lds, occ))
+    print("\n".join(sorted(rows)))
+    sys.exit(0)
 out = []
 for txt in texts:
     for n, v, a, sc, occ, ss, vs in re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+).*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", txt, re.S):

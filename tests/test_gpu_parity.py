@@ -553,7 +553,7 @@ np.savez(sys.argv[1], loss=loss, gnorm=m.last_gnorm(), **m.get_params())
 
 def test_bf16_tables_clipped_step_in_the_one_pass_form(tmp_path):
     """bf16 table storage through the speculative one-pass tail with the clip ACTIVE (TLSAN_LAZY_ONE_PASS=3: by default only
-    HBM-resident bf16 tables take this form, tlsan_api.hip `lazy_one_pass`).  The rows are written with coefficient 1
+    HBM-resident bf16 tables take this form, tlsan_api_tail.hip `plan_tail`).  The rows are written with coefficient 1
     (stochastic rounding at the magnitude of w - lr g), corrected by k_spec_commit (a second rounding) and read back through
     the folded table scale (a third): a stored element may be off by one bf16 ulp of the SPECULATIVE value plus two of the
     result -- not more; fp32 parameters keep the usual bound; two runs are bitwise equal.  (The split form, the default for
@@ -1256,7 +1256,7 @@ sys.path.insert(0, %r)
 from tests.helpers import make_config, random_batch, random_params
 from tlsan_amd.model import Model
 h = hashlib.sha256()
-# (categories of 300-450 items: shared by item; of 60-70: by use position -- category_split, tlsan_api.hip)
+# (categories of 300-450 items: shared by item; of 60-70: by use position -- category_split, tlsan_api_tail.hip)
 for d, Ls, C, td, I in ((128, 10, 3, "f32", 900), (128, 90, 2, "f32", 900), (64, 33, 5, "f32", 300), (128, 70, 3, "bf16", 200)):
     cfg = make_config(U=500, I=I, C=C, d=d, Ls=Ls, regulation_rate=1e-3, max_gradient_norm=1e4)
     p = {k: np.asarray(v, np.float32) for k, v in random_params(cfg, seed=13).items()}

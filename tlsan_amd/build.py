@@ -1,8 +1,10 @@
-"""Build libtlsan_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: fourteen translation
-units (the C ABI with every kernel but the fused one, the top-K selection and the candidate kernels; the top-K selection;
-the candidate scoring, ranks, negative sampling and the exclusion-list count; k_fwd_bwd for d = 64 / 128 / 128 as 8-sample workgroups / 256 with
-the window in registers / 256 streamed, all with 8 heads; k_fwd_bwd and the dense finalize kernels for each of the
-pairs 64/4, 128/16 and 128/4) compiled in parallel, one link.  `python -m tlsan_amd.build` or `build()`."""
+"""Build libtlsan_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: twenty translation units compiled in parallel,
+one link -- four host units of the C ABI by subsystem (tlsan_api.hip core, training and state, with every kernel of the step
+but the fused one and the dense finalize; tlsan_api_tail.hip the plan of a step's tail; tlsan_api_eval.hip evaluation;
+tlsan_api_shard.hip rows and the sharded step), the top-K selection, the candidate kernels, and per (d, heads) pair k_fwd_bwd
+(d = 128 / 8 also as 8-sample workgroups, d = 256 with the window in registers and streamed) and the dense finalize kernels.
+A unit is recompiled when a file named in the compiler's depfile of its last compile is newer than its object.
+`python -m tlsan_amd.build` or `build()`."""
 from __future__ import annotations
 
 import os
@@ -14,8 +16,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libtlsan_hip.so")
-SOURCES = ["tlsan_api.hip", "tlsan_topk.hip", "tlsan_cand.hip", "tlsan_attn_d64.hip", "tlsan_attn_d128.hip", "tlsan_attn_d128w4.hip", "tlsan_attn_d256.hip", "tlsan_attn_d256s.hip",
+SOURCES = ["tlsan_api.hip", "tlsan_api_tail.hip", "tlsan_api_eval.hip", "tlsan_api_shard.hip", "tlsan_topk.hip", "tlsan_cand.hip",
+           "tlsan_attn_d64.hip", "tlsan_attn_d128.hip", "tlsan_attn_d128w4.hip", "tlsan_attn_d256.hip", "tlsan_attn_d256s.hip",
            "tlsan_attn_d64h4.hip", "tlsan_attn_d128h16.hip", "tlsan_attn_d128h4.hip",
+           "tlsan_update_d64.hip", "tlsan_update_d128.hip", "tlsan_update_d256.hip",
            "tlsan_update_d64h4.hip", "tlsan_update_d128h16.hip", "tlsan_update_d128h4.hip"]
 # per-source extra flags (see the source's header comment)
 # -fno-honor-nans on the d <= 128 units: fmaxf on an MFMA result otherwise gets a canonicalising v_max x, x, x in front of it
@@ -34,10 +38,6 @@ SOURCE_FLAGS = {"tlsan_attn_d64.hip": _NONAN, "tlsan_attn_d128.hip": _NONAN, "tl
 if os.environ.get("TLSAN_SOURCE_FLAGS"):   # (experiments: JSON {source: [flags]}, replaces the entries it names)
     import json
     SOURCE_FLAGS.update(json.loads(os.environ["TLSAN_SOURCE_FLAGS"]))
-# headers only some units include (the others do not rebuild when they change)
-SOURCE_HEADERS = {"tlsan_api.hip": ["tlsan_topk.h", "tlsan_cand.h"], "tlsan_topk.hip": ["tlsan_topk.h"],
-                  "tlsan_cand.hip": ["tlsan_topk.h", "tlsan_cand.h"]}
-HEADERS = ["tlsan_common.h", "tlsan_attn.h", "tlsan_attn_inst.h", "tlsan_update.h", "tlsan_update_inst.h", "tlsan_eval.h", "tlsan_rows.h", "tlsan_shard.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC] + \
         os.environ.get("TLSAN_HIPCC_EXTRA", "").split()   # (experiments: extra compiler flags)
 
@@ -52,28 +52,31 @@ def _hipcc():
     raise RuntimeError("hipcc not found")
 
 
-def _stale(target, deps):
-    if not os.path.exists(target):
+def _stale(target, deps=None):
+    """deps None: an object file, whose prerequisites are those of the depfile its last compile wrote (-MD; none: stale)"""
+    if not os.path.exists(target) or (deps is None and not os.path.exists(target + ".d")):
         return True
+    if deps is None:
+        with open(target + ".d") as f:   # (make syntax: "target: prerequisite ... \", continued lines)
+            deps = [w for w in f.read().replace("\\\n", " ").split() if not w.endswith(":")]
     t = os.path.getmtime(target)
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(not os.path.exists(d) or os.path.getmtime(d) > t for d in deps)
 
 
 def build(force=False, verbose=False):
     hipcc = _hipcc()
     objdir = os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(INCLUDE, "tlsan.h")]
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
-        if force or _stale(o, [s] + hdrs + [os.path.join(CSRC, h) for h in SOURCE_HEADERS.get(src, [])]):
+        if force or _stale(o):
             jobs.append((s, o))
 
     def run(job):
         s, o = job
-        cmd = [hipcc] + FLAGS + SOURCE_FLAGS.get(os.path.basename(s), []) + ["-c", s, "-o", o]
+        cmd = [hipcc] + FLAGS + SOURCE_FLAGS.get(os.path.basename(s), []) + ["-MD", "-MF", o + ".d", "-c", s, "-o", o]
         if verbose:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -1,0 +1,247 @@
+// tlsan_api_eval.hip -- the evaluation entry points of the C ABI (include/tlsan.h): ranks of the labels among all items,
+// top-K items, caller-given candidates and negative sampling.  The kernels of tlsan_eval.h are compiled here; the top-K and
+// candidate kernels in units of their own (tlsan_topk.hip, tlsan_cand.hip).
+#include "tlsan_host.h"
+#include "tlsan_eval.h"
+#include "tlsan_topk.h"
+#include "tlsan_cand.h"
+
+extern "C" {
+
+// the exclusion lists of the _excl entry points and their two outputs (all NULL: none)
+struct ExclOut { const int32_t* off; const int32_t* ids; int32_t* ahead; int32_t* held; };
+
+// The one place that says which counting kernel ranks a table: the one that reads the dense item matrix when the
+// workspace holds one (carve: up to EVAL_DENSE_MAX bytes), else the gathering one.  k_excl_ahead follows it.
+static bool eval_rank_dense(const EvalArgs& e) { return e.all_emb != nullptr; }
+
+// s_label_in == NULL: the label's score is computed here (labels index THIS table); s_label_out != NULL: only that.
+static int eval_ranks_impl(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const int32_t* labels, int32_t B,
+                           int32_t* ranks, void* ws, size_t ws_bytes, void* stream, const float* s_label_in, int id_mul,
+                           int id_add, float* s_label_out, const ExclOut* xo = nullptr) {
+  Shape s;
+  int rc = shape_of(d, &s);
+  if (rc) return rc;
+  if ((rc = check_params(p))) return rc;
+  if (!u_t || !labels || (!ranks && !s_label_out) || B < 1) return fail(TLSAN_E_BADARG, "bad eval arguments");
+  if (!ws) return fail(TLSAN_E_WORKSPACE, "ws is NULL");
+  Ws w;
+  carve(d, s, B, 0, (char*)ws, &w);
+  if (w.bytes > ws_bytes) return fail(TLSAN_E_WORKSPACE, "workspace too small: need %zu have %zu", w.bytes, ws_bytes);
+  hipStream_t hs = (hipStream_t)stream;
+  EvalArgs e;
+  memset(&e, 0, sizeof(e));
+  e.p = norm_params(p, d); e.u_t = u_t; e.labels = labels; e.B = B; e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate;
+  e.s_label = s_label_out ? s_label_out : (s_label_in ? const_cast<float*>(s_label_in) : w.s_label);
+  e.ranks = ranks; e.all_emb = w.all_emb; e.id_mul = id_mul; e.id_add = id_add;
+  if (ranks && hipMemsetAsync(ranks, 0, sizeof(int32_t) * (size_t)B, hs) != hipSuccess) return fail(TLSAN_E_LAUNCH, "memset ranks");
+  const int ut = (B + 15) / 16;
+  const int ntiles = (d->item_count + 15) / 16;
+  int chunks = (ntiles + 3) / 4;
+  const int want = (2048 + ut - 1) / ut;  // enough workgroups to fill the chip
+  if (chunks > want) chunks = want;
+  if (chunks < 1) chunks = 1;
+  const int nae = (d->item_count * (s.D / 4) + 255) / 256;
+  int ngrp = ((d->item_count + 63) / 64 + 3) / 4;  // workgroups (4 wavefronts x 64 items) along the items
+  if (ngrp > want) ngrp = want;
+#define EVAL_LAUNCH(DD)                                                                                  \
+  do {                                                                                                   \
+    if (!s_label_in) hipLaunchKernelGGL(k_eval_label<DD>, dim3(ut), dim3(64), 0, hs, e);                 \
+    if (!ranks) break;                                                                                   \
+    if (eval_rank_dense(e)) {                                                                            \
+      hipLaunchKernelGGL(k_all_emb<DD>, dim3(nae), dim3(256), 0, hs, e);                                 \
+      hipLaunchKernelGGL(k_eval_rank_dense<DD>, dim3(ut, ngrp), dim3(256), 0, hs, e);                    \
+    } else {                                                                                             \
+      hipLaunchKernelGGL(k_eval_rank<DD>, dim3(ut, chunks), dim3(256), 0, hs, e);                        \
+    }                                                                                                    \
+  } while (0)
+  if (s.D == 64) EVAL_LAUNCH(64);
+  else if (s.D == 128) EVAL_LAUNCH(128);
+  else EVAL_LAUNCH(256);
+#undef EVAL_LAUNCH
+  CHECK_LAUNCH("k_eval");
+  if (xo) {   // after the count: the dense item matrix of this call is there, and s_label holds the labels' scores
+    if (hipMemsetAsync(xo->ahead, 0, sizeof(int32_t) * (size_t)B, hs) != hipSuccess ||
+        hipMemsetAsync(xo->held, 0, sizeof(int32_t) * (size_t)B, hs) != hipSuccess)
+      return fail(TLSAN_E_LAUNCH, "memset ahead / held");
+    ExclArgs xa;
+    memset(&xa, 0, sizeof(xa));
+    xa.e = e; xa.excl_off = xo->off; xa.excl_ids = xo->ids; xa.ahead = xo->ahead; xa.held = xo->held;
+    xa.fused = eval_rank_dense(e) ? 1 : 0;
+    const hipError_t err = tlsan_launch_excl_ahead(xa, s.D, hs);
+    if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_excl_ahead: %s", hipGetErrorString(err));
+  }
+  return TLSAN_OK;
+}
+
+int tlsan_eval_ranks(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const int32_t* labels, int32_t B,
+                     int32_t* ranks, void* ws, size_t ws_bytes, void* stream) {
+  return eval_ranks_impl(d, p, u_t, labels, B, ranks, ws, ws_bytes, stream, nullptr, 1, 0, nullptr);
+}
+
+int tlsan_eval_label_scores(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const int32_t* labels, int32_t B,
+                            float* scores, void* ws, size_t ws_bytes, void* stream) {
+  if (!scores) return fail(TLSAN_E_BADARG, "tlsan_eval_label_scores: scores is NULL");
+  return eval_ranks_impl(d, p, u_t, labels, B, nullptr, ws, ws_bytes, stream, nullptr, 1, 0, scores);
+}
+
+int tlsan_eval_counts_shard(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const float* label_scores,
+                            const int32_t* labels_global, int32_t B, int32_t id_mul, int32_t id_add, int32_t* counts,
+                            void* ws, size_t ws_bytes, void* stream) {
+  if (!label_scores || !counts || id_mul < 1 || id_add < 0) return fail(TLSAN_E_BADARG, "tlsan_eval_counts_shard: bad arguments");
+  return eval_ranks_impl(d, p, u_t, labels_global, B, counts, ws, ws_bytes, stream, label_scores, id_mul, id_add, nullptr);
+}
+
+int tlsan_eval_ranks_excl(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const int32_t* labels, int32_t B,
+                          const int32_t* excl_off, const int32_t* excl_ids, int32_t* ranks, int32_t* ahead, int32_t* held,
+                          void* ws, size_t ws_bytes, void* stream) {
+  if (!excl_off || !excl_ids || !ranks || !ahead || !held) return fail(TLSAN_E_BADARG, "tlsan_eval_ranks_excl: NULL argument");
+  const ExclOut xo = {excl_off, excl_ids, ahead, held};
+  return eval_ranks_impl(d, p, u_t, labels, B, ranks, ws, ws_bytes, stream, nullptr, 1, 0, nullptr, &xo);
+}
+
+int tlsan_eval_counts_shard_excl(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const float* label_scores,
+                                 const int32_t* labels_global, int32_t B, int32_t id_mul, int32_t id_add,
+                                 const int32_t* excl_off, const int32_t* excl_ids, int32_t* counts, int32_t* ahead,
+                                 int32_t* held, void* ws, size_t ws_bytes, void* stream) {
+  if (!label_scores || !counts || !excl_off || !excl_ids || !ahead || !held)
+    return fail(TLSAN_E_BADARG, "tlsan_eval_counts_shard_excl: NULL argument");
+  if (id_mul < 1 || id_add < 0 || (d && (long long)(d->item_count - 1) * id_mul + id_add >= (1LL << 31)))
+    return fail(TLSAN_E_BADARG, "tlsan_eval_counts_shard_excl: global ids n * id_mul + id_add must be non-negative int32");
+  const ExclOut xo = {excl_off, excl_ids, ahead, held};
+  return eval_ranks_impl(d, p, u_t, labels_global, B, counts, ws, ws_bytes, stream, label_scores, id_mul, id_add, nullptr, &xo);
+}
+
+// ---- top-K items over all items (tlsan_topk.h) ----
+struct TopkWs {
+  float* all_emb;      // dense [I, D] item matrix when it fits EVAL_DENSE_MAX (as the rank path), else NULL
+  int32_t* ids;        // [B, nsl, K] the slices' lists (nsl > 1)
+  float* scores;
+  size_t bytes;
+  int nsl;
+};
+
+static void carve_topk(const tlsan_dims* d, int D, int B, int K, char* base, TopkWs* w) {
+  size_t o = 0;
+  auto take = [&](size_t n) { char* p = base ? base + o : nullptr; o += al(n); return p; };
+  const int ut = (B + 15) / 16;
+  const int want = (2048 + ut - 1) / ut;  // enough workgroups to fill the chip (the rank path's slicing)
+  int nsl = ((d->item_count + 63) / 64 + 3) / 4;
+  if (nsl > want) nsl = want;
+  if (nsl < 1) nsl = 1;
+  w->nsl = nsl;
+  const size_t ae = sizeof(float) * (size_t)d->item_count * D;
+  w->all_emb = ae <= EVAL_DENSE_MAX ? (float*)take(ae) : nullptr;
+  const size_t nc = nsl > 1 ? (size_t)B * nsl * K : 0;
+  w->ids = (int32_t*)take(4 * nc);
+  w->scores = (float*)take(4 * nc);
+  w->bytes = o;
+}
+
+size_t tlsan_topk_workspace_bytes(const tlsan_dims* d, int32_t B, int32_t K) {
+  Shape s;
+  if (shape_of(d, &s) != TLSAN_OK) return 0;
+  if (K < 1 || K > TOPK_MAX) { fail(TLSAN_E_BADARG, "top-K: K must be in 1..%d (got %d)", TOPK_MAX, K); return 0; }
+  if (B < 1) { fail(TLSAN_E_BADARG, "top-K: B must be >= 1 (got %d)", B); return 0; }
+  TopkWs w;
+  carve_topk(d, s.D, B, K, nullptr, &w);
+  return w.bytes;
+}
+
+int tlsan_eval_topk(const tlsan_dims* d, const tlsan_params* p, const float* u_t, int32_t B, int32_t K,
+                    const int32_t* excl_off, const int32_t* excl_ids, int32_t id_mul, int32_t id_add, int32_t* ids,
+                    float* scores, void* ws, size_t ws_bytes, void* stream) {
+  Shape s;
+  int rc = shape_of(d, &s);
+  if (rc) return rc;
+  if ((rc = check_params(p))) return rc;
+  if (!u_t || !ids || !scores || B < 1) return fail(TLSAN_E_BADARG, "tlsan_eval_topk: bad arguments");
+  if (K < 1 || K > TOPK_MAX) return fail(TLSAN_E_BADARG, "tlsan_eval_topk: K must be in 1..%d (got %d)", TOPK_MAX, K);
+  if (!excl_off != !excl_ids) return fail(TLSAN_E_BADARG, "tlsan_eval_topk: excl_off and excl_ids go together");
+  if (id_mul < 1 || id_add < 0 || (long long)(d->item_count - 1) * id_mul + id_add >= (1LL << 31))
+    return fail(TLSAN_E_BADARG, "tlsan_eval_topk: global ids n * id_mul + id_add must be non-negative int32");
+  if (!ws) return fail(TLSAN_E_WORKSPACE, "ws is NULL");
+  TopkWs w;
+  carve_topk(d, s.D, B, K, (char*)ws, &w);
+  if (w.bytes > ws_bytes) return fail(TLSAN_E_WORKSPACE, "workspace too small: need %zu have %zu", w.bytes, ws_bytes);
+  hipStream_t hs = (hipStream_t)stream;
+  TopkArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  EvalArgs& e = ta.e;
+  e.p = norm_params(p, d); e.u_t = u_t; e.B = B; e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate;
+  e.all_emb = w.all_emb; e.id_mul = id_mul; e.id_add = id_add;
+  ta.K = K; ta.excl_off = excl_off; ta.excl_ids = excl_ids;
+  ta.ids = w.nsl > 1 ? w.ids : ids;
+  ta.scores = w.nsl > 1 ? w.scores : scores;
+  if (e.all_emb) {
+    const int nae = (d->item_count * (s.D / 4) + 255) / 256;
+    if (s.D == 64) hipLaunchKernelGGL(k_all_emb<64>, dim3(nae), dim3(256), 0, hs, e);
+    else if (s.D == 128) hipLaunchKernelGGL(k_all_emb<128>, dim3(nae), dim3(256), 0, hs, e);
+    else hipLaunchKernelGGL(k_all_emb<256>, dim3(nae), dim3(256), 0, hs, e);
+    CHECK_LAUNCH("k_all_emb");
+  }
+  hipError_t err = tlsan_launch_topk(ta, s.D, w.nsl, hs);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_eval_topk: %s", hipGetErrorString(err));
+  if (w.nsl > 1 && (err = tlsan_launch_topk_merge(w.ids, w.scores, B, w.nsl, K, ids, scores, hs)) != hipSuccess)
+    return fail(TLSAN_E_LAUNCH, "k_topk_merge: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+int tlsan_topk_merge(const int32_t* cand_ids, const float* cand_scores, int32_t B, int32_t n_lists, int32_t K,
+                     int32_t* ids, float* scores, void* stream) {
+  if (!cand_ids || !cand_scores || !ids || !scores || B < 1 || n_lists < 1)
+    return fail(TLSAN_E_BADARG, "tlsan_topk_merge: bad arguments");
+  if (K < 1 || K > TOPK_MAX) return fail(TLSAN_E_BADARG, "tlsan_topk_merge: K must be in 1..%d (got %d)", TOPK_MAX, K);
+  if ((long long)n_lists * K >= (1LL << 30)) return fail(TLSAN_E_UNSUPPORTED, "tlsan_topk_merge: n_lists * K too large");
+  const hipError_t err = tlsan_launch_topk_merge(cand_ids, cand_scores, B, n_lists, K, ids, scores, (hipStream_t)stream);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_topk_merge: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+// ---- caller-given candidates (tlsan_cand.h) ----
+int tlsan_score_candidates(const tlsan_dims* d, const tlsan_params* p, const float* u_t, int32_t B, int32_t C,
+                           const int32_t* cand, int32_t id_mul, int32_t id_add, float* scores, void* stream) {
+  Shape s;
+  int rc = shape_of(d, &s);
+  if (rc) return rc;
+  if ((rc = check_params(p))) return rc;
+  if (!u_t || !cand || !scores) return fail(TLSAN_E_BADARG, "tlsan_score_candidates: NULL argument");
+  if (B < 1 || C < 1) return fail(TLSAN_E_BADARG, "tlsan_score_candidates: B and C must be >= 1 (got %d, %d)", B, C);
+  if ((long long)B * C >= (1LL << 31)) return fail(TLSAN_E_UNSUPPORTED, "tlsan_score_candidates: B * C overflows int32");
+  if (id_mul < 1 || id_add < 0 || (long long)(d->item_count - 1) * id_mul + id_add >= (1LL << 31))
+    return fail(TLSAN_E_BADARG, "tlsan_score_candidates: global ids n * id_mul + id_add must be non-negative int32");
+  CandArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  EvalArgs& e = ca.e;
+  e.p = norm_params(p, d); e.u_t = u_t; e.B = B; e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate;
+  e.id_mul = id_mul; e.id_add = id_add;
+  ca.C = C; ca.cand = cand; ca.scores = scores;
+  const hipError_t err = tlsan_launch_score_cand(ca, s.D, (hipStream_t)stream);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_score_cand: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+int tlsan_candidate_ranks(const int32_t* cand, const float* scores, int32_t B, int32_t C, int32_t* ranks, void* stream) {
+  if (!cand || !scores || !ranks) return fail(TLSAN_E_BADARG, "tlsan_candidate_ranks: NULL argument");
+  if (B < 1 || C < 1) return fail(TLSAN_E_BADARG, "tlsan_candidate_ranks: B and C must be >= 1 (got %d, %d)", B, C);
+  const hipError_t err = tlsan_launch_cand_ranks(cand, scores, B, C, ranks, (hipStream_t)stream);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_cand_ranks: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+int tlsan_sample_negatives(int32_t item_count, const int32_t* labels, int32_t B, int32_t N, uint64_t seed, int64_t row0,
+                           const int32_t* excl_off, const int32_t* excl_ids, int32_t* out, void* stream) {
+  if (!labels || !out) return fail(TLSAN_E_BADARG, "tlsan_sample_negatives: NULL argument");
+  if (item_count < 1 || B < 1) return fail(TLSAN_E_BADARG, "tlsan_sample_negatives: item_count and B must be >= 1");
+  if (N < 1 || N > NEG_MAX) return fail(TLSAN_E_BADARG, "tlsan_sample_negatives: N must be in 1..%d (got %d)", NEG_MAX, N);
+  if (!excl_off != !excl_ids) return fail(TLSAN_E_BADARG, "tlsan_sample_negatives: excl_off and excl_ids go together");
+  NegArgs na;
+  memset(&na, 0, sizeof(na));
+  na.item_count = item_count; na.B = B; na.N = N; na.seed = seed; na.row0 = row0;
+  na.labels = labels; na.excl_off = excl_off; na.excl_ids = excl_ids; na.out = out;
+  const hipError_t err = tlsan_launch_sample_neg(na, (hipStream_t)stream);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_sample_neg: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // Candidate scoring, candidate ranks and negative sampling (tlsan_cand.h): the instantiations and their launches.
-// Arguments are checked by the callers in tlsan_api.hip (tlsan_score_candidates, tlsan_candidate_ranks,
+// Arguments are checked by the callers in tlsan_api_eval.hip (tlsan_score_candidates, tlsan_candidate_ranks,
 // tlsan_sample_negatives, tlsan_eval_ranks_excl / tlsan_eval_counts_shard_excl).
 #include "tlsan_cand.h"
 

@@ -123,9 +123,11 @@ struct GatherStaticArgs {
   float* rows_out; int32_t* recv_rows;
   unsigned long long* slots64; const uint32_t* stamp_dev;   // nullable; the step's stamp lives on the device (graph replay)
 };
-__global__ __launch_bounds__(256) void k_shard_gather_static(GatherStaticArgs a) {
-  const int e = blockIdx.x * 16 + (threadIdx.x >> 4), l16 = threadIdx.x & 15;
-  if (e >= a.G * a.cap) return;
+// the row of slot e (or -1), filed with the slot's mark by lane 0 of the slot's 16.  Args: GatherStaticArgs as the kernel
+// holds them -- by value, or by reference into its GatherWireArgs (either kernel's registers are then what they were
+// with these lines written out in it)
+template <class Args>
+__device__ __forceinline__ int gather_static_slot(Args a, int e, int l16) {
   const int s = e / a.cap, j = e - s * a.cap;
   const int c = a.recvbuf[(size_t)s * (1 + a.cap)];
   int r = j < c ? a.recvbuf[(size_t)s * (1 + a.cap) + 1 + j] : -1;
@@ -134,6 +136,12 @@ __global__ __launch_bounds__(256) void k_shard_gather_static(GatherStaticArgs a)
     a.recv_rows[e] = r;
     if (r >= 0 && a.slots64) a.slots64[(size_t)r * a.G + s] = ((unsigned long long)*a.stamp_dev << 32) | (unsigned)(e + 1);
   }
+  return r;
+}
+__global__ __launch_bounds__(256) void k_shard_gather_static(GatherStaticArgs a) {
+  const int e = blockIdx.x * 16 + (threadIdx.x >> 4), l16 = threadIdx.x & 15;
+  if (e >= a.G * a.cap) return;
+  const int r = gather_static_slot<GatherStaticArgs>(a, e, l16);
   if (r < 0) return;
   const float* src = a.shard + (size_t)r * a.ld;
   float* dst = a.rows_out + (size_t)e * a.W;
@@ -155,14 +163,7 @@ __global__ __launch_bounds__(256) void k_shard_gather_wire_bf16(GatherWireArgs w
   const GatherStaticArgs& a = w.g;
   const int e = blockIdx.x * 16 + (threadIdx.x >> 4), l16 = threadIdx.x & 15;
   if (e >= a.G * a.cap) return;
-  const int s = e / a.cap, j = e - s * a.cap;
-  const int c = a.recvbuf[(size_t)s * (1 + a.cap)];
-  int r = j < c ? a.recvbuf[(size_t)s * (1 + a.cap) + 1 + j] : -1;
-  if (r < 0 || r >= a.R) r = -1;
-  if (l16 == 0) {
-    a.recv_rows[e] = r;
-    if (r >= 0 && a.slots64) a.slots64[(size_t)r * a.G + s] = ((unsigned long long)*a.stamp_dev << 32) | (unsigned)(e + 1);
-  }
+  const int r = gather_static_slot<const GatherStaticArgs&>(a, e, l16);
   if (r < 0) return;
   const float* src = a.shard + (size_t)r * a.ld;
   char* dst = (char*)a.rows_out + (size_t)e * w.pitch;

@@ -1,5 +1,5 @@
 // Top-K selection over all items (tlsan_topk.h): the instantiations and their launches.  Arguments are checked by the
-// callers in tlsan_api.hip (tlsan_eval_topk, tlsan_topk_merge).
+// callers in tlsan_api_eval.hip (tlsan_eval_topk, tlsan_topk_merge).
 #include "tlsan_topk.h"
 
 // (kept list, append buffer) per user by K: LDS 18 / 24 / 64 KB per workgroup -- at K = 256 two workgroups share a CU

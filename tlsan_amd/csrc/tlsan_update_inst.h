@@ -1,7 +1,7 @@
 // tlsan_update_inst.h -- launchers of the dense finalize kernels (k_dense_finalize, k_finalize_presum,
-// k_finalize_update), one template per (hidden_units, channels per head).  The three (d, heads) pairs of 8 heads are
-// instantiated in tlsan_api.hip; the other pairs in units of their own (tlsan_update_d*.hip), so that they compile
-// beside it.
+// k_finalize_update), one template per (hidden_units, channels per head).  Every (d, heads) pair is instantiated in a
+// unit of its own (tlsan_update_d*.hip), so that the six compile side by side; tlsan_api.hip reaches them through
+// its table of pairs (g_pairs).
 #pragma once
 #include "tlsan_update.h"
 
