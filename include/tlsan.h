@@ -553,6 +553,38 @@ int tlsan_shard_apply_lazy(float* shard, int32_t ld, int32_t cI, int32_t R, int3
                            float* cate_emb, int32_t C, int32_t dc, const float* g_cate,
                            double* sumsq_out, float* sumsq_f32, float* scale, void* ws, size_t ws_bytes, void* stream);
 
+/* tlsan_shard_apply_lazy_opt: the owner-side update of lazy Adam / RMSProp / Adadelta -- the dense optimizer's step of
+ * tlsan_shard_apply_opt, from the same parameters and accumulators, restricted to the rows the GLOBAL batch (all ranks'
+ * batches together) used.  The arguments of tlsan_shard_apply_lazy, plus reg, cate_use, opt and lr.
+ *   item / user rows: the rows in `rows` (every received row is a use).  A used row gets, on its live columns,
+ *     g = coef * (gscale * sum over the sources in source order, in double + reg * W on the regularised columns)
+ *     and the optimizer's step with its two accumulators.  item_b (column reg_item of an item row; reg_item < W) moves where
+ *     its summed gradient is not zero, for all three kinds.  Padding columns and rows nobody sent keep W and both
+ *     accumulators bit for bit.
+ *   category rows: row c is used iff cate_use[c] != 0.  cate_use [C] must hold the same bits on every rank:
+ *     tlsan_shard_cate_use(cate_c, n, u_cate, B, C, use) writes this rank's part -- use[c] = 1 for the categories of its
+ *     batch (cate_c [n]: the item -> category map of the step's compact table, -1 for the rows that are no items, as
+ *     tlsan_route_plan leaves it; u_cate [B]: the batch's), 0 elsewhere -- into C floats that tlsan_amd/dist.py keeps at the
+ *     end of the vector the step all-reduces anyway, so cate_use[c] is the number of ranks that used c: exact in fp32.
+ *   opt: kind ADAM, RMSPROP or ADADELTA (TLSAN_OPT_LAZY may be OR-ed in; SGD is TLSAN_E_BADARG: tlsan_shard_apply_lazy),
+ *     shard_s1/2 and cate_s1/2 given (TLSAN_E_BADARG names the missing one), dense_s1/2 not looked at (the dense weights
+ *     move in tlsan_shard_summary_opt, under the dense kind).  opt->scale must be NULL (TLSAN_E_UNSUPPORTED): the update
+ *     works on the stored values, the table scale P is 1 and stays 1; a state with P != 1 must be folded first.
+ *   step_dev: as tlsan_shard_summary_opt leaves it without a scale ([1] = clip coefficient).
+ *   sumsq_out[0] += the change of the shard rows' sum of squares (regularised columns), sumsq_out[1] += that of cate_emb:
+ *     both stay the tables' sums while only some rows are written.  sumsq_f32 (nullable) receives (float)sumsq_out[0].
+ * W, dc <= 256 and G <= 16 as tlsan_shard_apply (TLSAN_E_UNSUPPORTED).  Fixed summation order, no atomics: bitwise
+ * reproducible.  ws: tlsan_shard_apply_lazy_opt_workspace(n_recv, C) bytes.  There is no static-shape form of this call.
+ * The three functions are additions: nothing else in the ABI changed (TLSAN_ABI_VERSION stays 14). */
+int tlsan_shard_cate_use(const int32_t* cate_c, int32_t n, const int32_t* u_cate, int32_t B, int32_t C, float* use, void* stream);
+size_t tlsan_shard_apply_lazy_opt_workspace(int32_t n_recv, int32_t C);
+int tlsan_shard_apply_lazy_opt(float* shard, int32_t ld, int32_t cI, int32_t R, int32_t W, int32_t reg_item, int32_t reg_user,
+                               const float* vals, int32_t ldv, const int32_t* rows, int32_t n_recv, const int32_t* src_off,
+                               int32_t G, uint64_t* slots64, uint32_t stamp, float gscale, const float* step_dev, float reg,
+                               float* cate_emb, int32_t C, int32_t dc, const float* g_cate, const float* cate_use,
+                               double* sumsq_out, float* sumsq_f32, const tlsan_shard_optimizer* opt, float lr,
+                               void* ws, size_t ws_bytes, void* stream);
+
 /* ---- static-shape forms of the sharded step (tlsan_amd/dist.py, ShardedModel(static_rows=True)).
  * Every (source, owner) pair exchanges exactly `cap` row slots in both directions, so no size ever has to reach
  * the host: the ids, the rows and the gradients travel in equal-split all-to-alls of fixed size, every kernel

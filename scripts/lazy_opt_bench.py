@@ -5,7 +5,10 @@ python scripts/lazy_opt_bench.py shape=bench|10m|c5 opt=sgd|adam|lazy_adam|rmspr
   10m:   10 M users / 5 M items / 10 k categories, d = 128, Ls = 10, B = 4096 (BASELINE.json's synthetic tables)
   c5:    the same tables at d = 256, Ls = 90, B = 4096
 sgd runs the lazy-L2 step; the dense optimizers sweep every row of the four tables every step.  One process per
-(shape, optimizer): the tables, their slots and the step's state are made on the device (init="device")."""
+(shape, optimizer): the tables, their slots and the step's state are made on the device (init="device").
+  sharded=1: the same step on a one-rank ShardedModel (tlsan_amd/dist.py, the step whose exchange sizes follow the batch,
+             plan of the next batch queued a step ahead): lazy_* with the owners' lazy optimizer update
+             (tlsan_shard_apply_lazy_opt), the dense names with the owners' sweep, sgd with the lazy-L2 owner update."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -23,6 +26,28 @@ cfg = synth.make_config("electronics", Ls=Ls, hidden_units=d, itemid_embedding_s
                         cateid_embedding_size=d // 2, user_count=s["U"], item_count=s["I"], cate_count=s["C"], optimizer=opt)
 lr = 1.0 if opt == "sgd" else 1e-3
 icl = synth.item_cate_list(cfg)
+W = int(kw.get("warmup", 5))
+N = int(kw.get("steps", 50))
+if kw.get("sharded", "0") == "1":
+    import torch.distributed as dist
+    from tlsan_amd.dist import ShardedModel
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29549")
+    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda:0"))
+    m = ShardedModel(cfg, icl, l2_mode="lazy" if (opt == "sgd" or opt.startswith("lazy_")) else "dense", init="device")
+    dbs = [m.device_batch(b) for b in synth.make_batches(cfg, 4, B, seed=1234)]
+    sstep = lambda k: m.train_async(dbs[k % 4], lr, next_batch=dbs[(k + 1) % 4])
+    for k in range(W):
+        sstep(k)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for k in range(W, W + N):
+        sstep(k)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / N
+    print("sharded=1 shape=%s opt=%s d=%d Ls=%d B=%d shard %.2f GB: %.1f us/step over %d steps, loss %.4f"
+          % (shape, opt, d, Ls, B, m.shard.numel() * 4 / 1e9, dt * 1e6, N, float(m.last_loss.item())), flush=True)
+    dist.destroy_process_group()
+    sys.exit(0)
 m = Model(cfg, icl, l2_mode="lazy" if opt == "sgd" else "dense", table_dtype=kw.get("td", "f32"),
           init="device")
 host = synth.make_batches(cfg, 4, B, seed=1234)
@@ -51,8 +76,6 @@ def step(k):
     m.train_async(dbs[k % 4], lr, next_batch=dbs[(k + 1) % 4], after_next=dbs[(k + 2) % 4])
 
 
-W = int(kw.get("warmup", 5))
-N = int(kw.get("steps", 50))
 for k in range(W):
     step(k)
 torch.cuda.synchronize()

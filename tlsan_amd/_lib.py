@@ -31,6 +31,7 @@ EXPORTS = [
     "tlsan_profile_collect", "tlsan_debug_stamps", "tlsan_rows_apply_workspace", "tlsan_rows_apply", "tlsan_scan_compact",
     "tlsan_route_plan", "tlsan_shard_gather", "tlsan_shard_summary", "tlsan_shard_apply_workspace", "tlsan_shard_apply",
     "tlsan_shard_summary_opt", "tlsan_shard_apply_opt", "tlsan_shard_apply_lazy_workspace", "tlsan_shard_apply_lazy",
+    "tlsan_shard_apply_lazy_opt_workspace", "tlsan_shard_apply_lazy_opt", "tlsan_shard_cate_use",
     "tlsan_route_plan_static", "tlsan_shard_gather_static", "tlsan_shard_apply_lazy_static", "tlsan_shard_gather_wire_bf16",
     "tlsan_shard_plan_static", "tlsan_shard_step_static", "tlsan_shard_plans_flush",
 ]
@@ -245,6 +246,15 @@ def load():
                                            C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.tlsan_shard_apply_lazy.restype = C.c_int
+    lib.tlsan_shard_apply_lazy_opt_workspace.argtypes = [C.c_int32, C.c_int32]
+    lib.tlsan_shard_apply_lazy_opt_workspace.restype = C.c_size_t
+    lib.tlsan_shard_apply_lazy_opt.argtypes = [C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                               P(C.c_int32), C.c_int32, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_float,
+                                               C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, P(ShardOptimizer), C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.tlsan_shard_apply_lazy_opt.restype = C.c_int
+    lib.tlsan_shard_cate_use.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.tlsan_shard_cate_use.restype = C.c_int
     lib.tlsan_route_plan_static.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + \
                                            [C.c_int32] + [C.c_void_p] * 5
     lib.tlsan_route_plan_static.restype = C.c_int

@@ -1,5 +1,5 @@
 // tlsan_api_shard.hip -- the generic row apply and the row-sharded step of the C ABI (include/tlsan.h): routing plans,
-// gathers, the summary, the owner-side applies, the static step's dispatcher and the launch thread of the announced
+// gathers, the summary, the owner-side applies (dense, lazy L2, lazy optimizers), the static step's dispatcher and the launch thread of the announced
 // batches' plans.  The kernels of tlsan_rows.h and tlsan_shard.h are compiled here; the index scan and k_reduce_double
 // belong to tlsan_api.hip and are reached through its launchers (tlsan_host.h).
 #include <chrono>
@@ -76,22 +76,33 @@ static int shard_front(Args& a, const char* who, float* shard, int32_t ld, int32
   return TLSAN_OK;
 }
 
-// The lazy owner update of both entry points: the slot marks (unless the gather left them), the update of the rows that
-// received gradients, the closing sums (static step, a.stamp_dev: they advance the device's stamp).
-static int shard_apply_lazy_launch(ShardLazyArgs& a, bool mark, double* sumsq_out, float* sumsq_f32, hipStream_t hs) {
+// The two launches around every stamped owner update: the slot marks (unless the gather left them), and the closing sums
+// (static step, a.stamp_dev: they advance the device's stamp; cate_delta: the category workgroups wrote changes too).
+static int shard_lazy_mark(ShardLazyArgs& a, bool mark, hipStream_t hs) {
   a.nb_rows = (a.n_recv + AP_ROWS_PB - 1) / AP_ROWS_PB;
   if (a.nb_rows < 1) a.nb_rows = 1;   // (workgroup 0 commits the scale)
   if (mark) {
     hipLaunchKernelGGL(k_slot_mark64, dim3((a.n_recv + 255) / 256), dim3(256), 0, hs, a);
     CHECK_LAUNCH("k_slot_mark64");
   }
-  hipLaunchKernelGGL(k_shard_apply_lazy, dim3(a.nb_rows + a.nb_cate), dim3(256), 0, hs, a);
-  CHECK_LAUNCH("k_shard_apply_lazy");
+  return TLSAN_OK;
+}
+static int shard_lazy_reduce(const ShardLazyArgs& a, bool cate_delta, double* sumsq_out, float* sumsq_f32, hipStream_t hs) {
   // (the closing sums stay a launch of their own: taken by the last workgroup to finish they cost ~2000 same-address
   //  ticket atomics, 29 us against 7 + 4)
-  hipLaunchKernelGGL(k_reduce_lazy2, dim3(2), dim3(256), 0, hs, a.part_out, a.nb_rows, a.nb_cate, sumsq_out, sumsq_f32, a.stamp_dev);
+  hipLaunchKernelGGL(k_reduce_lazy2, dim3(2), dim3(256), 0, hs, a.part_out, a.nb_rows, a.nb_cate, sumsq_out, sumsq_f32, a.stamp_dev,
+                     cate_delta ? 1 : 0);
   CHECK_LAUNCH("k_reduce_lazy2");
   return TLSAN_OK;
+}
+
+// The lazy-L2 owner update of both its entry points: the update of the rows that received gradients between the two.
+static int shard_apply_lazy_launch(ShardLazyArgs& a, bool mark, double* sumsq_out, float* sumsq_f32, hipStream_t hs) {
+  const int rc = shard_lazy_mark(a, mark, hs);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_shard_apply_lazy, dim3(a.nb_rows + a.nb_cate), dim3(256), 0, hs, a);
+  CHECK_LAUNCH("k_shard_apply_lazy");
+  return shard_lazy_reduce(a, false, sumsq_out, sumsq_f32, hs);
 }
 
 extern "C" {
@@ -182,6 +193,11 @@ int tlsan_shard_gather(const float* shard, int32_t ld, int32_t R, int32_t W, con
   return TLSAN_OK;
 }
 
+static void shard_opt_fill(const tlsan_shard_optimizer* o, int kind, float lr, OptCtx* oc) {
+  oc->opt = kind; oc->lr = lr; oc->b1 = o->beta1; oc->b2 = o->beta2; oc->eps = o->epsilon;
+  if (kind == TLSAN_OPT_ADAM) oc->alpha = adam_alpha(lr, o->beta1, o->beta2, o->step);
+}
+
 static int shard_opt_ctx(const tlsan_shard_optimizer* o, float lr, OptCtx* oc) {
   memset(oc, 0, sizeof(*oc));
   if (!o || o->kind == TLSAN_OPT_SGD) return TLSAN_OK;
@@ -191,8 +207,7 @@ static int shard_opt_ctx(const tlsan_shard_optimizer* o, float lr, OptCtx* oc) {
   if (!o->shard_s1 || !o->shard_s2 || !o->cate_s1 || !o->cate_s2 || !o->dense_s1 || !o->dense_s2)
     return fail(TLSAN_E_BADARG, "tlsan_shard_optimizer: NULL accumulator");
   if (o->kind == TLSAN_OPT_ADAM && o->step < 1) return fail(TLSAN_E_BADARG, "tlsan_shard_optimizer: Adam's step counts from 1");
-  oc->opt = o->kind; oc->lr = lr; oc->b1 = o->beta1; oc->b2 = o->beta2; oc->eps = o->epsilon;
-  if (o->kind == TLSAN_OPT_ADAM) oc->alpha = adam_alpha(lr, o->beta1, o->beta2, o->step);
+  shard_opt_fill(o, o->kind, lr, oc);
   return TLSAN_OK;
 }
 
@@ -300,6 +315,66 @@ int tlsan_shard_apply_lazy(float* shard, int32_t ld, int32_t cI, int32_t R, int3
   if (rc) return rc;
   a.slots64 = (unsigned long long*)slots64; a.stamp = stamp; a.P_dev = scale;
   return shard_apply_lazy_launch(a, n_recv > 0, sumsq_out, sumsq_f32, (hipStream_t)stream);
+}
+
+int tlsan_shard_cate_use(const int32_t* cate_c, int32_t n, const int32_t* u_cate, int32_t B, int32_t C, float* use, void* stream) {
+  if (!use || n < 0 || B < 0 || C < 1 || (n > 0 && !cate_c) || (B > 0 && !u_cate) || (long long)n + B >= (1LL << 31))
+    return fail(TLSAN_E_BADARG, "tlsan_shard_cate_use: NULL pointer / bad size");
+  hipStream_t hs = (hipStream_t)stream;
+  if (hipMemsetAsync(use, 0, 4 * (size_t)C, hs) != hipSuccess) return fail(TLSAN_E_LAUNCH, "tlsan_shard_cate_use: memset");
+  if (n + B > 0) {
+    hipLaunchKernelGGL(k_cate_use_mark, dim3((n + B + 255) / 256), dim3(256), 0, hs, cate_c, n, u_cate, B, C, use);
+    CHECK_LAUNCH("k_cate_use_mark");
+  }
+  return TLSAN_OK;
+}
+
+size_t tlsan_shard_apply_lazy_opt_workspace(int32_t n_recv, int32_t C) { return tlsan_shard_apply_lazy_workspace(n_recv, C); }
+
+int tlsan_shard_apply_lazy_opt(float* shard, int32_t ld, int32_t cI, int32_t R, int32_t W, int32_t reg_item, int32_t reg_user,
+                               const float* vals, int32_t ldv, const int32_t* rows, int32_t n_recv, const int32_t* src_off,
+                               int32_t G, uint64_t* slots64, uint32_t stamp, float gscale, const float* step_dev, float reg,
+                               float* cate_emb, int32_t C, int32_t dc, const float* g_cate, const float* cate_use,
+                               double* sumsq_out, float* sumsq_f32, const tlsan_shard_optimizer* opt, float lr,
+                               void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "tlsan_shard_apply_lazy_opt";
+  if (!shard || !slots64 || !step_dev || !cate_emb || !g_cate || !cate_use || !sumsq_out || !src_off || !opt || n_recv < 0 ||
+      (n_recv > 0 && (!vals || !rows)))
+    return fail(TLSAN_E_BADARG, "%s: NULL pointer / bad size", who);
+  const int kind = opt->kind & ~TLSAN_OPT_LAZY;   // (the lazy flag is what this call means: accepted, not required)
+  if (kind != TLSAN_OPT_ADAM && kind != TLSAN_OPT_RMSPROP && kind != TLSAN_OPT_ADADELTA)
+    return fail(TLSAN_E_BADARG, "%s: opt->kind %d: ADAM, RMSPROP or ADADELTA (SGD has tlsan_shard_apply_lazy)", who, opt->kind);
+  const char* missing = !opt->shard_s1 ? "shard_s1" : !opt->shard_s2 ? "shard_s2" : !opt->cate_s1 ? "cate_s1" : !opt->cate_s2 ? "cate_s2" : nullptr;
+  if (missing) return fail(TLSAN_E_BADARG, "%s: opt->%s is NULL", who, missing);
+  if (kind == TLSAN_OPT_ADAM && opt->step < 1) return fail(TLSAN_E_BADARG, "%s: Adam's step counts from 1", who);
+  if (opt->scale)
+    return fail(TLSAN_E_UNSUPPORTED, "%s: opt->scale must be NULL: the update works on the stored values (table scale P = 1)", who);
+  if (G < 1 || G > SHARD_GMAX) return fail(TLSAN_E_UNSUPPORTED, "%s: 1..%d ranks (G = %d)", who, SHARD_GMAX, G);
+  if (W < 4 || W % 4 || W > 16 * 4 * SHARD_NCH || dc < 4 || dc % 4 || dc > 16 * 4 * SHARD_NCH || ld < W || ld % 4 ||
+      (n_recv > 0 && (ldv < W || ldv % 4)) || cI < 0 || cI > R || reg_item < 0 || reg_item >= W || reg_user < 0 || reg_user > W ||
+      C < 1 || stamp == 0)
+    return fail(TLSAN_E_UNSUPPORTED, "%s: widths must be multiples of 4 up to %d (W = %d, dc = %d), reg_item < W, stamp != 0", who,
+                16 * 4 * SHARD_NCH, W, dc);
+  if (!ws || ws_bytes < tlsan_shard_apply_lazy_opt_workspace(n_recv, C)) return fail(TLSAN_E_WORKSPACE, "%s: workspace too small", who);
+  ShardLazyOptArgs x;
+  memset(&x, 0, sizeof(x));
+  int rc = shard_front(x.l, who, shard, ld, cI, R, W, reg_item, reg_user, vals, ldv, rows, n_recv, src_off, G, gscale, step_dev,
+                       cate_emb, C, dc, g_cate, ws);
+  if (rc) return rc;
+  x.l.slots64 = (unsigned long long*)slots64; x.l.stamp = stamp;
+  x.reg = reg; x.cate_use = cate_use;
+  shard_opt_fill(opt, kind, lr, &x.oc);
+  x.shard_s1 = opt->shard_s1; x.shard_s2 = opt->shard_s2; x.cate_s1 = opt->cate_s1; x.cate_s2 = opt->cate_s2;
+  hipStream_t hs = (hipStream_t)stream;
+  if ((rc = shard_lazy_mark(x.l, n_recv > 0, hs))) return rc;
+  const dim3 grid(x.l.nb_rows + x.l.nb_cate), blk(256);
+  const int wide = W > dc ? W : dc;
+  if (wide <= 64) hipLaunchKernelGGL(k_shard_apply_lazy_opt<1>, grid, blk, 0, hs, x);
+  else if (wide <= 128) hipLaunchKernelGGL(k_shard_apply_lazy_opt<2>, grid, blk, 0, hs, x);
+  else if (wide <= 192) hipLaunchKernelGGL(k_shard_apply_lazy_opt<3>, grid, blk, 0, hs, x);
+  else hipLaunchKernelGGL(k_shard_apply_lazy_opt<4>, grid, blk, 0, hs, x);
+  CHECK_LAUNCH("k_shard_apply_lazy_opt");
+  return shard_lazy_reduce(x.l, true, sumsq_out, sumsq_f32, hs);
 }
 
 // ---- static-shape forms of the three calls above (include/tlsan.h): fixed `cap` row slots per (source, owner) pair

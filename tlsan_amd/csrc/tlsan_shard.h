@@ -494,10 +494,161 @@ __global__ __launch_bounds__(256) void k_shard_apply_lazy(ShardLazyArgs a) {
   if (tid == 0) a.part_out[blockIdx.x] = shd[0] + shd[1] + shd[2] + shd[3];
 }
 
+// ---- lazy Adam / RMSProp / Adadelta owner update (tlsan_shard_apply_lazy_opt): the dense optimizer's step of
+// k_shard_apply restricted to the rows the GLOBAL batch used.  Entries are filed and owned as for k_shard_apply_lazy
+// (stamped slots, the entry of the lowest source owns its row); an owned row gets opt_elem on its live columns with
+//   g = coef * (gscale * sum over the sources, in source order, in double + reg * W on the regularised columns)
+// and its two slots.  item_b (the one live column of an item row that is not regularised) moves where its summed gradient
+// is not zero, for all three kinds; the padding columns, and every row nobody sent, keep W and both slots bit for bit.
+// The tables are the stored values (P = 1: no scale).  Category rows (trailing workgroups; gradient summed by the
+// all-reduce): the rows some rank's batch used, cate_use[c] != 0 -- a count that travelled in the same all-reduce, so
+// every rank decides alike.  part_out: the CHANGE of the regularised columns' sum of squares, for both kinds of workgroup.
+struct ShardLazyOptArgs {
+  ShardLazyArgs l;          // what k_slot_mark64 and the closing sums read; P_dev and stamp_dev are not used
+  float reg;
+  const float* cate_use;    // [C]
+  OptCtx oc;
+  float* shard_s1; float* shard_s2; float* cate_s1; float* cate_s2;
+};
+
+// This rank's part of cate_use (tlsan_shard_cate_use; `use` cleared by the caller): 1 for the category of every item row of
+// the step's compact table (cate_c, -1 for user rows) and for every u_cate of the batch.  Plain stores of one value.
+__global__ void k_cate_use_mark(const int32_t* cate_c, int n, const int32_t* u_cate, int B, int C, float* use) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n + B) return;
+  const int c = t < n ? cate_c[t] : u_cate[t - n];
+  if (c >= 0 && c < C) use[c] = 1.0f;
+}
+
+// NCH: f32x4 chunks per lane, 64 NCH floats >= the widest row.  NSRC sources in flight: four up to 128 columns, two beyond
+// (a row, its two slots, the double sums and NSRC gradient rows are live together: four waves per SIMD, three at NCH = 4,
+// which the second launch bound asks for -- left alone the compiler spends 256 registers on overlapping the per-element
+// updates and one wave per SIMD is left to hide the loads)
+template <int NCH>
+__global__ __launch_bounds__(256, NCH <= 3 ? 4 : 3) void k_shard_apply_lazy_opt(ShardLazyOptArgs x) {
+  __shared__ double shd[4];
+  const ShardLazyArgs& a = x.l;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, grp = lane >> 4, l16 = lane & 15;
+  constexpr int NSRC = NCH <= 2 ? 4 : 2;
+  const int blk = blockIdx.x;
+  const bool is_cate = blk >= a.nb_rows;
+  const int e = (is_cate ? blk - a.nb_rows : blk) * AP_ROWS_PB + wave * 4 + grp;   // entry, or category
+  int r = -1;
+  if (is_cate) {
+    if (e < a.C && x.cate_use[e] != 0.0f) r = e;
+  } else {
+    const int rr = e < a.n_recv ? a.rows[e] : -1;
+    if (rr >= 0 && rr < a.R) r = rr;
+  }
+  const bool item = !is_cate && r < a.cI;
+  const int reg_cols = is_cate ? a.dc : (item ? a.reg_item : a.reg_user);
+  const int n4 = r < 0 ? 0 : ((item ? reg_cols + 1 : reg_cols) + 3) / 4;          // chunks that hold a live column
+  const size_t off = (size_t)(r < 0 ? 0 : r) * (is_cate ? a.dc : a.ld);
+  float* Wr = (is_cate ? a.cate_emb : a.shard) + off;
+  float* S1 = (is_cate ? x.cate_s1 : x.shard_s1) + off;
+  float* S2 = (is_cate ? x.cate_s2 : x.shard_s2) + off;
+  // the row and its slots are requested first: in flight while the slot words and the gradient rows arrive
+  f32x4 w[NCH], m1[NCH], m2[NCH];
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch)
+    if (l16 + 16 * ch < n4) {
+      w[ch] = *(const f32x4*)(Wr + 4 * (l16 + 16 * ch));
+      m1[ch] = *(const f32x4*)(S1 + 4 * (l16 + 16 * ch));
+      m2[ch] = *(const f32x4*)(S2 + 4 * (l16 + 16 * ch));
+    }
+  double acc[NCH][4];
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[ch][i] = 0.0;
+  bool owner = r >= 0;
+  if (is_cate) {
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch)
+      if (l16 + 16 * ch < n4) {
+        const f32x4 v = *(const f32x4*)(a.g_cate + off + 4 * (l16 + 16 * ch));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[ch][i] = (double)v[i];
+      }
+  } else if (owner) {
+    int s = 0;
+    while (s + 1 < a.G && e >= a.src_off[s + 1]) ++s;
+    const unsigned long long* sl = a.slots64 + (size_t)r * a.G;
+    for (int s1 = 0; s1 < s; ++s1) owner = owner && (uint32_t)(sl[s1] >> 32) != a.stamp;
+    if (owner) {
+#pragma unroll 1
+      for (int s0 = s; s0 < a.G; s0 += NSRC) {  // NSRC sources in flight (clamped addresses, masked sum), in source order
+        uint32_t en[NSRC];
+#pragma unroll
+        for (int u = 0; u < NSRC; ++u) {
+          // (source s is this entry itself: its gradient row is requested without a look at the slots -- at one rank
+          //  no slot is read at all.  The others' entries are bounds-checked as well: see k_shard_apply_lazy)
+          const unsigned long long v = (s0 + u > s && s0 + u < a.G) ? sl[s0 + u] : 0ull;
+          en[u] = ((uint32_t)(v >> 32) == a.stamp && (uint32_t)v - 1u < (uint32_t)a.n_recv) ? (uint32_t)v : 0u;
+          if (s0 + u == s) en[u] = (uint32_t)e + 1u;
+        }
+        f32x4 v[NSRC][NCH];
+#pragma unroll
+        for (int u = 0; u < NSRC; ++u)
+          if (u < a.G) {   // (the same for every lane: fewer ranks than sources in flight request nothing for the rest)
+            const float* src = a.vals + (size_t)(en[u] ? en[u] - 1u : 0u) * a.ldv;
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch)
+              if (l16 + 16 * ch < n4) v[u][ch] = *(const f32x4*)(src + 4 * (l16 + 16 * ch));
+          }
+#pragma unroll
+        for (int u = 0; u < NSRC; ++u)
+          if (en[u]) {
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch)
+              if (l16 + 16 * ch < n4) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[ch][i] += (double)v[u][ch][i];
+              }
+          }
+      }
+    }
+  }
+  double part = 0.0;
+  if (owner) {
+    const float coef = a.step_dev[1];
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      const int c4 = l16 + 16 * ch;
+      if (c4 < n4) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int col = 4 * c4 + i;
+          const bool rg = col < reg_cols;
+          const float w0 = w[ch][i];
+          const float g = a.gscale * (float)acc[ch][i] + (rg ? x.reg * w0 : 0.0f);
+          // past the regularised columns only item_b is live, and it moves where a gradient arrived
+          if (rg || (item && col == reg_cols && g != 0.0f)) {
+            float wi = w0, a1 = m1[ch][i], a2 = m2[ch][i];
+            opt_elem(x.oc, wi, coef * g, a1, a2);
+            w[ch][i] = wi; m1[ch][i] = a1; m2[ch][i] = a2;
+            if (rg) part += (double)wi * (double)wi - (double)w0 * (double)w0;
+          }
+        }
+        *(f32x4*)(Wr + 4 * c4) = w[ch];
+        *(f32x4*)(S1 + 4 * c4) = m1[ch];
+        *(f32x4*)(S2 + 4 * c4) = m2[ch];
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) part += __shfl_xor(part, o);
+  if (lane == 0) shd[wave] = part;
+  __syncthreads();
+  if (tid == 0) a.part_out[blk] = shd[0] + shd[1] + shd[2] + shd[3];
+}
+
 // out[0] += sum(part[0, n0)) (changes of the stored shard rows' sum of squares), out[1] = sum(part[n0, n0+n1))
+// (cate_delta: the category workgroups wrote changes as well, out[1] += their sum -- tlsan_shard_apply_lazy_opt)
 // stamp_dev (nullable): the static-shape step keeps its stamp on the device; every workgroup of the apply has read this
 // step's value by now, the next step files under the next one (never 0, the value of a cleared slot)
-__global__ __launch_bounds__(256) void k_reduce_lazy2(const double* part, int n0, int n1, double* out, float* sq_f32, uint32_t* stamp_dev) {
+__global__ __launch_bounds__(256) void k_reduce_lazy2(const double* part, int n0, int n1, double* out, float* sq_f32, uint32_t* stamp_dev,
+                                                      int cate_delta) {
   __shared__ double shd[256];
   const int b = blockIdx.x;
   const double s = block_sum_double(part + (b ? n0 : 0), b ? n1 : n0, shd);
@@ -510,7 +661,7 @@ __global__ __launch_bounds__(256) void k_reduce_lazy2(const double* part, int n0
         *stamp_dev = n == 0xFFFFFFFFu ? 1u : n;
       }
     } else {
-      out[1] = s;
+      out[1] = cate_delta ? out[1] + s : s;
     }
   }
 }

@@ -29,7 +29,9 @@ communicator in program order):
   (5) all-to-all of the per-row gradients back to the owners;
   (6) tlsan_shard_apply: the owners file each received row under (row, source rank) -- rows of one
       source are distinct, so no counting sort -- and apply the update with dense L2 decay to every
-      local row in fixed source order (bitwise reproducible), category table included.
+      local row in fixed source order (bitwise reproducible), category table included.  (l2_mode="lazy": only the rows
+      that arrived -- tlsan_shard_apply_lazy for sgd, tlsan_shard_apply_lazy_opt for lazy_adam / lazy_rmsprop /
+      lazy_adadelta, whose category-use flags ride in the all-reduce of (3).)
 
 Items and users share one fused shard table and one exchange each way.
 
@@ -278,7 +280,13 @@ class ShardedModel:
                  wire_dtype="f32", init="numpy", deferred_ids=False, coalesce=False):
         """l2_mode: "dense" -- every owner decays every one of its rows every step, as the reference's dense L2
         gradient does; "lazy" (sgd) -- the same update kept as W = P * W_stored with one scale P that all ranks
-        advance alike, so an owner touches only the rows whose gradients arrived (tlsan_shard_apply_lazy).
+        advance alike, so an owner touches only the rows whose gradients arrived (tlsan_shard_apply_lazy); with
+        config["optimizer"] "lazy_adam" / "lazy_rmsprop" / "lazy_adadelta" (which need l2_mode="lazy") -- the dense optimizer's
+        step restricted to the rows the GLOBAL batch used (tlsan_shard_apply_lazy_opt): the item and user rows that reached
+        their owner, and the category rows some rank's batch used (a use flag per category rides in the step's all-reduce, so
+        every rank decides alike); every other row keeps its value and both accumulators bit for bit, the dense weights move
+        every step, loss and clip norm are the dense optimizer's, and the table scale stays 1.  The lazy optimizers have no
+        static-shape step: static_rows (and with it graph capture and wire_dtype="bf16") is refused for them.
           wire_dtype (static_rows only): "f32", or "bf16" -- rows cross the wire with bf16 embedding values (fp32 weights
         stay with their owners; see below).
           static_rows (lazy only): False -- exchange sizes follow the batch (the host reads them once per step);
@@ -322,14 +330,21 @@ class ShardedModel:
         self.optimizer = config.get("optimizer", "sgd")
         if self.optimizer not in OPTIMIZERS:
             raise ValueError("optimizer must be one of %s" % (sorted(OPTIMIZERS),))
-        if self.optimizer in LAZY_OPTIMIZERS:
-            raise NotImplementedError("optimizer=%r: the sharded step has no lazy optimizers (tlsan_amd.model.Model has)"
-                                      % self.optimizer)
+        # lazy_adam / lazy_rmsprop / lazy_adadelta: the owners apply the optimizer to the rows that arrived and to no other
+        # (tlsan_shard_apply_lazy_opt) -- the lazy owner update's form, as the C ABI's lazy kinds need TLSAN_L2_LAZY
+        self.lazy_opt = self.optimizer in LAZY_OPTIMIZERS
+        if self.lazy_opt and not self.lazy:
+            raise NotImplementedError("optimizer=%r: the lazy optimizers update only the rows that reach their owner, which is "
+                                      "the lazy owner update: pass l2_mode='lazy'" % self.optimizer)
+        if self.lazy_opt and static_rows:
+            raise NotImplementedError("optimizer=%r: the static-shape step (static_rows, and with it graph capture and "
+                                      "wire_dtype='bf16') is built for lazy-L2 SGD only: Adam's step count is a launch "
+                                      "argument, and the static step's driver has no lazy optimizer" % self.optimizer)
         self.dropout = float(config.get("dropout", 0.0))
         if not 0.0 <= self.dropout < 1.0:
             raise ValueError("dropout must be in [0, 1)")
         self._seed = int(seed)
-        if self.lazy and self.optimizer != "sgd":
+        if self.lazy and self.optimizer != "sgd" and not self.lazy_opt:
             raise NotImplementedError("l2_mode='lazy' is the SGD update's form; optimizer=%r sweeps every row" % self.optimizer)
         self.config = config
         self.lib = L.load()
@@ -368,7 +383,10 @@ class ShardedModel:
             raise NotImplementedError("fused shard rows up to 256 floats, up to 16 ranks")
         self._sq = torch.zeros(2, dtype=torch.float64, device=dev)   # sums of squares: local shard rows, cate_emb
         # all-reduced vector: dense grads | cate grads | mean BCE | per-use squares | local table squares | pad
-        self._flat = torch.zeros(self.lay.n_dense + Cc * self.dc + 4, dtype=torch.float32, device=dev)
+        # lazy optimizers: | C category-use flags (1 where this rank's batch uses the category: the sum over the ranks is
+        # the number of ranks that use it, exact in fp32 and the same bits everywhere)
+        self._flat = torch.zeros(self.lay.n_dense + Cc * self.dc + 4 + (Cc if self.lazy_opt else 0), dtype=torch.float32,
+                                 device=dev)
         self._gn_local = torch.zeros(1, dtype=torch.float32, device=dev)
         self._step_dev = torch.zeros(4, dtype=torch.float32, device=dev)     # lr * coef, coef, (lazy:) lr * coef / P_new, P_new
         self.renorm_every = 4096
@@ -382,7 +400,8 @@ class ShardedModel:
         self._sopt = None
         if self.optimizer != "sgd":
             kind, b1, b2, eps = OPTIMIZERS[self.optimizer]
-            one = 1.0 if self.optimizer == "rmsprop" else 0.0
+            kind &= ~L.OPT_LAZY      # (the dense weights move under the dense kind; the lazy apply is a call of its own)
+            one = 1.0 if self.optimizer in ("rmsprop", "lazy_rmsprop") else 0.0
             self.slots = dict(shard_s1=torch.full_like(self.shard, one), shard_s2=torch.zeros_like(self.shard),
                               cate_s1=torch.full_like(self.cate_emb, one), cate_s2=torch.zeros_like(self.cate_emb),
                               dense_s1=torch.full_like(self.dense, one), dense_s2=torch.zeros_like(self.dense))
@@ -743,13 +762,17 @@ class ShardedModel:
             flat[:k + 1].mul_(float(weight))
             flat[k + 1:k + 2].mul_(float(weight) ** 2)
             gf.mul_(float(weight))
+        if self.lazy_opt:
+            # the categories this rank's batch uses: those of the items of its compact table (user rows: -1) and its u_cate
+            L.check(self.lib.tlsan_shard_cate_use(sl["cate_c"].data_ptr(), sl["n"], db.u_cate.data_ptr(), db.B, Cc, tail + 16, st),
+                    "tlsan_shard_cate_use")
         # ---- one all-reduce: dense grads | cate grads | loss | per-use squares | local table squares
         if G > 1:
             allreduce_sum(flat, self.group)
         if self._sopt is not None:
             self._sopt.step = self._step + 1
         sopt = None if self._sopt is None else C.byref(self._sopt)
-        if self.lazy:
+        if self.lazy and not self.lazy_opt:
             sopt = C.byref(self._sopt_lazy)
         L.check(self.lib.tlsan_shard_summary_opt(fp, n_dense, n_cate, G, float(lr), self.reg, self.clip,
                                                  self._sq.data_ptr() + 8, self.dense.data_ptr(), self.dense_KT.data_ptr(),
@@ -762,7 +785,18 @@ class ShardedModel:
             a2a(vals[:sl["n_recv"]], gf[:sl["n"]], sl["recv"], sl["send"], self.group)
         else:
             vals = gf
-        if self.lazy:
+        if self.lazy_opt:
+            nws = int(self.lib.tlsan_shard_apply_lazy_opt_workspace(sl["n_recv"], Cc))
+            if self._lws is None or self._lws.numel() < nws:
+                self._lws = torch.empty(int(nws * 1.5) + 256, dtype=torch.uint8, device=dev)
+            L.check(self.lib.tlsan_shard_apply_lazy_opt(self.shard.data_ptr(), W, self.cI, self.router.R, W, di, di + Ls,
+                                                        vals.data_ptr(), W, sl["recv_rows"].data_ptr(), sl["n_recv"],
+                                                        sl["src_off"], G, self._slots64.data_ptr(), self._lazy_stamp(),
+                                                        1.0 / G, self._step_dev.data_ptr(), self.reg, self.cate_emb.data_ptr(),
+                                                        Cc, self.dc, fp + 4 * n_dense, tail + 16, self._sq.data_ptr(), tail + 8,
+                                                        sopt, float(lr), self._lws.data_ptr(), self._lws.numel(), st),
+                    "tlsan_shard_apply_lazy_opt")
+        elif self.lazy:
             nws = int(self.lib.tlsan_shard_apply_lazy_workspace(sl["n_recv"], Cc))
             if self._lws is None or self._lws.numel() < nws:
                 self._lws = torch.empty(int(nws * 1.5) + 256, dtype=torch.uint8, device=dev)
@@ -1491,7 +1525,7 @@ class ShardedModel:
         """lazy L2: multiply the scale into the stored tables (P -> 1); what is trained does not change.
         Done on a fixed schedule (renorm_every) so that P stays away from fp32 underflow, and before the
         parameters are read."""
-        if not self.lazy:
+        if not self.lazy or self.lazy_opt:     # (the lazy optimizers work on the stored values: P is 1 throughout)
             return
         P = self._P
         di, Ls = self.di, self.Ls

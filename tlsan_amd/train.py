@@ -519,11 +519,14 @@ def train_sharded(args):
         raise NotImplementedError("--norm_mode %s: the sharded step forms the clip norm as TF 1.8 does (tf18)" % args.norm_mode)
     if args.matrix_dtype != "f32":
         raise NotImplementedError("--matrix_dtype %s: the sharded step computes in fp32" % args.matrix_dtype)
-    if args.optimizer.startswith("lazy_"):
-        raise NotImplementedError("--optimizer %s: the sharded step has no lazy optimizers" % args.optimizer)
+    lazy_opt = args.optimizer.startswith("lazy_")
+    if lazy_opt and args.static_rows:
+        raise NotImplementedError("--optimizer %s: --static_rows is the lazy-L2 SGD step's form; the lazy optimizers run "
+                                  "the step whose exchange sizes follow the batch" % args.optimizer)
     resume = prepare_model_dir(args.model_dir, args.from_scratch, rank,
                                (lambda: dist.barrier()) if world > 1 else None)     # train.py:124-127
-    l2_mode = args.l2_mode if args.optimizer == "sgd" else "dense"
+    # (the lazy optimizers are the lazy owner update's form whatever --l2_mode says: train() treats both values alike too)
+    l2_mode = "lazy" if lazy_opt else (args.l2_mode if args.optimizer == "sgd" else "dense")
     if args.static_rows and l2_mode != "lazy":
         raise NotImplementedError("--static_rows is the lazy-L2 SGD step's form (--l2_mode lazy --optimizer sgd)")
     model = ShardedModel(config, icl, device=args.device, seed=args.seed, l2_mode=l2_mode,
