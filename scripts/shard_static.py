@@ -22,7 +22,7 @@ m0, dbs0, l0 = run(False)
 m1, dbs, l1 = run(True)
 print("losses dynamic:", ["%.6f" % x for x in l0[-4:]])
 print("losses static :", ["%.6f" % x for x in l1[-4:]])
-print("max |loss diff| %.3g; shard max diff %.3g; cap %d" % (max(abs(a - b) for a, b in zip(l0, l1)), (m0.shard * m0._P - m1.shard * m1._P).abs().max().item(), m1._st["cap"]))
+print("max |loss diff| %.3g; shard max diff %.3g; cap %d" % (max(abs(a - b) for a, b in zip(l0, l1)), (m0.shard * m0._P - m1.shard * m1._P).abs().max().item(), m1._static.cap))
 m1.check_static_overflow()
 def timeit(f, n=200, reps=4):
     best = 1e9

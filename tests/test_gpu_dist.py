@@ -67,7 +67,7 @@ def _worker(rank, world, port, ret, d, prefetch, ckpt, uneven=False, hotcat=Fals
         m = ShardedModel(cfg, cat, device="cuda:0", l2_mode="lazy" if lazy else "dense")
         m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
         if uneven:
-            m._pcap = 5     # a shared exchange capacity far too small: the overflow protocol must raise it in lockstep
+            m._dynamic.pcap = 5     # a shared exchange capacity far too small: the overflow protocol must raise it in lockstep
         steps = _split_batches(cfg, world, 4, B=150 if hotcat else 24, uneven=uneven)
         wgt = lambda per: len(per[rank]["u"]) * world / sum(len(q_["u"]) for q_ in per)
         losses = []
@@ -81,7 +81,7 @@ def _worker(rank, world, port, ret, d, prefetch, ckpt, uneven=False, hotcat=Fals
                 m.train_async(_tuple(per[rank]), 0.8, weight=wgt(per))
                 losses.append(float(m.last_loss.item()))
         if uneven:
-            assert m._pcap > 5 and all(sl is None or sl["pcap"] == min(m.router.R, m._pcap) for sl in m._slots[:2])
+            assert m._dynamic.pcap > 5 and all(sl is None or sl.pcap == min(m.router.R, m._dynamic.pcap) for sl in m._dynamic.slots[:2])
         got = m.gather_params()
         auc = m.eval_auc(None, tuple(list(_tuple(steps[0][rank]))[:2] + [steps[0][rank]["i"][::-1].copy()] + list(_tuple(steps[0][rank]))[3:]))
         if rank == 0:

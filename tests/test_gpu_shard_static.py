@@ -148,6 +148,63 @@ def test_static_step_equals_dynamic_step_at_one_rank():
     assert ret.get(0) == "ok", dict(ret)
 
 
+def _moved_branches_worker(port, ret):
+    import tempfile
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=0, world_size=1)
+    try:
+        from tlsan_amd import synth
+        from tlsan_amd.dist import ShardedModel
+        base = synth.make_config("electronics", user_count=3001, item_count=2203, cate_count=67)
+        icl = synth.item_cate_list(base)
+        batches = synth.make_batches(base, 4, 256, seed=5, sessions="amazon")
+        test_batch = synth.make_batches(base, 1, 64, seed=5, test=True, sessions="amazon")[0]
+        weights = (1.0, 0.5, 1.0, 0.25)
+
+        def run(static, model_dir):
+            m = ShardedModel(dict(base, model_dir=model_dir), icl, device="cuda:0", l2_mode="lazy", static_rows=static)
+            dbs = [m.device_batch(b) for b in batches]
+            losses, ranks = [], None
+            for s in range(8):
+                kw = dict(after_next=dbs[(s + 2) % 4]) if static else {}
+                m.train_async(dbs[s % 4], 0.7, next_batch=dbs[(s + 1) % 4], weight=weights[s % 4], **kw)
+                losses.append(float(m.last_loss.item()))
+                if s + 1 == 3:        # an evaluation between steps whose successors' plans are announced
+                    ranks = m.label_ranks(test_batch).cpu().numpy()
+                if s + 1 == 5:        # a restore in mid-run, with announced plans outstanding
+                    m.restore(None, m.save(sharded=True))
+            if static:
+                m.check_static_overflow()
+            return losses, ranks, m.gather_params()
+
+        with tempfile.TemporaryDirectory() as tmp:
+            l0, r0, p0 = run(False, os.path.join(tmp, "dynamic"))
+            l1, r1, p1 = run(True, os.path.join(tmp, "static"))
+        assert r0.shape == (64,) and np.array_equal(r0, r1), ("label ranks", r0, r1)
+        assert l1 == l0, ("losses", l0, l1)
+        for k in p0:
+            assert np.array_equal(p0[k], p1[k]), k
+        ret[0] = "ok"
+    except Exception:
+        import traceback
+        ret[0] = "FAIL: " + traceback.format_exc()
+    finally:
+        dist.destroy_process_group()
+
+
+def test_static_step_with_weights_evaluation_and_restore_equals_dynamic_step():
+    """The static step where the steps' weights differ from 1, with an evaluation and a save / restore between steps
+    that have announced both successors: the same losses, label ranks and parameters as the dynamic step, bit for bit."""
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    ret = ctx.Manager().dict()
+    p = ctx.Process(target=_moved_branches_worker, args=(_free_port(), ret))
+    p.start()
+    p.join(600)
+    assert ret.get(0) == "ok", dict(ret)
+
+
 def _two_rank_worker(rank, world, port, ret):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
