@@ -36,7 +36,7 @@ uses = -(-(B * (cfg["Ls"] + db.Sn + 2)) // C)
 ni = min(cfg["item_count"], B * (cfg["Ls"] + Sn + 1))
 nbI = (ni + 15) // 16
 nbU = (min(B, cfg["user_count"]) + 15) // 16
-# workgroups of the category part (category_split, tlsan_api_tail.hip; TLSAN_CSPLIT_FINE)
+# workgroups of the category part (category_split, tlsan_api_plan.hip; TLSAN_CSPLIT_FINE)
 nsh = min(64, uses // 128) if uses > 512 else 1
 if uses > 96 and os.environ.get("TLSAN_CSPLIT_FINE", "1") != "0":
     nsh = max(nsh, min(64, uses // 48, (1280 - (206 + nbI + nbU)) // C))
@@ -44,7 +44,7 @@ C = C * max(nsh, 1)
 if cfg["cate_count"] >= int(os.environ.get("TLSAN_CSEG_MIN", 2048)):      # category segments: 16 categories per workgroup
     C = (cfg["cate_count"] + 15) // 16
 print("blocks %d: cate %d, item %d, user %d, dense %d; span %.0f ticks (100 MHz -> %.1f us)" % (n, C, nbI, nbU, n - C - nbI - nbU, s[:, 6].max() - t0, (s[:, 6].max() - t0) / 100))
-# the one-pass row launch places the user-row workgroups ahead of the item-row workgroups where rows are wide (tlsan_api_tail.hip:
+# the one-pass row launch places the user-row workgroups ahead of the item-row workgroups where rows are wide (tlsan_api_plan.hip:
 # ApplyArgs.ufirst, and the shared-category form's own rule), and launches at most SPEC_ITEM_BLOCKS item-row workgroups
 WU = (cfg["hidden_units"] // 2 + cfg["Ls"] + 3) // 4 * 4
 ufirst = (cfg["hidden_units"] // 2 > 64 or WU > 128) and os.environ.get("TLSAN_LAZY_ONE_PASS", "1") != "0"

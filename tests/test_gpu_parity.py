@@ -553,7 +553,7 @@ np.savez(sys.argv[1], loss=loss, gnorm=m.last_gnorm(), **m.get_params())
 
 def test_bf16_tables_clipped_step_in_the_one_pass_form(tmp_path):
     """bf16 table storage through the speculative one-pass tail with the clip ACTIVE (TLSAN_LAZY_ONE_PASS=3: by default only
-    HBM-resident bf16 tables take this form, tlsan_api_tail.hip `plan_tail`).  The rows are written with coefficient 1
+    HBM-resident bf16 tables take this form, tlsan_api_plan.hip `plan_tail`).  The rows are written with coefficient 1
     (stochastic rounding at the magnitude of w - lr g), corrected by k_spec_commit (a second rounding) and read back through
     the folded table scale (a third): a stored element may be off by one bf16 ulp of the SPECULATIVE value plus two of the
     result -- not more; fp32 parameters keep the usual bound; two runs are bitwise equal.  (The split form, the default for
@@ -592,17 +592,45 @@ def test_bf16_tables_clipped_step_in_the_one_pass_form(tmp_path):
     assert worst > 3.0      # (the case does exercise the second rounding: otherwise it checks nothing the split form's test does not)
 
 
-def test_prefetched_index_equals_inline():
+# (shape of the model, Model keywords, first batch size): the products a prefetched index may carry, each on the smallest
+# shape that reaches it -- the rules are those of the planning unit, tlsan_amd/csrc/tlsan_api_plan.hip
+_PREFETCH_CASES = {
+    # d = 128 with 8 heads and at most 64 groups of 16 takes 8-sample groups (`train_group`, TLSAN_NW4 = 1): no ranking;
+    # B <= 32 C: no category list; C < TLSAN_CSEG_MIN_CATES = 2048: no category segments
+    "groups_of_8": (dict(d=128), dict(l2_mode="lazy"), 40),
+    # `balanced`: 16 < B <= BAL_CAP, Sn > 0, at most FUSED_DK_MAX_GROUPS = 256 groups, I <= 2^18, and d = 64 has no small
+    # group -- the index writes a ranking and the step reads it
+    "ranking": (dict(d=64, Ls=10), dict(l2_mode="lazy"), 40),
+    # Ls = 33 > TLSAN_LS_MAX = 10: streamed windows, ranked by window length (by_window = 1)
+    "ranking_by_window": (dict(d=64, Ls=33), dict(l2_mode="lazy"), 40),
+    # `uc_by_list`: B = 72 .. 86 > 32 C = 64 (and <= UC_LIST_CAP): k_uc_fill leaves the samples of every category
+    "category_list": (dict(d=128, C=2), dict(l2_mode="lazy"), 72),
+    # `cate_seg`: C = 2100 >= TLSAN_CSEG_MIN_CATES = 2048 and no category list (B <= 32 C)
+    "category_segments": (dict(d=128, I=2300, C=2100), dict(l2_mode="lazy"), 40),
+    # dense L2 sweeps every row: the index is built without TLSAN_INDEX_FOR_LAZY_SGD (offsets of every row)
+    "full_index": (dict(d=128), dict(l2_mode="dense"), 40),
+    # the index is planned without hyper-parameters, i.e. for the 8-sample groups of "groups_of_8"; with dropout the step
+    # runs 16-sample groups (`train_group`: the small-group kernel is built without dropout) -- neither may touch a
+    # ranking.  The keep / drop pattern is Model.dropout_seed(step): the same in all four runs.
+    "dropout": (dict(d=128, dropout=0.2), dict(l2_mode="lazy"), 40),
+}
+
+
+@pytest.mark.parametrize("case", list(_PREFETCH_CASES))
+def test_prefetched_index_equals_inline(case):
     """train_async(next_batch=..., after_next=...) builds the destination index of the next batch(es) on a second
     stream (tlsan_batch_index) one or two steps ahead; the result must be bitwise the same as building it inside the
-    step, for batches of different shapes."""
-    cfg = make_config(U=60, I=80, C=9, d=128, regulation_rate=1e-3)
+    step, for batches of different shapes -- and for every optional product of the index (_PREFETCH_CASES: a ranking
+    of the batch in either form, the category list, category segments, the full index of a dense-L2 step), which the
+    prefetching call plans from the dims and the batch alone and the step reads one or two steps later."""
+    shape, kw, B0 = _PREFETCH_CASES[case]
+    cfg = make_config(**dict(dict(U=60, I=80, C=9, regulation_rate=1e-3), **shape))
     p = _p32(random_params(cfg, seed=31))
     _, cat = random_batch(cfg, B=8, Sn=2, seed=0)
-    batches = [_tuple(random_batch(cfg, B=40 + 7 * (s % 3), Sn=1 + s % 4, seed=300 + s)[0]) for s in range(7)]
+    batches = [_tuple(random_batch(cfg, B=B0 + 7 * (s % 3), Sn=1 + s % 4, seed=300 + s)[0]) for s in range(7)]
     runs = []
     for prefetch in (0, 1, 2, 3):     # none / one step ahead / two steps ahead / two ahead, announced irregularly
-        m = _model(cfg, cat, p, l2_mode="lazy")
+        m = _model(cfg, cat, p, **kw)
         dbs = [m.device_batch(b) for b in batches]
         for s, db in enumerate(dbs):
             nxt = dbs[s + 1] if (prefetch and s + 1 < len(dbs)) else None
@@ -613,7 +641,7 @@ def test_prefetched_index_equals_inline():
         for k in runs[0]:
             assert np.array_equal(runs[0][k], r[k]), k
     # announcing a batch and then training another one is an error (its uses are already counted)
-    m = _model(cfg, cat, p, l2_mode="lazy")
+    m = _model(cfg, cat, p, **kw)
     dbs = [m.device_batch(b) for b in batches[:3]]
     m.train_async(dbs[0], 0.6, next_batch=dbs[1])
     with pytest.raises(RuntimeError):
@@ -1198,7 +1226,7 @@ np.savez(sys.argv[1], losses=np.asarray(losses), **m.get_params())
 
 def test_ranking_of_the_batch_changes_results_by_rounding_only(tmp_path):
     """which samples share a workgroup of the fused kernel is a ranked function of the batch where that was measured
-    to win (tlsan_api.hip `balanced`: table size, group count, TLSAN_BAL_REG) -- so the fp32 grouping of the per-group partial
+    to win (tlsan_api_plan.hip `balanced`: table size, group count, TLSAN_BAL_REG) -- so the fp32 grouping of the per-group partial
     sums, and with it the last bits of a step, depend on those.  Each setting is bitwise reproducible by itself (the
     determinism tests); across settings results may differ by fp32 rounding ONLY: three lazy steps of a batch with a partial
     last group, ranked (TLSAN_BAL_REG=1) and in the batch's own order (=0)."""
@@ -1256,7 +1284,7 @@ sys.path.insert(0, %r)
 from tests.helpers import make_config, random_batch, random_params
 from tlsan_amd.model import Model
 h = hashlib.sha256()
-# (categories of 300-450 items: shared by item; of 60-70: by use position -- category_split, tlsan_api_tail.hip)
+# (categories of 300-450 items: shared by item; of 60-70: by use position -- category_split, tlsan_api_plan.hip)
 for d, Ls, C, td, I in ((128, 10, 3, "f32", 900), (128, 90, 2, "f32", 900), (64, 33, 5, "f32", 300), (128, 70, 3, "bf16", 200)):
     cfg = make_config(U=500, I=I, C=C, d=d, Ls=Ls, regulation_rate=1e-3, max_gradient_norm=1e4)
     p = {k: np.asarray(v, np.float32) for k, v in random_params(cfg, seed=13).items()}

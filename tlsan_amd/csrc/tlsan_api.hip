@@ -1,12 +1,12 @@
 // tlsan_api.hip -- the core of the C ABI declared in include/tlsan.h: layout and sizes, the persistent state, the forward,
 // the batch pack and index, the train step, tlsan_grads and the profiling ring: argument checking, workspace carving and
-// kernel sequencing.  (Evaluation: tlsan_api_eval.hip; rows and the sharded step: tlsan_api_shard.hip; what the three
-// share: tlsan_host.h.)  No allocation, no synchronisation; everything is enqueued on the caller's stream (so a whole
+// kernel sequencing.  What a step builds and launches is decided in tlsan_api_plan.hip (tlsan_plan.h); this unit issues it.
+// (Evaluation: tlsan_api_eval.hip; rows and the sharded step: tlsan_api_shard.hip; what they share: tlsan_host.h.)  No allocation, no synchronisation; everything is enqueued on the caller's stream (so a whole
 // step can be captured into a hipGraph).
 #include <stdarg.h>
 #include <stdio.h>
 
-#include "tlsan_tail.h"
+#include "tlsan_plan.h"
 
 static thread_local char g_err[512] = "";   // (static: fail() and tlsan_last_error() are its only doors, for every unit)
 int fail(int code, const char* fmt, ...) {
@@ -59,9 +59,13 @@ struct Pair {
   int D, DH, NSB, NPB, CW;
   hipError_t (*fwd_bwd)(bool train, bool lstream, const FwdArgs& a, int grid, hipStream_t st, LaunchEvents ev);
   void (*finalize)(const FinLaunch& L, hipStream_t hs);
+  // optional: a training kernel of smaller workgroups for small batches, and its samples per pass (Shape::SG; when it is
+  // taken: FrontPlan::small, tlsan_api_plan.hip)
+  hipError_t (*fwd_bwd_small)(const FwdArgs& a, int grid, hipStream_t st, LaunchEvents ev);
+  int small_grp;
 };
-#define PAIR(D, DH, U) {D, DH, Geo<D, DH>::NSB, Geo<D, DH>::NPB, Geo<D, DH>::CW, tlsan_launch_fwd_bwd_##U, tlsan_launch_finalize_##U}
-static const Pair g_pairs[] = {PAIR(64, 8, d64),      PAIR(64, 16, d64h4),  PAIR(128, 16, d128),
+#define PAIR(D, DH, U, ...) {D, DH, Geo<D, DH>::NSB, Geo<D, DH>::NPB, Geo<D, DH>::CW, tlsan_launch_fwd_bwd_##U, tlsan_launch_finalize_##U, __VA_ARGS__}
+static const Pair g_pairs[] = {PAIR(64, 8, d64),      PAIR(64, 16, d64h4),   PAIR(128, 16, d128, tlsan_launch_fwd_bwd_d128w4, 8),
                                PAIR(128, 8, d128h16), PAIR(128, 32, d128h4), PAIR(256, 32, d256)};
 #undef PAIR
 static const Pair* pair_of(int D, int DH) {
@@ -84,7 +88,7 @@ int shape_of(const tlsan_dims* d, Shape* s) {
   const Pair* pr = pair_of(D, DH);
   if (!pr) return fail(TLSAN_E_UNSUPPORTED, "unsupported (hidden_units=%d, num_heads=%d): this build has (hidden_units, num_heads) = "
                        "64/4, 64/8, 128/4, 128/8, 128/16, 256/8", D, d->num_heads);
-  s->NSB = pr->NSB; s->NPB = pr->NPB; s->CW = pr->CW;
+  s->NSB = pr->NSB; s->NPB = pr->NPB; s->CW = pr->CW; s->SG = pr->small_grp;
   return TLSAN_OK;
 }
 
@@ -100,47 +104,14 @@ int check_params(const tlsan_params* p) {
 }
 
 static int ru4(int x) { return (x + 3) / 4 * 4; }
-// the dK product rides in k_fwd_bwd for D <= 128 (Geo::FUSE_DK); its launch then has at most this many workgroups
-// (each loops over its passes), so that the per-workgroup partials stay a few tens of MB at any batch size
-// ... when there is at most one partial per CU: more of them (d = 64 at 8192 sequences: 512) make the reduction in
-// k_dense_finalize the long pole of its launch (77 -> 91 us/step), and the separate k_dk_partial launch (<= 64 partials)
-// is the better deal again
-#define FUSED_DK_MAX_GROUPS 256
-// tables with at least this many categories take the category-segment path (cate_seg below; TLSAN_CSEG_MIN=<n> for tests
-// and experiments, read once per process)
-#define TLSAN_CSEG_MIN_CATES 2048
-static int cseg_min_cates() {
-  static const int v = [] { const char* e = getenv("TLSAN_CSEG_MIN"); return e ? atoi(e) : TLSAN_CSEG_MIN_CATES; }();
-  return v;
-}
-static bool fused_dk(int D, int ngroups) { return D <= 128 && ngroups <= FUSED_DK_MAX_GROUPS; }
-// Samples per workgroup pass of a TRAINING launch of the fused kernel (= per partial record): the width's NSB, or 8 at
-// d = 128 with 8 heads (4-wavefront workgroups: Geo<128, 16, 4>) with the window in registers and no dropout, when the batch is so
-// small that 16-sample workgroups would leave three quarters of the CUs idle -- a wavefront then runs alone on its SIMD
-// (profiles/r04_nw4_ab.md; at larger batches the 16-sample workgroups are faster).
-// TLSAN_NW4 (A/B measurements; read once): 0 never, 1 as described, 2 always.
-static int train_group(const Shape& s, const tlsan_dims* d, const tlsan_batch* b, const tlsan_hparams* hp) {
-  static const int mode = [] { const char* e = getenv("TLSAN_NW4"); return e ? atoi(e) : 1; }();
-  if (s.D != 128 || s.DH != 16 || d->Ls > TLSAN_LS_MAX || (hp && hp->dropout != 0.0f) || mode == 0) return s.NSB;
-  if (mode == 1 && (b->B + s.NSB - 1) / s.NSB > 64) return s.NSB;
-  return 8;
-}
-static int fwd_train_grid(int ngroups) { return ngroups; }    // (fused: ngroups <= FUSED_DK_MAX_GROUPS, one pass per workgroup)
-
-// windows longer than TLSAN_LS_MAX are streamed (the list form of the long block); shorter ones stay in registers
-static bool streamed(int Ls) { return Ls > TLSAN_LS_MAX; }
-
 void carve(const tlsan_dims* d, const Shape& s, int B, int Sn, char* base, Ws* w) {
   size_t o = 0;
   auto take = [&](size_t n) { char* p = base ? base + o : nullptr; o += al(n); return p; };
   const size_t NI = (size_t)B * (d->Ls + Sn + 1), D = s.D;
   tlsan_dense_layout L;
   tlsan_dense_layout_of(d, &L);
+  const Capacity cap = plan_capacity(d, s, B);
   w->WU = ru4(d->d_item + d->Ls);
-  w->ngroups = (B + 7) / 8;  // partial records: one per workgroup pass (the smallest pass any launch may take: train_group)
-  // dK partials: one per batch split of k_dk_partial, or (fused into the forward/backward kernel, D <= 128) one per
-  // workgroup of that launch -- which of the two, and how many, is the launch's choice (run_backward)
-  const int ngroups = (B + s.NSB - 1) / s.NSB;
   w->nbK = (s.D * s.D + 255) / 256;
   const int small_pb = s.D > 128 ? FIN_SMALL_PB : 16;      // (small parameters per finalize workgroup: dense_finalize_block)
   w->nbS = (L.n_dense - s.D * s.D + small_pb - 1) / small_pb;
@@ -149,23 +120,14 @@ void carve(const tlsan_dims* d, const Shape& s, int B, int Sn, char* base, Ws* w
   w->Gi = (float*)take(sizeof(float) * (NI + 1) * D);
   w->Gb = (float*)take(sizeof(float) * (NI + 1));
   w->Gu = (float*)take(sizeof(float) * (size_t)(B + 1) * w->WU);
-  // (CSEG: one row per u_cate use AND per item use -- sized for it whenever the table shape can take that path)
-  w->Gc = (float*)take(sizeof(float) * (size_t)(B + 1 + (d->cate_count >= cseg_min_cates() ? NI : 0)) * d->d_cate);
+  w->Gc = (float*)take(sizeof(float) * (size_t)(B + 1 + (cap.cseg ? NI : 0)) * d->d_cate);
   w->gLong = (float*)take(sizeof(float) * B * D);
   w->gDB = (float*)take(sizeof(float) * B * D);
-  // streamed windows with two 16-channel blocks per column (d = 256, and d = 128 with 4 heads): per-sample softmax
-  // statistics of the long block (k_fwd_bwd, FLATG: no room in the LDS)
-  w->gStat = (float*)take((s.CW > 16 && streamed(d->Ls)) ? sizeof(float) * (size_t)B * 2 * D : 0);
-  w->partials = (float*)take(sizeof(float) * w->ngroups * s.NPB);
-  // (sized so that the workspace of a batch also holds every smaller batch: the fused form of a smaller batch can
-  //  need more partials than the split form of a larger one)
-  int kp_slots = dk_nsplit(B, s.D);
-  if (s.D <= 128) {
-    const int ng8 = (s.D == 128 && s.DH == 16) ? (B + 7) / 8 : ngroups;    // (8-sample workgroups: twice the groups)
-    const int fmax = ng8 < FUSED_DK_MAX_GROUPS ? ng8 : FUSED_DK_MAX_GROUPS;
-    if (fmax > kp_slots) kp_slots = fmax;
-  }
-  w->Kp = (float*)take(sizeof(float) * kp_slots * D * D);
+  // windows too long for the registers (cap.lstream) with two 16-channel blocks per column (d = 256, and d = 128 with
+  // 4 heads): per-sample softmax statistics of the long block (k_fwd_bwd, FLATG: no room in the LDS)
+  w->gStat = (float*)take((s.CW > 16 && cap.lstream) ? sizeof(float) * (size_t)B * 2 * D : 0);
+  w->partials = (float*)take(sizeof(float) * cap.max_records * s.NPB);
+  w->Kp = (float*)take(sizeof(float) * cap.kp_slots * D * D);
   w->gd = (float*)take(sizeof(float) * L.n_dense);
   w->sqd = (float*)take(sizeof(float) * w->nfin);
   w->scal = (float*)take(sizeof(float) * 4);
@@ -229,55 +191,6 @@ int launch_reduce_double(const double* v, int n, double* out, hipStream_t hs) {
   return TLSAN_OK;
 }
 
-#define BAL_CAP (1 << 14)      // batches up to this many samples are ranked for the fused kernel's workgroups (BalArgs, tlsan_update.h)
-// Streamed windows: a workgroup's time is proportional to its windows' total length (d = 64, Ls = 90: 98 -> 87 us/step;
-// d = 256 at the C5 shape 496 -> 471; d = 128: the kernel alone 94 -> 72 us, 104 -> 93 beside the index build of the batch
-// after next).  Windows in registers: evenly loaded workgroups (ranked by session length alone) ran no faster in round 4
-// (bench 61.0 vs 61.1 us/step; Amazon session lengths 65.6 vs 66.2) -- the launch ends with the workgroups that hold one
-// of the few long sessions, however they are dealt; what does help is giving THOSE workgroups the batch's shortest
-// windows (round 5, BalArgs: bench 58.2 -> 57.15, Amazon session lengths 61.85 -> 59.05, d = 256 169.4 -> 162.0:
-// profiles/r05_ab_bal_reg.txt).
-// (round 5: windows in registers as well, with a ranking that gives the workgroups of the batch's longest sessions its
-//  shortest windows -- BalArgs; TLSAN_BAL_REG=0: streamed windows only, as before)
-static int bal_reg_mode() {   // 0 off, 1 on, 2 on without the reversed group numbering (A/B)
-  static const int reg = [] { const char* e = getenv("TLSAN_BAL_REG"); return e ? atoi(e) : 1; }();
-  return reg;
-}
-static bool balanced(const tlsan_dims* d, const tlsan_batch* b) {
-  if (!b || b->B <= 16 || b->B > BAL_CAP) return false;
-  if (streamed(d->Ls)) return true;
-  // windows in registers: where it was measured to win -- one round of workgroups (<= 256 groups of 16: a second round
-  // evens the workgroups out by itself, and 16384 sequences ran 5 % SLOWER ranked: 207 vs 196 us/step) and tables that the
-  // caches hold (10 M users / 5 M items: 101.7 vs 97.4 -- full windows side by side mean more HBM rows in flight at once);
-  // profiles/r05_ab_bal_reg_shapes2.txt
-  return bal_reg_mode() != 0 && b->Sn > 0 && (b->B + 15) / 16 <= FUSED_DK_MAX_GROUPS && d->item_count <= (1 << 18);
-}
-#define UC_LIST_CAP (1 << 18)  // batches up to this many samples may keep a per-category sample list in the state
-// ... and do when a category sees many of the batch's samples (cursor atomics on few addresses inside the
-// fused kernel cost more than the extra launch on the index stream): more than 32 samples per category
-static inline bool uc_by_list(const tlsan_dims* d, const tlsan_batch* b) {
-  return b && b->B <= UC_LIST_CAP && (long)b->B > 32L * d->cate_count;
-}
-// many categories (the 10 k of BASELINE.json configs[4]): the category half of every item use's gradient row is written
-// into the category's own segment of Gc (FwdArgs.cseg) -- a category block of the apply pass then sums one contiguous
-// segment instead of walking the category's items for their segments (500 items per category at 5 M items, of which a
-// batch uses five: k_finalize_presum 196 us at that shape).  With few categories the cursor draws would pile up on few
-// addresses (as the u_cate uses did, uc_by_list): the item walk stays.
-// (the category counts of CSEG need the item -> category map: tlsan_batch_index takes it as an argument -- round 3 kept
-//  a process-global registry state -> map filled by tlsan_state_init, which a re-allocated map or a recycled state
-//  address left stale)
-// Tables of at least this many rows take their side of a lazy-SGD step's index from a sort of the batch's ids instead of
-// a counter per row -- when its consumers reach it through ids and records only: the user table (UsortArgs: a bucket
-// sort inside one block), the item table with category segments (IsortArgs: a partitioned counting sort, tlsan_update.h).
-// TLSAN_ISORT_MIN=<rows> for tests (read once per process; it also sizes the state).
-static int isort_min_rows() {
-  static const int v = [] { const char* e = getenv("TLSAN_ISORT_MIN"); return e ? atoi(e) : (1 << 16); }();
-  return v;
-}
-static bool isort_rows_ok(int rows) { return rows >= isort_min_rows() && (long)rows <= (long)IS_MAXB * IS_BSZ; }
-static inline bool cate_seg(const tlsan_dims* d, const tlsan_batch* b) {
-  return d->cate_count >= cseg_min_cates() && !uc_by_list(d, b);
-}
 struct St {  // persistent state
   // two index slots (a batch's destination index depends only on its ids, so it lives with the
   // state, not in the per-call workspace whose layout follows the batch shape):
@@ -290,13 +203,13 @@ struct St {  // persistent state
   double *S_part, *S_total;
   DeltaRec* S_delta;                                      // per-workgroup changes of the sum of squares, tagged by step (tlsan_update.h)
   long long* scan_bsum[TLSAN_INDEX_SLOTS];                                // per-chunk sums of the index scan (large tables), per slot
-  int32_t* perm[TLSAN_INDEX_SLOTS];                                       // samples of every workgroup of the fused kernel (BalArgs), BAL_CAP each
+  int32_t* perm[TLSAN_INDEX_SLOTS];                                       // samples of every workgroup of the fused kernel (BalArgs), Capacity::rank_cap each
   int32_t* scan_ticket;                                                   // [index slot] arrivals of k_scan_block_sums (ScanArgs.bs_ticket), zero at rest
   int32_t* flag_user[TLSAN_INDEX_SLOTS];                                  // 256-row pieces of the user table that hold a count (ScanArgs.flag), zero at rest
-  int32_t* uc_list[TLSAN_INDEX_SLOTS];                                    // samples of every category (u_cate uses), UC_LIST_CAP each
+  int32_t* uc_list[TLSAN_INDEX_SLOTS];                                    // samples of every category (u_cate uses), Capacity::uc_list_cap each
   double* Rc64;                                           // category sums of a split PRESUM pass, zero at rest
   int32_t* hot_list[TLSAN_INDEX_SLOTS];                                   // slots (urec_item) of the hot item rows, AP_HOT_CAP each
-  // the item side of the index from a partitioned counting sort of the batch's ids (IsortArgs; tables of isort_min_rows() rows or more)
+  // the item side of the index from a partitioned counting sort of the batch's ids (IsortArgs; where Capacity::isort says so)
   int32_t *is_bh[TLSAN_INDEX_SLOTS], *is_ids[TLSAN_INDEX_SLOTS], *is_bstart[TLSAN_INDEX_SLOTS], *is_nd[TLSAN_INDEX_SLOTS];
   int4* is_tmp[TLSAN_INDEX_SLOTS];
   size_t bytes;
@@ -304,7 +217,8 @@ struct St {  // persistent state
   int nrec;   // records per step-parity array of S_delta: a workgroup each of the row blocks and the hot-row workgroups
 };
 
-static void carve_state(const tlsan_dims* d, char* base, St* s) {
+static void carve_state(const tlsan_dims* d, const Shape& shp, char* base, St* s) {
+  const Capacity cap = plan_capacity(d, shp, 1);   // (the state's answers do not depend on the batch)
   size_t o = 0;
   auto take = [&](size_t n) { char* p = base ? base + o : nullptr; o += al(n); return p; };
   s->nbI = (d->item_count + AP_ROWS_PB - 1) / AP_ROWS_PB;
@@ -331,17 +245,17 @@ static void carve_state(const tlsan_dims* d, char* base, St* s) {
   s->S_part = (double*)take(8 * (size_t)(s->nbI + s->nbU + s->nbC));
   s->nrec = s->nbI + s->nbU + s->nbC + AP_HOT_CAP;
   s->S_delta = (DeltaRec*)take(sizeof(DeltaRec) * 2 * (size_t)s->nrec);   // (two arrays, by step parity: DeltaRec)
-  for (int k = 0; k < TLSAN_INDEX_SLOTS; ++k) s->uc_list[k] = (int32_t*)take(4 * (size_t)UC_LIST_CAP);
+  for (int k = 0; k < TLSAN_INDEX_SLOTS; ++k) s->uc_list[k] = (int32_t*)take(4 * (size_t)cap.uc_list_cap);
   s->Rc64 = (double*)take(8 * (size_t)d->cate_count * d->d_cate);
   for (int k = 0; k < TLSAN_INDEX_SLOTS; ++k) s->hot_list[k] = (int32_t*)take(4 * (size_t)AP_HOT_CAP);
   for (int k = 0; k < TLSAN_INDEX_SLOTS; ++k)
     s->scan_bsum[k] = (long long*)take(8 * ((size_t)(d->item_count + 4095) / 4096 + (d->cate_count + 4095) / 4096 +
                                             (d->user_count + 4095) / 4096));
-  for (int k = 0; k < TLSAN_INDEX_SLOTS; ++k) s->perm[k] = (int32_t*)take(4 * (size_t)BAL_CAP);
+  for (int k = 0; k < TLSAN_INDEX_SLOTS; ++k) s->perm[k] = (int32_t*)take(4 * (size_t)cap.rank_cap);
   s->scan_ticket = (int32_t*)take(4 * 64);
   for (int k = 0; k < TLSAN_INDEX_SLOTS; ++k) s->flag_user[k] = (int32_t*)take(4 * (((size_t)d->user_count + 255) / 256));
   {
-    const bool on = isort_rows_ok(d->item_count);
+    const bool on = cap.isort;
     for (int k = 0; k < TLSAN_INDEX_SLOTS; ++k) {
       s->is_bh[k] = (int32_t*)take(on ? 4 * (size_t)(ISORT_MAX_SLOTS / IS_BLK_SLOTS) * IS_MAXB : 0);
       s->is_ids[k] = (int32_t*)take(on ? 4 * (size_t)ISORT_MAX_SLOTS : 0);
@@ -390,7 +304,7 @@ size_t tlsan_state_bytes(const tlsan_dims* d) {
   Shape s;
   if (shape_of(d, &s) != TLSAN_OK) return 0;
   St st;
-  carve_state(d, nullptr, &st);
+  carve_state(d, s, nullptr, &st);
   return st.bytes;
 }
 
@@ -404,7 +318,8 @@ static int check_batch(const tlsan_dims* d, const tlsan_batch* b, bool train) {
   return TLSAN_OK;
 }
 
-static void fill_apply(ApplyArgs& A, const tlsan_dims* d, const Shape& s, const tlsan_params* p, const tlsan_batch* b,
+// ix: the plan of the batch's index; NULL where there is no batch (recompute_sumsq)
+static void fill_apply(ApplyArgs& A, const tlsan_dims* d, const Shape& s, const tlsan_params* p, const IndexPlan* ix,
                        const tlsan_hparams* hp, const Ws& w, const St& st, const tlsan_dense_layout& L) {
   const int k = hp ? hp->index_slot : 0;
   memset(&A, 0, sizeof(A));
@@ -417,8 +332,8 @@ static void fill_apply(ApplyArgs& A, const tlsan_dims* d, const Shape& s, const 
   A.off_item = st.off_item[k]; A.off_uc = st.off_uc[k]; A.off_user = st.off_user[k];
   A.n_uniq_item = st.hdr ? &st.hdr->n_uniq[k][0] : nullptr; A.n_uniq_user = st.hdr ? &st.hdr->n_uniq[k][1] : nullptr;
   A.cate_off = st.cate_off; A.cate_cnt = st.cate_cnt; A.cate_items = st.cate_items;
-  A.uc_list = uc_by_list(d, b) ? st.uc_list[k] : nullptr;
-  A.cseg = (b && cate_seg(d, b)) ? 1 : 0;
+  A.uc_list = (ix && ix->uc_list) ? st.uc_list[k] : nullptr;
+  A.cseg = (ix && ix->cseg) ? 1 : 0;
   A.Rc64 = st.Rc64;
   A.csplit = 1; A.cpass = 256; A.cpos = 0;
   A.hot_n = st.hdr ? &st.hdr->n_hot[k] : nullptr; A.hot_list = st.hot_list[k];
@@ -477,7 +392,7 @@ static int open_state(const tlsan_dims* d, const tlsan_params* p, void* state, S
   if (rc) return rc;
   if ((rc = check_params(p))) return rc;
   if (!state) return fail(TLSAN_E_WORKSPACE, "state is NULL");
-  carve_state(d, (char*)state, st);
+  carve_state(d, *s, (char*)state, st);
   return TLSAN_OK;
 }
 
@@ -552,29 +467,29 @@ int tlsan_state_recategorize(const tlsan_dims* d, const tlsan_params* p, void* s
   return rc ? rc : cate_csr(d, p, st, (hipStream_t)stream);
 }
 
-static int launch_fwd(const Shape& s, bool train, const FwdArgs& a, hipStream_t hs, int grp = 0) {
-  int grid = a.ngroups < 4096 ? a.ngroups : 4096;
-  if (train && a.fuse_dk) grid = fwd_train_grid(a.ngroups);
+// the fused kernel as the plan says (a.ngroups, a.fuse_dk: the plan's as well)
+static int launch_fwd(const Shape& s, bool train, const FrontPlan& fp, const FwdArgs& a, hipStream_t hs) {
   hipError_t e;
-  const bool lstream = streamed(a.Ls);  // long windows are streamed, short ones stay in registers
   LaunchEvents ev = {nullptr, nullptr};
   if (train) ev = prof_kernel_events();
-  if (train && s.D == 128 && s.DH == 16 && grp == 8) e = tlsan_launch_fwd_bwd_d128w4(a, grid, hs, ev);
-  else e = pair_of(s.D, s.DH)->fwd_bwd(train, lstream, a, grid, hs, ev);   // (shape_of has refused every other pair)
+  const Pair* pr = pair_of(s.D, s.DH);   // (shape_of has refused every other pair)
+  if (fp.small) e = pr->fwd_bwd_small(a, fp.grid, hs, ev);
+  else e = pr->fwd_bwd(train, fp.lstream, a, fp.grid, hs, ev);
   if (e == hipErrorNotSupported)
     return fail(TLSAN_E_UNSUPPORTED, "dropout > 0 is built for train steps only (and not for the 8-sample workgroup form)");
   if (e != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_fwd_bwd: %s", hipGetErrorString(e));
   return TLSAN_OK;
 }
 
-static void fill_fwd(FwdArgs& a, const tlsan_dims* d, const Shape& s, const tlsan_params* p, const tlsan_batch* b,
-                     const Ws& w, const tlsan_dense_layout& L) {
+static void fill_fwd(FwdArgs& a, const tlsan_dims* d, const tlsan_params* p, const tlsan_batch* b, const FrontPlan& fp,
+                     const tlsan_dense_layout& L) {
   memset(&a, 0, sizeof(a));
   a.p = norm_params(p, d);
   a.b = *b;
   a.lay = L;
   a.Ls = d->Ls; a.di = d->d_item; a.dc = d->d_cate;
-  a.ngroups = (b->B + s.NSB - 1) / s.NSB;  // (training: overridden by run_backward)
+  a.ngroups = fp.ngroups;
+  a.fuse_dk = fp.fuse_dk ? 1 : 0;
   a.inv_B = 1.0f / (float)b->B;
   a.stamps = g_stamps;
 }
@@ -594,22 +509,22 @@ int tlsan_forward_att(const tlsan_dims* d, const tlsan_params* p, const tlsan_ba
   (void)ws; (void)ws_bytes;
   tlsan_dense_layout L;
   tlsan_dense_layout_of(d, &L);
-  Ws w;
-  memset(&w, 0, sizeof(w));
+  const FrontPlan fp = plan_forward(d, s, b);
   FwdArgs a;
-  fill_fwd(a, d, s, p, b, w, L);
+  fill_fwd(a, d, p, b, fp, L);
   a.logits_i = logits_i;
   a.logits_j = logits_j;
   a.u_t = u_t;
   a.att0 = att0; a.att1 = att1;
-  return launch_fwd(s, false, a, (hipStream_t)stream);
+  return launch_fwd(s, false, fp, a, (hipStream_t)stream);
 }
 
 // destination index of a batch into slot k: use counts per destination row -> first sorted position
 // of every row (+ records of the used rows)
-static int build_index(const tlsan_dims* d, const tlsan_batch* b, const int32_t* item_cate, const St& st, int k, hipStream_t hs,
-                       bool sparse_users = false) {
-  const bool cseg = cate_seg(d, b);
+static int build_index(const tlsan_dims* d, const tlsan_batch* b, const IndexPlan& ix, const int32_t* item_cate, const St& st,
+                       int k, hipStream_t hs) {
+  const bool cseg = ix.cseg, usort = ix.usort, isort = ix.isort;
+  const int nthr = ix.nthr;
   if (cseg && !item_cate) return fail(TLSAN_E_BADARG, "tables with %d categories count item uses per category: item_cate is NULL", d->cate_count);
   int rc;
   CountArgs ca;
@@ -620,12 +535,6 @@ static int build_index(const tlsan_dims* d, const tlsan_batch* b, const int32_t*
   ca.item_cate = cseg ? item_cate : nullptr; ca.cseg = cseg ? 1 : 0;
   ca.ncate = d->cate_count;
   ca.flag_user = st.flag_user[k];
-  // a table's side from a sort of the batch's ids when only the used rows are wanted and the table is large: the user
-  // table (UsortArgs); the item table (IsortArgs) when a lazy-SGD step with category segments consumes the index (it
-  // reaches item offsets / cursors through ids and records only)
-  const int nthr = b->B * (d->Ls + b->Sn + 1);
-  const bool usort = sparse_users && b->B <= USORT_MAX && d->user_count >= isort_min_rows();
-  const bool isort = sparse_users && cseg && nthr <= ISORT_MAX_SLOTS && isort_rows_ok(d->item_count);
   ca.skip_users = usort ? 1 : 0;
   ScanArgs sa;
   memset(&sa, 0, sizeof(sa));
@@ -682,47 +591,41 @@ static int build_index(const tlsan_dims* d, const tlsan_batch* b, const int32_t*
   sa.flag[2] = st.flag_user[k];
   // (sa.bs_ticket = st.scan_ticket + k: the sums scanned by the last block of k_scan_block_sums, one prefix read per scan
   //  block -- measured slower: 3663 publishing atomics on consecutive words, 134 -> 162 us/step at 10 M / 5 M rows)
-  // the user table of a lazy-L2 SGD step: its consumers reach off / cur through the batch's ids or the used-row records
-  // only (the dense sweeps and tlsan_grads read the offsets of every row)
-  // (category segments: nothing walks the item offsets per category either -- 5 M items: 40 MB of writes per step less)
-  sa.sparse = sparse_users ? ((1 << 2) | (cseg ? 1 : 0)) : 0;
+  sa.sparse = ix.sparse;
   sa.n_uniq[0] = &st.hdr->n_uniq[k][0]; sa.n_uniq[1] = nullptr; sa.n_uniq[2] = &st.hdr->n_uniq[k][1];
-  // (no ranking block for a launch that will not read it -- the 8-sample workgroups of small d = 128 batches take
-  //  the batch's own order; the index is built ahead of the step's hyper-parameters, so the groups are sized for a launch
-  //  without dropout, and run_backward asks the same question)
-  Shape shp;
-  if ((rc = shape_of(d, &shp))) return rc;
-  if (balanced(d, b) && train_group(shp, d, b, nullptr) == shp.NSB) {
+  if (ix.rank) {   // (a ranking block only for a launch that will read it: plan_front)
     sa.bal.sl = b->sl; sa.bal.sl_new = b->sl_new;
     sa.bal.B = b->B; sa.bal.Ls = d->Ls; sa.bal.Sn = b->Sn;
-    sa.bal.by_window = streamed(d->Ls) ? 1 : (bal_reg_mode() == 2 ? -1 : 0);
+    sa.bal.by_window = ix.by_window;
     sa.bal.perm = st.perm[k];
   }
   if ((rc = launch_scan(sa, nscan, st.scan_bsum[k], hs))) return rc;
-  if (uc_by_list(d, b)) {
+  if (ix.uc_list) {
     hipLaunchKernelGGL(k_uc_fill, dim3((b->B + 255) / 256), dim3(256), 0, hs, b->u_cate, b->B, d->cate_count, st.cur_uc[k], st.uc_list[k]);
     CHECK_LAUNCH("k_uc_fill");
   }
   return TLSAN_OK;
 }
 
-// shared front half of train_step / grads: index build, fused fwd+bwd, dK partials; fills f but for plan_tail's fields
+// shared front half of train_step / grads, as planned (plan_front): index build, fused fwd+bwd, dK partials; fills f but
+// for plan_tail's fields
 static int run_backward(const tlsan_dims* d, const Shape& s, const tlsan_params* p, const tlsan_batch* b,
                         const tlsan_hparams* hp, const tlsan_step_out* out, const Ws& w, const St& st,
-                        const tlsan_dense_layout& L, hipStream_t hs, bool sparse_index, FinArgs* f) {
+                        const tlsan_dense_layout& L, hipStream_t hs, const FrontPlan& fp, FinArgs* f) {
   const int k = hp->index_slot;
   int rc;
   prof_mark(0, hs);
-  if (!hp->index_prebuilt && (rc = build_index(d, b, p->item_cate, st, k, hs, sparse_index))) return rc;
+  if (!hp->index_prebuilt && (rc = build_index(d, b, fp.ix, p->item_cate, st, k, hs))) return rc;
   // --- fused forward + backward
   FwdArgs a;
-  fill_fwd(a, d, s, p, b, w, L);
+  fill_fwd(a, d, p, b, fp, L);
   a.logits_i = (out && out->logits) ? out->logits : w.logits;
   if (out && out->started) { a.started = out->started; a.started_val = out->started_value; }
   a.Gi = w.Gi; a.Gb = w.Gb; a.Gu = w.Gu; a.Gc = w.Gc; a.WU = w.WU;
   a.cur_item = st.cur_item[k]; a.cur_user = st.cur_user[k]; a.cur_uc = st.cur_uc[k];
-  a.uc_by_sample = uc_by_list(d, b) ? 1 : 0;
-  a.cseg = cate_seg(d, b) ? 1 : 0;
+  a.uc_by_sample = fp.ix.uc_list ? 1 : 0;
+  a.cseg = fp.ix.cseg ? 1 : 0;
+  a.perm = fp.read_rank ? st.perm[k] : nullptr;
   a.gLong = w.gLong; a.gDB = w.gDB; a.gStat = w.gStat; a.partials = w.partials; a.Kp = w.Kp;
   if (hp->dropout != 0.0f) {
     if (!(hp->dropout > 0.0f && hp->dropout < 1.0f)) return fail(TLSAN_E_BADARG, "dropout must be in [0, 1)");
@@ -733,19 +636,13 @@ static int run_backward(const tlsan_dims* d, const Shape& s, const tlsan_params*
     a.drop_seed = hp->dropout_seed;
     a.drop_sample0 = hp->dropout_sample0;
   }
-  const int grp = train_group(s, d, b, hp);  // samples per workgroup pass of the fused kernel (= per partial record)
-  // (the ranking deals the batch out in groups of 16: the 8-sample workgroups of small d = 128 batches take the batch's order)
-  a.perm = balanced(d, b) && grp == s.NSB && train_group(s, d, b, nullptr) == s.NSB ? st.perm[k] : nullptr;   // (what build_index left)
-  a.ngroups = (b->B + grp - 1) / grp;
-  a.fuse_dk = fused_dk(s.D, a.ngroups) ? 1 : 0;
   prof_mark(1, hs);
-  if ((rc = launch_fwd(s, true, a, hs, grp))) return rc;
+  if ((rc = launch_fwd(s, true, fp, a, hs))) return rc;
   prof_mark(2, hs);
-  const int nsplit = a.fuse_dk ? fwd_train_grid(a.ngroups) : dk_nsplit(b->B, s.D);   // dK partials the finalize sums
-  // --- dense-parameter gradients (D <= 128: the dK partials were left by k_fwd_bwd, one per workgroup)
-  if (!a.fuse_dk) {
+  // --- dense-parameter gradients (fused: the dK partials were left by k_fwd_bwd, one per workgroup)
+  if (!fp.fuse_dk) {
     const int spw = dk_spw(b->B, s.D), nq = (s.D / 64) * (s.D / 64);
-    const dim3 grid(nq * nsplit), blk(DK_WAVES * 64);
+    const dim3 grid(nq * fp.nsplit), blk(DK_WAVES * 64);
 #define DK_LAUNCH(DD)                                                                                           \
   do {                                                                                                          \
     (void)hipFuncSetAttribute((const void*)k_dk_partial<DD>, hipFuncAttributeMaxDynamicSharedMemorySize, DK_SMEM_BYTES); \
@@ -758,7 +655,7 @@ static int run_backward(const tlsan_dims* d, const Shape& s, const tlsan_params*
   }
   CHECK_LAUNCH("k_dk_partial");
   prof_mark(3, hs);
-  f->lay = L; f->partials = w.partials; f->nrec = (b->B + grp - 1) / grp; f->Kp = w.Kp; f->nsplit = nsplit;
+  f->lay = L; f->partials = w.partials; f->nrec = fp.ngroups; f->Kp = w.Kp; f->nsplit = fp.nsplit;
   f->sqd = w.sqd; f->scal = w.scal;
   f->S_delta = st.S_delta; f->delta_nrec = st.nrec; f->S_total = st.S_total;
   f->hdr = st.hdr; f->lr = hp->lr; f->reg = hp->reg; f->clip = hp->clip; f->inv_B = 1.0f / (float)b->B;
@@ -786,7 +683,7 @@ static int prep_step(const tlsan_dims* d, Shape* s, const tlsan_params* p, const
   if (!state || !ws) return fail(TLSAN_E_WORKSPACE, "state / ws is NULL");
   carve(d, *s, b->B, b->Sn, (char*)ws, w);
   if (w->bytes > ws_bytes) return fail(TLSAN_E_WORKSPACE, "workspace too small: need %zu have %zu", w->bytes, ws_bytes);
-  carve_state(d, (char*)state, st);
+  carve_state(d, *s, (char*)state, st);
   return TLSAN_OK;
 }
 
@@ -876,8 +773,8 @@ int tlsan_batch_index(const tlsan_dims* d, const tlsan_batch* b, const int32_t* 
   slot &= ~TLSAN_INDEX_FOR_LAZY_SGD;
   if (slot < 0 || slot >= TLSAN_INDEX_SLOTS) return fail(TLSAN_E_BADARG, "index slot must be 0 .. %d", TLSAN_INDEX_SLOTS - 1);
   if (!state) return fail(TLSAN_E_WORKSPACE, "state is NULL");
-  carve_state(d, (char*)state, &st);
-  return build_index(d, b, item_cate, st, slot, (hipStream_t)stream, lazy_sgd);
+  carve_state(d, s, (char*)state, &st);
+  return build_index(d, b, plan_index(d, s, b, lazy_sgd), item_cate, st, slot, (hipStream_t)stream);
 }
 
 static int check_slot(const tlsan_params* q, const char* name) {
@@ -914,8 +811,9 @@ int tlsan_train_step_opt(const tlsan_dims* d, const tlsan_params* p, const tlsan
   hipStream_t hs = (hipStream_t)stream;
   tlsan_dense_layout L;
   tlsan_dense_layout_of(d, &L);
+  const FrontPlan fp = plan_front(d, s, b, hp, plan_sparse(hp, true, 0));
   ApplyArgs A;
-  fill_apply(A, d, s, p, b, hp, w, st, L);
+  fill_apply(A, d, s, p, &fp.ix, hp, w, st, L);
   if (other) {
     A.opt = kind;
     A.s1 = norm_params(opt->slot1, d); A.s2 = norm_params(opt->slot2, d);
@@ -924,7 +822,7 @@ int tlsan_train_step_opt(const tlsan_dims* d, const tlsan_params* p, const tlsan
   }
   TailPlan P;
   if ((rc = plan_tail(d, s, b, hp, w, A, true, &P))) return rc;
-  if ((rc = run_backward(d, s, p, b, hp, out, w, st, L, hs, P.sparse_index, &P.fin.f))) return rc;
+  if ((rc = run_backward(d, s, p, b, hp, out, w, st, L, hs, fp, &P.fin.f))) return rc;
   return launch_tail(s, P, hp, out, w, st, hs);
 }
 
@@ -938,8 +836,9 @@ int tlsan_grads(const tlsan_dims* d, const tlsan_params* p, const tlsan_batch* b
   hipStream_t hs = (hipStream_t)stream;
   tlsan_dense_layout L;
   tlsan_dense_layout_of(d, &L);
+  const FrontPlan fp = plan_front(d, s, b, hp, plan_sparse(hp, false, g->sparse));
   ApplyArgs A;
-  fill_apply(A, d, s, p, b, hp, w, st, L);
+  fill_apply(A, d, s, p, &fp.ix, hp, w, st, L);
   A.go = *g;
   if (A.go.ld_item == 0) A.go.ld_item = d->d_item;
   if (A.go.ld_itemb == 0) A.go.ld_itemb = 1;
@@ -948,7 +847,7 @@ int tlsan_grads(const tlsan_dims* d, const tlsan_params* p, const tlsan_batch* b
   if (A.go.ld_item % 4 || A.go.ld_user % 4) return fail(TLSAN_E_UNSUPPORTED, "gradient row strides must be multiples of 4 floats");
   TailPlan P;
   if ((rc = plan_tail(d, s, b, hp, w, A, false, &P))) return rc;
-  if ((rc = run_backward(d, s, p, b, hp, out, w, st, L, hs, P.sparse_index, &P.fin.f))) return rc;
+  if ((rc = run_backward(d, s, p, b, hp, out, w, st, L, hs, fp, &P.fin.f))) return rc;
   return launch_tail(s, P, hp, out, w, st, hs);
 }
 

@@ -1,6 +1,6 @@
-// tlsan_host.h -- what the host units of the C ABI share (tlsan_api.hip: core, training and state; tlsan_api_eval.hip:
-// evaluation; tlsan_api_shard.hip: rows and the sharded step): error reporting, the shape and workspace carve-up, the
-// launchers of the kernel units, and the few host helpers one unit offers another.  Everything here is internal to the
+// tlsan_host.h -- what the host units of the C ABI share (tlsan_api.hip: core, training and state; tlsan_api_plan.hip: the
+// plans of a training step; tlsan_api_eval.hip: evaluation; tlsan_api_shard.hip: rows and the sharded step): error reporting,
+// the shape and workspace carve-up, the launchers of the kernel units, and the few host helpers one unit offers another.  Everything here is internal to the
 // library (hidden visibility: none of it is an exported symbol).
 #pragma once
 #include <stdlib.h>
@@ -27,6 +27,7 @@ static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Shape {  // derived geometry of the supported (d, heads) combinations
   int D, DH, NSB, NPB, CW;
+  int SG;   // samples per pass of the pair's small-group training kernel, 0: it has none (Pair, tlsan_api.hip)
 };
 int shape_of(const tlsan_dims* d, Shape* s);
 int check_params(const tlsan_params* p);
@@ -54,7 +55,7 @@ struct Ws {  // carve-up of the caller's scratch buffer
   double* rownorm_part;
   double* rownorm;
   size_t bytes;
-  int ngroups, nfin, nbK, nbS, WU;
+  int nfin, nbK, nbS, WU;
 };
 void carve(const tlsan_dims* d, const Shape& s, int B, int Sn, char* base, Ws* w);
 

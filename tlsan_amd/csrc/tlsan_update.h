@@ -13,7 +13,7 @@
 #include <cstddef>
 #include <type_traits>
 // TLSAN_ONCE: the kernels that are not templates belong to the unit that launches them (tlsan_api.hip); a unit that
-// includes this header for its templates or its structures only (tlsan_update_d*.hip, tlsan_api_tail.hip,
+// includes this header for its templates or its structures only (tlsan_update_d*.hip, tlsan_api_plan.hip,
 // tlsan_api_shard.hip) defines it as `static`
 #ifndef TLSAN_ONCE
 #define TLSAN_ONCE
@@ -2561,7 +2561,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? SPEC
   } else {
     const int blk = x.blk;
     if (blk < a.nbC) {
-      // (the wide form takes category segments only -- plan_tail, tlsan_api_tail.hip: the item-walk category workgroups in its
+      // (the wide form takes category segments only -- plan_tail, tlsan_api_plan.hip: the item-walk category workgroups in its
       //  kernel cost the row roles 44 more spilled bytes per lane)
       if (WIDE || a.cseg) apply_cseg_block<AP_UPDATE, true, NC, OWN, DT>(a, x, blk * AP_ROWS_PB, shp);
       else apply_cate_block<AP_UPDATE, true, NC, DT>(a, x, shd, shp, sh_pos, sh_lo, sh_n, sh_wtot);
