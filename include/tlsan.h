@@ -192,6 +192,22 @@ const float* tlsan_state_scale(const void* state);
  * parameters (checkpoint) or when P gets small (long lazy runs: P ~ exp(-sum lr c reg)). */
 int tlsan_state_renorm(const tlsan_dims* dims, const tlsan_params* p, void* state, void* stream);
 
+/* Make the correction that the last TLSAN_L2_LAZY step may still owe (see tlsan_train_step: the two-launch form).  After it
+ * the tables, the dense parameters and the scale are those of the reference's update.  One short launch, which returns
+ * at once on the device when nothing is owed -- and, unless `stream` is being captured, the call then waits for the stream
+ * and reads one word of the state: if a training step gave up its bounded wait for a correction (it left the scale NaN),
+ * the call returns TLSAN_E_LAUNCH and tlsan_last_error says so.  That is the only place where that failure reaches the
+ * host other than as a non-finite loss.  The library's own calls that read or rewrite the parameters through `state`
+ * (tlsan_train_step in another form or with an index it builds itself, tlsan_grads, tlsan_state_renorm,
+ * tlsan_state_reindex) flush by themselves; call it before anything that reads p's arrays without `state`: the forward
+ * and the evaluation calls, a copy to the host, a checkpoint.  Between two steps whose index was built ahead
+ * (tlsan_batch_index) no call is needed.
+ * Captured steps (stream capture into a graph): a replay passes the host by, so what keeps replays right is in the graph.
+ * A two-launch step that builds its own index records this flush in front of itself, always; one whose index was built
+ * ahead corrects at the head of its fused kernel, as outside a graph.  Either way a replay after a clipped replay is
+ * correct; anything ELSE that reads the parameters after a replay needs this call first. */
+int tlsan_state_flush(const tlsan_dims* dims, const tlsan_params* p, void* state, void* stream);
+
 /* Clear the use counters and rebuild the static category->items index for p->item_cate without
  * touching the sums of squares (used by callers whose item table changes every step). */
 int tlsan_state_reindex(const tlsan_dims* dims, const tlsan_params* p, void* state, void* stream);
@@ -235,7 +251,26 @@ int tlsan_forward_att(const tlsan_dims* dims, const tlsan_params* p, const tlsan
  * SPECULATIVE value, which is why bf16 tables that the caches hold keep the form that waits).  Category rows that several
  * workgroups share (a few, large categories) are updated by the second launch, with the true coefficient.  Unclipped steps
  * are bit-equal to the form that waits for the coefficient.  `state` grew by 64 sum-of-squares records for it
- * (tlsan_state_bytes); nothing else in the ABI changed (TLSAN_ABI_VERSION stays 14). */
+ * (tlsan_state_bytes); nothing else in the ABI changed (TLSAN_ABI_VERSION stays 14).
+ * The two-launch form (the shapes of the one-pass form without shared categories whose tables the caches hold -- tables
+ * of more than 512 MB keep the second launch, where it measured faster; TLSAN_TWO_LAUNCH=0 keeps it everywhere).  A CHANGE OF BEHAVIOUR under the same ABI number, for callers that read p's arrays themselves: after a
+ * clipped or non-finite step the arrays hold speculative values until the next step or a tlsan_state_flush.  A caller
+ * that trains and then evaluates, copies or saves calls tlsan_state_flush in between; it costs one launch.
+ * The step is k_fwd_bwd and k_finalize_update, nothing else, when its index was built ahead (hparams.index_prebuilt);
+ * a step that builds its own index is preceded by the flush launch (three launches, as before) when the state's last
+ * step had this form, because the correction walks the index slot that the build overwrites.  The finalize's workgroups store the dense
+ * weights with coefficient 1 as they reduce their gradients and its summary commits the scale; after an unclipped step
+ * -- nearly every step -- everything is committed when the stream drains.  After a clipped or non-finite step the rows and
+ * the dense weights hold the speculative values and the correction is OWED: the next step of this form makes it at the
+ * head of its fused kernel (the first 64 workgroups correct, every workgroup waits for them, bounded: after 2 s the scale
+ * becomes NaN and so does every later loss), any other call that reaches the parameters through `state` makes it first,
+ * and tlsan_state_flush makes it on request.  The step's index slot (hparams.index_slot) must not be rebuilt before that:
+ * a caller that builds indices ahead on another stream (tlsan_batch_index) starts the build of a slot only after
+ * tlsan_step_out.started of the step that FOLLOWS the slot's last step.  The correction also reads the owing step's
+ * gradient rows and reduced dense gradients in `ws`: until the next step or flush, `ws` must be the same block, still
+ * allocated, and not written by anything else (a caller that wants another workspace flushes first).  `state` grew by
+ * the step's arguments for it (tlsan_state_bytes); tlsan_state_flush is an added call and no structure changed, so
+ * TLSAN_ABI_VERSION stays 14 -- see the change of behaviour above. */
 int tlsan_train_step(const tlsan_dims* dims, const tlsan_params* p, const tlsan_batch* b,
                      const tlsan_hparams* hp, const tlsan_step_out* out,
                      void* state, void* ws, size_t ws_bytes, void* stream);

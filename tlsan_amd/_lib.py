@@ -23,7 +23,7 @@ NEG_MAX = 1024  # NEG_MAX (csrc/tlsan_cand.h): largest N of tlsan_sample_negativ
 EXPORTS = [
     "tlsan_abi_version", "tlsan_last_error", "tlsan_dense_layout_of", "tlsan_workspace_bytes",
     "tlsan_state_bytes", "tlsan_state_init", "tlsan_state_reindex", "tlsan_state_recategorize", "tlsan_state_scale",
-    "tlsan_state_renorm", "tlsan_sync_derived", "tlsan_forward", "tlsan_forward_att",
+    "tlsan_state_renorm", "tlsan_state_flush", "tlsan_sync_derived", "tlsan_forward", "tlsan_forward_att",
     "tlsan_train_step", "tlsan_train_step_opt", "tlsan_batch_pack", "tlsan_batch_index", "tlsan_grads", "tlsan_eval_ranks", "tlsan_eval_label_scores", "tlsan_eval_counts_shard",
     "tlsan_eval_ranks_excl", "tlsan_eval_counts_shard_excl",
     "tlsan_topk_workspace_bytes", "tlsan_eval_topk", "tlsan_topk_merge",
@@ -160,6 +160,9 @@ def load():
     lib.tlsan_state_scale.restype = C.c_void_p
     lib.tlsan_state_renorm.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_void_p]
     lib.tlsan_state_renorm.restype = C.c_int
+    if hasattr(lib, "tlsan_state_flush"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none and owes none)
+        lib.tlsan_state_flush.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_void_p]
+        lib.tlsan_state_flush.restype = C.c_int
     lib.tlsan_forward.argtypes = [P(Dims), P(Params), P(Batch), C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]
     lib.tlsan_forward_att.argtypes = [P(Dims), P(Params), P(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

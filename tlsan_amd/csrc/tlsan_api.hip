@@ -6,6 +6,9 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <mutex>
+#include <unordered_set>
+
 #include "tlsan_plan.h"
 
 static thread_local char g_err[512] = "";   // (static: fail() and tlsan_last_error() are its only doors, for every unit)
@@ -212,6 +215,7 @@ struct St {  // persistent state
   // the item side of the index from a partitioned counting sort of the batch's ids (IsortArgs; where Capacity::isort says so)
   int32_t *is_bh[TLSAN_INDEX_SLOTS], *is_ids[TLSAN_INDEX_SLOTS], *is_bstart[TLSAN_INDEX_SLOTS], *is_nd[TLSAN_INDEX_SLOTS];
   int4* is_tmp[TLSAN_INDEX_SLOTS];
+  void* fix_args;   // the ApplyArgs of the last two-launch step (k_finalize_update leaves them; spec_fix_blocks reads them)
   size_t bytes;
   int nbI, nbU, nbC;
   int nrec;   // records per step-parity array of S_delta: a workgroup each of the row blocks and the hot-row workgroups
@@ -264,9 +268,12 @@ static void carve_state(const tlsan_dims* d, const Shape& shp, char* base, St* s
       s->is_tmp[k] = (int4*)take(on ? 16 * (size_t)ISORT_MAX_SLOTS : 0);
     }
   }
+  s->fix_args = take(sizeof(ApplyArgs));
   s->S_total = base ? &s->hdr->St : nullptr;
   s->bytes = o;
 }
+
+static bool two_listed(const void* state, bool remove);   // (the states that may owe a correction: below, at tlsan_state_flush)
 
 extern "C" {
 
@@ -340,6 +347,7 @@ static void fill_apply(ApplyArgs& A, const tlsan_dims* d, const Shape& s, const 
   A.gd = w.gd;
   A.Rc = w.Rc; A.Ri = w.Ri; A.Rb = w.Rb; A.Ru = w.Ru;
   A.part_out = st.S_part; A.delta_out = st.S_delta; A.delta_nrec = st.nrec; A.hdr = st.hdr;
+  A.fix_args = st.fix_args;   // (plan_tail keeps it for the two-launch form only)
   A.urec_item = st.urec_item[k]; A.urec_user = st.urec_user[k];
   if (hp) { A.lr = hp->lr; A.reg = hp->reg; }
   A.nbI = st.nbI; A.nbU = st.nbU; A.nbC = st.nbC; A.nbD = (L.n_dense + 255) / 256;
@@ -422,6 +430,7 @@ int tlsan_state_init(const tlsan_dims* d, const tlsan_params* p, void* state, vo
   if (rc) return rc;
   if ((rc = tlsan_sync_derived(d, p, stream))) return rc;
   hipStream_t hs = (hipStream_t)stream;
+  two_listed(state, true);   // (a fresh state owes nothing)
   if (hipMemsetAsync(state, 0, st.bytes, hs) != hipSuccess) return fail(TLSAN_E_LAUNCH, "memset state");
   static const float one = 1.0f;  // table scale P = 1
   if (hipMemcpyAsync(&st.hdr->P, &one, sizeof(float), hipMemcpyHostToDevice, hs) != hipSuccess) return fail(TLSAN_E_LAUNCH, "init P");
@@ -431,12 +440,69 @@ int tlsan_state_init(const tlsan_dims* d, const tlsan_params* p, void* state, vo
 
 const float* tlsan_state_scale(const void* state) { return (const float*)state; }
 
+// The states whose last training step took the two-launch form: a clipped one may still owe its correction
+// (StateHdr::fix_pending), which the next step of that form makes at the head of its fused kernel.  Every other call that
+// reads or rewrites the tables, the dense parameters or that step's index slot flushes first -- a launch, so only for the
+// states in this set.  (A hint, not the truth: the truth is the header's word, and a flush of a state that owes nothing
+// returns at once.  The set has no limit; a state leaves it when it is flushed or initialised, so a state that is freed
+// without either leaves its eight bytes behind.  Replayed graphs pass the host by: see step_flush.)
+static std::mutex g_two_mu;
+static std::unordered_set<const void*> g_two_states;
+static bool two_listed(const void* state, bool remove) {
+  std::lock_guard<std::mutex> lk(g_two_mu);
+  return remove ? g_two_states.erase(state) != 0 : g_two_states.count(state) != 0;
+}
+static void two_list(const void* state) {
+  std::lock_guard<std::mutex> lk(g_two_mu);
+  g_two_states.insert(state);
+}
+static int flush_state(const tlsan_dims* d, const tlsan_params* p, const St& st, hipStream_t hs) {
+  tlsan_launch_spec_flush(apply_wide(d->d_item, d->d_cate, ru4(d->d_item + d->Ls)), p->table_dtype == TLSAN_TABLE_BF16, st.fix_args, st.hdr, hs);
+  CHECK_LAUNCH("k_spec_flush");
+  return TLSAN_OK;
+}
+static int flush_if_listed(const tlsan_dims* d, const tlsan_params* p, void* state, const St& st, hipStream_t hs) {
+  return two_listed(state, true) ? flush_state(d, p, st, hs) : TLSAN_OK;
+}
+static bool capturing(hipStream_t hs) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(hs, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+// The flush in front of a training step.  A two-launch step whose index was built ahead makes the correction at the head of
+// its fused kernel and needs none.  Every other step needs it if the state owes (a two-launch step that builds its own
+// index too: the correction walks its step's slot, which the build overwrites).  A graph replays what was recorded, not
+// what the set said on the day of the capture, and the state may owe at any replay: a two-launch step that is being
+// captured records the flush always (it returns at once on the device when nothing is owed).
+static int step_flush(const tlsan_dims* d, const tlsan_params* p, void* state, const St& st, hipStream_t hs, bool two, bool prebuilt) {
+  if (two && prebuilt) return TLSAN_OK;
+  if (two && capturing(hs)) { two_listed(state, true); return flush_state(d, p, st, hs); }
+  return flush_if_listed(d, p, state, st, hs);
+}
+
+int tlsan_state_flush(const tlsan_dims* d, const tlsan_params* p, void* state, void* stream) {
+  Shape s; St st;
+  int rc = open_state(d, p, state, &s, &st);
+  if (rc) return rc;
+  hipStream_t hs = (hipStream_t)stream;
+  two_listed(state, true);
+  if ((rc = flush_state(d, p, st, hs)) || capturing(hs)) return rc;
+  // StateHdr::fix_failed: a fused kernel gave up its bounded wait for the correcting workgroups (spec_fix_head) and left the
+  // scale NaN.  The device cannot reach the host's error word; this call, which its callers make before they read, can.
+  uint32_t failed = 0;
+  if (hipMemcpyAsync(&failed, &st.hdr->fix_failed, sizeof(failed), hipMemcpyDeviceToHost, hs) != hipSuccess ||
+      hipStreamSynchronize(hs) != hipSuccess)
+    return fail(TLSAN_E_LAUNCH, "tlsan_state_flush: reading the state's header");
+  if (failed) return fail(TLSAN_E_LAUNCH, "a training step gave up waiting for a clipped step's correction: the table scale is NaN (tlsan_state_init starts over)");
+  return TLSAN_OK;
+}
+
 int tlsan_state_renorm(const tlsan_dims* d, const tlsan_params* p, void* state, void* stream) {
   Shape s; St st;
   int rc = open_state(d, p, state, &s, &st);
   if (rc) return rc;
   const tlsan_params q = norm_params(p, d);
   hipStream_t hs = (hipStream_t)stream;
+  if ((rc = flush_if_listed(d, p, state, st, hs))) return rc;
   const int dt = q.table_dtype;
   // (changes of the sum of squares the last update left as records: part of St before St is rescaled)
   hipLaunchKernelGGL(k_fold_delta, dim3(1), dim3(256), 0, hs, st.S_delta, st.nrec, st.hdr, st.S_total);
@@ -453,9 +519,10 @@ int tlsan_state_renorm(const tlsan_dims* d, const tlsan_params* p, void* state, 
 
 int tlsan_state_reindex(const tlsan_dims* d, const tlsan_params* p, void* state, void* stream) {
   Shape s; St st;
-  const int rc = open_state(d, p, state, &s, &st);
+  int rc = open_state(d, p, state, &s, &st);
   if (rc) return rc;
   hipStream_t hs = (hipStream_t)stream;
+  if ((rc = flush_if_listed(d, p, state, st, hs))) return rc;   // (the correction walks the index this call clears)
   const size_t skip = al(sizeof(StateHdr));  // keep P / St
   if (hipMemsetAsync((char*)state + skip, 0, st.bytes - skip, hs) != hipSuccess) return fail(TLSAN_E_LAUNCH, "memset state");
   return cate_csr(d, p, st, hs);
@@ -611,7 +678,7 @@ static int build_index(const tlsan_dims* d, const tlsan_batch* b, const IndexPla
 // for plan_tail's fields
 static int run_backward(const tlsan_dims* d, const Shape& s, const tlsan_params* p, const tlsan_batch* b,
                         const tlsan_hparams* hp, const tlsan_step_out* out, const Ws& w, const St& st,
-                        const tlsan_dense_layout& L, hipStream_t hs, const FrontPlan& fp, FinArgs* f) {
+                        const tlsan_dense_layout& L, hipStream_t hs, const FrontPlan& fp, FinArgs* f, bool two = false) {
   const int k = hp->index_slot;
   int rc;
   prof_mark(0, hs);
@@ -626,6 +693,7 @@ static int run_backward(const tlsan_dims* d, const Shape& s, const tlsan_params*
   a.uc_by_sample = fp.ix.uc_list ? 1 : 0;
   a.cseg = fp.ix.cseg ? 1 : 0;
   a.perm = fp.read_rank ? st.perm[k] : nullptr;
+  if (two) { a.fix_hdr = st.hdr; a.fix_args = st.fix_args; }   // (the two-launch form: the snapshot, and a clipped predecessor's correction)
   a.gLong = w.gLong; a.gDB = w.gDB; a.gStat = w.gStat; a.partials = w.partials; a.Kp = w.Kp;
   if (hp->dropout != 0.0f) {
     if (!(hp->dropout > 0.0f && hp->dropout < 1.0f)) return fail(TLSAN_E_BADARG, "dropout must be in [0, 1)");
@@ -736,6 +804,7 @@ static int launch_tail(const Shape& s, const TailPlan& P, const tlsan_hparams* h
       break;
     case TAIL_SPEC_SHARED:
     case TAIL_SPEC:
+      if (P.two) break;   // (nothing follows the finalize: its workgroups committed, TailPlan::two)
       tlsan_launch_spec_commit(P.wide, bf16, P.form == TAIL_SPEC_SHARED, P.grid, A, hs);
       CHECK_LAUNCH("k_spec_commit");
       break;
@@ -822,7 +891,10 @@ int tlsan_train_step_opt(const tlsan_dims* d, const tlsan_params* p, const tlsan
   }
   TailPlan P;
   if ((rc = plan_tail(d, s, b, hp, w, A, true, &P))) return rc;
-  if ((rc = run_backward(d, s, p, b, hp, out, w, st, L, hs, fp, &P.fin.f))) return rc;
+  // (a correction the state may owe: at the head of this step's fused kernel, or a flush in front of the step)
+  if ((rc = step_flush(d, p, state, st, hs, P.two, hp->index_prebuilt != 0))) return rc;
+  if ((rc = run_backward(d, s, p, b, hp, out, w, st, L, hs, fp, &P.fin.f, P.two))) return rc;
+  if (P.two) two_list(state);
   return launch_tail(s, P, hp, out, w, st, hs);
 }
 
@@ -847,6 +919,7 @@ int tlsan_grads(const tlsan_dims* d, const tlsan_params* p, const tlsan_batch* b
   if (A.go.ld_item % 4 || A.go.ld_user % 4) return fail(TLSAN_E_UNSUPPORTED, "gradient row strides must be multiples of 4 floats");
   TailPlan P;
   if ((rc = plan_tail(d, s, b, hp, w, A, false, &P))) return rc;
+  if ((rc = flush_if_listed(d, p, state, st, hs))) return rc;
   if ((rc = run_backward(d, s, p, b, hp, out, w, st, L, hs, fp, &P.fin.f))) return rc;
   return launch_tail(s, P, hp, out, w, st, hs);
 }

@@ -287,6 +287,7 @@ int plan_tail(const tlsan_dims* d, const Shape& s, const tlsan_batch* b, const t
   }
   P->form = form;
 
+  if (form != TAIL_SPEC) A.fix_args = nullptr;   // (fill_apply's: the two-launch form's alone)
   if (form == TAIL_SPLIT) {
     // the exact row sums of the apply pass share the finalize's launch (they wait for nothing it produces)
     A.nbC = A.cseg ? (A.C + AP_ROWS_PB - 1) / AP_ROWS_PB : A.C * A.csplit;
@@ -326,6 +327,17 @@ int plan_tail(const tlsan_dims* d, const Shape& s, const tlsan_batch* b, const t
     fl.shared = shared; fl.bf16 = bf16; fl.wide = apply_wide(A) && !shared;
     fl.low = tables_in_hbm(d);   // (the low-occupancy form: see SPEC_WPE, tlsan_update.h)
     f.count_step = 0; f.spec = 1;
+    // The two-launch form: everything k_spec_commit does has a place where its inputs are final at a launch boundary (the
+    // finalize's workgroups, its summary, the head of the next fused kernel), so the launch -- 4.4 us of a 56 us step for
+    // 17.6 k dense stores and two words -- goes.  Not with shared categories, whose rows the commit launch updates.
+    // Not where the tables live in HBM either: there the step is bound by the index stream beside it, and at 10 M / 5 M rows,
+    // d = 128 two launches LOSE 3 us of 78 in every one of five interleaved rounds (profiles/two_launch.md).
+    // TLSAN_TWO_LAUNCH=0: the three-launch form everywhere (A/B, and the reference of the bit-equality test); 2: the
+    // two-launch form for tables in HBM as well (the A/B of that loss).
+    static const int two_launch = [] { const char* e = getenv("TLSAN_TWO_LAUNCH"); return e ? atoi(e) : 1; }();
+    P->two = !shared && two_launch != 0 && (!fl.low || two_launch == 2);
+    if (P->two) { f.spec = 2; f.spec_w = A.p.dense; f.spec_wKT = A.p.dense_KT; }
+    else A.fix_args = nullptr;
     // k_spec_commit: the dense parameters, (shared: the category-row blocks,) then at most SPEC_FIX_BLOCKS correcting workgroups
     const int nrow = A.nbH + (shared ? 0 : A.nbC) + A.nbI + A.nbU;
     P->grid = dim3(A.nbD + (shared ? A.nbC : 0) + (nrow < SPEC_FIX_BLOCKS ? nrow : SPEC_FIX_BLOCKS));

@@ -20,6 +20,79 @@
 // batched after the loops.
 #pragma once
 #include "tlsan_common.h"
+
+// ---- The rare correcting pass of the two-launch lazy-L2 step, at the head of the NEXT step's k_fwd_bwd (spec_fix_head
+// below).  Its row block functions (tlsan_update.h) are written for 256 threads and synchronise them with a workgroup
+// barrier; here they run in the first four wavefronts of a workgroup that may have eight, so in this unit their barrier is
+// one of those four wavefronts alone: an arrival counter in the LDS (word 0 of the kernel's dynamic block, which nothing
+// else owns before the first pass).  A count that only grows needs no generation: the wavefront that arrives as number
+// 4 k + j waits for 4 (k + 1).  All four are resident, so the wait ends.
+#define TLSAN_FIX_WGS 64          // workgroups that correct (fewer when the grid is smaller)
+#define TLSAN_FIX_LDS_BYTES (16 + FIX_LDS_BYTES)   // counter + FixLds (tlsan_update.h)
+__device__ __forceinline__ void fix_team_sync() {
+  extern __shared__ __attribute__((aligned(16))) int fix_lds[];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  if ((threadIdx.x & 63) == 0) {
+    const int old = __hip_atomic_fetch_add(fix_lds, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    const int want = (old / 4 + 1) * 4;
+    while (__hip_atomic_load(fix_lds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < want) __builtin_amdgcn_s_sleep(1);
+  }
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+#define AP_SYNC() fix_team_sync()
+#ifndef TLSAN_ONCE
+#define TLSAN_ONCE static   // (the kernels of tlsan_update.h that are not templates: tlsan_api.hip's)
+#endif
+#include "tlsan_update.h"
+
+// Every workgroup of a training launch calls this when the header says that the previous step was clipped
+// (StateHdr::fix_pending): the first F = min(grid, TLSAN_FIX_WGS) workgroups walk that step's row blocks and dense blocks with
+// stride F (spec_fix_blocks, the arithmetic of k_spec_commit's correcting pass), publish at device scope and count
+// themselves in; every workgroup then waits for the count F, acquires, and returns to gather.  No cooperative
+// launch is needed: workgroups are dealt to the XCDs round-robin and each XCD dispatches its share in order, so on every XCD
+// the correcting workgroups precede that XCD's waiters, F / 8 of them are far below the slots an XCD offers, and a correcting
+// workgroup waits for nothing before it has counted itself in.
+// The wait is bounded (FIX_WAIT_TICKS of the 100 MHz clock): on expiry the table scale becomes NaN -- this step's loss and
+// every later one are non-finite -- and StateHdr::fix_failed is set, which tlsan_state_flush reports.  Cold and out of line: the fused kernel's registers
+// are spoken for.
+#define FIX_WAIT_TICKS 200000000ull   // 2 s
+template <int DT>
+static __device__ __noinline__ void spec_fix_head(StateHdr* hdr, const ApplyArgs* pa) {
+  extern __shared__ __attribute__((aligned(16))) int fix_lds[];
+  const int tid = threadIdx.x;
+  const int F = min((int)gridDim.x, TLSAN_FIX_WGS);
+  if (tid == 0) fix_lds[0] = 0;
+  __syncthreads();
+  if ((int)blockIdx.x < F && tid < 256) {
+    char* base = (char*)fix_lds + 16;
+    constexpr int o_shp = 8 * FIX_SHD_DOUBLES, o_pos = o_shp + 8 * 4, o_lo = o_pos + 4 * AP_CAP, o_n = o_lo + 4 * 256, o_wtot = o_n + 4 * 256;
+    static_assert(o_wtot + 4 * 4 == FIX_LDS_BYTES, "FixLds: the carve and the bytes the launch asks for (TLSAN_FIX_LDS_BYTES)");
+    const FixLds m = {(double*)base, (double*)(base + o_shp), (int*)(base + o_pos), (int*)(base + o_lo), (int*)(base + o_n), (int*)(base + o_wtot)};
+    const ApplyArgs& a = *pa;
+    ApCtx x = spec_fix_ctx(a);
+    if (a.di > 64 || a.dc > 64 || a.WU > 128) spec_fix_blocks<true, DT>(a, x, (int)blockIdx.x, F, true, m);   // (apply_wide, tlsan_plan.h)
+    else spec_fix_blocks<false, DT>(a, x, (int)blockIdx.x, F, true, m);
+    __threadfence();     // (every lane's stores, at device scope, before the team's count)
+    fix_team_sync();
+    if (tid == 0) __hip_atomic_fetch_add(&hdr->fix_arrive, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (tid == 0) {
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    while (__hip_atomic_load(&hdr->fix_arrive, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < F) {
+      __builtin_amdgcn_s_sleep(8);
+      if (__builtin_amdgcn_s_memrealtime() - t0 > FIX_WAIT_TICKS) {
+        hdr->fix_failed = 1;
+        *(uint32_t*)&hdr->P = 0x7fc00000u;        // (a NaN by its bits: the unit is built with -fno-honor-nans)
+        *(uint32_t*)&hdr->P_snap = 0x7fc00000u;
+        break;
+      }
+    }
+  }
+  __syncthreads();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+}
+
 #ifndef TLSAN_STAMPS
 #define TLSAN_STAMPS 0   // 1: the diagnostic build with in-kernel cycle stamps (scripts/stamps.py)
 #endif
@@ -521,7 +594,16 @@ __global__ __launch_bounds__(512) void k_fwd_bwd(FwdArgs a) {
     return base + (((size_t)(ch / DH) * a.b.B + b) * T_ + p) * DH + (ch % DH);
   };
   if constexpr (TRAIN) {
-    // (tlsan_step_out.started: this kernel running means everything queued before the step is complete)
+    // the two-launch lazy-L2 step (FwdArgs.fix_hdr): workgroup 0 leaves the snapshot of P and nstep that the row workgroups
+    // of this step's k_finalize_update read (its summary commits both beside them), and every workgroup looks -- one
+    // compare -- whether the previous step still owes its correction
+    if (a.fix_hdr != nullptr) {
+      StateHdr* hdr = (StateHdr*)a.fix_hdr;
+      if (blockIdx.x == 0 && tid == 0) { hdr->P_snap = hdr->P; hdr->nstep_snap = hdr->nstep; }
+      if (__builtin_amdgcn_readfirstlane((int)hdr->fix_pending) != 0) spec_fix_head<DT>(hdr, (const ApplyArgs*)a.fix_args);
+    }
+    // (tlsan_step_out.started: this kernel running means everything queued before the step is complete -- and, after a
+    //  clipped two-launch step, that its correction no longer needs that step's index slot)
     if (a.started != nullptr && blockIdx.x == 0 && tid == 0)
       __hip_atomic_store(a.started, a.started_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }

@@ -34,7 +34,9 @@ static hipError_t launch_variant_dt(const FwdArgs& a, int grid, hipStream_t st, 
   }
   // (the copy of `long` for the fused dK product only in launches that fuse: at d = 64 it is what decides whether two
   //  workgroups fit a CU's LDS -- 8192 sequences, not fused: 77 us/step with it left out, 95 with it)
-  const size_t smem = fwd_smem_bytes<D, DH, NWV>(TRAIN, LSTREAM, a.fuse_dk != 0, a.b.Sn, a.cseg != 0, DROP);
+  size_t smem = fwd_smem_bytes<D, DH, NWV>(TRAIN, LSTREAM, a.fuse_dk != 0, a.b.Sn, a.cseg != 0, DROP);
+  // (the correcting pass at the kernel's head borrows the block: spec_fix_head.  Every training form is far above this)
+  if (TRAIN && smem < TLSAN_FIX_LDS_BYTES) smem = TLSAN_FIX_LDS_BYTES;
   auto k = k_fwd_bwd<D, DH, TRAIN, LSTREAM, DT, DROP, MM, CSEG, NWV>;
   // (per kernel variant AND device: the attribute is raised once, not on every launch; relaxed atomics -- two threads
   //  racing on a first launch both raise it, which is harmless)

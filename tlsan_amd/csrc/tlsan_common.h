@@ -542,6 +542,10 @@ struct FwdArgs {
   uint32_t drop_sample0;          // index of this batch's first sample in the pattern (a rank's share of a global batch)
   uint32_t* started;              // optional host-visible word: workgroup 0 stores started_val there when the kernel begins
   uint32_t started_val;
+  // the two-launch lazy-L2 step (training, tlsan_attn.h: spec_fix_head): the state's header (StateHdr) and the place where
+  // the previous step's k_finalize_update left its ApplyArgs; NULL in every other launch
+  void* fix_hdr;
+  const void* fix_args;
 };
 
 // Keep / drop pattern of tf.nn.dropout as the scale the element is multiplied with (0 or 1/keep_prob):

@@ -77,6 +77,8 @@ void tlsan_launch_finalize_d128h4(const FinLaunch& L, hipStream_t hs);
 void tlsan_launch_finalize_d256(const FinLaunch& L, hipStream_t hs);
 // k_spec_commit of every pair (compiled beside k_finalize_update: tlsan_update_d128.hip)
 void tlsan_launch_spec_commit(bool wide, bool bf16, bool shared, dim3 grid, const ApplyArgs& A, hipStream_t hs);
+// ... and k_spec_flush: the correction a clipped two-launch step owes, from the arguments it left in the state
+void tlsan_launch_spec_flush(bool wide, bool bf16, const void* args, void* hdr, hipStream_t hs);
 // ---- top-K selection over all items (tlsan_topk.hip)
 hipError_t tlsan_launch_topk(const TopkArgs& a, int D, int nslices, hipStream_t hs);
 hipError_t tlsan_launch_topk_merge(const int32_t* cid, const float* csc, int B, int nl, int K, int32_t* ids, float* scores,

@@ -49,7 +49,7 @@ struct Capacity {
 enum TailForm {
   TAIL_APPLY,        // k_dense_finalize, then k_apply over every row (dense L2, tlsan_grads with full gradients)
   TAIL_SPLIT,        // row sums beside the finalize (k_finalize_presum), then k_update_lazy (sparse tlsan_grads: k_rc64_to_float)
-  TAIL_SPEC,         // the speculative one pass: k_finalize_update, then k_spec_commit
+  TAIL_SPEC,         // the speculative one pass: k_finalize_update, then k_spec_commit -- or nothing (TailPlan::two)
   TAIL_SPEC_SHARED,  // the same, the shared categories summed beside it and updated by the commit (k_*<.., CSPL>)
 };
 struct TailPlan {
@@ -59,10 +59,15 @@ struct TailPlan {
   dim3 grid;           // the second launch's (TAIL_APPLY: launch_apply's own)
   bool wide;           // TAIL_SPLIT / TAIL_SPEC*: the second launch's wide row form
   int nbC16;           // TAIL_SPLIT update: k_update_lazy's blocks of 16 category rows
+  // TAIL_SPEC, the two-launch form: no second launch.  The finalize's workgroups store the dense parameters and its summary
+  // commits P and nstep; a clipped step's correction runs at the head of the next step's fused kernel, or in k_spec_flush
+  // (tlsan_state_flush) when something else comes first.  run_backward hands the fused kernel the state's header for it.
+  bool two;
 };
 
 #pragma GCC visibility push(hidden)
-static inline bool apply_wide(const ApplyArgs& A) { return A.di > 64 || A.dc > 64 || A.WU > 128; }  // more float4 chunks per lane
+static inline bool apply_wide(int di, int dc, int WU) { return di > 64 || dc > 64 || WU > 128; }  // more float4 chunks per lane
+static inline bool apply_wide(const ApplyArgs& A) { return apply_wide(A.di, A.dc, A.WU); }
 // the tail walks the index's used-row records (a lazy-L2 step; tlsan_grads' per-row sums, out_sparse = tlsan_grads_out.sparse):
 // the `sparse` of plan_index / plan_front
 bool plan_sparse(const tlsan_hparams* hp, bool update, int out_sparse);

@@ -38,10 +38,21 @@ struct StateHdr {
   // stay put while the first launch's row workgroups read them
   float P_next;
   uint32_t spec_salt;
-  float pad0[12];
+  // the two-launch form of that update (FinArgs.spec == 2: no commit launch).  The step summary commits P and nstep itself,
+  // so the row workgroups beside it read the SNAPSHOT of both that k_fwd_bwd of the same step left (workgroup 0, at its
+  // start).  fix_pending != 0: the step was clipped (coefficient != 1, non-finite included) and its rows and dense
+  // parameters still hold the speculative values -- corrected at the head of the next k_fwd_bwd (spec_fix_head,
+  // tlsan_attn.h) or by k_spec_flush (tlsan_state_flush), from the step's ApplyArgs kept in the state (St::fix_args)
+  float P_snap;
+  uint32_t nstep_snap;
+  uint32_t fix_pending;
+  uint32_t fix_failed;     // != 0: a k_fwd_bwd gave up waiting for the correcting workgroups (it also left P = NaN: the step's loss and every later one are non-finite)
+  float pad0[8];
   // ---- its own 128-B line: hammered by atomics, must not share a line with anything that is read
   int32_t ticket;          // arrival counter of k_dense_finalize: the last workgroup writes the step summary
-  int32_t pad1[31];
+  int32_t fix_arrive;      // correcting workgroups of k_fwd_bwd that are done (zeroed by the summary that sets fix_pending)
+  int32_t fix_ticket;      // arrival counter of k_spec_flush: its last workgroup clears fix_pending
+  int32_t pad1[29];
 };
 static_assert(sizeof(StateHdr) == 256, "StateHdr layout");
 static_assert(offsetof(StateHdr, St) == 32, "StateHdr layout: St is read at byte 32 (tests/test_gpu_parity.py)");
@@ -986,6 +997,10 @@ struct FinArgs {
   int32_t count_step;      // an update follows (train step, not tlsan_grads): advance hdr->nstep
   int32_t spec;            // speculative one-pass lazy update: neither P nor nstep are touched here (commit = count_step = 0);
                            // the scale after the step and the step's salt go to hdr->P_next / hdr->spec_salt (k_spec_commit)
+                           // 2: the two-launch form -- no commit launch follows.  The finalize workgroups store the dense
+                           // parameters with coefficient 1 as they reduce their gradients (spec_w / spec_wKT), and the
+                           // summary commits P and nstep and says whether a correction is due (hdr->fix_pending)
+  float* spec_w; float* spec_wKT;   // spec == 2: tlsan_params.dense / dense_KT
   float* out_loss; float* out_gnorm; float* out_sq;
 };
 
@@ -1042,8 +1057,19 @@ __device__ __forceinline__ void step_summary(const FinArgs& a, int nsqd, double*
     if (a.count_step) a.hdr->nstep += 1;
     if (a.commit) a.hdr->P = P * (1.0f - a.lr * coef * a.reg);
     if (a.spec) {
-      a.hdr->P_next = P * (1.0f - a.lr * coef * a.reg);
-      a.hdr->spec_salt = a.hdr->nstep + 1;
+      const float Pn = P * (1.0f - a.lr * coef * a.reg);
+      const uint32_t ns = a.hdr->nstep + 1;
+      a.hdr->P_next = Pn;
+      a.hdr->spec_salt = ns;
+      if (a.spec == 2) {
+        // (the row workgroups beside this one read hdr->P_snap / nstep_snap; the next launch finds everything committed.
+        //  A clipped step -- NaN included: NaN != 1 -- leaves its correction to the head of the next k_fwd_bwd or to k_spec_flush)
+        a.hdr->P = Pn;
+        a.hdr->nstep = ns;
+        a.hdr->fix_arrive = 0;
+        a.hdr->fix_ticket = 0;
+        a.hdr->fix_pending = coef == 1.0f ? 0u : 1u;
+      }
     }
     if (a.norm_mode == TLSAN_NORM_TF18 && a.out_gnorm) *a.out_gnorm = norm;
     if (a.out_loss) *a.out_loss = sc0 * a.inv_B + a.reg * (float)(0.5 * St);
@@ -1131,6 +1157,8 @@ __device__ __forceinline__ void dense_finalize_block(const FinArgs& a, int nbK, 
   } else if (blk < nbK) {
     const int idx = blk * 256 + tid;
     if (idx < D * D) {
+      // (spec == 2: the parameter travels beside the partials, no dependent trip)
+      const float w_spec = a.spec == 2 ? a.spec_w[L.K + idx] : 0.0f;
       // the partials in chunks of KCH, all loads of a chunk in flight at once (clamped addresses, masked sum), fixed order
       // (64 since round 5: 256 partials in four dependent rounds instead of eight, about 2 us each; the sum's order does
       //  not depend on the chunk.  Measured and not kept, profiles/r05_cate_lists.md: 64 entries per workgroup with a
@@ -1158,6 +1186,11 @@ __device__ __forceinline__ void dense_finalize_block(const FinArgs& a, int nbK, 
       else chunks(std::integral_constant<int, 32>());
       g = (g0 + g1) + (g2 + g3);
       a.gd[L.K + idx] = g;
+      if (a.spec == 2) {   // (k_spec_commit's expression with coefficient 1: lr * 1 is lr; dense_store)
+        const float wn = w_spec - a.lr * g;
+        a.spec_w[L.K + idx] = wn;
+        a.spec_wKT[(size_t)(idx % D) * D + idx / D] = wn;
+      }
       owner = true;
     }
   } else if constexpr (D > 128) {
@@ -1197,6 +1230,7 @@ __device__ __forceinline__ void dense_finalize_block(const FinArgs& a, int nbK, 
       e1 = two ? e[1] : e[0];
     }
     const int q = (a.nrec + 3) / 4, r_lo = wave * q, r_hi = min(a.nrec, r_lo + q);   // this wavefront's records
+    const float w_spec = (a.spec == 2 && wave == 0 && valid) ? a.spec_w[n] : 0.0f;
     float t = 0.0f;
     if (valid) {
       // (chunks of FIN_SMALL_KCH loads in flight; of 4 when a wavefront has no more records than that -- small batches: clamped loads
@@ -1225,6 +1259,7 @@ __device__ __forceinline__ void dense_finalize_block(const FinArgs& a, int nbK, 
     if (wave == 0 && valid) {
       g = (shf[lane] + shf[64 + lane]) + (shf[128 + lane] + shf[192 + lane]);
       a.gd[n] = g;
+      if (a.spec == 2) a.spec_w[n] = w_spec - a.lr * g;   // (never one of K's: no transposed copy)
       owner = true;
     }
     __syncthreads();   // (shd is reused below)
@@ -1257,6 +1292,7 @@ __device__ __forceinline__ void dense_finalize_block(const FinArgs& a, int nbK, 
       float t = 0.0f;
       const bool two = HPC > 1 && e[1] >= 0;
       const int e1 = two ? e[1] : e[0];
+      const float w_spec = (a.spec == 2 && rl == 0) ? a.spec_w[n] : 0.0f;
       for (int r0 = rl; r0 < a.nrec; r0 += 16 * 8) {  // 8 records in flight per lane, fixed order
         float v0[8], v1[8];
 #pragma unroll
@@ -1274,6 +1310,7 @@ __device__ __forceinline__ void dense_finalize_block(const FinArgs& a, int nbK, 
       g = t;
       if (rl == 0) {
         a.gd[n] = g;
+        if (a.spec == 2) a.spec_w[n] = w_spec - a.lr * g;
         owner = true;
       }
     }
@@ -1397,6 +1434,9 @@ struct ApplyArgs {
   // with nbI_l < nbI a workgroup takes the blocks nbI_l apart until the used rows end
   int32_t nbI_l;
   int32_t ufirst;          // k_finalize_update: the user-row workgroups lead the item-row workgroups
+  // k_finalize_update, two-launch form (FinArgs.spec == 2): where the launch leaves a copy of these arguments for the
+  // correcting pass of a clipped step (spec_fix_blocks), which runs in a later launch; NULL: the three-launch form
+  void* fix_args;
   // optimizers other than SGD (dense UPDATE only): accumulator tables shaped like p, see tlsan_optimizer
   tlsan_params s1, s2;
   int32_t opt;
@@ -1449,14 +1489,21 @@ __device__ __forceinline__ void combine_groups(double (&acc)[NCH][4]) {
     }
 }
 
+// The barrier of the 256 threads that run a row block function.  A unit whose workgroups are larger (the fused kernel,
+// whose first four wavefronts run the correcting pass of a clipped two-launch step: spec_fix_head, tlsan_attn.h) defines
+// its own before it includes this header.
+#ifndef AP_SYNC
+#define AP_SYNC() __syncthreads()
+#endif
+
 // record i of step `tag` (in that step's parity array of a.delta_out).  accum: add to the record this step's first launch
 // left (the correcting pass of a speculative update, k_spec_commit)
 __device__ __forceinline__ void block_delta_store(double part, double* shd, const ApplyArgs& a, int i, unsigned long long tag, bool accum = false) {
-  __syncthreads();
+  AP_SYNC();
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) part += __shfl_xor(part, o);
   if ((threadIdx.x & 63) == 0) shd[threadIdx.x >> 6] = part;
-  __syncthreads();
+  AP_SYNC();
   if (threadIdx.x == 0) {
     DeltaRec* dst = delta_recs(a.delta_out, a.delta_nrec, tag) + i;
     const double v = shd[0] + shd[1] + shd[2] + shd[3];
@@ -1665,7 +1712,7 @@ __device__ __forceinline__ void apply_cate_block(const ApplyArgs& a, const ApCtx
         if (lane >= o) inc += t;
       }
       if (lane == 63) sh_wtot[wave] = inc;
-      __syncthreads();
+      AP_SYNC();
       int pre = inc - n;
 #pragma unroll
       for (int w_ = 0; w_ < 4; ++w_) pre += (w_ < wave) ? sh_wtot[w_] : 0;
@@ -1686,14 +1733,14 @@ __device__ __forceinline__ void apply_cate_block(const ApplyArgs& a, const ApCtx
           for (int j = 0; j < n; ++j) sh_pos[pre + j] = lo + j;
         }
         for (int j = tid; j < extra; j += 256) sh_pos[T + j] = ~(a.uc_list ? a.uc_list[ou + j] : ou + j);
-        __syncthreads();
+        AP_SYNC();
         AP_STAMP(1);
         list_accum<NCH>(a, sh_pos, T + extra, gid, l16, W4, acc);
         AP_STAMP(2);
       } else {  // very hot category: segment after segment, the 16 groups striding over each
         sh_lo[tid] = lo;
         sh_n[tid] = n;
-        __syncthreads();
+        AP_SYNC();
         const int cnt = max(0, min(PS, ni - p0));
         int run = 0;   // (by_pos) concatenated position of the segment's first use
         for (int t = 0; t < cnt; ++t) {
@@ -1723,7 +1770,7 @@ __device__ __forceinline__ void apply_cate_block(const ApplyArgs& a, const ApCtx
           }
         }
       }
-      __syncthreads();  // sh_pos / sh_wtot are rewritten by the next pass
+      AP_SYNC();  // sh_pos / sh_wtot are rewritten by the next pass
     }
     combine_groups(acc);
     if (grp == 0) {
@@ -1732,7 +1779,7 @@ __device__ __forceinline__ void apply_cate_block(const ApplyArgs& a, const ApCtx
 #pragma unroll
         for (int i = 0; i < 4; ++i) shd[((wave * 16 + l16) * NCH + ch) * 4 + i] = acc[ch][i];
     }
-    __syncthreads();
+    AP_SYNC();
     if (wave == 0 && grp == 0) {
 #pragma unroll
       for (int ch = 0; ch < NCH; ++ch)
@@ -2252,7 +2299,7 @@ __device__ __forceinline__ void presum_hot_block(const ApplyArgs& a, int h, doub
       for (int i = 0; i < 4; ++i) shd[((wave * 16 + l16) * NCH + ch) * 4 + i] = acc[ch][i];
   }
   if (lane == 0) shp[wave] = tb;
-  __syncthreads();
+  AP_SYNC();
   if constexpr (UPD) {
     const ApCtx& x = *xp;
     double part = 0.0;
@@ -2498,8 +2545,20 @@ __device__ __forceinline__ double update_cate_rows(const ApplyArgs& a, int c, in
 // the number of category-row blocks of the COMMIT launch (16 rows each: they own the records [0, nbC) of S_delta); this
 // launch carries C * csplit category workgroups.  User rows of up to 256 floats (d = 128 with 90-entry windows) in two
 // passes of the narrow form, as the row-sum launch takes them.
+// The launch's ApplyArgs, dword by dword from the kernel-argument segment (KA: the kernel's parameters as a structure,
+// which the segment lays out alike) to *dst: a correcting pass in a later launch reads them from there.  256 threads.
+struct FinUpdateKernarg { FinArgs f; int nbK, nbS; ApplyArgs a; };
+template <class KA>
+__device__ __forceinline__ void keep_apply_args(void* dst) {
+  typedef const uint32_t __attribute__((address_space(4))) * kword;
+  const kword src = (kword)((const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(KA, a));
+  for (int k = threadIdx.x; k < (int)(sizeof(ApplyArgs) / 4); k += 256) ((uint32_t*)dst)[k] = src[k];
+}
+
 template <int D, int DH, bool WIDE, int DT, bool LOWOCC = false, bool CSPL = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? SPEC_WPE : (LOWOCC ? 3 : (DT == TLSAN_TABLE_F32 ? SPEC_WPE_NARROW : SPEC_WPE_NARROW_BF16))))) void k_finalize_update(FinArgs f, int nbK, int nbS, ApplyArgs a) {
+// (LOWOCC: three and no more -- the attribute's second number; 0 leaves the most open.  Left open, a build whose allocation
+//  happens to fit 128 registers runs four)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? SPEC_WPE : (LOWOCC ? 3 : (DT == TLSAN_TABLE_F32 ? SPEC_WPE_NARROW : SPEC_WPE_NARROW_BF16)), (!WIDE && LOWOCC) ? 3 : 0))) void k_finalize_update(FinArgs f, int nbK, int nbS, ApplyArgs a) {
   static_assert(!(WIDE && CSPL), "shared categories: narrow form only");
   constexpr int NC = WIDE ? 2 : 1, NI = WIDE ? 2 : 1, NU = WIDE ? 4 : 2;
   constexpr int OWN = WIDE ? SPEC_OWN : AP_OWN;
@@ -2520,8 +2579,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? SPEC
   }
   // P: stable (this launch's summary does not commit); step: coefficient 1; salt: what the step's salt and record tag
   // will be (hdr->spec_salt)
-  ApCtx x = ap_ctx(a, nfin, a.hdr->P, a.lr, a.hdr->nstep + 1, 1.0f);
+  // (two-launch form: this launch's summary DOES commit both -- k_fwd_bwd left their values at the step's start in the header)
+  const bool two = a.fix_args != nullptr;
+  ApCtx x = ap_ctx(a, nfin, *(two ? &a.hdr->P_snap : &a.hdr->P), a.lr, *(two ? &a.hdr->nstep_snap : &a.hdr->nstep) + 1, 1.0f);
   if (x.blk == 0 && x.tid == 0) a.hdr->spart_n[x.salt & 1] = a.nbC + a.nbI + a.nbU + a.nbH;
+  if (two && x.blk == 0) keep_apply_args<FinUpdateKernarg>(a.fix_args);
   if (x.blk < a.nbH) {          // hot item rows lead the row workgroups
     presum_hot_block<NI, true, DT>(a, x.blk, shd, shp, &x);
     return;
@@ -2590,11 +2652,69 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? SPEC
   if (stp && x.tid == 0) { stp[6] = __builtin_amdgcn_s_memtime(); stp[5] = __builtin_amdgcn_s_memrealtime(); }
 }
 
+// ---- the correcting pass of a clipped speculative step, shared by k_spec_commit (three launches), the head of the next
+// k_fwd_bwd (spec_fix_head, tlsan_attn.h) and k_spec_flush (two launches)
+struct FixLds { double* shd; double* shp; int* sh_pos; int* sh_lo; int* sh_n; int* sh_wtot; };   // the row block functions' scratch
+// ... and its size, for a caller that carves it from a block of its own (spec_fix_head, tlsan_attn.h): shd as the wide form
+// wants it (two float4 chunks per lane), then shp[4], sh_pos[AP_CAP], sh_lo[256], sh_n[256], sh_wtot[4]
+constexpr int FIX_SHD_DOUBLES = 4 * 16 * 2 * 4;
+constexpr int FIX_LDS_BYTES = 8 * FIX_SHD_DOUBLES + 8 * 4 + 4 * AP_CAP + 4 * 256 + 4 * 256 + 4 * 4;
+
+// rows: w_spec + (scale_spec - scale_true) * sum, i.e. w_old - scale_true * sum up to one rounding; the scalars are the
+// clipped step's, as its summary left them (P_prev, spec_salt, coef)
+__device__ __forceinline__ ApCtx spec_fix_ctx(const ApplyArgs& a) {
+  const int tid = threadIdx.x;
+  const float st_true = a.lr * a.hdr->coef;
+  ApCtx x;
+  x.tid = tid; x.wave = tid >> 6; x.lane = tid & 63; x.grp = x.lane >> 4; x.l16 = x.lane & 15;
+  x.gid = x.wave * 4 + x.grp;
+  x.blk = 0;
+  x.P = a.hdr->P_prev;
+  x.invP = 1.0f / x.P;
+  x.step = st_true - a.lr;                                                   // item_b: w_spec - (st_true - lr) g = w_old - st_true g
+  x.lazy_scale = st_true / (x.P * (1.0f - st_true * a.reg)) - a.lr / (x.P * (1.0f - a.lr * a.reg));
+  x.salt = a.hdr->spec_salt;
+  x.coef = a.hdr->coef;
+  x.accum = true;
+  return x;
+}
+
+// 256 threads take the row blocks v0, v0 + stride, ... of [hot rows | categories | item rows | user rows] (not for shared
+// categories) and, with `dense`, the blocks of 256 dense parameters the same way (the two-launch form stored them with
+// coefficient 1 as well: dense_finalize_block)
+template <bool WIDE, int DT>
+__device__ __forceinline__ void spec_fix_blocks(const ApplyArgs& a, ApCtx& x, int v0, int stride, bool dense, const FixLds& m) {
+  constexpr int NC = WIDE ? 2 : 1, NI = WIDE ? 2 : 1, NU = WIDE ? 4 : 2;
+  constexpr int OWN = WIDE ? SPEC_OWN : AP_OWN;
+  for (int v = v0; v < a.nbH + a.nbC + a.nbI + a.nbU; v += stride) {
+    if (v < a.nbH) {
+      presum_hot_block<NI, true, DT>(a, v, m.shd, m.shp, &x);
+    } else {
+      const int blk = v - a.nbH;
+      x.blk = blk;
+      if (blk < a.nbC) {
+        if (WIDE || a.cseg) apply_cseg_block<AP_UPDATE, true, NC, OWN, DT>(a, x, blk * AP_ROWS_PB, m.shp);
+        else apply_cate_block<AP_UPDATE, true, NC, DT>(a, x, m.shd, m.shp, m.sh_pos, m.sh_lo, m.sh_n, m.sh_wtot);
+      }
+      else if (blk < a.nbC + a.nbI) apply_rows_block<AP_UPDATE, true, true, NI, OWN, DT>(a, x, (blk - a.nbC) * AP_ROWS_PB, m.shp);
+      else apply_rows_block<AP_UPDATE, true, false, NU, (WIDE ? SPEC_OWN : AP_OWN / 2), DT>(a, x, (blk - a.nbC - a.nbI) * AP_ROWS_PB, m.shp);
+    }
+    AP_SYNC();   // (the shared scratch is reused by the next block of rows)
+  }
+  if (dense) {
+    for (int v = v0; v < a.nbD; v += stride) {
+      const int nd = v * 256 + x.tid;
+      if (nd < a.lay.n_dense) dense_store(a, nd, a.p.dense[nd] - x.step * a.gd[nd]);
+    }
+  }
+}
+
 // grid: nbD blocks of 256 dense parameters, (CSPL: a.nbC blocks of 16 category rows, updated here from the shared categories'
 // exact sums with the step's true coefficient,) then at most SPEC_FIX_BLOCKS correcting workgroups (which return at once
 // when the step was not clipped)
+// (the narrow fp32 form at four waves per SIMD, as it has always run: two registers more and it would run at three)
 template <bool WIDE, int DT, bool CSPL = false>
-__global__ __launch_bounds__(256) void k_spec_commit(ApplyArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((!WIDE && DT == TLSAN_TABLE_F32) ? 4 : 2))) void k_spec_commit(ApplyArgs a) {
   constexpr int NC = WIDE ? 2 : 1, NI = WIDE ? 2 : 1, NU = WIDE ? 4 : 2;
   constexpr int OWN = WIDE ? SPEC_OWN : AP_OWN;
   __shared__ double shd[4 * 16 * NC * 4];
@@ -2627,18 +2747,10 @@ __global__ __launch_bounds__(256) void k_spec_commit(ApplyArgs a) {
     }
   }
   if (coef == 1.0f) return;   // (block-uniform) the speculation held.  (A NaN coefficient takes the correcting pass and poisons the rows.)
-  ApCtx x;
-  x.tid = tid; x.wave = tid >> 6; x.lane = tid & 63; x.grp = x.lane >> 4; x.l16 = x.lane & 15;
-  x.gid = x.wave * 4 + x.grp;
-  x.P = a.hdr->P_prev;
-  x.invP = 1.0f / x.P;
-  x.step = st_true - a.lr;                                                   // item_b: w_spec - (st_true - lr) g = w_old - st_true g
-  x.lazy_scale = st_true / (x.P * (1.0f - st_true * a.reg)) - a.lr / (x.P * (1.0f - a.lr * a.reg));
-  x.salt = a.hdr->spec_salt;
-  x.coef = coef;
-  x.accum = true;
   // (the launch carries at most SPEC_FIX_BLOCKS correcting workgroups, each walking row blocks with the grid's stride: an
   //  unclipped step -- nearly every step -- pays for a few hundred workgroups that return at once, not for one per 16 rows)
+  [[maybe_unused]] const FixLds m = {shd, shp, sh_pos, sh_lo, sh_n, sh_wtot};
+  ApCtx x = spec_fix_ctx(a);
   if constexpr (CSPL) {
     for (int v = (int)blockIdx.x - fix0; v < a.nbH + a.nbI + a.nbU; v += (int)gridDim.x - fix0) {
       if (v < a.nbH) {
@@ -2658,22 +2770,41 @@ __global__ __launch_bounds__(256) void k_spec_commit(ApplyArgs a) {
       }
       __syncthreads();
     }
-    return;
+  } else {
+    spec_fix_blocks<WIDE, DT>(a, x, (int)blockIdx.x - a.nbD, (int)gridDim.x - a.nbD, false, m);
   }
-  for (int v = (int)blockIdx.x - a.nbD; v < a.nbH + a.nbC + a.nbI + a.nbU; v += (int)gridDim.x - a.nbD) {
-    if (v < a.nbH) {
-      presum_hot_block<NI, true, DT>(a, v, shd, shp, &x);
-    } else {
-      const int blk = v - a.nbH;
-      x.blk = blk;
-      if (blk < a.nbC) {
-        if (WIDE || a.cseg) apply_cseg_block<AP_UPDATE, true, NC, OWN, DT>(a, x, blk * AP_ROWS_PB, shp);
-        else apply_cate_block<AP_UPDATE, true, NC, DT>(a, x, shd, shp, sh_pos, sh_lo, sh_n, sh_wtot);
-      }
-      else if (blk < a.nbC + a.nbI) apply_rows_block<AP_UPDATE, true, true, NI, OWN, DT>(a, x, (blk - a.nbC) * AP_ROWS_PB, shp);
-      else apply_rows_block<AP_UPDATE, true, false, NU, (WIDE ? SPEC_OWN : AP_OWN / 2), DT>(a, x, (blk - a.nbC - a.nbI) * AP_ROWS_PB, shp);
-    }
-    __syncthreads();   // (the shared scratch is reused by the next block of rows)
+}
+
+// (keep_apply_args reads the launch's ApplyArgs at offsetof(FinUpdateKernarg, a): the structure has to list what the kernel takes)
+static_assert(std::is_same<decltype(&k_finalize_update<128, 16, false, TLSAN_TABLE_F32>), void (*)(FinArgs, int, int, ApplyArgs)>::value &&
+              std::is_same<decltype(FinUpdateKernarg::f), FinArgs>::value && std::is_same<decltype(FinUpdateKernarg::a), ApplyArgs>::value &&
+              offsetof(FinUpdateKernarg, nbK) == sizeof(FinArgs) && offsetof(FinUpdateKernarg, nbS) == sizeof(FinArgs) + sizeof(int) &&
+              offsetof(FinUpdateKernarg, a) == (sizeof(FinArgs) + 2 * sizeof(int) + alignof(ApplyArgs) - 1) / alignof(ApplyArgs) * alignof(ApplyArgs) &&
+              sizeof(ApplyArgs) % 4 == 0,
+              "FinUpdateKernarg mirrors k_finalize_update's parameters: edit both");
+
+// The rare second half of the two-launch form outside the fused kernel (tlsan_state_flush): the correcting pass of a
+// clipped step whose successor has not run -- before anything else reads the tables or the dense parameters.  The step's
+// arguments come from the state (ApplyArgs.fix_args); the launch returns at once when nothing is pending, and its last
+// workgroup, by ticket, says so.
+template <bool WIDE, int DT>
+__global__ __launch_bounds__(256) void k_spec_flush(const ApplyArgs* pa, StateHdr* hdr) {
+  constexpr int NC = WIDE ? 2 : 1;
+  static_assert(4 * 16 * NC * 4 <= FIX_SHD_DOUBLES, "FixLds: shd");
+  __shared__ double shd[4 * 16 * NC * 4];
+  __shared__ double shp[4];
+  __shared__ int sh_pos[AP_CAP];
+  __shared__ int sh_lo[256], sh_n[256];
+  __shared__ int sh_wtot[4];
+  if (hdr->fix_pending == 0) return;   // (grid-uniform: only the last workgroup to finish clears it)
+  const FixLds m = {shd, shp, sh_pos, sh_lo, sh_n, sh_wtot};
+  const ApplyArgs& a = *pa;
+  ApCtx x = spec_fix_ctx(a);
+  spec_fix_blocks<WIDE, DT>(a, x, (int)blockIdx.x, (int)gridDim.x, true, m);
+  __syncthreads();
+  if (threadIdx.x == 0 && atomicAdd(&hdr->fix_ticket, 1) == (int)gridDim.x - 1) {
+    hdr->fix_ticket = 0;
+    hdr->fix_pending = 0;
   }
 }
 

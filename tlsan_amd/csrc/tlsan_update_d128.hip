@@ -15,3 +15,13 @@ void tlsan_launch_spec_commit(bool wide, bool bf16, bool shared, dim3 grid, cons
   else if (wide) hipLaunchKernelGGL((k_spec_commit<true, TLSAN_TABLE_F32>), grid, blk, 0, hs, A);
   else hipLaunchKernelGGL((k_spec_commit<false, TLSAN_TABLE_F32>), grid, blk, 0, hs, A);
 }
+
+void tlsan_launch_spec_flush(bool wide, bool bf16, const void* args, void* hdr, hipStream_t hs) {
+  const dim3 grid(256), blk(256);   // (each workgroup walks the row blocks with the grid's stride: spec_fix_blocks)
+  const ApplyArgs* pa = (const ApplyArgs*)args;
+  StateHdr* h = (StateHdr*)hdr;
+  if (bf16 && wide) hipLaunchKernelGGL((k_spec_flush<true, TLSAN_TABLE_BF16>), grid, blk, 0, hs, pa, h);
+  else if (bf16) hipLaunchKernelGGL((k_spec_flush<false, TLSAN_TABLE_BF16>), grid, blk, 0, hs, pa, h);
+  else if (wide) hipLaunchKernelGGL((k_spec_flush<true, TLSAN_TABLE_F32>), grid, blk, 0, hs, pa, h);
+  else hipLaunchKernelGGL((k_spec_flush<false, TLSAN_TABLE_F32>), grid, blk, 0, hs, pa, h);
+}

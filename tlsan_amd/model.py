@@ -509,7 +509,28 @@ class DeviceBatch:
                        p(self.u_cate))
 
 
+def _flushing(name):
+    """A Model tensor (tables, dense parameters, state) as an attribute whose READ first makes the correction a clipped
+    two-launch step may owe (Model._flush): whoever takes the tensor sees the reference's update.  The training step
+    itself goes by the raw tensors and pointers."""
+    raw = "_" + name
+
+    def get(self):
+        if raw not in self.__dict__:
+            raise AttributeError(name)      # (hasattr before the tensor exists, as any attribute answers)
+        self._flush()
+        return self.__dict__[raw]
+
+    def put(self, value):
+        self.__dict__[raw] = value
+    return property(get, put)
+
+
 class Model(object):
+    _fix_owed = False     # a training step ran since the last flush (_flush)
+    item_emb, item_b, user_emb, usert_emb, cate_emb = (_flushing(k) for k in ("item_emb", "item_b", "user_emb", "usert_emb", "cate_emb"))
+    dense, state = _flushing("dense"), _flushing("state")
+
     def __init__(self, config, item_cate_list, device="cuda:0", seed=1234, norm_mode="tf18", l2_mode="dense",
                  table_dtype="f32", init="numpy", matrix_dtype="f32"):
         """table_dtype: "f32" (the reference's precision) or "bf16" -- item_emb / user_emb / cate_emb stored
@@ -705,15 +726,28 @@ class Model(object):
         kind, b1, b2, eps = OPTIMIZERS[self.optimizer]
         self._copt = L.Optimizer(kind, 0, b1, b2, eps, C.addressof(self._cslots[0]), C.addressof(self._cslots[1]))
 
+    def _flush(self):
+        """A clipped lazy-L2 SGD step in the two-launch form leaves its correction to the next step's fused kernel
+        (include/tlsan.h, tlsan_train_step): make it now -- one short launch on the current stream, nothing when no step
+        ran since the last flush.  Everything that reads the tables, the dense parameters or the state other than the
+        next training step comes through here: the accessors below, the forward, grads, the checkpoint, a graph capture."""
+        if self._fix_owed:
+            self._fix_owed = False
+            L.check(self.lib.tlsan_state_flush(C.byref(self.dims), C.byref(self.cparams), self._state.data_ptr(),
+                                               self._stream()), "tlsan_state_flush")
+
     def _train_call(self, db, hp, out, ws):
+        # (only the lazy-L2 SGD step has the two-launch form; a library without the call -- an older build loaded for an
+        #  A/B -- has no such form either)
+        self._fix_owed = self.l2_mode == L.L2_LAZY and self._copt is None and hasattr(self.lib, "tlsan_state_flush")
         if self._copt is None:
             L.check(self.lib.tlsan_train_step(C.byref(self.dims), C.byref(self.cparams), C.byref(db.c), C.byref(hp),
-                                              C.byref(out), self.state.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              C.byref(out), self._state.data_ptr(), ws.data_ptr(), ws.numel(),
                                               self._stream()), "tlsan_train_step")
         else:
             self._copt.step = self._step + 1      # Adam's beta powers: updates applied so far + 1
             L.check(self.lib.tlsan_train_step_opt(C.byref(self.dims), C.byref(self.cparams), C.byref(db.c), C.byref(hp),
-                                                  C.byref(self._copt), C.byref(out), self.state.data_ptr(),
+                                                  C.byref(self._copt), C.byref(out), self._state.data_ptr(),
                                                   ws.data_ptr(), ws.numel(), self._stream()), "tlsan_train_step_opt")
 
     def get_slots(self):
@@ -754,6 +788,7 @@ class Model(object):
     def fold_scale(self):
         """lazy L2: fold the table scale P into the stored tables (P = 1 afterwards).  The lazy optimizers keep P = 1:
         nothing to fold."""
+        self._flush()
         if self.l2_mode == L.L2_LAZY and not self.lazy_opt:
             L.check(self.lib.tlsan_state_renorm(C.byref(self.dims), C.byref(self.cparams), self.state.data_ptr(),
                                                 self._stream()), "tlsan_state_renorm")
@@ -771,6 +806,7 @@ class Model(object):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _sync_state(self):
+        self._fix_owed = False     # (the state is cleared: whatever a step owed goes with it)
         # tlsan_state_init clears the whole state, both destination-index slots included: an index that was
         # prefetched for an announced successor (train_async(next_batch=)) is gone with it -- wait for the side
         # stream to be done with the slot, then forget the announcement (the next step builds its index inline)
@@ -790,6 +826,7 @@ class Model(object):
             n = self.lib.tlsan_workspace_bytes(C.byref(self.dims), kB, kS)
             if n == 0:
                 raise L.TlsanError("tlsan_workspace_bytes: %s" % self.lib.tlsan_last_error().decode())
+            self._flush()     # (an owed correction reads the last step's gradient rows in the old block)
             torch.cuda.synchronize(self.device)
             self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
             self._ws_key = (kB, kS)
@@ -914,7 +951,7 @@ class Model(object):
                     self.started_at.append(tq)
             for ndb, kk in ahead:
                 flag = L.INDEX_FOR_LAZY_SGD if (self.l2_mode == L.L2_LAZY and (self.optimizer == "sgd" or self.lazy_opt)) else 0
-                L.check(self.lib.tlsan_batch_index(C.byref(self.dims), C.byref(ndb.c), self.cparams.item_cate, self.state.data_ptr(), kk | flag,
+                L.check(self.lib.tlsan_batch_index(C.byref(self.dims), C.byref(ndb.c), self.cparams.item_cate, self._state.data_ptr(), kk | flag,
                                                    C.c_void_p(self._side.cuda_stream)), "tlsan_batch_index")
                 self._idx_event[kk].record(self._side)
                 self._idx_ready[kk] = ndb
@@ -925,8 +962,13 @@ class Model(object):
     def capture_step(self, batch, lr):
         """Capture one training step on `batch` into a hipGraph (fork/join of the index-build
         side stream included) and return the graph: `g.replay()` re-runs the step on the same
-        device buffers.  lr is baked in (re-capture when it changes, train.py:232-233)."""
+        device buffers.  lr is baked in (re-capture when it changes, train.py:232-233).
+        A lazy-L2 SGD step in the two-launch form may leave a correction owed (_flush).  The captured step builds its own
+        index, so the library records its flush launch in the graph in front of the step, whatever the state owed on the
+        day of the capture (include/tlsan.h, tlsan_state_flush): replay after replay is right by what the graph holds, and
+        replay() marks the model as owing for everything else that reads."""
         db = self.device_batch(batch)
+        self._flush()
         # the graph bakes the workspace pointer in: size it for the worst case of this batch size once (the
         # longest session the kernels take, TLSAN_SN_CAP), so that a later, longer batch cannot make
         # _workspace() reallocate it under graphs captured earlier
@@ -948,6 +990,7 @@ class Model(object):
             # above), but it is no longer the model's -- recapture rather than run on a stale pointer
             raise RuntimeError("replay: the workspace was reallocated after this graph was captured; recapture the step")
         g.replay()
+        self._fix_owed = self.l2_mode == L.L2_LAZY and self._copt is None and hasattr(self.lib, "tlsan_state_flush")
         self._step += 1
 
     def train(self, sess, batch, lr, add_summary=False):
@@ -982,6 +1025,7 @@ class Model(object):
     def grads(self, batch, lr=1.0):
         """tf.gradients(loss, trainables) (model.py:198) as numpy arrays; test/diagnostic API."""
         db = self.device_batch(batch)
+        self._flush()
         ws = self._workspace(db.B, db.Sn)
         g = {k: torch.zeros_like(getattr(self, k), dtype=torch.float32) for k in TABLE_KEYS}
         gd = torch.zeros_like(self.dense)
@@ -1009,6 +1053,7 @@ class Model(object):
         want_att: also leave the reference's two attention-weight tensors (model.py:122, 386-394) on the model:
         self.att0 [H*B, Ls, d/H] and self.att1 [H*B, 1+Sn, d/H], row h*B + b (`sess.run([model.att0, model.att1])`)."""
         db = self.device_batch(batch, is_test)
+        self._flush()
         li = torch.empty(db.B, dtype=torch.float32, device=self.device)
         lj = torch.empty(db.B, dtype=torch.float32, device=self.device) if db.j is not None else None
         ut = torch.empty(db.B, self.config["hidden_units"], dtype=torch.float32, device=self.device) if want_u_t else None
