@@ -264,7 +264,7 @@ def test_sharded_train_driver_with_lazy_adam(tmp_path):
 
 
 def _np_opt_elem(kind, lr, b1, b2, eps, step, w, g, s1, s2):
-    """opt_elem of csrc/tlsan_update.h in float64 (TF 1.8's Adam / RMSProp / Adadelta)"""
+    """opt_elem of csrc/tlsan_opt.h in float64 (TF 1.8's Adam / RMSProp / Adadelta)"""
     if kind == "adam":
         s1 = s1 * b1 + g * (1.0 - b1)
         s2 = s2 * b2 + g * g * (1.0 - b2)

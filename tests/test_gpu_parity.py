@@ -1363,7 +1363,7 @@ def test_shared_categories_one_pass_equals_the_split_form():
 @pytest.mark.parametrize("d", [64, 128])
 def test_lazy_sum_of_squares_tracks_the_tables(d, table_dtype):
     """Lazy L2 keeps the stored tables' sum of squares (StateHdr::St, state bytes 32..40) from per-workgroup records of its
-    changes, which the next step folds in (DeltaRec, tlsan_update.h): after any sequence of updates it equals the tables'
+    changes, which the next step folds in (DeltaRec, tlsan_state.h): after any sequence of updates it equals the tables'
     own.  Batches of varying B and Sn make the records an update leaves shrink and grow; a large L2 rate at lr = 1 makes
     one workgroup's change a visible part of the sum; the first steps clip (the correcting pass adds to its records); the
     scale is folded into the tables every third step.  The tables are large enough that fp32 rounding in that fold stays far
@@ -1403,7 +1403,7 @@ def test_lazy_sum_of_squares_tracks_the_tables(d, table_dtype):
 def test_speculative_one_pass_lazy_update():
     """Tables that live in HBM (more than 512 MB of user / item rows, category segments) take the lazy-L2 step as ONE pass
     over the used rows BESIDE the finalize, with clip coefficient 1, and a second launch that commits the table scale and --
-    after a clipped step only -- corrects the rows (k_finalize_update / k_spec_commit, tlsan_update.h).
+    after a clipped step only -- corrects the rows (k_finalize_update, tlsan_finalize_rows.h / k_spec_commit, tlsan_spec_commit.h).
     TLSAN_LAZY_ONE_PASS=2 with TLSAN_CSEG_MIN=1 (both read once per process) sends every table that way: the oracle tests of
     lazy train steps must hold -- clip inactive AND active (test_lazy_l2_matches_dense_oracle[0.02]: the correcting pass),
     bf16 tables, hipGraph replay, a diverged step -- and unclipped steps must leave the SAME BITS as the split form (row sums

@@ -15,7 +15,7 @@ TABLE_F32, TABLE_BF16 = 0, 1
 MATRIX_F32, MATRIX_BF16 = 0, 1
 L2_DENSE, L2_LAZY = 0, 1
 INDEX_FOR_LAZY_SGD = 0x100   # TLSAN_INDEX_FOR_LAZY_SGD (include/tlsan.h)
-INDEX_SLOTS = 3   # TLSAN_INDEX_SLOTS (csrc/tlsan_update.h): destination-index slots of the state
+INDEX_SLOTS = 3   # TLSAN_INDEX_SLOTS (csrc/tlsan_state.h): destination-index slots of the state
 SN_CAP = 96     # TLSAN_SN_CAP (csrc/tlsan_common.h): longest session of a training batch
 TOPK_MAX = 256  # TOPK_MAX (csrc/tlsan_topk.h): largest K of tlsan_eval_topk
 NEG_MAX = 1024  # NEG_MAX (csrc/tlsan_cand.h): largest N of tlsan_sample_negatives

@@ -10,6 +10,50 @@
 #include <unordered_set>
 
 #include "tlsan_plan.h"
+#include "tlsan_index.h"
+#include "tlsan_finalize.h"
+#include "tlsan_apply.h"
+#include "tlsan_update_lazy.h"
+
+// ---- the small kernels of the dense side that only this unit launches
+// (tlsan_state_renorm: the sum of squares must be complete before it is rescaled)
+__global__ __launch_bounds__(256) void k_fold_delta(const DeltaRec* S_delta, int nrec, StateHdr* hdr, double* S_total) {
+  __shared__ double shd[256];
+  fold_delta(S_delta, nrec, hdr, S_total, shd);
+}
+
+// dedup-norm mode: norm^2 = sum over destination rows of |summed row gradient|^2 (ROWNORM pass)
+// + dense gradients; overrides the coefficient / norm of the step summary
+__global__ __launch_bounds__(256) void k_clip_dedup(const double* rown_part, int nrow, const float* sqd, int nsqd,
+                                                    StateHdr* hdr, float clip, float* out_gnorm) {
+  __shared__ double shd[256];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (int k = tid; k < nrow; k += 256) s += rown_part[k];
+  for (int k = tid; k < nsqd; k += 256) s += (double)sqd[k];
+  shd[tid] = s;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (tid < o) shd[tid] += shd[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const float norm = (float)sqrt(shd[0]);
+    hdr->coef = clip_coef(norm, clip);
+    if (out_gnorm) *out_gnorm = norm;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_reduce_double(const double* v, int n, double* out) {
+  __shared__ double shd[256];
+  const double s = block_sum_double(v, n, shd);
+  if (threadIdx.x == 0) *out = s;
+}
+
+__global__ void k_transpose_K(const float* __restrict__ K, float* __restrict__ KT, int D) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < D * D) KT[(size_t)(t % D) * D + t / D] = K[t];
+}
 
 static thread_local char g_err[512] = "";   // (static: fail() and tlsan_last_error() are its only doors, for every unit)
 int fail(int code, const char* fmt, ...) {
@@ -204,7 +248,7 @@ struct St {  // persistent state
   int32_t *cate_off, *cate_cnt, *cate_cur, *cate_items;   // static CSR category -> items
   StateHdr* hdr;
   double *S_part, *S_total;
-  DeltaRec* S_delta;                                      // per-workgroup changes of the sum of squares, tagged by step (tlsan_update.h)
+  DeltaRec* S_delta;                                      // per-workgroup changes of the sum of squares, tagged by step (tlsan_state.h)
   long long* scan_bsum[TLSAN_INDEX_SLOTS];                                // per-chunk sums of the index scan (large tables), per slot
   int32_t* perm[TLSAN_INDEX_SLOTS];                                       // samples of every workgroup of the fused kernel (BalArgs), Capacity::rank_cap each
   int32_t* scan_ticket;                                                   // [index slot] arrivals of k_scan_block_sums (ScanArgs.bs_ticket), zero at rest

@@ -3,8 +3,8 @@
 // geometry and where the dK product runs.  The tail (plan_tail): the launches after the fused kernel, their grids and the
 // split of the categories.  The buffers those rules can ask for (plan_capacity).  Host code only, and every environment
 // switch of the library is read here; tlsan_api.hip issues the plans (build_index, run_backward, launch_tail).
-#define TLSAN_ONCE static   // (the kernels of tlsan_update.h that are not templates: tlsan_api.hip's)
 #include "tlsan_plan.h"
+#include "tlsan_index_args.h"
 
 // ================================================================ the front ================================================
 // windows longer than TLSAN_LS_MAX are streamed (the list form of the long block); shorter ones stay in registers
@@ -31,7 +31,7 @@ static int train_group(const Shape& s, const tlsan_dims* d, const tlsan_batch* b
   return s.SG;
 }
 
-#define BAL_CAP (1 << 14)      // batches up to this many samples are ranked for the fused kernel's workgroups (BalArgs, tlsan_update.h)
+#define BAL_CAP (1 << 14)      // batches up to this many samples are ranked for the fused kernel's workgroups (BalArgs, tlsan_index_args.h)
 // Streamed windows: a workgroup's time is proportional to its windows' total length (d = 64, Ls = 90: 98 -> 87 us/step;
 // d = 256 at the C5 shape 496 -> 471; d = 128: the kernel alone 94 -> 72 us, 104 -> 93 beside the index build of the batch
 // after next).  Windows in registers: evenly loaded workgroups (ranked by session length alone) ran no faster in round 4
@@ -81,7 +81,7 @@ static bool cate_seg(const tlsan_dims* d, const tlsan_batch* b) {
 }
 // Tables of at least this many rows take their side of a lazy-SGD step's index from a sort of the batch's ids instead of
 // a counter per row -- when its consumers reach it through ids and records only: the user table (UsortArgs: a bucket
-// sort inside one block), the item table with category segments (IsortArgs: a partitioned counting sort, tlsan_update.h).
+// sort inside one block), the item table with category segments (IsortArgs: a partitioned counting sort, tlsan_index.h).
 // TLSAN_ISORT_MIN=<rows> for tests (read once per process; it also sizes the state).
 static int isort_min_rows() {
   static const int v = [] { const char* e = getenv("TLSAN_ISORT_MIN"); return e ? atoi(e) : (1 << 16); }();
@@ -228,7 +228,7 @@ static void category_split(ApplyArgs& A, const tlsan_dims* d, const tlsan_batch*
   }
 }
 
-// The lazy update as ONE pass over the used rows (round 6; k_finalize_update / k_spec_commit, tlsan_update.h).  The split
+// The lazy update as ONE pass over the used rows (round 6; k_finalize_update, tlsan_finalize_rows.h / k_spec_commit, tlsan_spec_commit.h).  The split
 // form (row sums in the finalize's launch, then k_update_lazy) sends every summed row through memory -- written by one
 // launch, read by the next beside the parameter row's read-modify-write -- and ends in a launch of its own; in the one-pass
 // form a 16-lane group sums its row's segment and updates the row, speculating on clip coefficient 1, beside the finalize.
@@ -325,7 +325,7 @@ int plan_tail(const tlsan_dims* d, const Shape& s, const tlsan_batch* b, const t
     fl.kind = FinLaunch::UPDATE;
     fl.grid = dim3(w.nfin + 1 + A.nbH + (shared ? A.C * A.csplit : A.nbC) + (A.nbI_l > 0 ? A.nbI_l : A.nbI) + A.nbU);
     fl.shared = shared; fl.bf16 = bf16; fl.wide = apply_wide(A) && !shared;
-    fl.low = tables_in_hbm(d);   // (the low-occupancy form: see SPEC_WPE, tlsan_update.h)
+    fl.low = tables_in_hbm(d);   // (the low-occupancy form: see SPEC_WPE, tlsan_finalize_rows.h)
     f.count_step = 0; f.spec = 1;
     // The two-launch form: everything k_spec_commit does has a place where its inputs are final at a launch boundary (the
     // finalize's workgroups, its summary, the head of the next fused kernel), so the launch -- 4.4 us of a 56 us step for

@@ -10,8 +10,8 @@
 #include <thread>
 #include <stdio.h>
 
-#define TLSAN_ONCE static   // (the kernels of tlsan_update.h that are not templates: tlsan_api.hip's)
 #include "tlsan_host.h"
+#include "tlsan_index_args.h"   // ScanArgs (launch_scan)
 #include "tlsan_shard.h"
 
 // counting sort of gi.n destinations by row with the generic index kernels: clear the counts, count, scan them into `off`

@@ -22,13 +22,13 @@
 #include "tlsan_common.h"
 
 // ---- The rare correcting pass of the two-launch lazy-L2 step, at the head of the NEXT step's k_fwd_bwd (spec_fix_head
-// below).  Its row block functions (tlsan_update.h) are written for 256 threads and synchronise them with a workgroup
+// below).  Its row block functions (tlsan_apply.h) are written for 256 threads and synchronise them with a workgroup
 // barrier; here they run in the first four wavefronts of a workgroup that may have eight, so in this unit their barrier is
 // one of those four wavefronts alone: an arrival counter in the LDS (word 0 of the kernel's dynamic block, which nothing
 // else owns before the first pass).  A count that only grows needs no generation: the wavefront that arrives as number
 // 4 k + j waits for 4 (k + 1).  All four are resident, so the wait ends.
 #define TLSAN_FIX_WGS 64          // workgroups that correct (fewer when the grid is smaller)
-#define TLSAN_FIX_LDS_BYTES (16 + FIX_LDS_BYTES)   // counter + FixLds (tlsan_update.h)
+#define TLSAN_FIX_LDS_BYTES (16 + FIX_LDS_BYTES)   // counter + FixLds (tlsan_fix.h)
 __device__ __forceinline__ void fix_team_sync() {
   extern __shared__ __attribute__((aligned(16))) int fix_lds[];
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -41,10 +41,7 @@ __device__ __forceinline__ void fix_team_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 #define AP_SYNC() fix_team_sync()
-#ifndef TLSAN_ONCE
-#define TLSAN_ONCE static   // (the kernels of tlsan_update.h that are not templates: tlsan_api.hip's)
-#endif
-#include "tlsan_update.h"
+#include "tlsan_fix.h"
 
 // Every workgroup of a training launch calls this when the header says that the previous step was clipped
 // (StateHdr::fix_pending): the first F = min(grid, TLSAN_FIX_WGS) workgroups walk that step's row blocks and dense blocks with

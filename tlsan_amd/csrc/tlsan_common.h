@@ -524,7 +524,7 @@ struct FwdArgs {
   float* Gu;        // [B, WU]           [user_emb | usert_emb | pad] rows, grouped by user id
   float* Gc;        // [B, dc]           u_cate rows, grouped by category
   int32_t* cur_item; int32_t* cur_user; int32_t* cur_uc;
-  const int32_t* perm;    // optional: perm[16 g + j] = sample j of workgroup pass g (>= B: none); BalArgs, tlsan_update.h
+  const int32_t* perm;    // optional: perm[16 g + j] = sample j of workgroup pass g (>= B: none); BalArgs, tlsan_index_args.h
   int32_t uc_by_sample;   // != 0: Gc rows are written in SAMPLE order (row b = sample b) and the index holds the
                           // samples of every category (uc_list, k_uc_fill): no cursor is drawn for the u_cate use
   int32_t fuse_dk;  // != 0: this launch forms the dK partials itself (Geo::FUSE_DK builds; chosen per launch, tlsan_api.hip)

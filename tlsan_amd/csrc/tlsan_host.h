@@ -8,8 +8,8 @@
 
 #include "tlsan_common.h"
 
-struct FinLaunch;                                  // tlsan_update_inst.h
-struct ScanArgs; struct ApplyArgs;                 // tlsan_update.h
+struct ScanArgs;                                   // tlsan_index_args.h
+struct FinLaunch; struct ApplyArgs;                // tlsan_update_args.h
 struct TopkArgs;                                   // tlsan_topk.h
 struct CandArgs; struct NegArgs; struct ExclArgs;  // tlsan_cand.h
 
@@ -89,7 +89,7 @@ hipError_t tlsan_launch_cand_ranks(const int32_t* cand, const float* scores, int
 hipError_t tlsan_launch_sample_neg(const NegArgs& a, hipStream_t hs);
 hipError_t tlsan_launch_excl_ahead(const ExclArgs& a, int D, hipStream_t hs);
 
-// ---- tlsan_api.hip owns the index scan and k_reduce_double (tlsan_update.h)
+// ---- tlsan_api.hip owns the index scan (tlsan_index.h) and k_reduce_double
 int launch_scan(ScanArgs& sa, int nscan, long long* bsum, hipStream_t hs);
 int scan_compact_impl(const int32_t* cnt, int32_t n, int32_t* prefix, int32_t* uniq, int32_t* n_uniq, long long* bsum,
                       hipStream_t hs);

@@ -4,7 +4,7 @@
 // unit can ask them again.
 #pragma once
 #include "tlsan_host.h"
-#include "tlsan_update_inst.h"
+#include "tlsan_update_args.h"
 
 // What build_index builds for a batch.  Planned from the dims, the shape, the batch and the sparse flag only -- what
 // tlsan_batch_index has, one or two steps ahead of the step and without its hyper-parameters (plan_index).

@@ -3,7 +3,7 @@
 // integer atomics only decide WHICH contributions belong to a row; the float sum is exact
 // (exact_term), so any order gives the same bits.
 #pragma once
-#include "tlsan_update.h"
+#include "tlsan_update_args.h"   // AP_OWN, AP_ROWS_PB: the row geometry of k_apply
 
 struct GIdxArgs {
   const int32_t* dest;

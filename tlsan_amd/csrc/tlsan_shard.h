@@ -5,6 +5,7 @@
 // model.py:198-205 on the rows a rank owns.
 #pragma once
 #include "tlsan_rows.h"
+#include "tlsan_opt.h"
 
 struct RouteArgs {
   const int32_t* keys;      // [n_keys] key of every id the batch touches (duplicates fine)

@@ -1,6 +1,6 @@
 // dense finalize kernels (tlsan_update_inst.h) for hidden_units = 128 with 8 heads (16 channels per head)
-#define TLSAN_ONCE static
 #include "tlsan_update_inst.h"
+#include "tlsan_spec_commit.h"
 void tlsan_launch_finalize_d128(const FinLaunch& L, hipStream_t hs) { launch_finalize<128, 16>(L, hs); }
 
 // ... and k_spec_commit of every pair: compiled beside k_finalize_update, whose row helpers it shares -- alone in a unit the

@@ -3,21 +3,7 @@
 // unit of its own (tlsan_update_d*.hip), so that the six compile side by side; tlsan_api.hip reaches them through
 // its table of pairs (g_pairs).
 #pragma once
-#include "tlsan_update.h"
-
-struct FinLaunch {   // one launch of the dense finalize, in any of its three forms
-  enum Kind { DENSE = 0, PRESUM = 1, UPDATE = 2 };
-  FinArgs f;
-  ApplyArgs A;       // PRESUM, UPDATE: the row workgroups of the launch
-  dim3 grid;
-  int nbK, nbS;
-  int kind;
-  bool shared;       // UPDATE: shared categories (plan_tail: TAIL_SPEC_SHARED)
-  bool bf16;         // UPDATE: bf16 tables
-  bool wide;         // PRESUM, UPDATE: the wide row form
-  bool low;          // UPDATE: the low-occupancy form (tables in HBM)
-  bool csplit;       // PRESUM: categories split over several workgroups
-};
+#include "tlsan_finalize_rows.h"
 
 template <int D, int DH>
 static void launch_finalize(const FinLaunch& L, hipStream_t hs) {

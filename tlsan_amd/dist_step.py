@@ -44,7 +44,7 @@ from .dist_comm import _staged, a2a, allreduce_sum
 from .model import _STARTED_WORDS, concurrent_streams, grow_workspace
 
 
-_STATE_HDR_BYTES = 256   # sizeof(StateHdr), csrc/tlsan_update.h: what tlsan_state_reindex keeps
+_STATE_HDR_BYTES = 256   # sizeof(StateHdr), csrc/tlsan_state.h: what tlsan_state_reindex keeps
 _STATIC_SLOTS = 4     # routing plans of the static-shape step: the current batch and up to two announced successors
 
 # the announced batches' plans are issued by a launch thread of the library (tlsan_shard_step_static, TLSAN_PLAN_ASYNC);
