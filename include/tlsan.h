@@ -314,8 +314,28 @@ int tlsan_train_step(const tlsan_dims* dims, const tlsan_params* p, const tlsan_
  * TLSAN_OPT_LAZY alone (or with SGD) is TLSAN_E_BADARG.  An index prebuilt with TLSAN_INDEX_FOR_LAZY_SGD serves these
  * steps too.  The row launch reads the summed gradient, W, m and v of the used rows and writes W, m and v: seven row
  * widths per used row, where the lazy SGD update moves three (category rows: every row's summed gradient is read, W, m
- * and v of the used ones only). */
-enum { TLSAN_OPT_SGD = 0, TLSAN_OPT_ADAM = 1, TLSAN_OPT_RMSPROP = 2, TLSAN_OPT_ADADELTA = 3 };
+ * and v of the used ones only).
+ *
+ * TLSAN_OPT_ADAGRAD | TLSAN_OPT_LAZY and TLSAN_OPT_ROWWISE_ADAGRAD | TLSAN_OPT_LAZY: Adagrad on the used rows, with ONE
+ * accumulator -- slot1; slot2 is never read or written and may be NULL.  Everything above holds for them (used rows,
+ * item_b, dense weights, unused rows and their accumulators bit for bit, P, the contract) but the rule, which is TF 1.8's
+ * ApplyAdagrad:  acc += g^2;  w -= lr * g / sqrt(acc).  No epsilon; beta1, beta2, epsilon and step are not looked at.  The
+ * library never initialises slots: TF's initial_accumulator_value is 0.1.
+ *   ADAGRAD          (TF's AdagradOptimizer): an accumulator per element; slot1 has the shapes of the parameters.
+ *   ROWWISE_ADAGRAD  (the row-wise Adagrad of DLRM / FBGEMM / TorchRec): an accumulator per table ROW.
+ *            slot1->item_emb, user_emb, usert_emb and cate_emb are contiguous arrays of one float per row ([item_count],
+ *            [user_count], [user_count], [cate_count]; their ld_* fields are not looked at, no stride rule).  For a used
+ *            row of n live columns (item_emb, user_emb: d_item; usert_emb: Ls; cate_emb: d_cate)
+ *              acc_row += (1 / n) * sum_j g_j^2;  w_j -= lr * g_j / sqrt(acc_row) for every j, with the new acc_row.
+ *            user_emb and usert_emb are two variables with an accumulator each.  item_b and the dense weights have width 1
+ *            and take the elementwise rule (slot1->item_b, slot1->dense as under ADAGRAD): on a row of width 1 the two
+ *            kinds are the same arithmetic.  The row sum has a fixed order (each of the row's 16 lanes adds the squares of
+ *            its own columns in ascending order, then a four-step butterfly): two runs leave the same bits.
+ *            The row launch moves three row widths and one float per used row and table.
+ * Both are valid only with TLSAN_OPT_LAZY: without it TLSAN_E_UNSUPPORTED, before any launch (the dense sweep is not built
+ * for them).  A NULL slot1, or a NULL table in it, is TLSAN_E_BADARG.  The tlsan_shard_* calls do not take them. */
+enum { TLSAN_OPT_SGD = 0, TLSAN_OPT_ADAM = 1, TLSAN_OPT_RMSPROP = 2, TLSAN_OPT_ADADELTA = 3,
+       TLSAN_OPT_ADAGRAD = 4, TLSAN_OPT_ROWWISE_ADAGRAD = 5 };
 #define TLSAN_OPT_LAZY 0x100
 typedef struct {
   int32_t kind;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Train-step time of the lazy optimizers against lazy-L2 SGD and the dense optimizer (single GPU, resident batches):
-python scripts/lazy_opt_bench.py shape=bench|10m|c5 opt=sgd|adam|lazy_adam|rmsprop|lazy_rmsprop|... [steps=N] [td=bf16]
+python scripts/lazy_opt_bench.py shape=bench|10m|c5 opt=sgd|adam|lazy_adam|rmsprop|lazy_rmsprop|lazy_adagrad|lazy_rowwise_adagrad|... [steps=N] [td=bf16]
   bench: the Electronics bench shape (40 k users / 22 k items / 673 categories, d = 128, Ls = 10, B = 4096)
   10m:   10 M users / 5 M items / 10 k categories, d = 128, Ls = 10, B = 4096 (BASELINE.json's synthetic tables)
   c5:    the same tables at d = 256, Ls = 90, B = 4096
@@ -59,7 +59,8 @@ def row_launch_bytes(b):
     """Bytes the lazy optimizers' row launch (k_update_lazy_opt) moves for batch b: per used item / user row the summed
     gradient, W, m and v read and W, m, v written (seven row widths; item_b of the candidates beside them), every category
     row's summed gradient and use count read and the used ones' W, m, v read and written, the dense parameters and their
-    slots."""
+    slots.  The Adagrad forms (k_update_lazy_adagrad) keep one accumulator: a row width less read and written, or -- row-wise
+    -- one float per row and table."""
     u, i, _, hi, hin, _, sl, sln, uc = (np.asarray(x) for x in b)
     Sn = hin.shape[1] if hin.ndim == 2 else 0
     items = [i, hi[np.arange(Ls)[None, :] < sl[:, None]]]
@@ -68,7 +69,14 @@ def row_launch_bytes(b):
     it = np.unique(np.concatenate(items))
     nc_used = len(np.unique(np.concatenate([icl[it], uc])))
     di, dc, WU = d // 2, d // 2, (d // 2 + Ls + 3) // 4 * 4
-    return (len(it) * 7 * di * 4 + len(np.unique(i)) * 7 * 4 + len(np.unique(u)) * (7 * (di + Ls) + (WU - di - Ls)) * 4
+    ni, nb, nu = len(it), len(np.unique(i)), len(np.unique(u))
+    if opt == "lazy_adagrad":           # (k_update_lazy_adagrad) one accumulator per element: five row widths
+        return (ni * 5 * di * 4 + nb * 5 * 4 + nu * (5 * (di + Ls) + (WU - di - Ls)) * 4
+                + cfg["cate_count"] * (dc + 1) * 4 + nc_used * 4 * dc * 4 + m.lay.n_dense * 6 * 4)
+    if opt == "lazy_rowwise_adagrad":   # one accumulator per row: three row widths, and a float read and written per row and table
+        return (ni * (3 * di + 2) * 4 + nb * 5 * 4 + nu * (3 * (di + Ls) + (WU - di - Ls) + 4) * 4
+                + cfg["cate_count"] * (dc + 1) * 4 + nc_used * (2 * dc + 2) * 4 + m.lay.n_dense * 6 * 4)
+    return (ni * 7 * di * 4 + nb * 7 * 4 + nu * (7 * (di + Ls) + (WU - di - Ls)) * 4
             + cfg["cate_count"] * (dc + 1) * 4 + nc_used * 6 * dc * 4 + m.lay.n_dense * 8 * 4)
 
 

@@ -77,6 +77,7 @@ class Optimizer(C.Structure):
 
 
 OPT_SGD, OPT_ADAM, OPT_RMSPROP, OPT_ADADELTA = 0, 1, 2, 3
+OPT_ADAGRAD, OPT_ROWWISE_ADAGRAD = 4, 5   # with OPT_LAZY only: one accumulator set (slot1), per element / per table row
 OPT_LAZY = 0x100   # TLSAN_OPT_LAZY (include/tlsan.h): OR-ed into ADAM / RMSPROP / ADADELTA, the used rows only
 
 

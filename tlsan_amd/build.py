@@ -1,6 +1,6 @@
 """Build libtlsan_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: twenty translation units compiled in parallel,
 one link -- four host units of the C ABI by subsystem (tlsan_api.hip core, training and state, with every kernel of the step
-but the fused one and the dense finalize -- tlsan_index.h, tlsan_apply.h, tlsan_update_lazy.h; tlsan_api_plan.hip the plans of a step's front and tail; tlsan_api_eval.hip evaluation;
+but the fused one and the dense finalize -- tlsan_index.h, tlsan_apply.h, tlsan_update_lazy.h, tlsan_update_adagrad.h; tlsan_api_plan.hip the plans of a step's front and tail; tlsan_api_eval.hip evaluation;
 tlsan_api_shard.hip rows and the sharded step), the top-K selection, the candidate kernels, and per (d, heads) pair k_fwd_bwd
 (d = 128 / 8 also as 8-sample workgroups, d = 256 with the window in registers and streamed) and the dense finalize kernels.
 A unit is recompiled when a file named in the compiler's depfile of its last compile is newer than its object.

@@ -14,6 +14,7 @@
 #include "tlsan_finalize.h"
 #include "tlsan_apply.h"
 #include "tlsan_update_lazy.h"
+#include "tlsan_update_adagrad.h"
 
 // ---- the small kernels of the dense side that only this unit launches
 // (tlsan_state_renorm: the sum of squares must be complete before it is rescaled)
@@ -829,7 +830,19 @@ static int launch_tail(const Shape& s, const TailPlan& P, const tlsan_hparams* h
       if ((rc = launch_apply(P.update ? AP_UPDATE : AP_GRADS, A, true, hs))) return rc;
       break;
     case TAIL_SPLIT:
-      if (P.update && A.opt != TLSAN_OPT_SGD) {   // lazy Adam / RMSProp / Adadelta: the used rows and their slots
+      if (P.update && (A.opt == TLSAN_OPT_ADAGRAD || A.opt == TLSAN_OPT_ROWWISE_ADAGRAD)) {   // lazy (row-wise) Adagrad: one accumulator
+#define ADAGRAD_LAUNCH(RW)                                                                                                      \
+  do {                                                                                                                          \
+    if (bf16 && P.wide) hipLaunchKernelGGL((k_update_lazy_adagrad<true, TLSAN_TABLE_BF16, RW>), P.grid, blk, 0, hs, A, P.nbC16);  \
+    else if (bf16) hipLaunchKernelGGL((k_update_lazy_adagrad<false, TLSAN_TABLE_BF16, RW>), P.grid, blk, 0, hs, A, P.nbC16);      \
+    else if (P.wide) hipLaunchKernelGGL((k_update_lazy_adagrad<true, TLSAN_TABLE_F32, RW>), P.grid, blk, 0, hs, A, P.nbC16);      \
+    else hipLaunchKernelGGL((k_update_lazy_adagrad<false, TLSAN_TABLE_F32, RW>), P.grid, blk, 0, hs, A, P.nbC16);                 \
+  } while (0)
+        if (A.opt == TLSAN_OPT_ROWWISE_ADAGRAD) ADAGRAD_LAUNCH(true);
+        else ADAGRAD_LAUNCH(false);
+#undef ADAGRAD_LAUNCH
+        CHECK_LAUNCH("k_update_lazy_adagrad");
+      } else if (P.update && A.opt != TLSAN_OPT_SGD) {   // lazy Adam / RMSProp / Adadelta: the used rows and their slots
         if (bf16 && P.wide) hipLaunchKernelGGL((k_update_lazy_opt<true, TLSAN_TABLE_BF16>), P.grid, blk, 0, hs, A, P.nbC16);
         else if (bf16) hipLaunchKernelGGL((k_update_lazy_opt<false, TLSAN_TABLE_BF16>), P.grid, blk, 0, hs, A, P.nbC16);
         else if (P.wide) hipLaunchKernelGGL((k_update_lazy_opt<true, TLSAN_TABLE_F32>), P.grid, blk, 0, hs, A, P.nbC16);
@@ -890,10 +903,11 @@ int tlsan_batch_index(const tlsan_dims* d, const tlsan_batch* b, const int32_t* 
   return build_index(d, b, plan_index(d, s, b, lazy_sgd), item_cate, st, slot, (hipStream_t)stream);
 }
 
-static int check_slot(const tlsan_params* q, const char* name) {
+// (rows: the four tables of the set are [rows] floats -- TLSAN_OPT_ROWWISE_ADAGRAD -- whose strides are not looked at)
+static int check_slot(const tlsan_params* q, const char* name, bool rows = false) {
   if (!q || !q->item_emb || !q->item_b || !q->user_emb || !q->usert_emb || !q->cate_emb || !q->dense)
     return fail(TLSAN_E_BADARG, "tlsan_optimizer: NULL table in %s", name);
-  if (q->ld_item % 4 || q->ld_user % 4) return fail(TLSAN_E_UNSUPPORTED, "tlsan_optimizer: row strides of %s must be multiples of 4 floats", name);
+  if (!rows && (q->ld_item % 4 || q->ld_user % 4)) return fail(TLSAN_E_UNSUPPORTED, "tlsan_optimizer: row strides of %s must be multiples of 4 floats", name);
   return TLSAN_OK;
 }
 
@@ -910,15 +924,19 @@ int tlsan_train_step_opt(const tlsan_dims* d, const tlsan_params* p, const tlsan
   if (rc) return rc;
   const bool other = opt && opt->kind != TLSAN_OPT_SGD;
   const int kind = other ? opt->kind & ~TLSAN_OPT_LAZY : TLSAN_OPT_SGD;
+  const bool adagrad = kind == TLSAN_OPT_ADAGRAD || kind == TLSAN_OPT_ROWWISE_ADAGRAD;
   if (other) {
-    if (kind != TLSAN_OPT_ADAM && kind != TLSAN_OPT_RMSPROP && kind != TLSAN_OPT_ADADELTA)
-      return fail(TLSAN_E_BADARG, "tlsan_optimizer: kind %d (TLSAN_OPT_LAZY goes with ADAM, RMSPROP or ADADELTA)", opt->kind);
+    if (kind != TLSAN_OPT_ADAM && kind != TLSAN_OPT_RMSPROP && kind != TLSAN_OPT_ADADELTA && !adagrad)
+      return fail(TLSAN_E_BADARG, "tlsan_optimizer: kind %d (TLSAN_OPT_LAZY goes with ADAM, RMSPROP, ADADELTA, ADAGRAD or ROWWISE_ADAGRAD)", opt->kind);
+    if (adagrad && !(opt->kind & TLSAN_OPT_LAZY))
+      return fail(TLSAN_E_UNSUPPORTED, "tlsan_optimizer: kind %d: the dense sweep is not built for ADAGRAD / ROWWISE_ADAGRAD (OR TLSAN_OPT_LAZY in)", opt->kind);
     if (opt->kind & TLSAN_OPT_LAZY) {   // (prep_step checked the rest of the lazy-L2 contract: TF18 norm, params->scale)
       if (hp->l2_mode != TLSAN_L2_LAZY) return fail(TLSAN_E_UNSUPPORTED, "TLSAN_OPT_LAZY updates the used rows only: l2_mode must be TLSAN_L2_LAZY");
     } else if (hp->l2_mode != TLSAN_L2_DENSE) {
       return fail(TLSAN_E_UNSUPPORTED, "optimizers other than sgd update every row: l2_mode must be TLSAN_L2_DENSE");
     }
-    if ((rc = check_slot(opt->slot1, "slot1")) || (rc = check_slot(opt->slot2, "slot2"))) return rc;
+    // (Adagrad keeps one accumulator: slot2 is never looked at)
+    if ((rc = check_slot(opt->slot1, "slot1", kind == TLSAN_OPT_ROWWISE_ADAGRAD)) || (!adagrad && (rc = check_slot(opt->slot2, "slot2")))) return rc;
     if (kind == TLSAN_OPT_ADAM && opt->step < 1) return fail(TLSAN_E_BADARG, "tlsan_optimizer: Adam's step counts from 1");
   }
   hipStream_t hs = (hipStream_t)stream;
@@ -929,7 +947,8 @@ int tlsan_train_step_opt(const tlsan_dims* d, const tlsan_params* p, const tlsan
   fill_apply(A, d, s, p, &fp.ix, hp, w, st, L);
   if (other) {
     A.opt = kind;
-    A.s1 = norm_params(opt->slot1, d); A.s2 = norm_params(opt->slot2, d);
+    A.s1 = norm_params(opt->slot1, d);
+    if (!adagrad) A.s2 = norm_params(opt->slot2, d);
     A.ob1 = opt->beta1; A.ob2 = opt->beta2; A.oeps = opt->epsilon;
     if (kind == TLSAN_OPT_ADAM) A.oalpha = adam_alpha(hp->lr, opt->beta1, opt->beta2, opt->step);
   }

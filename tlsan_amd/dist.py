@@ -29,7 +29,7 @@ from . import _lib as L
 from .dist_comm import (ExchangePlan, KeyRouter, ModPartition, RowExchange, _staged, a2a, allgather_rows,  # noqa: F401
                         allreduce_sum, torch_scan)
 from .dist_step import DynamicStep, FlatLayout, StaticStep, fused_params
-from .model import (LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer, candidate_tensor, eval_topk,
+from .model import (LAZY_ADAGRAD_OPTIMIZERS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer, candidate_tensor, eval_topk,
                     exclusion_csr, grow_workspace, hits_and_rows, pack_dense, read_checkpoint, sample_negatives, sampled_ranks,
                     score_candidates, topk_merge, unpack_dense, write_checkpoint)
 
@@ -94,6 +94,9 @@ class ShardedModel:
         self.optimizer = config.get("optimizer", "sgd")
         if self.optimizer not in OPTIMIZERS:
             raise ValueError("optimizer must be one of %s" % (sorted(OPTIMIZERS),))
+        if self.optimizer in LAZY_ADAGRAD_OPTIMIZERS:
+            raise NotImplementedError("optimizer=%r: the owners' update is built for lazy_adam, lazy_rmsprop and lazy_adadelta; "
+                                      "the Adagrad forms train on one GPU (tlsan_amd.model.Model)" % self.optimizer)
         # lazy_adam / lazy_rmsprop / lazy_adadelta: the owners apply the optimizer to the rows that arrived and to no other
         # (tlsan_shard_apply_lazy_opt) -- the lazy owner update's form, as the C ABI's lazy kinds need TLSAN_L2_LAZY
         self.lazy_opt = self.optimizer in LAZY_OPTIMIZERS

@@ -115,8 +115,8 @@ def unpack_dense(lay, d, heads, flat):
 
 def write_checkpoint(path, step, epoch, params, slots=None):
     """The single-file checkpoint TLSAN-<step>.npz: the two counters, every parameter under its name and, when the
-    optimizer has accumulators (two dicts named like the parameters), those as slot1/<name> and slot2/<name> --
-    tf.train.Saver keeps the optimizer's slot variables too."""
+    optimizer has accumulators (a list of dicts named like the parameters: two, or the Adagrad forms' one), those as
+    slot1/<name>, slot2/<name> -- tf.train.Saver keeps the optimizer's slot variables too."""
     extra = {}
     for n, sl in enumerate(slots or (), 1):
         extra.update({"slot%d/%s" % (n, k): v for k, v in sl.items()})
@@ -124,13 +124,16 @@ def write_checkpoint(path, step, epoch, params, slots=None):
 
 
 def read_checkpoint(path, want_slots=True):
-    """write_checkpoint's file -> (step, epoch, params, slots); slots is None when the file holds none (an sgd run)
-    or want_slots is false."""
+    """write_checkpoint's file -> (step, epoch, params, slots); slots lists as many slot sets as the file holds, None
+    when it holds none (an sgd run) or want_slots is false."""
     z = np.load(path)
     keys = TABLE_KEYS + DENSE_KEYS
     slots = None
     if want_slots and "slot1/item_emb" in z.files:
-        slots = [{k: z["slot%d/%s" % (n, k)] for k in keys} for n in (1, 2)]
+        slots, n = [], 1
+        while "slot%d/item_emb" % n in z.files:
+            slots.append({k: z["slot%d/%s" % (n, k)] for k in keys})
+            n += 1
     return int(z["global_step"]), int(z["global_epoch_step"]), {k: z[k] for k in keys}, slots
 # optimizer -> (TLSAN_OPT_*, beta1 | decay | rho, beta2 | momentum, epsilon): TF 1.8's constructor
 # defaults, which model.py:188-193 keeps (only learning_rate is passed)
@@ -141,6 +144,13 @@ LAZY_OPTIMIZERS = ("lazy_adam", "lazy_rmsprop", "lazy_adadelta")
 OPTIMIZERS.update({"lazy_adam": (L.OPT_ADAM | L.OPT_LAZY, 0.9, 0.999, 1e-8),
                    "lazy_rmsprop": (L.OPT_RMSPROP | L.OPT_LAZY, 0.9, 0.0, 1e-10),
                    "lazy_adadelta": (L.OPT_ADADELTA | L.OPT_LAZY, 0.95, 0.0, 1e-8)})
+# lazy Adagrad (TF's AdagradOptimizer restricted to the used rows) and row-wise Adagrad (one accumulator per table row, the
+# default of DLRM / FBGEMM / TorchRec): ONE slot set, no constants but the accumulators' initial value (include/tlsan.h)
+LAZY_ADAGRAD_OPTIMIZERS = ("lazy_adagrad", "lazy_rowwise_adagrad")
+OPTIMIZERS.update({"lazy_adagrad": (L.OPT_ADAGRAD | L.OPT_LAZY, 0.0, 0.0, 0.0),
+                   "lazy_rowwise_adagrad": (L.OPT_ROWWISE_ADAGRAD | L.OPT_LAZY, 0.0, 0.0, 0.0)})
+ADAGRAD_INITIAL_ACCUMULATOR = 0.1    # TF 1.8's initial_accumulator_value
+ROW_SLOT_KEYS = ("item_emb", "user_emb", "usert_emb", "cate_emb")   # lazy_rowwise_adagrad: [rows] accumulators
 
 
 _STREAM_CACHE = {}
@@ -541,7 +551,8 @@ class Model(object):
         configs[4]; no host copy of the tables is ever made).
         config["optimizer"]: "sgd", "adam", "rmsprop", "adadelta" (the reference's), or "lazy_adam", "lazy_rmsprop",
         "lazy_adadelta": the same optimizers restricted to the rows each batch used (unused rows keep their values and
-        slots bit for bit; include/tlsan.h, TLSAN_OPT_LAZY).  A lazy optimizer runs the lazy tail whatever l2_mode
+        slots bit for bit; include/tlsan.h, TLSAN_OPT_LAZY), or "lazy_adagrad", "lazy_rowwise_adagrad": Adagrad on the used
+        rows with one accumulator per element / per table row.  A lazy optimizer runs the lazy tail whatever l2_mode
         says: "dense" and "lazy" are both accepted, with the same result; norm_mode must be "tf18"."""
         if init not in ("numpy", "device"):
             raise ValueError("init must be 'numpy' or 'device'")
@@ -571,7 +582,7 @@ class Model(object):
             raise ValueError("optimizer must be one of %s" % (sorted(OPTIMIZERS),))
         # lazy_adam / lazy_rmsprop / lazy_adadelta update only the rows a batch used (include/tlsan.h, TLSAN_OPT_LAZY): they
         # always run the lazy tail, whatever l2_mode says -- "dense" and "lazy" are both accepted and give the same result
-        self.lazy_opt = self.optimizer in LAZY_OPTIMIZERS
+        self.lazy_opt = self.optimizer in LAZY_OPTIMIZERS or self.optimizer in LAZY_ADAGRAD_OPTIMIZERS
         if self.lazy_opt:
             if l2_mode not in ("dense", "lazy"):
                 raise ValueError("l2_mode must be 'dense' or 'lazy'")
@@ -709,22 +720,31 @@ class Model(object):
 
     def _alloc_slots(self):
         """Accumulators of adam / rmsprop / adadelta (tlsan_optimizer in include/tlsan.h): two sets of
-        tables shaped like the parameters; RMSProp's first slot starts at one as in TF 1.8."""
+        tables shaped like the parameters; RMSProp's first slot starts at one as in TF 1.8.  The Adagrad forms keep ONE
+        set, filled with TF's initial_accumulator_value; lazy_rowwise_adagrad's four tables are [rows] vectors."""
         self.slots = None
         self._copt = None
         if self.optimizer == "sgd":
             return
         self.slots, self._cslots = [], []
-        for which in range(2):
+        adagrad = self.optimizer in LAZY_ADAGRAD_OPTIMIZERS
+        row_slots = self.optimizer == "lazy_rowwise_adagrad"
+        for which in range(1 if adagrad else 2):
             fill = 1.0 if (self.optimizer in ("rmsprop", "lazy_rmsprop") and which == 0) else 0.0
+            if adagrad:
+                fill = ADAGRAD_INITIAL_ACCUMULATOR
             t = {k: torch.full_like(getattr(self, k), fill, dtype=torch.float32) for k in TABLE_KEYS}
+            if row_slots:
+                for k in ROW_SLOT_KEYS:
+                    t[k] = torch.full((getattr(self, k).shape[0],), fill, dtype=torch.float32, device=self.device)
             t["dense"] = torch.full_like(self.dense, fill)
             self.slots.append(t)
             self._cslots.append(L.Params(t["item_emb"].data_ptr(), t["item_b"].data_ptr(), t["user_emb"].data_ptr(),
                                          t["usert_emb"].data_ptr(), t["cate_emb"].data_ptr(), t["dense"].data_ptr(),
                                          None, None, 0, 0, 0, 0, None, L.TABLE_F32))
         kind, b1, b2, eps = OPTIMIZERS[self.optimizer]
-        self._copt = L.Optimizer(kind, 0, b1, b2, eps, C.addressof(self._cslots[0]), C.addressof(self._cslots[1]))
+        self._copt = L.Optimizer(kind, 0, b1, b2, eps, C.addressof(self._cslots[0]),
+                                 None if adagrad else C.addressof(self._cslots[1]))
 
     def _flush(self):
         """A clipped lazy-L2 SGD step in the two-launch form leaves its correction to the next step's fused kernel
@@ -751,7 +771,8 @@ class Model(object):
                                                   ws.data_ptr(), ws.numel(), self._stream()), "tlsan_train_step_opt")
 
     def get_slots(self):
-        """The optimizer's accumulators as two dicts of numpy arrays named like the parameters (None for sgd)."""
+        """The optimizer's accumulators as a list of dicts of numpy arrays named like the parameters: two, the Adagrad
+        forms one (lazy_rowwise_adagrad: the four tables' entries are [rows] arrays); None for sgd."""
         if self.slots is None:
             return None
         out = []
@@ -761,7 +782,18 @@ class Model(object):
             out.append(d)
         return out
 
+    def _check_slots(self, slots):
+        """Slot sets as get_slots returns them (a checkpoint's) must be this optimizer's: as many, shaped alike."""
+        if len(slots) != len(self.slots):
+            raise ValueError("%d slot set(s) do not fit optimizer=%r, which keeps %d" % (len(slots), self.optimizer, len(self.slots)))
+        for n, (t, src) in enumerate(zip(self.slots, slots), 1):
+            for k in TABLE_KEYS:
+                if tuple(np.shape(src[k])) != tuple(t[k].shape):
+                    raise ValueError("slot%d/%s of shape %s does not fit optimizer=%r, whose accumulator has shape %s"
+                                     % (n, k, tuple(np.shape(src[k])), self.optimizer, tuple(t[k].shape)))
+
     def set_slots(self, slots):
+        self._check_slots(slots)      # (before anything is copied)
         for t, src in zip(self.slots, slots):
             for k in TABLE_KEYS:
                 t[k].copy_(torch.as_tensor(np.asarray(src[k], np.float32)))
@@ -1182,6 +1214,8 @@ class Model(object):
     def restore(self, sess, path):
         """model.py:310-313."""
         step, epoch, params, slots = read_checkpoint(path, want_slots=self.slots is not None)
+        if slots is not None:
+            self._check_slots(slots)      # (another optimizer's checkpoint: refused before anything is loaded)
         self.set_params(params)
         self._step, self._epoch = step, epoch
         if slots is not None:

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .input import DataInput, DataInputTest, PackedSet, load_packed
-from .model import KS, Model, SeenItems, full_ranking_metrics, hits_and_rows, metrics_from_histogram
+from .model import KS, LAZY_ADAGRAD_OPTIMIZERS, Model, SeenItems, full_ranking_metrics, hits_and_rows, metrics_from_histogram
 
 FLAGS = [  # (name, type, default)  -- train.py:26-54
     ("hidden_units", int, 64), ("num_blocks", int, 1), ("num_heads", int, 8), ("Ls", int, 10),
@@ -519,6 +519,8 @@ def train_sharded(args):
         raise NotImplementedError("--norm_mode %s: the sharded step forms the clip norm as TF 1.8 does (tf18)" % args.norm_mode)
     if args.matrix_dtype != "f32":
         raise NotImplementedError("--matrix_dtype %s: the sharded step computes in fp32" % args.matrix_dtype)
+    if args.optimizer in LAZY_ADAGRAD_OPTIMIZERS:
+        raise NotImplementedError("--optimizer %s: the sharded step has no Adagrad owner update; train it on one GPU" % args.optimizer)
     lazy_opt = args.optimizer.startswith("lazy_")
     if lazy_opt and args.static_rows:
         raise NotImplementedError("--optimizer %s: --static_rows is the lazy-L2 SGD step's form; the lazy optimizers run "
