@@ -2,7 +2,7 @@
 """Diagnostic: per-phase cycle shares of k_fwd_bwd from in-kernel s_memtime stamps."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the production kernel carries no stamp code: build the variant first (scripts/mkvariants.sh stamps:"-DTLSAN_STAMPS=1")
+# the production kernel carries no stamp code: build the variant first (scripts/mkvariants.sh stamps:"-DTLSAN_STAMPS=1"; scripts/refresh.py runs the stamps as its group `stamps`)
 os.environ.setdefault("TLSAN_LIB_PATH", os.path.join(ROOT, "ab_run", "stamps.so"))
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
