@@ -579,7 +579,10 @@ int tlsan_shard_summary_opt(const float* flat, int32_t n_dense, int32_t n_cate, 
  * row (dense L2, as the reference).  Fixed summation order -> bitwise reproducible.
  * slots: int32 [R*G] device scratch that must be zero on entry and is zero again on exit.
  * sumsq_out[2] (device doubles): sums of squares of the regularised columns of shard / cate_emb
- * after the update; sumsq_f32 (nullable) receives (float)sumsq_out[0]. */
+ * after the update; sumsq_f32 (nullable) receives (float)sumsq_out[0].
+ * Refused before any launch, with nothing written (these two calls and tlsan_shard_apply_lazy alike): G outside 1..16,
+ * W or dc no multiple of 4, W or dc above 256 (the dense forms), a stamp of 0 (the lazy form): TLSAN_E_UNSUPPORTED;
+ * src_off that does not run from 0 to n_recv: TLSAN_E_BADARG; ws_bytes below the _workspace value: TLSAN_E_WORKSPACE. */
 size_t tlsan_shard_apply_workspace(int32_t R, int32_t C);
 int tlsan_shard_apply(float* shard, int32_t ld, int32_t cI, int32_t R, int32_t W, int32_t reg_item, int32_t reg_user,
                       const float* vals, int32_t ldv, const int32_t* rows, int32_t n_recv, const int32_t* src_off,
@@ -655,7 +658,9 @@ int tlsan_shard_apply_lazy_opt(float* shard, int32_t ld, int32_t cI, int32_t R, 
  * tlsan_shard_gather_static: rows_out [G * cap, W], recv_rows [G * cap] (-1 = empty slot); when slots64 is
  *   given, the lazy apply's slot marks are written here (saves a launch): stamp is a DEVICE uint32 (never 0).
  * tlsan_shard_apply_lazy_static: tlsan_shard_apply_lazy over the G * cap slots (rows[e] < 0: skipped); the
- *   device-side stamp is advanced for the next step.  marked != 0: the slot marks were written by the gather. */
+ *   device-side stamp is advanced for the next step: stamps run 1 .. 2^32 - 2, the successor of 2^32 - 2 is 1 (the
+ *   numbering tlsan_amd/dist_step.py gives the host-side stamp of tlsan_shard_apply_lazy).  marked != 0: the slot marks
+ *   were written by the gather. */
 int tlsan_route_plan_static(const int32_t* keys, int32_t n_keys, int32_t R, int32_t G, const int32_t* cate_by_key,
                             int32_t* flags, int32_t* rank, int32_t* uniq, int32_t* n_uniq, int32_t* sendbuf, int32_t cap,
                             int32_t* cate_c, int32_t* comp, int32_t* counts_out, int32_t* status, void* stream);

@@ -11,6 +11,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from tests.helpers import make_config, random_batch, random_params
+from tests.shard_ref import _np_opt_elem
 from tests.test_gpu_dist import _concat, _driver_worker, _free_port
 from tests.test_gpu_lazy_opt import (LR, ROW_TABLES, _check, _cover_all_batch, _p32, _sync_amb, _tuple, random_slots,
                                      restricted_step, used_rows)
@@ -261,22 +262,6 @@ def test_sharded_train_driver_with_lazy_adam(tmp_path):
     extra = ("--optimizer", "lazy_adam", "--learning_rate", "0.01")
     mp.spawn(_driver_worker, args=(2, _free_port(), ret, str(tmp_path), extra), nprocs=2, join=True)
     assert all(v == "ok" for v in dict(ret).values()) and len(ret) == 2, dict(ret)
-
-
-def _np_opt_elem(kind, lr, b1, b2, eps, step, w, g, s1, s2):
-    """opt_elem of csrc/tlsan_opt.h in float64 (TF 1.8's Adam / RMSProp / Adadelta)"""
-    if kind == "adam":
-        s1 = s1 * b1 + g * (1.0 - b1)
-        s2 = s2 * b2 + g * g * (1.0 - b2)
-        alpha = lr * np.sqrt(1.0 - b2 ** step) / (1.0 - b1 ** step)
-        return w - alpha * s1 / (np.sqrt(s2) + eps), s1, s2
-    if kind == "rmsprop":
-        s1 = s1 * b1 + g * g * (1.0 - b1)
-        s2 = s2 * b2 + lr * g / np.sqrt(s1 + eps)
-        return w - s2, s1, s2
-    s1 = s1 * b1 + g * g * (1.0 - b1)
-    upd = np.sqrt(s2 + eps) / np.sqrt(s1 + eps) * g
-    return w - upd * lr, s1, s2 * b1 + upd * upd * (1.0 - b1)
 
 
 # (di, Ls, dc, ranks): the four row-width forms of the kernel (64 NCH floats per row, NCH = 1..4), and more ranks than it
