@@ -11,6 +11,8 @@
 // Per-use gradient rows are written once with plain 16-B stores at destination-sorted
 // positions (drawn from the fill cursors of the inverted index with one returning integer
 // atomic per use); k_apply_* sum each row's contiguous segment with exact arithmetic.
+// The variant predicates and the layout of the dynamic LDS block are AttnLds (tlsan_attn_lds.h), which the launcher
+// sizes the block by.
 //
 // The kernel is bound by the latency of ONE wavefront's dependent chain (4096 samples are
 // only 2 wavefronts per SIMD), so the code is organised to keep that chain short:
@@ -28,7 +30,6 @@
 // else owns before the first pass).  A count that only grows needs no generation: the wavefront that arrives as number
 // 4 k + j waits for 4 (k + 1).  All four are resident, so the wait ends.
 #define TLSAN_FIX_WGS 64          // workgroups that correct (fewer when the grid is smaller)
-#define TLSAN_FIX_LDS_BYTES (16 + FIX_LDS_BYTES)   // counter + FixLds (tlsan_fix.h)
 __device__ __forceinline__ void fix_team_sync() {
   extern __shared__ __attribute__((aligned(16))) int fix_lds[];
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -42,6 +43,8 @@ __device__ __forceinline__ void fix_team_sync() {
 }
 #define AP_SYNC() fix_team_sync()
 #include "tlsan_fix.h"
+#include "tlsan_attn_lds.h"
+static_assert(TLSAN_FIX_LDS_BYTES == 16 + FIX_LDS_BYTES, "the floor of a training launch's LDS block: counter + FixLds");
 
 // Every workgroup of a training launch calls this when the header says that the previous step was clipped
 // (StateHdr::fix_pending): the first F = min(grid, TLSAN_FIX_WGS) workgroups walk that step's row blocks and dense blocks with
@@ -89,10 +92,6 @@ static __device__ __noinline__ void spec_fix_head(StateHdr* hdr, const ApplyArgs
   __syncthreads();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }
-
-#ifndef TLSAN_STAMPS
-#define TLSAN_STAMPS 0   // 1: the diagnostic build with in-kernel cycle stamps (scripts/stamps.py)
-#endif
 
 // ---------------------------------------------------------------------------------------
 // feature_wise_attention forward (model.py:370-394) over NPOS static positions held in
@@ -478,74 +477,42 @@ __global__ __launch_bounds__(512) void k_fwd_bwd(FwdArgs a) {
   static_assert(!DROP || TRAIN, "dropout: train steps only");
   static_assert(!CSEG || TRAIN, "category segments: train steps only");
   using G = Geo<D, DH, NWV>;
-  static_assert(G::NSB == 16 || (G::NSB == 8 && !LSTREAM), "8-sample workgroups: windows in registers only");
   using opd = typename MMT<MM>::opd;   // an operand of one 16-deep contraction (tlsan_common.h)
   constexpr int NB = G::NB, CPS = G::CPS, SPW = G::SPW, NW = G::NW, NSB = G::NSB;
-  constexpr int LS = LSTREAM ? 1 : TLSAN_LS_MAX;             // positions held in registers
-  constexpr int LSC = LSTREAM ? TLSAN_LS_CAP : TLSAN_LS_MAX;  // position slots in the LDS tables
+  using Lds = AttnLds<G, TRAIN, LSTREAM, DROP, CSEG, float*>;   // the variant predicates and the LDS block's layout (tlsan_attn_lds.h)
+  static_assert(Lds::SUPPORTED, "8-sample workgroups: windows in registers only");
+  static_assert(Lds::fits(), "k_fwd_bwd's LDS block: more than a workgroup may have");
+  constexpr int LS = Lds::LS, LSC = Lds::LSC, LSCP = Lds::LSCP, NF = Lds::NF, NLK = Lds::NLK;
   constexpr int LSTR = G::LSTR, TSTR = G::TSTR, CW = G::CW;
-  constexpr int WB = 2 * DH * DH + 2 * DH;    // floats of one attention block's weights
-  // per-sample position slots: long, session (the batch's padded session length, rounded up to 4), 3 singles
-  // (CSEG keeps two such arrays and sizes them by the batch; otherwise the slot count is a compile-time constant)
-
-  constexpr bool LKEY = NB == 1 && !LSTREAM;   // row keys reach a sample's lanes through the LDS (see g_item below, P1, fetch_row_of)
-  constexpr int NLK = 16;                                    // session entries per chunk of keys
+  constexpr int WB = Lds::WB, PP = Lds::PP, WBP = Lds::WBP;
+  constexpr bool LKEY = Lds::LKEY, FLAT = Lds::FLAT, FLATG = Lds::FLATG, USE_SW = Lds::USE_SW, PERM = Lds::PERM, KEEP_A = Lds::KEEP_A;
   const bool FUSE_RT = a.fuse_dk != 0;   // (this launch forms the dK partials itself; as a compile-time constant: -0.2 us/step, not worth a variant)
-  // FLAT (streamed windows): the window positions of the workgroup's 16 samples form ONE list that is dealt out evenly
-  // to its 16 column groups (a wavefront's lanes that share a sample slot) -- see P1.  Its entries, the per-sample
-  // softmax statistics and the long-term vectors live in the LDS, where any group can reach them.
-  constexpr bool FLAT = LSTREAM && !DROP;   // (dropout keeps a window per column group: its pattern is indexed by (sample, position))
-  constexpr int NF = FLAT ? NSB * TLSAN_LS_CAP : 0;      // entries of the flat list (every window at the cap)
-  // NB > 1 (d = 256): the LDS has no room for the per-sample statistics and long-term vectors beside the list -- they
-  // go through global memory (FwdArgs.gStat, gLong: 32 KB per workgroup, L2-resident), the attention weights are
-  // read from `dense` instead of an LDS copy, and the position tables keep session slots only
-  constexpr bool FLATG = FLAT && NB > 1;
-  constexpr bool USE_SW = G::USE_SW && !FLATG;          // attention weights staged in LDS (when they fit)
-  constexpr int LSCP = FLAT ? 0 : LSC;                  // long slots of the position tables (FLAT: the list holds them)
-  // (8-sample workgroups size them by the batch as well: two workgroups must fit a CU's LDS)
-  // (the diagnostic stamps build as well: its 2 KB of stamps must fit beside the 160 KB the d = 128 training kernel fills)
-  const int SNS = (CSEG || FLATG || NSB < 16 || TLSAN_STAMPS) ? ((a.b.Sn + 3) & ~3) : TLSAN_SN_CAP;
-  const int PSTR = LSCP + SNS + 4;
-  const int P_TGT = LSCP + SNS, P_USR = P_TGT + 1, P_UC = P_TGT + 2;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sA = smem;                   // [NSB][LSTR]  long -> dbridge
-  float* sB0 = sA + NSB * LSTR;       // [NSB][LSTR]  bridge -> dlong  (FLAT: placed in front of sT instead, see sPart)
-  float* sL = FLAT ? sB0 : sB0 + NSB * LSTR;   // [NSB][LSTR]  long, kept for the fused dK product (TRAIN && FUSE_DK) and for FLAT's backward
-  float* sS = sL + ((TRAIN && ((G::FUSE_DK && FUSE_RT) || (FLAT && !FLATG))) ? NSB * LSTR : 0);  // [NW][4] scalar staging  (sL exists in launches that fuse: tlsan_attn_inst.h)
-  int* sSK = (int*)(sS + NW * 4);     // LKEY: [NW][2][SPW][NLK] item ids | categories of the current chunk of session entries
-  float* sH = (float*)(sSK + (LKEY ? NW * 2 * SPW * NLK : 0));   // [NSB][2*LS] hist_t and usert*hist_t of the pass  (FLAT: [2][NF], by flat index)
-  float* sW = sH + NSB * 2 * LSC;     // [2][WB] attention weights (W1,b1,W2,b2) of both blocks  (PERM: [2][WBP], see below)
-  // PERM (two 16-channel blocks per column, d = 256): the weight fragments are re-read from the LDS at every position
-  // (Geo::AT_USE), and read from the row-major copy that costs 8 two-dword reads with computed addresses per fragment,
-  // four-way bank-conflicted (a fragment's lanes (q, r) read W[(16 kb + 4 q + s) * 32 + 16 jb + r]: the four q hit the
-  // same banks) -- 26 M conflict cycles per launch, 28 % of the kernel's time (profiles/r04_pmc_d256_summary.txt).  The LDS
-  // copy is therefore kept in FRAGMENT order, every matrix twice: table [pair][lane][4] with pair = the fragment's
-  // (out block, in block) -- a fragment is NB * NB conflict-free 16-byte reads at constant offsets from the lane's base.
-  // Per attention block: [W1 as T fragments | W2 as T | W1 as N | W2 as N | b1 | b2].
-  constexpr bool PERM = USE_SW && NB > 1 && !LSTREAM;   // (streamed windows with dropout keep the row-major copy: the 16 KB more do not fit beside their position tables)
-  constexpr int PP = NB * NB * 256;            // floats of one fragment table
-  constexpr int WBP = 4 * PP + 2 * DH;         // floats of one attention block's weights in fragment order
-  int* sP = (int*)(sW + (USE_SW ? (PERM ? 2 * WBP : 2 * WB) : 0));  // [NSB][PSTR] destination-sorted row of every use
-  // CSEG (FwdArgs.cseg, many categories): the category half of an item use's gradient row goes to the category's own
-  // segment of Gc -- its position, drawn from the category's cursor, sits in sPc beside the item position in sP
-  int* sPc = sP + (TRAIN ? NSB * PSTR : 0);      // [NSB][PSTR], only when a.cseg
-  int* sFid = sPc + ((TRAIN && CSEG) ? NSB * PSTR : 0);   // FLAT: [NF] item id, category, (slot << 8 | position) of every list entry,
-  int* sFct = sFid + NF;                                  //       its destination rows (TRAIN), and below the per-sample statistics
-  int* sFst = sFct + NF;
-  int* sFpos = sFst + NF;
-  int* sFcpos = sFpos + (TRAIN ? NF : 0);
-  float* sMx = (float*)(sFcpos + ((TRAIN && CSEG) ? NF : 0));   // [NSB][LSTR] per-channel max of the window's scores
-  float* sIz = sMx + ((FLAT && !FLATG && TRAIN) ? NSB * LSTR : 0);   // [NSB][LSTR] 1 / sum of exponentials
-  int* sBx = (int*)(sIz + ((FLAT && !FLATG && TRAIN) ? NSB * LSTR : 0));   // FLATG: [NSB] the slots' samples (rows of gStat / gLong)
-  int* sSb = sBx + (FLATG ? NSB : 0);                   // evaluation, FLAT: [NSB] the slots' samples (rows of FwdArgs.att0)
-  float* sB = FLAT ? (float*)(sSb + ((!TRAIN && FLAT) ? NSB : 0)) : sB0;
-  float* sT = FLAT ? sB + NSB * LSTR : (float*)sFid;  // per-wave transpose scratch / staging
-  // FLAT: the partial softmax states of P1, 32 slots of [3][D], lie over sB and sT (neither is touched before P2)
-  float* sPart = sB;
-  static_assert(!FLAT || 32 * 3 * D <= NSB * LSTR + NW * G::WSCR, "partial states must fit sB + sT");
-  float* sFht = sH;
-  float* sFuh = sH + NF;
-  constexpr bool KEEP_A = G::KEEP_A && TRAIN && !LSTREAM;
+  const Lds L = {smem, a.b.Sn, FUSE_RT};
+  const int PSTR = L.PSTR, P_TGT = L.P_TGT, P_USR = L.P_USR, P_UC = L.P_UC;
+  float* sA = L.A.at;
+  float* sB0 = L.B0.at;
+  float* sL = L.L.at;
+  float* sS = L.S.at;
+  int* sSK = L.SK.at;
+  float* sH = L.H.at;
+  float* sW = L.W.at;
+  int* sP = L.P.at;
+  int* sPc = L.Pc.at;
+  int* sFid = L.Fid.at;
+  int* sFct = L.Fct.at;
+  int* sFst = L.Fst.at;
+  int* sFpos = L.Fpos.at;
+  int* sFcpos = L.Fcpos.at;
+  float* sMx = L.Mx.at;
+  float* sIz = L.Iz.at;
+  int* sBx = L.Bx.at;
+  int* sSb = L.Sb.at;
+  float* sB = L.B.at;
+  float* sT = L.T.at;
+  float* sPart = L.Part.at;
+  float* sFht = L.Fht.at;
+  float* sFuh = L.Fuh.at;
   constexpr bool PIPE5 = KEEP_A && !DROP;       // long backward as a skewed software pipeline (see P5)
   constexpr bool LPF = NB == 1;                 // streamed windows: the next position's row is prefetched
   // ... and the next chunk's ids / weights / categories are loaded a chunk ahead (d = 256 in fp32 has no registers for
@@ -556,7 +523,7 @@ __global__ __launch_bounds__(512) void k_fwd_bwd(FwdArgs a) {
   const int s_loc = r / CPS, col = r % CPS;
   const int srow = wave * SPW + s_loc;  // sample row inside the workgroup pass
   float* T = sT + wave * G::WSCR;
-  float* sAw = sT + NW * G::WSCR + wave * (LS * NB * 256) + lane * 4;  // this lane's slot of the kept softmax weights
+  float* sAw = L.Aw.at + wave * Lds::AW_WAVE + lane * 4;  // this lane's slot of the kept softmax weights
   int chb[NB];
 #pragma unroll
   for (int kb = 0; kb < NB; ++kb) chb[kb] = col * CW + 16 * kb + 4 * q;
@@ -654,11 +621,8 @@ __global__ __launch_bounds__(512) void k_fwd_bwd(FwdArgs a) {
   // diagnostic cycle stamps: only in a -DTLSAN_STAMPS=1 build (scripts/stamps.py loads it through TLSAN_LIB_PATH;
   // the production kernel carries no stamp code).  Kept in the LDS while the pass runs -- a global store per stamp
   // would sit in front of every later vmcnt(0) wait and distort what it measures -- and copied out at the end.
-#ifndef TLSAN_STAMPS
-#define TLSAN_STAMPS 0
-#endif
 #if TLSAN_STAMPS
-  unsigned long long* sStamp = (unsigned long long*)(sT + NW * G::WSCR + ((G::KEEP_A && TRAIN && !LSTREAM) ? NW * LS * NB * 256 : 0)) + wave * 32;
+  unsigned long long* sStamp = (unsigned long long*)L.Stamp.at + wave * 32;
 #define TLSAN_STAMP(k)                                                                       \
   do {                                                                                       \
     if (a.stamps != nullptr && lane == 0) sStamp[k] = __builtin_amdgcn_s_memtime();          \
@@ -696,7 +660,7 @@ __global__ __launch_bounds__(512) void k_fwd_bwd(FwdArgs a) {
       int rank = 0;
 #pragma unroll
       for (int j = 0; j < NSB; ++j) rank += (__builtin_amdgcn_readlane(key, j) > key) ? 1 : 0;
-      int* sPerm = (int*)T;                       // (the wave's own scratch: free until P3)
+      int* sPerm = (int*)T;                       // (the wave's own scratch, free until P3: Lds::Perm)
       // (windows held in registers, two samples per wavefront: the wavefront with the k-th longest session also takes
       // the k-th shortest -- its lanes then share the long one, see HELP in P3)
       const int slot = (SPW == 2 && !DROP) ? (rank < NSB / 2 ? 2 * rank : 2 * (NSB - 1 - rank) + 1) : rank;
@@ -1328,7 +1292,7 @@ __global__ __launch_bounds__(512) void k_fwd_bwd(FwdArgs a) {
       *(f32x4*)(sA + srow * LSTR + chb[kb]) = long4[kb];
       if constexpr (TRAIN && G::FUSE_DK) {
         // (FLATG, d = 128 with 32 channels per head: the streamed backward reads `long` from gLong, not from sL)
-        if (FUSE_RT || (FLAT && !FLATG)) *(f32x4*)(sL + srow * LSTR + chb[kb]) = long4[kb];
+        if (L.has_sL) *(f32x4*)(sL + srow * LSTR + chb[kb]) = long4[kb];
         if ((!FUSE_RT || FLATG) && vs) *(f32x4*)(a.gLong + (size_t)bidx_t * D + chb[kb]) = long4[kb];
       } else if (TRAIN && vs) {
         *(f32x4*)(a.gLong + (size_t)bidx_t * D + chb[kb]) = long4[kb];
