@@ -476,6 +476,52 @@ int tlsan_eval_topk(const tlsan_dims* dims, const tlsan_params* p, const float* 
 int tlsan_topk_merge(const int32_t* cand_ids, const float* cand_scores, int32_t B, int32_t n_lists, int32_t K,
                      int32_t* ids, float* scores, void* stream);
 
+/* Similar-items lists ("more like this"): for each query item the K nearest items of the table by the representation
+ * the model scores with,  w_n = [item_emb[n] || cate_emb[item_cate[n]]]  (d columns; bf16 tables widened exactly to
+ * fp32), without materialising the [Q, I] similarities.  No user context, no forward pass, no bias.  With
+ *   acc(q, n) the fp32 MFMA accumulation of w_q . w_n on STORED values, in the k-order and instruction chain of
+ *     tlsan_eval_topk's tiles,
+ *   inv(n) = 1 / sqrtf(ss_n),  ss_n = sum_k w_n[k]^2  in fp32 in one fixed order that does not depend on the launch
+ *     (0 when ss_n == 0), computed by one device function for queries and table items alike,
+ *   P the table scale (*p->scale; 1 when NULL),
+ * the score of item n for query q is
+ *   TLSAN_SIM_DOT:     s = fl(acc * fl(P * P))             -- the product of the true vectors
+ *   TLSAN_SIM_COSINE:  s = fl(acc * fl(inv(q) * inv(n)))   -- P cancels and is not applied
+ * Both are symmetric in bits: s(a, b) and s(b, a) are the same float, as are the scores of bit-identical rows.
+ * Order: tlsan_eval_topk's -- higher score first, equal scores -> lower GLOBAL id first; +0.0 == -0.0 (a zero score is
+ * returned as +0.0); a NaN score ranks after every other score.  1 <= K <= 256.
+ *
+ * tlsan_item_vectors: vec[q] = w of item ids[q] and inv_norm[q] = inv of it (inv_norm may be NULL), for every id this
+ *   table holds: local item n is global id n * id_mul + id_add (1 and 0 for a whole table), as in
+ *   tlsan_eval_counts_shard.  Ids the table does not hold, and negative ids, get ZEROS in both, so that the results of
+ *   the ranks of a sharded table combine (exactly one rank holds an id).  vec [Q, d] float32, inv_norm [Q].
+ *
+ * tlsan_similar_topk: ids [Q, K] int32 (global), scores [Q, K] float32 for the queries
+ *   qvec [Q, d] / qinv [Q]: what tlsan_item_vectors wrote (qinv may be NULL for TLSAN_SIM_DOT); qids [Q]: their global
+ *   ids.  The query item never appears in its own list.  A row with qids[q] < 0 is padding -- all id -1, score -inf --
+ *   and so is, in the whole-table form (id_mul == 1, id_add == 0), a row with qids[q] >= item_count.
+ *   excl_off [Q + 1] / excl_ids (both NULL: none): row q's list excl_ids[excl_off[q] .. excl_off[q+1]) of global ids,
+ *     ascending, tlsan_eval_topk's format; those items never appear in the row (repeats and ids outside the table are
+ *     ignored).
+ *   Rows with fewer than K eligible items end in id -1, score -inf.
+ *   Item-sharded form: every rank passes the same queries and its own table; the ranks' lists of a row merge with
+ *     tlsan_topk_merge.
+ *   A row's result does not depend on Q, on the other rows, on the launch geometry or on the number of ranks.
+ * Neither call changes the parameters, P or any state.  A sum of squares that overflows fp32 has inv 0.
+ * Workspace: tlsan_similar_workspace_bytes (0, with tlsan_last_error set, for bad dims / K / Q).  Refused before any
+ * launch, with the function's name in tlsan_last_error: NULL pointers, K outside 1..256, Q < 1, an unknown metric, bad
+ * dims (TLSAN_E_BADARG / TLSAN_E_UNSUPPORTED as everywhere), a workspace that is NULL or too small (TLSAN_E_WORKSPACE).
+ * The three functions and the two constants are additions: nothing else in the ABI changed (TLSAN_ABI_VERSION stays 14). */
+#define TLSAN_SIM_DOT 0
+#define TLSAN_SIM_COSINE 1
+int tlsan_item_vectors(const tlsan_dims* dims, const tlsan_params* p, const int32_t* ids, int32_t Q, int32_t id_mul,
+                       int32_t id_add, float* vec, float* inv_norm, void* stream);
+size_t tlsan_similar_workspace_bytes(const tlsan_dims* dims, int32_t Q, int32_t K);
+int tlsan_similar_topk(const tlsan_dims* dims, const tlsan_params* p, const float* qvec, const float* qinv,
+                       const int32_t* qids, int32_t Q, int32_t K, int32_t metric, const int32_t* excl_off,
+                       const int32_t* excl_ids, int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws,
+                       size_t ws_bytes, void* stream);
+
 /* Scores of caller-given candidates (a re-ranking of a retrieval stage's items, or a sampled evaluation):
  *   scores[b, c] = u_t[b] . [item_emb || cate_emb[item_cate]][g] + item_b[g],  g = cand[b, c] (global id),
  * for u_t [B, d], cand [B, C] int32, scores [B, C] float32.  Each score equals tlsan_eval_label_scores' for the

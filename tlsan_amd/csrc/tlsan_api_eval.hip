@@ -1,9 +1,12 @@
 // tlsan_api_eval.hip -- the evaluation entry points of the C ABI (include/tlsan.h): ranks of the labels among all items,
-// top-K items, caller-given candidates and negative sampling.  The kernels of tlsan_eval.h are compiled here; the top-K and
-// candidate kernels in units of their own (tlsan_topk.hip, tlsan_cand.hip).
+// top-K items, similar-items lists, caller-given candidates and negative sampling.  The kernels of tlsan_eval.h are compiled
+// here; the top-K, similar-items and candidate kernels in units of their own (tlsan_topk.hip, tlsan_similar.hip, tlsan_cand.hip).
+#include <stdio.h>
+
 #include "tlsan_host.h"
 #include "tlsan_eval.h"
 #include "tlsan_topk.h"
+#include "tlsan_similar.h"
 #include "tlsan_cand.h"
 
 extern "C" {
@@ -195,6 +198,103 @@ int tlsan_topk_merge(const int32_t* cand_ids, const float* cand_scores, int32_t 
   if ((long long)n_lists * K >= (1LL << 30)) return fail(TLSAN_E_UNSUPPORTED, "tlsan_topk_merge: n_lists * K too large");
   const hipError_t err = tlsan_launch_topk_merge(cand_ids, cand_scores, B, n_lists, K, ids, scores, (hipStream_t)stream);
   if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_topk_merge: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+// ---- similar-items lists (tlsan_similar.h) ----
+// a refusal of shape_of / check_params, with the entry point's name in front of its message
+static int sim_named(const char* fn, int rc) {
+  char m[384];
+  snprintf(m, sizeof(m), "%s", tlsan_last_error());
+  return fail(rc, "%s: %s", fn, m);
+}
+
+static bool sim_ids_ok(const tlsan_dims* d, int32_t id_mul, int32_t id_add) {
+  return id_mul >= 1 && id_add >= 0 && (long long)(d->item_count - 1) * id_mul + id_add < (1LL << 31);
+}
+
+int tlsan_item_vectors(const tlsan_dims* d, const tlsan_params* p, const int32_t* ids, int32_t Q, int32_t id_mul,
+                       int32_t id_add, float* vec, float* inv_norm, void* stream) {
+  Shape s;
+  int rc = shape_of(d, &s);
+  if (rc || (rc = check_params(p))) return sim_named("tlsan_item_vectors", rc);
+  if (!ids || !vec) return fail(TLSAN_E_BADARG, "tlsan_item_vectors: NULL argument");
+  if (Q < 1) return fail(TLSAN_E_BADARG, "tlsan_item_vectors: Q must be >= 1 (got %d)", Q);
+  if (!sim_ids_ok(d, id_mul, id_add))
+    return fail(TLSAN_E_BADARG, "tlsan_item_vectors: global ids n * id_mul + id_add must be non-negative int32");
+  VecArgs va;
+  memset(&va, 0, sizeof(va));
+  EvalArgs& e = va.e;
+  e.p = norm_params(p, d); e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate; e.id_mul = id_mul; e.id_add = id_add;
+  va.ids = ids; va.Q = Q; va.vec = vec; va.inv = inv_norm;
+  const hipError_t err = tlsan_launch_item_vectors(va, s.D, (hipStream_t)stream);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_item_vectors: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+struct SimWs {
+  TopkWs t;            // the dense item matrix (or none) and the slices' lists, as top-K's
+  float* inv;          // [I] inv of the table's items
+  size_t bytes;
+};
+
+static void carve_similar(const tlsan_dims* d, int D, int Q, int K, char* base, SimWs* w) {
+  carve_topk(d, D, Q, K, base, &w->t);
+  w->inv = base ? (float*)(base + w->t.bytes) : nullptr;
+  w->bytes = w->t.bytes + al(sizeof(float) * (size_t)d->item_count);
+}
+
+size_t tlsan_similar_workspace_bytes(const tlsan_dims* d, int32_t Q, int32_t K) {
+  Shape s;
+  const int rc = shape_of(d, &s);
+  if (rc) { sim_named("tlsan_similar_workspace_bytes", rc); return 0; }
+  if (K < 1 || K > TOPK_MAX) { fail(TLSAN_E_BADARG, "tlsan_similar_workspace_bytes: K must be in 1..%d (got %d)", TOPK_MAX, K); return 0; }
+  if (Q < 1) { fail(TLSAN_E_BADARG, "tlsan_similar_workspace_bytes: Q must be >= 1 (got %d)", Q); return 0; }
+  SimWs w;
+  carve_similar(d, s.D, Q, K, nullptr, &w);
+  return w.bytes;
+}
+
+int tlsan_similar_topk(const tlsan_dims* d, const tlsan_params* p, const float* qvec, const float* qinv, const int32_t* qids,
+                       int32_t Q, int32_t K, int32_t metric, const int32_t* excl_off, const int32_t* excl_ids,
+                       int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws, size_t ws_bytes, void* stream) {
+  Shape s;
+  int rc = shape_of(d, &s);
+  if (rc || (rc = check_params(p))) return sim_named("tlsan_similar_topk", rc);
+  if (metric != SIM_DOT && metric != SIM_COSINE)
+    return fail(TLSAN_E_BADARG, "tlsan_similar_topk: metric must be TLSAN_SIM_DOT or TLSAN_SIM_COSINE (got %d)", metric);
+  if (!qvec || !qids || !ids || !scores || (metric == SIM_COSINE && !qinv))
+    return fail(TLSAN_E_BADARG, "tlsan_similar_topk: NULL argument");
+  if (Q < 1) return fail(TLSAN_E_BADARG, "tlsan_similar_topk: Q must be >= 1 (got %d)", Q);
+  if (K < 1 || K > TOPK_MAX) return fail(TLSAN_E_BADARG, "tlsan_similar_topk: K must be in 1..%d (got %d)", TOPK_MAX, K);
+  if (!excl_off != !excl_ids) return fail(TLSAN_E_BADARG, "tlsan_similar_topk: excl_off and excl_ids go together");
+  if (!sim_ids_ok(d, id_mul, id_add))
+    return fail(TLSAN_E_BADARG, "tlsan_similar_topk: global ids n * id_mul + id_add must be non-negative int32");
+  if (!ws) return fail(TLSAN_E_WORKSPACE, "tlsan_similar_topk: ws is NULL");
+  SimWs w;
+  carve_similar(d, s.D, Q, K, (char*)ws, &w);
+  if (w.bytes > ws_bytes)
+    return fail(TLSAN_E_WORKSPACE, "tlsan_similar_topk: workspace too small: need %zu have %zu", w.bytes, ws_bytes);
+  hipStream_t hs = (hipStream_t)stream;
+  const int nsl = w.t.nsl;
+  SimArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  TopkArgs& ta = sa.t;
+  EvalArgs& e = ta.e;
+  e.p = norm_params(p, d); e.u_t = qvec; e.B = Q; e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate;
+  e.all_emb = w.t.all_emb; e.id_mul = id_mul; e.id_add = id_add;
+  ta.K = K; ta.excl_off = excl_off; ta.excl_ids = excl_ids;
+  ta.ids = nsl > 1 ? w.t.ids : ids;
+  ta.scores = nsl > 1 ? w.t.scores : scores;
+  sa.qinv = qinv; sa.qids = qids; sa.inv = w.inv; sa.metric = metric;
+  hipError_t err = hipSuccess;
+  // the inv pass also builds the dense item matrix; dot without one needs neither
+  if ((metric == SIM_COSINE || e.all_emb) && (err = tlsan_launch_sim_prep(e, s.D, w.inv, hs)) != hipSuccess)
+    return fail(TLSAN_E_LAUNCH, "k_sim_prep: %s", hipGetErrorString(err));
+  if ((err = tlsan_launch_similar_topk(sa, s.D, nsl, hs)) != hipSuccess)
+    return fail(TLSAN_E_LAUNCH, "k_similar_topk: %s", hipGetErrorString(err));
+  if (nsl > 1 && (err = tlsan_launch_topk_merge(w.t.ids, w.t.scores, Q, nsl, K, ids, scores, hs)) != hipSuccess)
+    return fail(TLSAN_E_LAUNCH, "k_topk_merge: %s", hipGetErrorString(err));
   return TLSAN_OK;
 }
 

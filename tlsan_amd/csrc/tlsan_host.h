@@ -12,6 +12,8 @@ struct ScanArgs;                                   // tlsan_index_args.h
 struct FinLaunch; struct ApplyArgs;                // tlsan_update_args.h
 struct TopkArgs;                                   // tlsan_topk.h
 struct CandArgs; struct NegArgs; struct ExclArgs;  // tlsan_cand.h
+struct EvalArgs;                                   // tlsan_eval.h
+struct SimArgs; struct VecArgs;                    // tlsan_similar.h
 
 #pragma GCC visibility push(hidden)
 
@@ -83,6 +85,10 @@ void tlsan_launch_spec_flush(bool wide, bool bf16, const void* args, void* hdr, 
 hipError_t tlsan_launch_topk(const TopkArgs& a, int D, int nslices, hipStream_t hs);
 hipError_t tlsan_launch_topk_merge(const int32_t* cid, const float* csc, int B, int nl, int K, int32_t* ids, float* scores,
                                    hipStream_t hs);
+// ---- similar-items lists (tlsan_similar.hip): the inv pass (with the dense item matrix), the selection, the query vectors
+hipError_t tlsan_launch_sim_prep(const EvalArgs& e, int D, float* inv, hipStream_t hs);
+hipError_t tlsan_launch_similar_topk(const SimArgs& a, int D, int nslices, hipStream_t hs);
+hipError_t tlsan_launch_item_vectors(const VecArgs& a, int D, hipStream_t hs);
 // ---- candidate scoring, candidate ranks, negative sampling (tlsan_cand.hip)
 hipError_t tlsan_launch_score_cand(const CandArgs& a, int D, hipStream_t hs);
 hipError_t tlsan_launch_cand_ranks(const int32_t* cand, const float* scores, int B, int C, int32_t* ranks, hipStream_t hs);

@@ -31,7 +31,7 @@ from .dist_comm import (ExchangePlan, KeyRouter, ModPartition, RowExchange, _sta
 from .dist_step import DynamicStep, FlatLayout, StaticStep, fused_params
 from .model import (LAZY_ADAGRAD_OPTIMIZERS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer, candidate_tensor, eval_topk,
                     exclusion_csr, grow_workspace, hits_and_rows, pack_dense, read_checkpoint, sample_negatives, sampled_ranks,
-                    score_candidates, topk_merge, unpack_dense, write_checkpoint)
+                    score_candidates, item_vectors, similar_queries, similar_topk, topk_merge, unpack_dense, write_checkpoint)
 
 
 def _ru4(x):
@@ -423,6 +423,39 @@ class ShardedModel:
                 a2a(rsc, csc, None, None, self.group)
                 cid, csc = topk_merge(self.lib, rid.view(self.world, B, k).transpose(0, 1).contiguous(),
                                       rsc.view(self.world, B, k).transpose(0, 1).contiguous(), st)
+        return cid, csc
+
+    def similar_items(self, items, k, metric="cosine", exclude=None):
+        """Model.similar_items, collective: every rank passes the same items (and k, metric, exclude) and every rank
+        gets all Q lists.  Each rank reads the stored vectors and inverse norms of the queries ITS item shard holds
+        (tlsan_item_vectors, zeros for the others); they are all-gathered and each query's are SELECTED from the one
+        rank that holds it (a sum would turn -0 into +0); every rank selects the k nearest of its shard for all queries
+        (tlsan_similar_topk, global ids n * world + rank), the lists are all-gathered and merged (tlsan_topk_merge).
+        Same ids and score bits as Model.similar_items on the gathered parameters."""
+        qids, mc, excl = similar_queries(items, self.I, metric, exclude, self.device)
+        if self._static is not None:   # (plans announced ahead may be running on the side streams)
+            self._static.drain()
+        Q, k, st = int(qids.shape[0]), int(k), self._stream()
+        nloc, ldims, lp = self._item_shard()
+        if nloc > 0:
+            vec, inv = item_vectors(self.lib, ldims, lp, qids, self.world, self.rank, st)
+        else:
+            vec = torch.zeros(Q, self.d, dtype=torch.float32, device=self.device)
+            inv = torch.zeros(Q, dtype=torch.float32, device=self.device)
+        if self.world > 1:
+            owner = (qids % self.world).long()
+            vec = torch.gather(allgather_rows(vec, self.group).view(self.world, Q, self.d), 0,
+                               owner[None, :, None].expand(1, Q, self.d))[0].contiguous()
+            inv = torch.gather(allgather_rows(inv, self.group).view(self.world, Q), 0, owner[None])[0].contiguous()
+        if nloc > 0:
+            cid, csc = similar_topk(self.lib, ldims, lp, vec, inv, qids, k, mc, excl, self.world, self.rank,
+                                    lambda nbytes: grow_workspace(self, "_tws", nbytes), st)
+        else:
+            cid = torch.full((Q, k), -1, dtype=torch.int32, device=self.device)
+            csc = torch.full((Q, k), float("-inf"), dtype=torch.float32, device=self.device)
+        if self.world > 1:
+            cid, csc = topk_merge(self.lib, allgather_rows(cid, self.group).view(self.world, Q, k).transpose(0, 1).contiguous(),
+                                  allgather_rows(csc, self.group).view(self.world, Q, k).transpose(0, 1).contiguous(), st)
         return cid, csc
 
     def _score_owned(self, ut, cand):

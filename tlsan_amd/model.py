@@ -271,14 +271,25 @@ def exclusion_csr(db, exclude, n_items):
             raise ValueError("exclude must be None, 'history', a SeenItems or a sequence of per-row id arrays")
         vals = _input_items(db, pad)
     else:
-        if len(exclude) != B:
-            raise ValueError("exclude: %d lists for %d rows" % (len(exclude), B))
-        lists = [np.asarray(x, np.int64).reshape(-1) for x in exclude]
-        host = np.full((B, max([len(x) for x in lists] + [1])), pad, np.int64)
-        for r, x in enumerate(lists):
-            host[r, :len(x)] = x
-        host[(host < 0) | (host >= n_items)] = pad
-        vals = torch.as_tensor(host.astype(np.int32)).to(dev)
+        vals = _listed_items(exclude, B, n_items, dev, pad)
+    return _csr_of_slots(vals, pad)
+
+
+def _listed_items(exclude, B, n_items, dev, pad):
+    """A sequence of B arrays of item ids -> [B, widest] int32 device tensor, the rest (and ids outside the table) `pad`."""
+    if len(exclude) != B:
+        raise ValueError("exclude: %d lists for %d rows" % (len(exclude), B))
+    lists = [np.asarray(x, np.int64).reshape(-1) for x in exclude]
+    host = np.full((B, max([len(x) for x in lists] + [1])), pad, np.int64)
+    for r, x in enumerate(lists):
+        host[r, :len(x)] = x
+    host[(host < 0) | (host >= n_items)] = pad
+    return torch.as_tensor(host.astype(np.int32)).to(dev)
+
+
+def _csr_of_slots(vals, pad):
+    """[B, w] item ids (unused slots `pad`) -> the CSR of exclusion_csr: every row sorted, its repeats set to `pad`."""
+    B, dev = vals.shape[0], vals.device
     vals = torch.sort(vals, 1).values
     vals[:, 1:] = torch.where(vals[:, 1:] == vals[:, :-1], pad, vals[:, 1:])    # repeats
     vals = torch.sort(vals, 1).values.contiguous()
@@ -311,6 +322,58 @@ def eval_topk(lib, dims, cparams, ut, B, k, excl, id_mul, id_add, workspace, str
                                 None if off is None else off.data_ptr(), None if xid is None else xid.data_ptr(),
                                 id_mul, id_add, ids.data_ptr(), scores.data_ptr(), ws.data_ptr(), ws.numel(), stream),
             "tlsan_eval_topk")
+    return ids, scores
+
+
+SIMILAR_METRICS = {"dot": L.SIM_DOT, "cosine": L.SIM_COSINE}
+SIMILAR_CHUNK = 4096   # queries per tlsan_similar_topk call: bounds the slices' lists in the workspace (Q x slices x K)
+
+
+def similar_queries(items, item_count, metric, exclude, device):
+    """Checks similar_items' arguments -> (ids [Q] int32 device tensor, metric constant, exclusion CSR)."""
+    if metric not in SIMILAR_METRICS:
+        raise ValueError("metric must be 'cosine' or 'dot', got %r" % (metric,))
+    host = items.detach().cpu().numpy() if isinstance(items, torch.Tensor) else np.asarray(items)
+    if host.ndim != 1 or host.size < 1 or host.dtype.kind not in "iu":
+        raise ValueError("items: want a 1-D sequence of item ids, got shape %s dtype %s" % (host.shape, host.dtype))
+    host = host.astype(np.int64)
+    if host.min() < 0 or host.max() >= item_count:
+        raise ValueError("items: ids must be in [0, %d)" % item_count)
+    pad = np.iinfo(np.int32).max
+    excl = (None, None) if exclude is None else _csr_of_slots(_listed_items(exclude, len(host), item_count, device, pad), pad)
+    return torch.as_tensor(host.astype(np.int32)).to(device), SIMILAR_METRICS[metric], excl
+
+
+def item_vectors(lib, dims, cparams, qids, id_mul, id_add, stream):
+    """tlsan_item_vectors for the global ids qids [Q] int32 -> (vec [Q, d] float32, inv [Q] float32): the stored vectors
+    and inverse norms of the ids this table holds, zeros for the others."""
+    Q = int(qids.shape[0])
+    vec = torch.empty(Q, dims.d, dtype=torch.float32, device=qids.device)
+    inv = torch.empty(Q, dtype=torch.float32, device=qids.device)
+    L.check(lib.tlsan_item_vectors(C.byref(dims), C.byref(cparams), qids.data_ptr(), Q, id_mul, id_add, vec.data_ptr(),
+                                   inv.data_ptr(), stream), "tlsan_item_vectors")
+    return vec, inv
+
+
+def similar_topk(lib, dims, cparams, vec, inv, qids, k, metric, excl, id_mul, id_add, workspace, stream):
+    """tlsan_similar_topk over the queries (vec, inv, qids), SIMILAR_CHUNK at a time -> (ids [Q, k] int32, scores [Q, k]
+    float32) device tensors.  workspace(nbytes) returns a uint8 device tensor of at least nbytes."""
+    Q, k = int(qids.shape[0]), int(k)
+    ids = torch.empty(Q, k, dtype=torch.int32, device=qids.device)
+    scores = torch.empty(Q, k, dtype=torch.float32, device=qids.device)
+    off, xid = excl
+    for q0 in range(0, Q, SIMILAR_CHUNK):
+        n = min(SIMILAR_CHUNK, Q - q0)
+        nws = lib.tlsan_similar_workspace_bytes(C.byref(dims), n, k)
+        if nws == 0:
+            raise L.TlsanError("tlsan_similar_workspace_bytes: %s" % lib.tlsan_last_error().decode())
+        ws = workspace(nws)
+        # (a chunk's rows keep their offsets into the one id array: the offsets are absolute)
+        L.check(lib.tlsan_similar_topk(C.byref(dims), C.byref(cparams), vec[q0:].data_ptr(), inv[q0:].data_ptr(),
+                                       qids[q0:].data_ptr(), n, k, metric,
+                                       None if off is None else off[q0:].data_ptr(), None if xid is None else xid.data_ptr(),
+                                       id_mul, id_add, ids[q0:].data_ptr(), scores[q0:].data_ptr(), ws.data_ptr(),
+                                       ws.numel(), stream), "tlsan_similar_topk")
     return ids, scores
 
 
@@ -1151,6 +1214,21 @@ class Model(object):
         _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
         return eval_topk(self.lib, self.dims, self.cparams, ut, db.B, k, exclusion_csr(db, exclude, self.config["item_count"]),
                          1, 0, self._topk_workspace, self._stream())
+
+    def similar_items(self, items, k, metric="cosine", exclude=None):
+        """The k nearest items of each item of `items` (a 1-D list, array or tensor of global ids; outside
+        [0, item_count): ValueError) by the representation the model scores with, [item_emb || cate_emb[item_cate]]:
+        metric "cosine" or "dot" (the product of the true vectors: the table scale enters twice); no bias, no user.
+        -> (ids [Q, k] int32, scores [Q, k] float32) device tensors in recommend's order; the query never appears in
+        its own list, nor do the items of exclude (None, or a sequence of Q id sequences); rows with fewer than k
+        eligible items end in -1 / -inf.  Selected inside the scoring kernel (tlsan_similar_topk): the [Q, I]
+        similarities are never materialised.  Reads the tables as they are stored: an owed lazy-L2 correction lands
+        first, the scale is NOT folded -- parameters, scale and state keep their bits."""
+        qids, mc, excl = similar_queries(items, self.config["item_count"], metric, exclude, self.device)
+        self._flush()
+        st = self._stream()
+        vec, inv = item_vectors(self.lib, self.dims, self.cparams, qids, 1, 0, st)
+        return similar_topk(self.lib, self.dims, self.cparams, vec, inv, qids, k, mc, excl, 1, 0, self._topk_workspace, st)
 
     def score_candidates(self, batch, candidates):
         """Scores of caller-given items: candidates [B, C] global item ids (array or tensor; -1 = padding, which scores

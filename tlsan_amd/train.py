@@ -75,6 +75,11 @@ def parse(argv=None):
                     help="items kept out of the recommendations: 'history' = the items the test row's input holds (its "
                          "last Ls items and its current session -- what the batch carries), 'none' = nothing, 'seen' = "
                          "every item of the user's training samples and the row's input")
+    ap.add_argument("--similar_k", type=int, default=0,
+                    help="at the end of training, write <model_dir>/similar-<K>.npz: the K nearest items of every item "
+                         "(item [I], ids [I, K], scores [I, K]; 0 = off)")
+    ap.add_argument("--similar_metric", default="cosine", choices=["cosine", "dot"],
+                    help="the similarity of --similar_k: cosine, or the dot product of the item vectors")
     ap.add_argument("--eval_negatives", type=int, default=0,
                     help="sampled evaluation at every evaluation point: rank each test label among N sampled negatives "
                          "and report HR@k, NDCG@k (k = 1, 5, 10, 20), MRR and AUC_N; 0 = off")
@@ -120,6 +125,29 @@ def recommend_path(model_dir, k):
 def write_recommendations(model_dir, k, user, ids, scores):
     path = recommend_path(model_dir, k)
     np.savez(path, user=np.asarray(user, np.int64), ids=np.asarray(ids, np.int32), scores=np.asarray(scores, np.float32))
+    return path
+
+
+def similar_path(model_dir, k):
+    return os.path.join(model_dir, "similar-%d.npz" % k)
+
+
+SIMILAR_ROWS = 16384   # query items per similar_items call of write_similar
+
+
+def write_similar(model, model_dir, k, metric, item_count, write=True):
+    """The k nearest items of EVERY item (model.similar_items; collective on a sharded model, where only the process
+    with write=True keeps the lists) -> the path of the .npz written: item [I], ids [I, k], scores [I, k]."""
+    ids, scores = [], []
+    for i0 in range(0, item_count, SIMILAR_ROWS):
+        a, b = model.similar_items(np.arange(i0, min(i0 + SIMILAR_ROWS, item_count)), k, metric=metric)
+        if write:
+            ids.append(a.cpu().numpy())
+            scores.append(b.cpu().numpy())
+    if not write:
+        return None
+    path = similar_path(model_dir, k)
+    np.savez(path, item=np.arange(item_count, dtype=np.int32), ids=np.concatenate(ids), scores=np.concatenate(scores))
     return path
 
 
@@ -422,6 +450,11 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
         if rec is not None:                                    # (rank 0 holds the rows)
             path = write_recommendations(args.model_dir, args.recommend_k, *rec)
             say("Recommendations: %s" % path)
+    if args.similar_k:
+        path = write_similar(model, args.model_dir, args.similar_k, args.similar_metric, rows.config["item_count"],
+                             write=rows.rank in (None, 0))
+        if path is not None:
+            say("Similar items: %s" % path)
     model.train_writer.flush()
     model.eval_writer.flush()
     say("Best test_auc:", best_auc)
