@@ -207,6 +207,33 @@ def test_independence_and_symmetry():
         assert np.array_equal(S, S.T)
 
 
+@pytest.mark.parametrize("k", [16, 17, 256])
+def test_topk_on_the_queries_vectors_equals_dot(k):
+    """k_eval_topk and k_similar_topk are two texts of one scan (k_eval_topk's own, and topk_scan with SimScore) that
+    must stay the same tiles and the same selection; this is the guard that they do.  With P = 1 and no bias the
+    recommendation score of u_t = the queries' stored vectors IS the dot product, so excluding each row's own id gives
+    the dot lists, ids and scores.  I = 300: the last 64-item group is partial; Q = 20: so is the second row tile."""
+    import torch
+    from tlsan_amd import model as M
+    I = 300
+    cfg = make_config(U=8, I=I, C=5, d=64, H=8)
+    cat = _cat(cfg)
+    p = _params(cfg, seed=111)
+    p["item_b"] = np.zeros_like(p["item_b"])
+    m = _model(cfg, cat, p)
+    assert m.table_scale() == 1.0
+    qids = np.random.RandomState(112).randint(0, I, 20)
+    qids[7] = I + 5                                          # no row of the table: nothing to compare
+    vec, _, (sid, ssc) = _c_call(m, qids, k, "dot")
+    own = (torch.arange(21, dtype=torch.int32, device=m.device), torch.as_tensor(qids.astype(np.int32)).to(m.device))
+    tid, tsc = _host(M.eval_topk(m.lib, m.dims, m.cparams, torch.as_tensor(vec).to(m.device), 20, k, own, 1, 0,
+                                 m._topk_workspace, m._stream()))
+    rows = np.arange(20) != 7
+    assert sid[7].tolist() == [-1] * k and (sid[rows] >= 0).all()
+    assert np.array_equal(tid[rows], sid[rows])
+    assert np.array_equal(tsc[rows], ssc[rows])              # (==: a zero of either sign is a zero)
+
+
 # ---- 5. the lazy-L2 state
 def test_lazy_l2_state_is_read_not_changed():
     cfg = make_config(U=40, I=500, C=7, d=128, H=8)
@@ -259,7 +286,7 @@ def test_gathering_form_past_the_dense_cap():
 
 
 def test_gathering_form_at_d256():
-    """d = 256 past the dense cap with K <= 16 and K <= 64: the two instantiations that keep spilled registers"""
+    """d = 256 past the dense cap with K <= 16 and K <= 64: the two instantiations under the most register pressure"""
     I = (1 << 18) + 3                                        # I * 256 * 4 B > 256 MB
     cfg = make_config(U=8, I=I, C=50, d=256, H=8)
     rng = np.random.RandomState(93)

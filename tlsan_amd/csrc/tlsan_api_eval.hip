@@ -18,6 +18,25 @@ struct ExclOut { const int32_t* off; const int32_t* ids; int32_t* ahead; int32_t
 // workspace holds one (carve: up to EVAL_DENSE_MAX bytes), else the gathering one.  k_excl_ahead follows it.
 static bool eval_rank_dense(const EvalArgs& e) { return e.all_emb != nullptr; }
 
+// what every scoring kernel reads: the tables, the rows of u_t and the id mapping of this table; the rest zero
+static EvalArgs eval_args(const tlsan_dims* d, const tlsan_params* p, const float* u_t, int32_t B, int32_t id_mul, int32_t id_add) {
+  EvalArgs e;
+  memset(&e, 0, sizeof(e));
+  e.p = norm_params(p, d); e.u_t = u_t; e.B = B; e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate;
+  e.id_mul = id_mul; e.id_add = id_add;
+  return e;
+}
+
+// global ids n * id_mul + id_add of the table's items must be non-negative int32 (d NULL: left to shape_of's refusal)
+static bool eval_ids_ok(const tlsan_dims* d, int32_t id_mul, int32_t id_add) {
+  return id_mul >= 1 && id_add >= 0 && (!d || (long long)(d->item_count - 1) * id_mul + id_add < (1LL << 31));
+}
+
+static void launch_all_emb(const EvalArgs& e, int D, hipStream_t hs) {
+  const int nae = (e.I * (D / 4) + 255) / 256;
+  dispatch_d(D, [&](auto dd) { hipLaunchKernelGGL(k_all_emb<dd.value>, dim3(nae), dim3(256), 0, hs, e); });
+}
+
 // s_label_in == NULL: the label's score is computed here (labels index THIS table); s_label_out != NULL: only that.
 static int eval_ranks_impl(const tlsan_dims* d, const tlsan_params* p, const float* u_t, const int32_t* labels, int32_t B,
                            int32_t* ranks, void* ws, size_t ws_bytes, void* stream, const float* s_label_in, int id_mul,
@@ -32,36 +51,20 @@ static int eval_ranks_impl(const tlsan_dims* d, const tlsan_params* p, const flo
   carve(d, s, B, 0, (char*)ws, &w);
   if (w.bytes > ws_bytes) return fail(TLSAN_E_WORKSPACE, "workspace too small: need %zu have %zu", w.bytes, ws_bytes);
   hipStream_t hs = (hipStream_t)stream;
-  EvalArgs e;
-  memset(&e, 0, sizeof(e));
-  e.p = norm_params(p, d); e.u_t = u_t; e.labels = labels; e.B = B; e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate;
+  EvalArgs e = eval_args(d, p, u_t, B, id_mul, id_add);
+  e.labels = labels; e.ranks = ranks; e.all_emb = w.all_emb;
   e.s_label = s_label_out ? s_label_out : (s_label_in ? const_cast<float*>(s_label_in) : w.s_label);
-  e.ranks = ranks; e.all_emb = w.all_emb; e.id_mul = id_mul; e.id_add = id_add;
   if (ranks && hipMemsetAsync(ranks, 0, sizeof(int32_t) * (size_t)B, hs) != hipSuccess) return fail(TLSAN_E_LAUNCH, "memset ranks");
   const int ut = (B + 15) / 16;
-  const int ntiles = (d->item_count + 15) / 16;
-  int chunks = (ntiles + 3) / 4;
-  const int want = (2048 + ut - 1) / ut;  // enough workgroups to fill the chip
-  if (chunks > want) chunks = want;
-  if (chunks < 1) chunks = 1;
-  const int nae = (d->item_count * (s.D / 4) + 255) / 256;
-  int ngrp = ((d->item_count + 63) / 64 + 3) / 4;  // workgroups (4 wavefronts x 64 items) along the items
-  if (ngrp > want) ngrp = want;
-#define EVAL_LAUNCH(DD)                                                                                  \
-  do {                                                                                                   \
-    if (!s_label_in) hipLaunchKernelGGL(k_eval_label<DD>, dim3(ut), dim3(64), 0, hs, e);                 \
-    if (!ranks) break;                                                                                   \
-    if (eval_rank_dense(e)) {                                                                            \
-      hipLaunchKernelGGL(k_all_emb<DD>, dim3(nae), dim3(256), 0, hs, e);                                 \
-      hipLaunchKernelGGL(k_eval_rank_dense<DD>, dim3(ut, ngrp), dim3(256), 0, hs, e);                    \
-    } else {                                                                                             \
-      hipLaunchKernelGGL(k_eval_rank<DD>, dim3(ut, chunks), dim3(256), 0, hs, e);                        \
-    }                                                                                                    \
-  } while (0)
-  if (s.D == 64) EVAL_LAUNCH(64);
-  else if (s.D == 128) EVAL_LAUNCH(128);
-  else EVAL_LAUNCH(256);
-#undef EVAL_LAUNCH
+  const int chunks = eval_slices(ut, ((d->item_count + 15) / 16 + 3) / 4);   // workgroups (4 wavefronts x 16 items) along the items
+  const int ngrp = eval_slices(ut, ((d->item_count + 63) / 64 + 3) / 4);     // ... (4 wavefronts x 64 items)
+  if (!s_label_in) dispatch_d(s.D, [&](auto dd) { hipLaunchKernelGGL(k_eval_label<dd.value>, dim3(ut), dim3(64), 0, hs, e); });
+  if (ranks && eval_rank_dense(e)) {
+    launch_all_emb(e, s.D, hs);
+    dispatch_d(s.D, [&](auto dd) { hipLaunchKernelGGL(k_eval_rank_dense<dd.value>, dim3(ut, ngrp), dim3(256), 0, hs, e); });
+  } else if (ranks) {
+    dispatch_d(s.D, [&](auto dd) { hipLaunchKernelGGL(k_eval_rank<dd.value>, dim3(ut, chunks), dim3(256), 0, hs, e); });
+  }
   CHECK_LAUNCH("k_eval");
   if (xo) {   // after the count: the dense item matrix of this call is there, and s_label holds the labels' scores
     if (hipMemsetAsync(xo->ahead, 0, sizeof(int32_t) * (size_t)B, hs) != hipSuccess ||
@@ -109,7 +112,7 @@ int tlsan_eval_counts_shard_excl(const tlsan_dims* d, const tlsan_params* p, con
                                  int32_t* held, void* ws, size_t ws_bytes, void* stream) {
   if (!label_scores || !counts || !excl_off || !excl_ids || !ahead || !held)
     return fail(TLSAN_E_BADARG, "tlsan_eval_counts_shard_excl: NULL argument");
-  if (id_mul < 1 || id_add < 0 || (d && (long long)(d->item_count - 1) * id_mul + id_add >= (1LL << 31)))
+  if (!eval_ids_ok(d, id_mul, id_add))
     return fail(TLSAN_E_BADARG, "tlsan_eval_counts_shard_excl: global ids n * id_mul + id_add must be non-negative int32");
   const ExclOut xo = {excl_off, excl_ids, ahead, held};
   return eval_ranks_impl(d, p, u_t, labels_global, B, counts, ws, ws_bytes, stream, label_scores, id_mul, id_add, nullptr, &xo);
@@ -127,12 +130,7 @@ struct TopkWs {
 static void carve_topk(const tlsan_dims* d, int D, int B, int K, char* base, TopkWs* w) {
   size_t o = 0;
   auto take = [&](size_t n) { char* p = base ? base + o : nullptr; o += al(n); return p; };
-  const int ut = (B + 15) / 16;
-  const int want = (2048 + ut - 1) / ut;  // enough workgroups to fill the chip (the rank path's slicing)
-  int nsl = ((d->item_count + 63) / 64 + 3) / 4;
-  if (nsl > want) nsl = want;
-  if (nsl < 1) nsl = 1;
-  w->nsl = nsl;
+  const int nsl = w->nsl = eval_slices((B + 15) / 16, ((d->item_count + 63) / 64 + 3) / 4);   // (the rank path's slicing)
   const size_t ae = sizeof(float) * (size_t)d->item_count * D;
   w->all_emb = ae <= EVAL_DENSE_MAX ? (float*)take(ae) : nullptr;
   const size_t nc = nsl > 1 ? (size_t)B * nsl * K : 0;
@@ -161,7 +159,7 @@ int tlsan_eval_topk(const tlsan_dims* d, const tlsan_params* p, const float* u_t
   if (!u_t || !ids || !scores || B < 1) return fail(TLSAN_E_BADARG, "tlsan_eval_topk: bad arguments");
   if (K < 1 || K > TOPK_MAX) return fail(TLSAN_E_BADARG, "tlsan_eval_topk: K must be in 1..%d (got %d)", TOPK_MAX, K);
   if (!excl_off != !excl_ids) return fail(TLSAN_E_BADARG, "tlsan_eval_topk: excl_off and excl_ids go together");
-  if (id_mul < 1 || id_add < 0 || (long long)(d->item_count - 1) * id_mul + id_add >= (1LL << 31))
+  if (!eval_ids_ok(d, id_mul, id_add))
     return fail(TLSAN_E_BADARG, "tlsan_eval_topk: global ids n * id_mul + id_add must be non-negative int32");
   if (!ws) return fail(TLSAN_E_WORKSPACE, "ws is NULL");
   TopkWs w;
@@ -170,17 +168,13 @@ int tlsan_eval_topk(const tlsan_dims* d, const tlsan_params* p, const float* u_t
   hipStream_t hs = (hipStream_t)stream;
   TopkArgs ta;
   memset(&ta, 0, sizeof(ta));
-  EvalArgs& e = ta.e;
-  e.p = norm_params(p, d); e.u_t = u_t; e.B = B; e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate;
-  e.all_emb = w.all_emb; e.id_mul = id_mul; e.id_add = id_add;
+  EvalArgs& e = ta.e = eval_args(d, p, u_t, B, id_mul, id_add);
+  e.all_emb = w.all_emb;
   ta.K = K; ta.excl_off = excl_off; ta.excl_ids = excl_ids;
   ta.ids = w.nsl > 1 ? w.ids : ids;
   ta.scores = w.nsl > 1 ? w.scores : scores;
   if (e.all_emb) {
-    const int nae = (d->item_count * (s.D / 4) + 255) / 256;
-    if (s.D == 64) hipLaunchKernelGGL(k_all_emb<64>, dim3(nae), dim3(256), 0, hs, e);
-    else if (s.D == 128) hipLaunchKernelGGL(k_all_emb<128>, dim3(nae), dim3(256), 0, hs, e);
-    else hipLaunchKernelGGL(k_all_emb<256>, dim3(nae), dim3(256), 0, hs, e);
+    launch_all_emb(e, s.D, hs);
     CHECK_LAUNCH("k_all_emb");
   }
   hipError_t err = tlsan_launch_topk(ta, s.D, w.nsl, hs);
@@ -209,10 +203,6 @@ static int sim_named(const char* fn, int rc) {
   return fail(rc, "%s: %s", fn, m);
 }
 
-static bool sim_ids_ok(const tlsan_dims* d, int32_t id_mul, int32_t id_add) {
-  return id_mul >= 1 && id_add >= 0 && (long long)(d->item_count - 1) * id_mul + id_add < (1LL << 31);
-}
-
 int tlsan_item_vectors(const tlsan_dims* d, const tlsan_params* p, const int32_t* ids, int32_t Q, int32_t id_mul,
                        int32_t id_add, float* vec, float* inv_norm, void* stream) {
   Shape s;
@@ -220,12 +210,11 @@ int tlsan_item_vectors(const tlsan_dims* d, const tlsan_params* p, const int32_t
   if (rc || (rc = check_params(p))) return sim_named("tlsan_item_vectors", rc);
   if (!ids || !vec) return fail(TLSAN_E_BADARG, "tlsan_item_vectors: NULL argument");
   if (Q < 1) return fail(TLSAN_E_BADARG, "tlsan_item_vectors: Q must be >= 1 (got %d)", Q);
-  if (!sim_ids_ok(d, id_mul, id_add))
+  if (!eval_ids_ok(d, id_mul, id_add))
     return fail(TLSAN_E_BADARG, "tlsan_item_vectors: global ids n * id_mul + id_add must be non-negative int32");
   VecArgs va;
   memset(&va, 0, sizeof(va));
-  EvalArgs& e = va.e;
-  e.p = norm_params(p, d); e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate; e.id_mul = id_mul; e.id_add = id_add;
+  va.e = eval_args(d, p, nullptr, 0, id_mul, id_add);
   va.ids = ids; va.Q = Q; va.vec = vec; va.inv = inv_norm;
   const hipError_t err = tlsan_launch_item_vectors(va, s.D, (hipStream_t)stream);
   if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_item_vectors: %s", hipGetErrorString(err));
@@ -268,7 +257,7 @@ int tlsan_similar_topk(const tlsan_dims* d, const tlsan_params* p, const float* 
   if (Q < 1) return fail(TLSAN_E_BADARG, "tlsan_similar_topk: Q must be >= 1 (got %d)", Q);
   if (K < 1 || K > TOPK_MAX) return fail(TLSAN_E_BADARG, "tlsan_similar_topk: K must be in 1..%d (got %d)", TOPK_MAX, K);
   if (!excl_off != !excl_ids) return fail(TLSAN_E_BADARG, "tlsan_similar_topk: excl_off and excl_ids go together");
-  if (!sim_ids_ok(d, id_mul, id_add))
+  if (!eval_ids_ok(d, id_mul, id_add))
     return fail(TLSAN_E_BADARG, "tlsan_similar_topk: global ids n * id_mul + id_add must be non-negative int32");
   if (!ws) return fail(TLSAN_E_WORKSPACE, "tlsan_similar_topk: ws is NULL");
   SimWs w;
@@ -280,9 +269,8 @@ int tlsan_similar_topk(const tlsan_dims* d, const tlsan_params* p, const float* 
   SimArgs sa;
   memset(&sa, 0, sizeof(sa));
   TopkArgs& ta = sa.t;
-  EvalArgs& e = ta.e;
-  e.p = norm_params(p, d); e.u_t = qvec; e.B = Q; e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate;
-  e.all_emb = w.t.all_emb; e.id_mul = id_mul; e.id_add = id_add;
+  EvalArgs& e = ta.e = eval_args(d, p, qvec, Q, id_mul, id_add);
+  e.all_emb = w.t.all_emb;
   ta.K = K; ta.excl_off = excl_off; ta.excl_ids = excl_ids;
   ta.ids = nsl > 1 ? w.t.ids : ids;
   ta.scores = nsl > 1 ? w.t.scores : scores;
@@ -308,13 +296,11 @@ int tlsan_score_candidates(const tlsan_dims* d, const tlsan_params* p, const flo
   if (!u_t || !cand || !scores) return fail(TLSAN_E_BADARG, "tlsan_score_candidates: NULL argument");
   if (B < 1 || C < 1) return fail(TLSAN_E_BADARG, "tlsan_score_candidates: B and C must be >= 1 (got %d, %d)", B, C);
   if ((long long)B * C >= (1LL << 31)) return fail(TLSAN_E_UNSUPPORTED, "tlsan_score_candidates: B * C overflows int32");
-  if (id_mul < 1 || id_add < 0 || (long long)(d->item_count - 1) * id_mul + id_add >= (1LL << 31))
+  if (!eval_ids_ok(d, id_mul, id_add))
     return fail(TLSAN_E_BADARG, "tlsan_score_candidates: global ids n * id_mul + id_add must be non-negative int32");
   CandArgs ca;
   memset(&ca, 0, sizeof(ca));
-  EvalArgs& e = ca.e;
-  e.p = norm_params(p, d); e.u_t = u_t; e.B = B; e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate;
-  e.id_mul = id_mul; e.id_add = id_add;
+  ca.e = eval_args(d, p, u_t, B, id_mul, id_add);
   ca.C = C; ca.cand = cand; ca.scores = scores;
   const hipError_t err = tlsan_launch_score_cand(ca, s.D, (hipStream_t)stream);
   if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_score_cand: %s", hipGetErrorString(err));

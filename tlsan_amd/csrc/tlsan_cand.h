@@ -2,9 +2,9 @@
 //
 // k_score_cand: scores[b, c] = u_t[b] . [item_emb || cate_emb[item_cate]][g] * P + item_b[g] for g = cand[b, c], in the
 // form of k_eval_label: a wavefront holds the A fragments of 16 rows (load_user_frag) and, for each candidate column
-// c, scores one 16x16 tile whose lane column r is row r's candidate (score_tile) and keeps the diagonal.  The diagonal
-// element is the same MFMA chain on the same operands as the label's own score, and the two roundings (* P, + bias)
-// are kept apart, so a candidate's score equals tlsan_eval_label_scores' (and a tlsan_eval_topk list entry's) bit for
+// c, scores one 16x16 tile whose lane column r is row r's candidate (score_tile) and keeps the diagonal (tile_diag).  The
+// diagonal element is the same MFMA chain on the same operands as the label's own score, and the two roundings (* P,
+// + bias) are kept apart (eval_score), so a candidate's score equals tlsan_eval_label_scores' (and a tlsan_eval_topk list entry's) bit for
 // bit.  One MFMA column in 16 is kept; the kernel is bound by the row gathers, not by the matrix pipe.
 //
 // k_cand_ranks (tlsan_cand.hip): how many candidates c >= 1 of a row come ahead of candidate 0, in tf.nn.top_k's
@@ -31,15 +31,15 @@ struct CandArgs {
 // k_excl_ahead: row b's list is excl_ids[excl_off[b] .. excl_off[b + 1]) (global ids, ascending).  An entry counts when
 // it is the first of its value, is not the row's label and is held by this table (cand_local); held[b] += 1 for it, and
 // ahead[b] += 1 when the rank kernel of this table counted it ahead of the label.  `fused` says which rank kernel that
-// was: k_eval_rank_dense (e.all_emb set) forms the score as ONE fused multiply-add fma(acc, P, bias), k_eval_rank as a
-// rounded product and a rounded sum (read off their ISA: v_fma_f32 / v_fmac_f32 against v_pk_mul_f32 + v_add_f32, every width).
+// was, by the score form it calls (tlsan_eval.h): k_eval_rank_dense (e.all_emb set) eval_score_fma, one fused
+// multiply-add; k_eval_rank eval_score, a rounded product and a rounded sum.  k_excl_ahead calls the same helper.
 struct ExclArgs {
   EvalArgs e;               // p, u_t, labels (global ids), s_label, B, I, di, dc, all_emb (dense form), id_mul, id_add
   const int32_t* excl_off;  // [B + 1]
   const int32_t* excl_ids;
   int32_t* ahead;           // [B], zeroed before the launch
   int32_t* held;            // [B], zeroed before the launch
-  int32_t fused;            // 1: fma(acc, P, bias) (k_eval_rank_dense); 0: (acc * P) + bias (k_eval_rank)
+  int32_t fused;            // 1: eval_score_fma (k_eval_rank_dense); 0: eval_score (k_eval_rank)
 };
 
 // Local item of global id g, or -1 when this table does not hold it.
@@ -53,8 +53,6 @@ __device__ __forceinline__ int cand_local(int g, int I, int id_mul, int id_add) 
 // grid (ceil(B/16), slices); wavefront w of slice y scores columns c = (y * 4 + w) + k * 4 * slices.
 template <int D>
 __global__ __launch_bounds__(256) void k_score_cand(CandArgs ca) {
-  // (score = (acc * P) + bias in two roundings, as k_eval_label forms the label's score)
-#pragma clang fp contract(off)
   const EvalArgs& a = ca.e;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
   const int u0 = blockIdx.x * 16, u = u0 + r;
@@ -62,21 +60,16 @@ __global__ __launch_bounds__(256) void k_score_cand(CandArgs ca) {
   const bool whole = a.id_mul == 1 && a.id_add == 0;   // whole table: ids outside it score -inf (else: not ours, skipped)
   f32x4 af[D / 16];
   load_user_frag<D>(a, u0, q, r, af);
-  const float P = a.p.scale ? *a.p.scale : 1.0f;
+  const float P = eval_scale(a);
   const int32_t* crow = ca.cand + (size_t)(uv ? u : 0) * ca.C;
   float* srow = ca.scores + (size_t)(uv ? u : 0) * ca.C;
   for (int c = blockIdx.y * 4 + wave; c < ca.C; c += gridDim.y * 4) {
     const int n = uv ? cand_local(crow[c], a.I, a.id_mul, a.id_add) : -1;
     const int item = n >= 0 ? n : 0;
-    const f32x4 acc = score_tile<D>(a, af, item, q) * P;
-    const float bias = a.p.item_b[(size_t)item * a.p.ld_itemb];
-    // diagonal: row (4q+i) == column r
-    if (uv && q == (r >> 2)) {
-      float v = acc[0];
-      if ((r & 3) == 1) v = acc[1];
-      if ((r & 3) == 2) v = acc[2];
-      if ((r & 3) == 3) v = acc[3];
-      if (n >= 0) srow[c] = v + bias;
+    // (two roundings, as k_eval_label forms the label's score)
+    const f32x4 s = eval_score(score_tile<D>(a, af, item, q), P, a.p.item_b[(size_t)item * a.p.ld_itemb]);
+    if (uv && q == (r >> 2)) {   // the diagonal: row r's candidate
+      if (n >= 0) srow[c] = tile_diag(s, r);
       else if (whole) srow[c] = -__builtin_inff();
     }
   }

@@ -72,11 +72,10 @@ __global__ __launch_bounds__(64) void k_sample_neg(NegArgs na) {
 // of 16 rows, column r of a tile is row r's e-th list entry, and the diagonal lane (row r, column r) takes the rank
 // kernel's decision for it.  The 16x16 tile is the rank kernels' MFMA chain on the same operand values (the dense
 // matrix where the rank path built one -- it holds the tables' stored values -- else the tables), and the last two
-// operations are spelled out per form (ExclArgs.fused), so the decision is the counting kernel's bit for bit.
+// operations are the score helper that kernel calls (ExclArgs.fused), so the decision is the counting kernel's bit for bit.
 // grid (ceil(B/16), slices); wavefront w of slice y takes the entries e = (y * 4 + w) + k * 4 * slices.
 template <int D>
 __global__ __launch_bounds__(256) void k_excl_ahead(ExclArgs xa) {
-#pragma clang fp contract(off)
   const EvalArgs& a = xa.e;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
   const int u0 = blockIdx.x * 16, u = u0 + r;
@@ -100,7 +99,7 @@ __global__ __launch_bounds__(256) void k_excl_ahead(ExclArgs xa) {
   if (e0 >= lmax) return;
   f32x4 af[D / 16];
   load_user_frag<D>(a, u0, q, r, af);
-  const float P = a.p.scale ? *a.p.scale : 1.0f;
+  const float P = eval_scale(a);
   const int lab = uv ? a.labels[u] : -1;
   const float sl = uv ? a.s_label[u] : 0.0f;
   const bool diag = uv && q == (r >> 2);
@@ -113,31 +112,13 @@ __global__ __launch_bounds__(256) void k_excl_ahead(ExclArgs xa) {
       n = (first && g != lab) ? cand_local(g, a.I, a.id_mul, a.id_add) : -1;
     }
     const int item = n >= 0 ? n : 0;
-    f32x4 acc;
-    if (a.all_emb) {
-      const float* row = a.all_emb + (size_t)item * D + 4 * q;
-      acc = (f32x4)(0.0f);
-#pragma unroll
-      for (int kc = 0; kc < D / 16; ++kc) {
-        const f32x4 bv = *(const f32x4*)(row + 16 * kc);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc = TLSAN_MFMA(af[kc][s], bv[s], acc);
-      }
-    } else {
-      acc = score_tile<D>(a, af, item, q);
-    }
+    const f32x4 acc = a.all_emb ? score_tile_dense<D>(a.all_emb, af, item, q) : score_tile<D>(a, af, item, q);
     const float bias = a.p.item_b[(size_t)item * a.p.ld_itemb];
     if (diag && n >= 0) {
-      float v = acc[0];
-      if ((r & 3) == 1) v = acc[1];
-      if ((r & 3) == 2) v = acc[2];
-      if ((r & 3) == 3) v = acc[3];
-      // (this function's contract(off) keeps the second form two roundings; __fmul_rn / __fadd_rn would not: they are
-      //  inlined with their header's contraction flags and fuse)
-      const float vp = v * P;
-      const float s = xa.fused ? __builtin_fmaf(v, P, bias) : vp + bias;
+      const float v = tile_diag(acc, r);
+      const float s = xa.fused ? eval_score_fma(v, P, bias) : eval_score(v, P, bias);
       n_held += 1;
-      n_ahead += (s > sl || (s == sl && g < lab)) ? 1 : 0;
+      n_ahead += rank_ahead(s, sl, g, lab) ? 1 : 0;   // (g != lab: such an entry has n < 0)
     }
   }
   if (diag) {
@@ -148,25 +129,16 @@ __global__ __launch_bounds__(256) void k_excl_ahead(ExclArgs xa) {
 
 hipError_t tlsan_launch_excl_ahead(const ExclArgs& a, int D, hipStream_t hs) {
   const int ut = (a.e.B + 15) / 16;
-  int nsl = (2048 + ut - 1) / ut;         // enough workgroups to fill the chip (the rank path's slicing); a wavefront
-  if (nsl > 64) nsl = 64;                 // whose first entry lies past its tile's longest list leaves at once
-  const dim3 grid(ut, nsl);
-  if (D == 64) hipLaunchKernelGGL(k_excl_ahead<64>, grid, dim3(256), 0, hs, a);
-  else if (D == 128) hipLaunchKernelGGL(k_excl_ahead<128>, grid, dim3(256), 0, hs, a);
-  else hipLaunchKernelGGL(k_excl_ahead<256>, grid, dim3(256), 0, hs, a);
+  // (at most 64 slices: a wavefront whose first entry lies past its tile's longest list leaves at once)
+  const dim3 grid(ut, eval_slices(ut, 64));
+  dispatch_d(D, [&](auto d) { hipLaunchKernelGGL(k_excl_ahead<d.value>, grid, dim3(256), 0, hs, a); });
   return hipGetLastError();
 }
 
 hipError_t tlsan_launch_score_cand(const CandArgs& a, int D, hipStream_t hs) {
   const int ut = (a.e.B + 15) / 16;
-  const int want = (2048 + ut - 1) / ut;  // enough workgroups to fill the chip (the rank path's slicing)
-  int nsl = (a.C + 3) / 4;
-  if (nsl > want) nsl = want;
-  if (nsl < 1) nsl = 1;
-  const dim3 grid(ut, nsl);
-  if (D == 64) hipLaunchKernelGGL(k_score_cand<64>, grid, dim3(256), 0, hs, a);
-  else if (D == 128) hipLaunchKernelGGL(k_score_cand<128>, grid, dim3(256), 0, hs, a);
-  else hipLaunchKernelGGL(k_score_cand<256>, grid, dim3(256), 0, hs, a);
+  const dim3 grid(ut, eval_slices(ut, (a.C + 3) / 4));
+  dispatch_d(D, [&](auto d) { hipLaunchKernelGGL(k_score_cand<d.value>, grid, dim3(256), 0, hs, a); });
   return hipGetLastError();
 }
 

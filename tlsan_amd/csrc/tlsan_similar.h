@@ -1,6 +1,6 @@
 // tlsan_similar.h -- similar-items lists: for each query item the K nearest items of the table by dot product or cosine
 // of the representation the model scores with, w_n = [item_emb[n] || cate_emb[item_cate[n]]] (the matrix k_all_emb
-// builds), selected inside the scoring kernel as k_eval_topk does: the [Q, I] similarity matrix is never materialised.
+// builds), selected inside the scoring kernel by k_eval_topk's loop in its shared form (topk_scan): the [Q, I] similarity matrix is never materialised.
 //
 //   acc(q, n)  the fp32 MFMA accumulation of w_q . w_n on STORED values: the chains of k_eval_topk's tiles, the
 //              query's stored vector in the place of u_t.  The products commute and the k-order is the chain's, so
@@ -89,103 +89,38 @@ __global__ __launch_bounds__(256) void k_item_vectors(VecArgs va) {
   if (c == 0 && va.inv) va.inv[qi] = w;
 }
 
-// grid (ceil(Q/16), slices): k_eval_topk's tile loop and selection (tlsan_topk.h: the same tiles, chains, TopkSmem and
-// phases -- a copy, because k_eval_topk moved to a shared loop does not compile to the code it has now) with
-//   the epilogue  s = acc * fl(qm * nm): cosine qm = inv(q), nm = inv(n); dot qm = fl(P * P), nm = 1 (exact), and
-//   the eligibility test, which also rejects the query's own id and everything for a padding row.
+// The similarity score for topk_scan (tlsan_topk.h: the tiles, chains, TopkSmem and phases of k_eval_topk, which keeps
+// its own text of the loop for its speed):
+//   s = acc * fl(qm * nm): cosine qm = inv(q), nm = inv(n); dot qm = fl(P * P), nm = 1 (exact);
+// a row is a query this table can answer (a padding row selects nothing), and no query selects its own id.
+struct SimScore {
+  const SimArgs& sa;
+  const bool cosine, whole;
+  const float P, P2;
+  float qm[4], nm;
+  int qid[4];
+  f32x4 acc;
+  __device__ __forceinline__ explicit SimScore(const SimArgs& s)
+      : sa(s), cosine(s.metric == SIM_COSINE), whole(s.t.e.id_mul == 1 && s.t.e.id_add == 0), P(eval_scale(s.t.e)), P2(P * P) {}
+  __device__ __forceinline__ bool row(int i, int u) {
+    const EvalArgs& a = sa.t.e;
+    qid[i] = u < a.B ? sa.qids[u] : -1;
+    const bool v = qid[i] >= 0 && !(whole && qid[i] >= a.I);
+    qm[i] = cosine ? (v ? sa.qinv[u] : 0.0f) : P2;
+    return v;
+  }
+  __device__ __forceinline__ void col(const f32x4& tile, int item) {
+    acc = tile;
+    nm = cosine ? sa.inv[item] : 1.0f;
+  }
+  __device__ __forceinline__ float score(int i) const { return acc[i] * (qm[i] * nm); }   // (products only: nothing to fuse)
+  __device__ __forceinline__ bool may(int i, int gn) const { return gn != qid[i]; }
+};
+
+// grid (ceil(Q/16), slices)
 template <int D, int KP, int BUF, bool DENSE>
 __global__ __launch_bounds__(256, 2) void k_similar_topk(SimArgs sa) {
-#pragma clang fp contract(off)
   __shared__ TopkSmem<KP, BUF> sm;
-  const TopkArgs& ta = sa.t;
-  const EvalArgs& a = ta.e;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
-  const int u0 = blockIdx.x * 16;
-  topk_init(sm);
-  f32x4 af[D / 16];
-  load_user_frag<D>(a, u0, q, r, af);
-  const bool cosine = sa.metric == SIM_COSINE;
-  const float P = a.p.scale ? *a.p.scale : 1.0f;
-  const float P2 = P * P;
-  const bool whole = a.id_mul == 1 && a.id_add == 0;
-  bool uv[4];
-  int xlo[4], xhi[4], qid[4];
-  float qm[4];
-  topk_key_t thr[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int u = u0 + 4 * q + i;
-    qid[i] = u < a.B ? sa.qids[u] : -1;
-    uv[i] = qid[i] >= 0 && !(whole && qid[i] >= a.I);
-    qm[i] = cosine ? (uv[i] ? sa.qinv[u] : 0.0f) : P2;
-    xlo[i] = (uv[i] && ta.excl_off) ? ta.excl_off[u] : 0;
-    xhi[i] = (uv[i] && ta.excl_off) ? ta.excl_off[u + 1] : 0;
-    thr[i] = 0ull;
-  }
-  __syncthreads();
-  const int step = gridDim.y * 256;
-  const int nround = (a.I + step - 1) / step;
-  int ph = 0;
-  for (int rd = 0; rd < nround; ++rd) {
-    const int n0 = rd * step + (blockIdx.y * 4 + wave) * 64;
-    topk_key_t key[16];
-    unsigned pend = 0;
-    if (n0 < a.I) {
-      int item[4];
-      f32x4 acc[4];
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) item[tt] = min(n0 + 16 * tt + r, a.I - 1);
-      if (DENSE) {
-        const float* rows[4];
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-          rows[tt] = a.all_emb + (size_t)item[tt] * D + 4 * q;
-          acc[tt] = (f32x4)(0.0f);
-        }
-#pragma unroll
-        for (int kc = 0; kc < D / 16; ++kc) {
-          f32x4 bv[4];
-#pragma unroll
-          for (int tt = 0; tt < 4; ++tt) bv[tt] = *(const f32x4*)(rows[tt] + 16 * kc);
-#pragma unroll
-          for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) acc[tt] = TLSAN_MFMA(af[kc][s], bv[tt][s], acc[tt]);
-        }
-      } else {
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) acc[tt] = score_tile<D>(a, af, item[tt], q);
-      }
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) {
-        const int n = n0 + 16 * tt + r;
-        const bool vn = n < a.I;
-        const int gn = n * a.id_mul + a.id_add;  // global item id
-        const float nm = cosine ? sa.inv[item[tt]] : 1.0f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float s = acc[tt][i] * (qm[i] * nm);
-          key[4 * tt + i] = topk_key(s, gn);
-          // (the exclusion list is searched only for scores that pass the threshold)
-          if (vn && uv[i] && gn != qid[i] && key[4 * tt + i] > thr[i] &&
-              !topk_in_list(ta.excl_ids, xlo[i], xhi[i], gn))
-            pend |= 1u << (4 * tt + i);
-        }
-      }
-    }
-    for (;;) {
-      bool ovf = false;
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        if (!(pend & (1u << c))) continue;
-        if (key[c] <= thr[c & 3] || topk_push(sm, 4 * q + (c & 3), key[c])) pend &= ~(1u << c);
-        else ovf = true;
-      }
-      if (!topk_phase_end(sm, ovf, ph)) break;
-      topk_reselect(sm);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) thr[i] = sm.kept[4 * q + i][ta.K - 1];
-    }
-  }
-  topk_finish(sm, u0, a.B, ta.K, gridDim.y, blockIdx.y, ta.ids, ta.scores);
+  SimScore pol(sa);
+  topk_scan<D, KP, BUF, DENSE>(sm, sa.t, pol);
 }

@@ -7,7 +7,8 @@
 // Key 0 is "no item" (id -1, score -inf in the output).
 //
 // Selection: a workgroup owns 16 users x an item slice (the tiling of k_eval_rank / k_eval_rank_dense, whose 16x16
-// tiles it computes with the same MFMA chains on the same operands -- scores are bit-identical to the rank path's).
+// tiles it computes with the same MFMA chains on the same operands -- the accumulators are bit-identical to the rank
+// path's).
 // Per user the LDS holds the best KP keys so far (sorted) and an append buffer of BUF keys; a score that does not
 // beat the user's K-th best key so far is rejected with one compare, a survivor is appended.  When a buffer
 // overflows, the workgroup sorts the buffers (bitonic), merges them into the kept lists and raises the thresholds.
@@ -161,9 +162,99 @@ __device__ __forceinline__ void topk_finish(TopkSmem<KP, BUF>& sm, int u0, int B
   }
 }
 
+// Offers the thread's N keys (bit c of pend: key[c] is still to be placed) to the buffers: key c belongs to user ub + c % NT,
+// whose threshold is thr[c % NT].  All 256 threads, every round: a phase appends what fits; while some buffer of the
+// workgroup overflowed, the buffers are folded into the kept lists, the thresholds raised and the rest offered again.
+template <int N, int NT, int KP, int BUF>
+__device__ __forceinline__ void topk_offer(TopkSmem<KP, BUF>& sm, const topk_key_t (&key)[N], unsigned pend, int ub,
+                                           topk_key_t (&thr)[NT], int K, int& ph) {
+  bool again;
+  do {
+    bool ovf = false;
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+      if (!(pend & (1u << c))) continue;
+      if (key[c] <= thr[c % NT] || topk_push(sm, ub + c % NT, key[c])) pend &= ~(1u << c);
+      else ovf = true;
+    }
+    again = topk_phase_end(sm, ovf, ph);
+    if (again) {
+      topk_reselect(sm);
+#pragma unroll
+      for (int i = 0; i < NT; ++i) thr[i] = sm.kept[ub + i][K - 1];
+    }
+  } while (again);
+}
+
+// The scan behind a score policy -- k_eval_topk's loop below, in the form the similar-items lists run (tlsan_similar.h:
+// SimScore).  k_eval_topk itself keeps its own text: on this loop with a policy of its own (built in the kernel or
+// inside the loop), and with only score_tiles4 or only topk_offer put into its text, it measured 1-2 % slower with an
+// exclusion list or at K > 64 (profiles/eval_scan.md).  So a fix to the scan's prologue, tile loop or offer loop goes
+// into both; the push, the phases, the reselection and the finish are shared functions.
+// A workgroup of grid (ceil(B/16), slices): wavefront w of slice y scores items n0 .. n0 + 63,
+// n0 = (round * slices + y) * 256 + 64 w, as 4 tiles of 16 rows x 16 items (score_tiles4: DENSE from all_emb, the chains
+// of k_eval_rank_dense; else through all_emb4, k_eval_rank's), and offers the eligible scores that beat their row's
+// threshold.  What a score is and which rows and items are eligible is the policy's:
+//   bool row(i, u)        sets up the lane's row i (row u of u_t); false: nothing is selected for it
+//   void col(acc, item)   takes in a tile: its accumulator and the local item of the lane's column
+//   float score(i)        row i's score of that column
+//   bool may(i, gn)       whether row i may select global item gn
+template <int D, int KP, int BUF, bool DENSE, class Policy>
+__device__ __forceinline__ void topk_scan(TopkSmem<KP, BUF>& sm, const TopkArgs& ta, Policy& pol) {
+  const EvalArgs& a = ta.e;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
+  const int u0 = blockIdx.x * 16;
+  topk_init(sm);
+  f32x4 af[D / 16];
+  load_user_frag<D>(a, u0, q, r, af);
+  bool uv[4];
+  int xlo[4], xhi[4];
+  topk_key_t thr[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int u = u0 + 4 * q + i;
+    uv[i] = pol.row(i, u);
+    xlo[i] = (uv[i] && ta.excl_off) ? ta.excl_off[u] : 0;
+    xhi[i] = (uv[i] && ta.excl_off) ? ta.excl_off[u + 1] : 0;
+    thr[i] = 0ull;
+  }
+  __syncthreads();
+  const int step = gridDim.y * 256;
+  const int nround = (a.I + step - 1) / step;
+  int ph = 0;
+  for (int rd = 0; rd < nround; ++rd) {
+    const int n0 = rd * step + (blockIdx.y * 4 + wave) * 64;
+    topk_key_t key[16];
+    unsigned pend = 0;
+    if (n0 < a.I) {
+      int item[4];
+      f32x4 acc[4];
+#pragma unroll
+      for (int tt = 0; tt < 4; ++tt) item[tt] = min(n0 + 16 * tt + r, a.I - 1);
+      score_tiles4<D, DENSE>(a, af, item, q, acc);
+#pragma unroll
+      for (int tt = 0; tt < 4; ++tt) {
+        const int n = n0 + 16 * tt + r;
+        const bool vn = n < a.I;
+        const int gn = n * a.id_mul + a.id_add;  // global item id
+        pol.col(acc[tt], item[tt]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          key[4 * tt + i] = topk_key(pol.score(i), gn);
+          // (the exclusion list is searched only for scores that pass the threshold)
+          if (vn && uv[i] && pol.may(i, gn) && key[4 * tt + i] > thr[i] && !topk_in_list(ta.excl_ids, xlo[i], xhi[i], gn))
+            pend |= 1u << (4 * tt + i);
+        }
+      }
+    }
+    topk_offer(sm, key, pend, 4 * q, thr, ta.K, ph);
+  }
+  topk_finish(sm, u0, a.B, ta.K, gridDim.y, blockIdx.y, ta.ids, ta.scores);
+}
+
 // grid (ceil(B/16), slices); wavefront w of slice y scores items n0 .. n0 + 63, n0 = (round * slices + y) * 256 + 64 w,
 // as 4 tiles of 16 users x 16 items: DENSE -- from all_emb, the chains of k_eval_rank_dense; else through all_emb4,
-// score_tile's chains (k_eval_rank).
+// score_tile's chains (k_eval_rank).  The text of topk_scan with the score written in (see there why it is kept).
 template <int D, int KP, int BUF, bool DENSE>
 __global__ __launch_bounds__(256, 2) void k_eval_topk(TopkArgs ta) {
   // (score = (acc * P) + bias in two roundings, as k_eval_label forms the label's score: contracted into one FMA it
@@ -257,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void k_eval_topk(TopkArgs ta) {
 }
 
 // [B, nl, K] lists (each sorted, the lists' items disjoint) -> [B, K].  16 rows per workgroup, 16 threads per row;
-// a phase offers 64 entries of every row.
+// a round offers 64 entries of every row.
 template <int KP, int BUF>
 __global__ __launch_bounds__(256) void k_topk_merge(const int32_t* cid, const float* csc, int B, int nl, int K,
                                                     int32_t* ids, float* scores) {
@@ -269,7 +360,7 @@ __global__ __launch_bounds__(256) void k_topk_merge(const int32_t* cid, const fl
   __syncthreads();
   const int n = nl * K;
   const int nround = (n + 63) / 64;
-  topk_key_t thr = 0ull;
+  topk_key_t thr[1] = {0ull};
   int ph = 0;
   for (int rd = 0; rd < nround; ++rd) {
     topk_key_t key[4];
@@ -283,20 +374,17 @@ __global__ __launch_bounds__(256) void k_topk_merge(const int32_t* cid, const fl
         const int id = cid[o];
         if (id >= 0) key[j] = topk_key(csc[o], id);
       }
-      if (key[j] > thr) pend |= 1u << j;
+      if (key[j] > thr[0]) pend |= 1u << j;
     }
-    for (;;) {
-      bool ovf = false;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (!(pend & (1u << j))) continue;
-        if (key[j] <= thr || topk_push(sm, u, key[j])) pend &= ~(1u << j);
-        else ovf = true;
-      }
-      if (!topk_phase_end(sm, ovf, ph)) break;
-      topk_reselect(sm);
-      thr = sm.kept[u][K - 1];
-    }
+    topk_offer(sm, key, pend, u, thr, K, ph);
   }
   topk_finish(sm, u0, B, K, 1, 0, ids, scores);
 }
+
+// (kept list, append buffer) per row by K: LDS 18 / 24 / 64 KB per workgroup -- at K = 256 two workgroups share a CU
+#define TOPK_DISPATCH(K, F) \
+  do {                        \
+    if ((K) <= 16) F(16, 128);  \
+    else if ((K) <= 64) F(64, 128); \
+    else F(256, 256);           \
+  } while (0)

@@ -2,30 +2,17 @@
 // callers in tlsan_api_eval.hip (tlsan_eval_topk, tlsan_topk_merge).
 #include "tlsan_topk.h"
 
-// (kept list, append buffer) per user by K: LDS 18 / 24 / 64 KB per workgroup -- at K = 256 two workgroups share a CU
-#define TOPK_DISPATCH(K, F) \
-  do {                        \
-    if ((K) <= 16) F(16, 128);  \
-    else if ((K) <= 64) F(64, 128); \
-    else F(256, 256);           \
-  } while (0)
-
-template <int D>
-static void launch_topk(const TopkArgs& a, dim3 grid, hipStream_t hs) {
-#define TOPK_L(KP, BUF)                                                                         \
-  do {                                                                                          \
-    if (a.e.all_emb) hipLaunchKernelGGL((k_eval_topk<D, KP, BUF, true>), grid, dim3(256), 0, hs, a); \
-    else hipLaunchKernelGGL((k_eval_topk<D, KP, BUF, false>), grid, dim3(256), 0, hs, a);            \
-  } while (0)
-  TOPK_DISPATCH(a.K, TOPK_L);
-#undef TOPK_L
-}
-
 hipError_t tlsan_launch_topk(const TopkArgs& a, int D, int nslices, hipStream_t hs) {
   const dim3 grid((a.e.B + 15) / 16, nslices);
-  if (D == 64) launch_topk<64>(a, grid, hs);
-  else if (D == 128) launch_topk<128>(a, grid, hs);
-  else launch_topk<256>(a, grid, hs);
+  dispatch_d(D, [&](auto d) {
+#define TOPK_L(KP, BUF)                                                                                    \
+  do {                                                                                                     \
+    if (a.e.all_emb) hipLaunchKernelGGL((k_eval_topk<d.value, KP, BUF, true>), grid, dim3(256), 0, hs, a); \
+    else hipLaunchKernelGGL((k_eval_topk<d.value, KP, BUF, false>), grid, dim3(256), 0, hs, a);            \
+  } while (0)
+    TOPK_DISPATCH(a.K, TOPK_L);
+#undef TOPK_L
+  });
   return hipGetLastError();
 }
 
