@@ -522,6 +522,36 @@ int tlsan_similar_topk(const tlsan_dims* dims, const tlsan_params* p, const floa
                        const int32_t* excl_ids, int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws,
                        size_t ws_bytes, void* stream);
 
+/* Diversified lists: the second stage behind tlsan_eval_topk.  From each row's POOL of N entries (1 <= K <= N <= 256, in
+ * tlsan_eval_topk's order: higher score first, ties -> lower global id) pick K by greedy maximal marginal relevance
+ * under a per-category cap.  Pool entry j of a row has a global id g_j and the model score s_j (pool_ids, pool_scores
+ * [B, N]), and, at flattened position b * N + j, its stored vector w_j (vec [B * N, d], d = 64, 128 or 256), inv_j (inv
+ * [B * N]) -- both what tlsan_item_vectors wrote for the flattened pool ids, so an id -1 has zeros -- and its category
+ * c_j (cate [B * N]).  The call reads no table: one form serves a whole table and a sharded one, with the same bits.
+ *   Valid entries: g_j >= 0 and s_j finite.  The others are never selected.
+ *   Relevance: r_j = (s_j - s_lo) / (s_hi - s_lo), s_hi / s_lo the scores of the row's first / last valid entry;
+ *     r_j = 0 for every j when s_hi == s_lo.
+ *   Similarity: cos(i, j) = (w_i . w_j) * (inv_i * inv_j) in fp32, the sum in one fixed order that depends on d and
+ *     the lane only; a zero row has inv 0 and so cos 0; the table scale P cancels, as in TLSAN_SIM_COSINE.
+ *   Greedy selection, t = 1 .. K, with diversity theta in [0, 1] and per_category m >= 0 (0: no cap):
+ *     eligible entries are valid, not yet selected and (m > 0) share their category with fewer than m selected entries;
+ *     the value of j is (1 - theta) r_j for t = 1, afterwards (1 - theta) r_j - theta * max over the selected i of
+ *     cos(i, j); the eligible entry of largest value is picked, equal values -> lower pool position; when no entry is
+ *     eligible the row ends there and the remaining outputs are id -1, score -inf.
+ *     A value that is NaN (a vector holding inf or NaN) counts as -inf.
+ *   Output: ids [B, K], scores [B, K] in selection order; the scores are the pool's own s_j, bit for bit.
+ *   theta = 0, m = 0 returns the valid entries of the pool in their order (the first K entries unchanged when they
+ *   are valid).  theta = 0, m > 0: a row that comes back with K valid entries is the capped greedy ranking over ALL
+ *   eligible items of the table, because the pool is the exact score-order prefix; a short row means the pool was too
+ *   small.  With theta = 0 no product is formed: the selection is integer logic on the order of the scores.
+ *   A row's result depends on its own pool only: not on B, the other rows, the launch geometry or the number of ranks.
+ * Refused before any launch, with the function's name in tlsan_last_error: NULL pointers, N outside 1..256, K outside
+ * 1..N, theta outside [0, 1] or NaN, m < 0, B < 1 or B * N >= 2^31 (TLSAN_E_BADARG), d not 64 / 128 / 256
+ * (TLSAN_E_UNSUPPORTED).  An addition: nothing else in the ABI changed (TLSAN_ABI_VERSION stays 14). */
+int tlsan_rerank(const int32_t* pool_ids, const float* pool_scores, const float* vec, const float* inv,
+                 const int32_t* cate, int32_t B, int32_t N, int32_t d, int32_t K, float diversity, int32_t per_category,
+                 int32_t* ids, float* scores, void* stream);
+
 /* Scores of caller-given candidates (a re-ranking of a retrieval stage's items, or a sampled evaluation):
  *   scores[b, c] = u_t[b] . [item_emb || cate_emb[item_cate]][g] + item_b[g],  g = cand[b, c] (global id),
  * for u_t [B, d], cand [B, C] int32, scores [B, C] float32.  Each score equals tlsan_eval_label_scores' for the

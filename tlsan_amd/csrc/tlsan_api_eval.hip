@@ -1,12 +1,13 @@
 // tlsan_api_eval.hip -- the evaluation entry points of the C ABI (include/tlsan.h): ranks of the labels among all items,
-// top-K items, similar-items lists, caller-given candidates and negative sampling.  The kernels of tlsan_eval.h are compiled
-// here; the top-K, similar-items and candidate kernels in units of their own (tlsan_topk.hip, tlsan_similar.hip, tlsan_cand.hip).
+// top-K items, similar-items lists, diversified lists, caller-given candidates and negative sampling.  The kernels of tlsan_eval.h are compiled
+// here; the top-K, similar-items, re-ranking and candidate kernels in units of their own (tlsan_topk.hip, tlsan_similar.hip, tlsan_rerank.hip, tlsan_cand.hip).
 #include <stdio.h>
 
 #include "tlsan_host.h"
 #include "tlsan_eval.h"
 #include "tlsan_topk.h"
 #include "tlsan_similar.h"
+#include "tlsan_rerank.h"
 #include "tlsan_cand.h"
 
 extern "C" {
@@ -283,6 +284,29 @@ int tlsan_similar_topk(const tlsan_dims* d, const tlsan_params* p, const float* 
     return fail(TLSAN_E_LAUNCH, "k_similar_topk: %s", hipGetErrorString(err));
   if (nsl > 1 && (err = tlsan_launch_topk_merge(w.t.ids, w.t.scores, Q, nsl, K, ids, scores, hs)) != hipSuccess)
     return fail(TLSAN_E_LAUNCH, "k_topk_merge: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+// ---- diversified lists (tlsan_rerank.h) ----
+int tlsan_rerank(const int32_t* pool_ids, const float* pool_scores, const float* vec, const float* inv, const int32_t* cate,
+                 int32_t B, int32_t N, int32_t d, int32_t K, float diversity, int32_t per_category, int32_t* ids,
+                 float* scores, void* stream) {
+  if (N < 1 || N > RERANK_MAX) return fail(TLSAN_E_BADARG, "tlsan_rerank: N must be in 1..%d (got %d)", RERANK_MAX, N);
+  if (K < 1 || K > N) return fail(TLSAN_E_BADARG, "tlsan_rerank: K must be in 1..N (got K %d, N %d)", K, N);
+  if (d != 64 && d != 128 && d != 256) return fail(TLSAN_E_UNSUPPORTED, "tlsan_rerank: d must be 64, 128 or 256 (got %d)", d);
+  if (!(diversity >= 0.0f && diversity <= 1.0f))   // (a NaN fails both)
+    return fail(TLSAN_E_BADARG, "tlsan_rerank: diversity must be in [0, 1] (got %g)", (double)diversity);
+  if (per_category < 0) return fail(TLSAN_E_BADARG, "tlsan_rerank: per_category must be >= 0 (got %d)", per_category);
+  if (B < 1 || (long long)B * N >= (1LL << 31))
+    return fail(TLSAN_E_BADARG, "tlsan_rerank: B must be >= 1 and B * N below 2^31 (got B %d, N %d)", B, N);
+  if (!pool_ids || !pool_scores || !vec || !inv || !cate || !ids || !scores)
+    return fail(TLSAN_E_BADARG, "tlsan_rerank: NULL argument");
+  RerankArgs a;
+  memset(&a, 0, sizeof(a));
+  a.pool_ids = pool_ids; a.pool_scores = pool_scores; a.vec = vec; a.inv = inv; a.cate = cate;
+  a.B = B; a.N = N; a.K = K; a.per_category = per_category; a.diversity = diversity; a.ids = ids; a.scores = scores;
+  const hipError_t err = tlsan_launch_rerank(a, d, (hipStream_t)stream);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_rerank: %s", hipGetErrorString(err));
   return TLSAN_OK;
 }
 

@@ -31,7 +31,7 @@ from .dist_comm import (ExchangePlan, KeyRouter, ModPartition, RowExchange, _sta
 from .dist_step import DynamicStep, FlatLayout, StaticStep, fused_params
 from .model import (LAZY_ADAGRAD_OPTIMIZERS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer, candidate_tensor, eval_topk,
                     exclusion_csr, grow_workspace, hits_and_rows, pack_dense, read_checkpoint, sample_negatives, sampled_ranks,
-                    score_candidates, item_vectors, similar_queries, similar_topk, topk_merge, unpack_dense, write_checkpoint)
+                    score_candidates, item_vectors, rerank, rerank_chunk, rerank_pool, similar_queries, similar_topk, topk_merge, unpack_dense, write_checkpoint)
 
 
 def _ru4(x):
@@ -399,13 +399,18 @@ class ShardedModel:
         ldims = L.Dims(self.U, max(nloc, 1), self.C, self.d, self.di, self.dc, self.H, self.Ls)
         return nloc, ldims, fused_params(self, self.shard, self._icl_local)
 
-    def recommend(self, batch, k, exclude=None):
-        """Model.recommend for this rank's rows (every rank calls it, with the same k and exclusion mode): u_t and
-        the exclusion lists are all-gathered, every rank selects the k best of ITS item shard for all rows
-        (tlsan_eval_topk, global ids n * world + rank), each row's lists go to the rank that owns the row (one
-        all-to-all) and are merged there (tlsan_topk_merge).  Same ids and scores as Model.recommend."""
+    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None):
+        """Model.recommend for this rank's rows (every rank calls it, with the same k, exclusion mode and diversity
+        settings): u_t and the exclusion lists are all-gathered, every rank selects the k best of ITS item shard for all
+        rows (tlsan_eval_topk, global ids n * world + rank), each row's lists go to the rank that owns the row (one
+        all-to-all) and are merged there (tlsan_topk_merge).  Same ids and scores as Model.recommend.
+        diversity / per_category / pool (Model.recommend's second stage): the lists selected and merged are the pools
+        of N entries; _rerank picks the k of each.  Same ids and score bits as Model.recommend on the gathered
+        parameters."""
+        N = rerank_pool(k, diversity, per_category, pool)
+        want = int(k)
         with self._eval_forward(batch) as (db, _, _, _, ut):
-            B, k, st = db.B, int(k), self._stream()
+            B, k, st = db.B, want if N is None else N, self._stream()
             ut_all = allgather_rows(ut, self.group)
             Bt = int(ut_all.shape[0])
             off, xid = self._gather_excl(*exclusion_csr(db, exclude, self.I), B)
@@ -423,7 +428,45 @@ class ShardedModel:
                 a2a(rsc, csc, None, None, self.group)
                 cid, csc = topk_merge(self.lib, rid.view(self.world, B, k).transpose(0, 1).contiguous(),
                                       rsc.view(self.world, B, k).transpose(0, 1).contiguous(), st)
+            if N is not None:
+                cid, csc = self._rerank(cid, csc, want, diversity, per_category)
         return cid, csc
+
+    def _rerank(self, pid, psc, k, diversity, per_category):
+        """The second stage of a diversified recommend on this rank's merged pools [B, N] (collective; B, N the same on
+        every rank): the pool ids of a chunk of rows are all-gathered, every rank reads the stored vectors and inverse
+        norms of the ids ITS item shard holds (tlsan_item_vectors, zeros for the others), one all-to-all returns each
+        rank's rows and every entry's are SELECTED from the rank that holds its id, g % world (a sum would turn -0 into
+        +0); the categories come from the replicated map; tlsan_rerank picks.  A chunk's all-gathered vectors stay
+        within model.RERANK_STAGING bytes."""
+        B, N = pid.shape
+        st, W, d = self._stream(), self.world, self.d
+        ids = torch.empty(B, k, dtype=torch.int32, device=self.device)
+        scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        nloc, ldims, lp = self._item_shard()
+        rows = rerank_chunk(N, d, W)
+        for r0 in range(0, B, rows):
+            flat = pid[r0:r0 + rows].reshape(-1)
+            Q = int(flat.shape[0])
+            asked = allgather_rows(flat, self.group)           # rank r's entries at [r Q, (r + 1) Q)
+            if nloc > 0:
+                vec, inv = item_vectors(self.lib, ldims, lp, asked, W, self.rank, st)
+            else:
+                vec = torch.zeros(W * Q, d, dtype=torch.float32, device=self.device)
+                inv = torch.zeros(W * Q, dtype=torch.float32, device=self.device)
+            if W > 1:
+                # block s of what arrives is rank s's reading of this rank's entries
+                gvec, ginv = torch.empty_like(vec), torch.empty_like(inv)
+                a2a(gvec, vec, None, None, self.group)
+                a2a(ginv, inv, None, None, self.group)
+                owner = torch.where(flat >= 0, flat % W, torch.zeros_like(flat)).long()
+                vec = torch.gather(gvec.view(W, Q, d), 0, owner[None, :, None].expand(1, Q, d))[0].contiguous()
+                inv = torch.gather(ginv.view(W, Q), 0, owner[None])[0].contiguous()
+            g = flat.clamp(min=0).long()
+            cate = self.cate_by_key[(g % W) * self.router.R + g // W]      # (the replicated item -> category map)
+            rerank(self.lib, pid[r0:r0 + rows], psc[r0:r0 + rows], vec, inv, cate, k, diversity, per_category,
+                   ids[r0:r0 + rows], scores[r0:r0 + rows], st)
+        return ids, scores
 
     def similar_items(self, items, k, metric="cosine", exclude=None):
         """Model.similar_items, collective: every rank passes the same items (and k, metric, exclude) and every rank

@@ -325,6 +325,43 @@ def eval_topk(lib, dims, cparams, ut, B, k, excl, id_mul, id_add, workspace, str
     return ids, scores
 
 
+RERANK_STAGING = 256 << 20   # bytes: no staging buffer of a diversified recommend is larger (k_all_emb's rule)
+
+
+def rerank_pool(k, diversity, per_category, pool):
+    """Checks recommend's diversity arguments -> the pool size N of the re-ranking stage, or None when none is asked for
+    (diversity == 0 and per_category == 0: the plain top-k path).  N = pool, or min(256, max(4 k, 32))."""
+    k, per_category = int(k), int(per_category)
+    diversity = float(diversity)
+    if not 0.0 <= diversity <= 1.0:   # (a NaN fails)
+        raise ValueError("diversity must be in [0, 1], got %r" % (diversity,))
+    if per_category < 0:
+        raise ValueError("per_category must be >= 0, got %d" % per_category)
+    if diversity == 0.0 and per_category == 0:
+        if pool is not None:
+            raise ValueError("pool is the candidate pool of a diversified list: give diversity or per_category with it")
+        return None
+    N = int(pool) if pool is not None else min(L.RERANK_MAX, max(4 * k, 32))
+    if not 1 <= k <= N <= L.RERANK_MAX:
+        raise ValueError("want 1 <= k <= pool <= %d, got k %d, pool %d" % (L.RERANK_MAX, k, N))
+    return N
+
+
+def rerank_chunk(N, d, copies=1):
+    """Rows of a diversified recommend handled at a time: `copies` staged [rows * N, d] float32 matrices stay within
+    RERANK_STAGING bytes."""
+    return max(1, RERANK_STAGING // (copies * N * d * 4))
+
+
+def rerank(lib, pool_ids, pool_scores, vec, inv, cate, k, diversity, per_category, ids, scores, stream):
+    """tlsan_rerank on the pools [B, N] with their entries' vectors [B * N, d], inverse norms and categories [B * N]
+    -> written into ids [B, k] int32 and scores [B, k] float32 (contiguous device tensors)."""
+    B, N = pool_ids.shape
+    L.check(lib.tlsan_rerank(pool_ids.data_ptr(), pool_scores.data_ptr(), vec.data_ptr(), inv.data_ptr(), cate.data_ptr(),
+                             B, N, int(vec.shape[1]), int(k), float(diversity), int(per_category), ids.data_ptr(),
+                             scores.data_ptr(), stream), "tlsan_rerank")
+
+
 SIMILAR_METRICS = {"dot": L.SIM_DOT, "cosine": L.SIM_COSINE}
 SIMILAR_CHUNK = 4096   # queries per tlsan_similar_topk call: bounds the slices' lists in the workspace (Q x slices x K)
 
@@ -1204,16 +1241,41 @@ class Model(object):
         ranks = ranks - ahead
         return (ranks, (self.config["item_count"] - 1) - held) if return_eligible else ranks
 
-    def recommend(self, batch, k, exclude=None):
+    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None):
         """The k best items over ALL items for each row -- what tf.nn.top_k(eval_logits, k) gives the reference
         (model.py:140) -- without materialising the [B, I] scores.  Takes label_ranks' batches (the label and the
         negative are not used).  -> (ids [B, k] int32, scores [B, k] float32) device tensors, in tf.nn.top_k's
         order (higher score first, ties -> lower id); rows with fewer than k eligible items end in -1 / -inf.
         exclude: None; "history" -- the items the row's input holds (the last Ls items and the current session);
-        a sequence of B arrays of item ids; or a SeenItems holder -- the user's seen items and the row's input.  Scores equal label_ranks' / eval_label_scores' bit for bit."""
+        a sequence of B arrays of item ids; or a SeenItems holder -- the user's seen items and the row's input.  Scores equal label_ranks' / eval_label_scores' bit for bit.
+        diversity (theta in [0, 1]), per_category (m >= 0; 0 = no cap), pool: a second stage over
+        the row's N = pool (default min(256, max(4 k, 32)); k <= N <= 256) best items, tlsan_rerank.  Valid pool entries
+        (id >= 0, finite score) get the relevance r_j = (s_j - s_lo) / (s_hi - s_lo) over the pool's first / last valid
+        score (0 when equal) and the list is picked greedily: an entry is eligible while it is not selected and (m > 0)
+        fewer than m selected entries share its category; its value is (1 - theta) r_j for the first pick, afterwards
+        (1 - theta) r_j - theta * max over the selected i of cos(i, j), the cosine of similar_items; the largest value
+        wins, equal values -> higher in the pool; when nobody is eligible the row ends in -1 / -inf.  The scores
+        returned are the model's own, bit for bit, in selection order.  theta = 0 with m > 0 is exact whenever the row
+        comes back full: it is the capped ranking over ALL eligible items (the pool is the exact score-order prefix); a
+        short row means the pool was too small -- raise it.  With both left at 0 nothing changes: the plain top-k path,
+        the same launches and bits (pool alone is a ValueError)."""
+        N = rerank_pool(k, diversity, per_category, pool)
         _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
-        return eval_topk(self.lib, self.dims, self.cparams, ut, db.B, k, exclusion_csr(db, exclude, self.config["item_count"]),
-                         1, 0, self._topk_workspace, self._stream())
+        excl, st = exclusion_csr(db, exclude, self.config["item_count"]), self._stream()
+        if N is None:
+            return eval_topk(self.lib, self.dims, self.cparams, ut, db.B, k, excl, 1, 0, self._topk_workspace, st)
+        # (forward has landed an owed lazy-L2 correction; the vectors are read as stored, the scale not folded)
+        pid, psc = eval_topk(self.lib, self.dims, self.cparams, ut, db.B, N, excl, 1, 0, self._topk_workspace, st)
+        ids = torch.empty(db.B, int(k), dtype=torch.int32, device=self.device)
+        scores = torch.empty(db.B, int(k), dtype=torch.float32, device=self.device)
+        rows = rerank_chunk(N, self.config["hidden_units"])
+        for r0 in range(0, db.B, rows):
+            flat = pid[r0:r0 + rows].reshape(-1)
+            vec, inv = item_vectors(self.lib, self.dims, self.cparams, flat, 1, 0, st)
+            cate = self.item_cate[flat.clamp(min=0).long()]
+            rerank(self.lib, pid[r0:r0 + rows], psc[r0:r0 + rows], vec, inv, cate, k, diversity, per_category,
+                   ids[r0:r0 + rows], scores[r0:r0 + rows], st)
+        return ids, scores
 
     def similar_items(self, items, k, metric="cosine", exclude=None):
         """The k nearest items of each item of `items` (a 1-D list, array or tensor of global ids; outside

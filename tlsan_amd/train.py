@@ -75,6 +75,14 @@ def parse(argv=None):
                     help="items kept out of the recommendations: 'history' = the items the test row's input holds (its "
                          "last Ls items and its current session -- what the batch carries), 'none' = nothing, 'seen' = "
                          "every item of the user's training samples and the row's input")
+    ap.add_argument("--recommend_diversity", type=float, default=0.0,
+                    help="with --recommend_k: re-rank each row's pool by maximal marginal relevance, theta in [0, 1] "
+                         "(0 = relevance only, 1 = novelty only after the first pick; Model.recommend's diversity)")
+    ap.add_argument("--recommend_per_category", type=int, default=0,
+                    help="with --recommend_k: at most this many items of one category in a row's list (0 = no cap)")
+    ap.add_argument("--recommend_pool", type=int, default=0,
+                    help="with --recommend_diversity / --recommend_per_category: the best N items per row the list is picked "
+                         "from, recommend_k <= N <= 256 (0 = min(256, max(4 K, 32)))")
     ap.add_argument("--similar_k", type=int, default=0,
                     help="at the end of training, write <model_dir>/similar-<K>.npz: the K nearest items of every item "
                          "(item [I], ids [I, K], scores [I, K]; 0 = off)")
@@ -122,10 +130,23 @@ def recommend_path(model_dir, k):
     return os.path.join(model_dir, "recommend_top%d.npz" % k)
 
 
-def write_recommendations(model_dir, k, user, ids, scores):
+def write_recommendations(model_dir, k, user, ids, scores, settings=None):
+    """settings: the diversity keywords of recommend (recommend_settings), recorded beside the lists when any is set."""
     path = recommend_path(model_dir, k)
-    np.savez(path, user=np.asarray(user, np.int64), ids=np.asarray(ids, np.int32), scores=np.asarray(scores, np.float32))
+    extra = {} if not settings else dict(diversity=np.float64(settings["diversity"]),
+                                         per_category=np.int64(settings["per_category"]),
+                                         pool=np.int64(settings["pool"] or 0))
+    np.savez(path, user=np.asarray(user, np.int64), ids=np.asarray(ids, np.int32), scores=np.asarray(scores, np.float32),
+             **extra)
     return path
+
+
+def recommend_settings(args):
+    """The diversity keywords of model.recommend from the flags; {} when none is set (the plain top-K lists)."""
+    if not (args.recommend_diversity or args.recommend_per_category or args.recommend_pool):
+        return {}
+    return dict(diversity=args.recommend_diversity, per_category=args.recommend_per_category,
+                pool=args.recommend_pool or None)
 
 
 def similar_path(model_dir, k):
@@ -331,12 +352,13 @@ def eval_prec_recall(model, test_set, config, rows=None, summary=True):
     return prec, recall
 
 
-def recommend_test_set(model, rows, k, exclude):
-    """model.recommend over every test row -> (user, ids, scores) host arrays in test-set order; None but on rank 0."""
+def recommend_test_set(model, rows, k, exclude, **settings):
+    """model.recommend over every test row (settings: its diversity keywords) -> (user, ids, scores) host arrays in
+    test-set order; None but on rank 0."""
     parts = []
     for batch, real, _ in rows.launches(True):
         db = model.device_batch(batch, is_test=True)
-        parts.append(rows.gather((db.u,) + tuple(model.recommend(db, k, exclude=exclude)), real))
+        parts.append(rows.gather((db.u,) + tuple(model.recommend(db, k, exclude=exclude, **settings)), real))
     if parts[0] is not None:
         return tuple(torch.cat(x).cpu().numpy() for x in zip(*parts))
 
@@ -446,9 +468,10 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
     final_full = full_now() if full_mode else None
     model.save(None)                                           # train.py:239
     if args.recommend_k:
-        rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen))
+        settings = recommend_settings(args)
+        rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen), **settings)
         if rec is not None:                                    # (rank 0 holds the rows)
-            path = write_recommendations(args.model_dir, args.recommend_k, *rec)
+            path = write_recommendations(args.model_dir, args.recommend_k, *rec, settings=settings)
             say("Recommendations: %s" % path)
     if args.similar_k:
         path = write_similar(model, args.model_dir, args.similar_k, args.similar_metric, rows.config["item_count"],
