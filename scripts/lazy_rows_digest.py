@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from tests.helpers import make_config, random_batch, random_params
-from tests.test_gpu_lazy_opt import random_slots
+from tests.lazy_opt_ref import random_slots
 from tlsan_amd.model import Model
 
 CLIP = 0.05

@@ -47,8 +47,8 @@ def initial_accumulators(p, kind):
 def restricted_adagrad_step(q, acc, cat, b, cfg, lr, kind, clip):
     """One lazy step from parameters q and accumulators acc (dicts of fp64 arrays; acc is updated in place).
     -> (loss, new parameters, info, used): info carries the oracle's and "g", the clipped gradients; used the row masks of
-    tests/test_gpu_lazy_opt.py's used_rows with its saturated-candidate entry item_b_amb."""
-    from tests.test_gpu_lazy_opt import used_rows
+    tests/lazy_opt_ref.py's used_rows with its saturated-candidate entry item_b_amb."""
+    from tests.lazy_opt_ref import used_rows
     assert kind in KINDS
     q = {k: np.asarray(v, np.float64) for k, v in q.items()}
     loss, _, info = orc.train_step(q, cat, b, cfg["num_heads"], cfg["regulation_rate"], lr=lr, clip=clip, optimizer="sgd")
@@ -61,7 +61,7 @@ def restricted_adagrad_step(q, acc, cat, b, cfg, lr, kind, clip):
         else:
             newq[k], acc[k] = elementwise_rule(q[k], g[k], acc[k], lr)
     used = used_rows(b, cat, cfg)
-    # (item_b: the saturated candidates are compared nowhere -- restricted_step of tests/test_gpu_lazy_opt.py)
+    # (item_b: the saturated candidates are compared nowhere -- restricted_step of tests/lazy_opt_ref.py)
     near = np.abs(np.asarray(info["logits"], np.float64).reshape(-1)) > 15.0
     amb = np.zeros_like(used["item_b"])
     amb[np.asarray(b["i"])[near]] = True

@@ -1,4 +1,6 @@
-"""Shared test helpers: seeded configs, random batches, fixture batches."""
+"""Shared test helpers: seeded configs, random batches, fixture batches; models set up from oracle parameters, the batch as
+the tuple the models take, host copies and bit patterns of results.  Importable without a GPU (torch and tlsan_amd are
+imported inside the functions that need them)."""
 import os
 
 import numpy as np
@@ -64,6 +66,97 @@ def random_batch(cfg, B, Sn, seed=0, test=False, full=False):
     b = {k: (np.asarray(v, np.int64) if np.asarray(v).dtype.kind in "iu" else v) for k, v in b.items()}
     cat = rng.randint(0, C, I).astype(np.int32)
     return b, cat
+
+
+BF16_TABLES = ("item_emb", "user_emb", "cate_emb")
+
+
+def model(cfg, cat, p=None, slots=None, **kw):
+    from tlsan_amd.model import Model
+    m = Model(cfg, cat, **kw)
+    if p is not None:
+        m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
+    if slots is not None:
+        m.set_slots([{k: np.asarray(v, np.float32) for k, v in s.items()} for s in slots])
+    return m
+
+
+def sharded(cfg, cat, p=None, slots=None, l2_mode="lazy", **kw):
+    from tlsan_amd.dist import ShardedModel
+    m = ShardedModel(cfg, cat, device="cuda:0", l2_mode=l2_mode, **kw)
+    if p is not None:
+        m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
+    if slots is not None:
+        m._set_slots([{k: np.asarray(v, np.float32) for k, v in s.items()} for s in slots])
+    return m
+
+
+def lazy_model(I, table_dtype, seed):
+    """A d = 256 model after two lazy-L2 steps: its table scale P is no longer 1."""
+    cfg = make_config(U=300, I=I, C=31, d=256)
+    p = random_params(cfg, seed=seed)
+    tb, cat = random_batch(cfg, B=256, Sn=3, seed=seed + 1)
+    m = model(cfg, cat, p, l2_mode="lazy", table_dtype=table_dtype)
+    for _ in range(2):
+        m.train(None, (tb["u"], tb["i"], tb["y"], tb["hist_i"], tb["hist_i_new"], tb["hist_t"], tb["sl"], tb["sl_new"],
+                       tb["u_cate"]), 1.0)
+    assert m.table_scale() != 1.0
+    return cfg, m
+
+
+def batch_tuple(b, test=False):
+    return (b["u"], b["i"], b["j"] if test else b["y"], b["hist_i"], b["hist_i_new"], b["hist_t"],
+            b["sl"], b["sl_new"], b["u_cate"])
+
+
+def concat_batches(per):
+    """the global batch all ranks train on together (pad session columns to a common width)"""
+    Sn = max(b["hist_i_new"].shape[1] for b in per)
+    out = {}
+    for k in per[0]:
+        if k == "hist_i_new":
+            out[k] = np.concatenate([np.pad(b[k], ((0, 0), (0, Sn - b[k].shape[1]))) for b in per], 0)
+        else:
+            out[k] = np.concatenate([b[k] for b in per], 0)
+    return out
+
+
+def p32(p):
+    """oracle params rounded to fp32 (what the device holds), kept in fp64 for the oracle."""
+    return {k: np.asarray(v, np.float32).astype(np.float64) for k, v in p.items()}
+
+
+def bf16_round(a):
+    """round-to-nearest-even to bfloat16, back to float32 (what Model.set_params stores)"""
+    import torch
+    return torch.as_tensor(np.asarray(a, np.float32)).to(torch.bfloat16).float().numpy()
+
+
+def host(t):
+    return t.cpu().numpy()
+
+
+def bits(x):
+    """the bit patterns of float32 values (of nothing else: another dtype is refused, not reinterpreted)"""
+    x = np.ascontiguousarray(x)
+    assert x.dtype == np.float32, x.dtype
+    return x.view(np.int32)
+
+
+def history_sets(b):
+    return [set(b["hist_i"][r, :b["sl"][r]].tolist()) | set(b["hist_i_new"][r, :b["sl_new"][r]].tolist())
+            for r in range(len(b["u"]))]
+
+
+def label_scores(m, db, ut):
+    import ctypes as C
+    import torch
+    from tlsan_amd import _lib as L
+    out = torch.empty(db.B, dtype=torch.float32, device=m.device)
+    ws = m._workspace(db.B, db.Sn)
+    L.check(m.lib.tlsan_eval_label_scores(C.byref(m.dims), C.byref(m.cparams), ut.data_ptr(), db.i.data_ptr(), db.B,
+                                          out.data_ptr(), ws.data_ptr(), ws.numel(), m._stream()), "label scores")
+    return host(out)
 
 
 def fixture_batch(name, cls_name="DataInput", bs=32, k=10, bi=0):

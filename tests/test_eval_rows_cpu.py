@@ -4,16 +4,13 @@ and shares at world 1) and over 2 and 3 gloo processes.  What is compared are ex
 P@k / R@k hit counters, the two rank histograms -- and the recommendation arrays, each against the value computed
 straight from the test set's arrays."""
 import inspect
-import os
-import socket
 import types
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
+from tests.ranks import run_ranks
 from tlsan_amd import train as T
 from tlsan_amd.input import PackedSet
 from tlsan_amd.model import KS, TopKCounters
@@ -191,35 +188,16 @@ def test_evaluations_one_process(monkeypatch):
     assert quiet.eval_writer.rows == [] and quiet._topk.n_p == N
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        got = _evaluate(T.EvalRows(_test_set(), CFG, rank, world))
-        assert (got["rec"] is None) == (rank != 0)             # rank 0 alone holds (and writes) the recommendations
-        if rank == 0:
-            _check(got, _expected())
-        ret[rank] = "ok"
-    except Exception:
-        import traceback
-        ret[rank] = "FAIL: " + traceback.format_exc()
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world):
+    got = _evaluate(T.EvalRows(_test_set(), CFG, rank, world))
+    assert (got["rec"] is None) == (rank != 0)             # rank 0 alone holds (and writes) the recommendations
+    if rank == 0:
+        _check(got, _expected())
 
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_evaluations_over_gloo(world):
-    ret = mp.Manager().dict()
-    mp.spawn(_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
-    assert dict(ret) == {r: "ok" for r in range(world)}, dict(ret)
+    run_ranks(_worker, world)
 
 
 def test_drivers_hand_run_the_rows():

@@ -13,8 +13,8 @@ import pytest
 
 from oracle import tlsan_oracle as orc
 from tests import adagrad_ref as ref
-from tests.helpers import make_config, random_batch, random_params
-from tests.test_gpu_lazy_opt import (BF16_TABLES, ROW_TABLES, SPARSE_CATEGORY_CASES, _bf16_round, _cmp, _model, _p32, _tuple)
+from tests.helpers import BF16_TABLES, batch_tuple, bf16_round, make_config, model, p32, random_batch, random_params
+from tests.lazy_opt_ref import ROW_TABLES, SPARSE_CATEGORY_CASES, compared
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +23,7 @@ ELEMENTWISE, ROWWISE = ref.KINDS
 LR = 0.05
 
 
-def _sync_amb(m, q, acc, used):
+def sync_amb(m, q, acc, used):
     """carry the device's item_b (and its accumulator) of the saturated candidates into the reference for the next steps"""
     amb = used["item_b_amb"]
     if amb.any():
@@ -31,7 +31,7 @@ def _sync_amb(m, q, acc, used):
         acc["item_b"] = np.where(amb, np.asarray(m.get_slots()[0]["item_b"], np.float64), acc["item_b"])
 
 
-def _check(m, q, acc, p_prev, used, tol_n, exact_unused=None):
+def check_step(m, q, acc, p_prev, used, tol_n, exact_unused=None):
     got = m.get_params()
     slots = m.get_slots()
     assert len(slots) == 1
@@ -40,11 +40,11 @@ def _check(m, q, acc, p_prev, used, tol_n, exact_unused=None):
         assert np.shape(s1[k]) == np.shape(acc[k]), k
         if k.endswith("_b2"):
             continue      # (gradient = rounding noise, see test_gpu_parity.test_other_optimizers_track_oracle)
-        a = _cmp(k, np.asarray(got[k], np.float64).reshape(np.shape(q[k])), used)
-        r, r0 = _cmp(k, q[k], used), _cmp(k, p_prev[k], used)
+        a = compared(k, np.asarray(got[k], np.float64).reshape(np.shape(q[k])), used)
+        r, r0 = compared(k, q[k], used), compared(k, p_prev[k], used)
         step = np.abs(r - r0).max()
         assert np.abs(a - r).max() < 2e-3 * step * tol_n + 1e-7, k
-        gs, rs = _cmp(k, s1[k], used), _cmp(k, acc[k], used)
+        gs, rs = compared(k, s1[k], used), compared(k, acc[k], used)
         assert np.abs(gs - rs).max() < 2e-3 * np.abs(rs).max() + 1e-9, k
     if exact_unused is not None:
         P0, S0 = exact_unused
@@ -61,11 +61,11 @@ def test_adagrad_tracks_the_reference(kind, tmp_path):
     their accumulator bit for bit."""
     cfg = make_config(U=300, I=450, C=20, d=64, regulation_rate=1e-3, max_gradient_norm=0.05, optimizer=kind,
                       model_dir=str(tmp_path))
-    p = _p32(random_params(cfg, seed=71))
+    p = p32(random_params(cfg, seed=71))
     acc = ref.random_accumulators(p, kind, 72)
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=16 + 4 * s, Sn=1 + s % 3, seed=700 + s)[0] for s in range(6)]
-    m = _model(cfg, cat, p, [acc])
+    m = model(cfg, cat, p, [acc])
     q = dict(p)
     for n, b in enumerate(batches):
         clip = 0.05 if n < 5 else 1e3
@@ -74,14 +74,14 @@ def test_adagrad_tracks_the_reference(kind, tmp_path):
         prev = q
         loss, q, info, used = ref.restricted_adagrad_step(q, acc, cat, b, cfg, LR, kind, clip)
         assert (info["coef"] < 1.0) == (n < 5)
-        l = m.train(None, _tuple(b), LR)
+        l = m.train(None, batch_tuple(b), LR)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss)), (n, l, loss)
         assert not used["user_emb"].all() and not used["item_emb"].all()
-        _check(m, q, acc, prev, used, n + 1, exact_unused=before)
-        _sync_amb(m, q, acc, used)
+        check_step(m, q, acc, prev, used, n + 1, exact_unused=before)
+        sync_amb(m, q, acc, used)
         if n == 2:                                # checkpoint round trip in the middle of the run
             path = m.save()
-            m = _model(cfg, cat, None)
+            m = model(cfg, cat, None)
             m.restore(None, path)
     assert m.table_scale() == 1.0
 
@@ -91,31 +91,31 @@ def test_restore_refuses_another_optimizers_slots(tmp_path):
     optimizer, and nothing is loaded."""
     cfg = make_config(U=30, I=45, C=5, d=64, optimizer=ELEMENTWISE, model_dir=str(tmp_path))
     _, cat = random_batch(cfg, B=4, Sn=1, seed=0)
-    path = _model(cfg, cat).save()
-    m = _model(dict(cfg, optimizer=ROWWISE), cat)
+    path = model(cfg, cat).save()
+    m = model(dict(cfg, optimizer=ROWWISE), cat)
     before = m.get_params()
     with pytest.raises(ValueError) as e:
         m.restore(None, path)
     assert ROWWISE in str(e.value) and "(45, 32)" in str(e.value) and "(45,)" in str(e.value)
     with pytest.raises(ValueError):
-        _model(dict(cfg, optimizer="lazy_adam"), cat).restore(None, path)
+        model(dict(cfg, optimizer="lazy_adam"), cat).restore(None, path)
     after = m.get_params()
     assert all(np.array_equal(before[k], after[k]) for k in before)
 
 
 def _run(cfg, cat, kind, batches, clip=0.05, seed=80, table_dtype="f32", after_step=None):
-    p = _p32(random_params(cfg, seed=seed))
+    p = p32(random_params(cfg, seed=seed))
     acc = ref.random_accumulators(p, kind, seed + 1)
-    m = _model(dict(cfg, optimizer=kind), cat, p, [acc], table_dtype=table_dtype)
+    m = model(dict(cfg, optimizer=kind), cat, p, [acc], table_dtype=table_dtype)
     q = dict(p)
     for s, b in enumerate(batches):
         before = (m.get_params(), m.get_slots())
         prev = q
         loss, q, info, used = ref.restricted_adagrad_step(q, acc, cat, b, cfg, LR, kind, clip)
-        l = m.train(None, _tuple(b), LR)
+        l = m.train(None, batch_tuple(b), LR)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss)), (s, l, loss)
-        _check(m, q, acc, prev, used, s + 1, exact_unused=before)
-        _sync_amb(m, q, acc, used)
+        check_step(m, q, acc, prev, used, s + 1, exact_unused=before)
+        sync_amb(m, q, acc, used)
         if after_step is not None:
             after_step(b, used)
 
@@ -145,13 +145,13 @@ def test_row_accumulator_is_a_row_mean():
     the stored elements."""
     kind = ROWWISE
     cfg = make_config(U=200, I=300, C=20, d=128, Ls=10, regulation_rate=1e-3, max_gradient_norm=1e3, optimizer=kind)
-    p = _p32(random_params(cfg, seed=90))
+    p = p32(random_params(cfg, seed=90))
     acc = ref.random_accumulators(p, kind, 91)
     acc0 = {k: v.copy() for k, v in acc.items()}
     b, cat = random_batch(cfg, B=24, Sn=3, seed=92)
-    m = _model(cfg, cat, p, [acc])
+    m = model(cfg, cat, p, [acc])
     loss, q, info, used = ref.restricted_adagrad_step(dict(p), acc, cat, b, cfg, LR, kind, 1e3)
-    l = m.train(None, _tuple(b), LR)
+    l = m.train(None, batch_tuple(b), LR)
     assert abs(l - loss) < 2e-4 * max(1.0, abs(loss))
     got, s1 = m.get_params(), m.get_slots()[0]
     eps = 2.0 ** -23
@@ -174,15 +174,15 @@ def test_width_one_parameters_agree_between_the_kinds():
     """From the same parameters with every accumulator at 0.1 (what Model allocates), one step of each kind: item_b and
     every dense weight -- width 1, the elementwise rule in both -- come out bit-equal, with their accumulators."""
     cfg = make_config(U=200, I=300, C=20, d=64, regulation_rate=1e-3, max_gradient_norm=0.05)
-    p = _p32(random_params(cfg, seed=93))
+    p = p32(random_params(cfg, seed=93))
     b, cat = random_batch(cfg, B=24, Sn=3, seed=94)
     out = []
     for kind in ref.KINDS:
-        m = _model(dict(cfg, optimizer=kind), cat, p)
+        m = model(dict(cfg, optimizer=kind), cat, p)
         s0 = m.get_slots()
         assert len(s0) == 1 and all(np.all(v == np.float32(0.1)) for v in s0[0].values())
         assert s0[0]["item_emb"].shape == ((300,) if kind == ROWWISE else (300, 32))
-        m.train(None, _tuple(b), LR)
+        m.train(None, batch_tuple(b), LR)
         out.append((m.get_params(), m.get_slots()[0]))
     (pe, se), (pr, sr) = out
     moved = 0
@@ -229,7 +229,7 @@ _CSEG = r"""
 import sys
 sys.path.insert(0, sys.argv[1])
 from tests.test_gpu_adagrad import ROWWISE, _row_form_run, _sparse_category_run
-from tests.test_gpu_lazy_opt import SPARSE_CATEGORY_CASES
+from tests.lazy_opt_ref import SPARSE_CATEGORY_CASES
 _row_form_run(64, 10, 40, ROWWISE, B=32, seed=90)
 _row_form_run(128, 24, 40, ROWWISE, B=32, seed=91)
 for _, C, item_cates, ucate_cates, B, d in SPARSE_CATEGORY_CASES:
@@ -251,14 +251,14 @@ def test_rowwise_adagrad_on_a_scaled_state():
     row-wise step then acts on the true values P * stored and leaves P as it is."""
     kind = ROWWISE
     cfg = make_config(U=300, I=450, C=20, d=64, regulation_rate=0.05, max_gradient_norm=0.05, optimizer=kind)
-    p = _p32(random_params(cfg, seed=131))
+    p = p32(random_params(cfg, seed=131))
     acc = ref.random_accumulators(p, kind, 132)
     _, cat = random_batch(cfg, B=8, Sn=3, seed=133)
-    m = _model(cfg, cat, p, [acc])
+    m = model(cfg, cat, p, [acc])
     copt, m._copt = m._copt, None            # two unclipped lazy-L2 SGD steps (tlsan_train_step): P = (1 - lr reg)^2
     cfg["max_gradient_norm"] = 1e3
     for s in range(2):
-        m.train(None, _tuple(random_batch(cfg, B=16, Sn=2, seed=134 + s)[0]), 1.0)
+        m.train(None, batch_tuple(random_batch(cfg, B=16, Sn=2, seed=134 + s)[0]), 1.0)
     m._copt = copt
     cfg["max_gradient_norm"] = 0.05
     P = m.table_scale()
@@ -269,7 +269,7 @@ def test_rowwise_adagrad_on_a_scaled_state():
     q0 = true(stored0, P)
     b = random_batch(cfg, B=20, Sn=2, seed=136)[0]
     loss, q, info, used = ref.restricted_adagrad_step(dict(q0), acc, cat, b, cfg, LR, kind, 0.05)
-    l = m.train(None, _tuple(b), LR)
+    l = m.train(None, batch_tuple(b), LR)
     assert abs(l - loss) < 2e-4 * max(1.0, abs(loss)), (l, loss)
     assert m.table_scale() == P
     stored = m.get_params()
@@ -278,9 +278,9 @@ def test_rowwise_adagrad_on_a_scaled_state():
     for k in q:
         if k.endswith("_b2"):
             continue
-        a, r, r0 = (_cmp(k, np.asarray(x).reshape(np.shape(q[k])), used) for x in (got[k], q[k], q0[k]))
+        a, r, r0 = (compared(k, np.asarray(x).reshape(np.shape(q[k])), used) for x in (got[k], q[k], q0[k]))
         assert np.abs(a - r).max() < 2e-3 * np.abs(r - r0).max() + 1e-6, k
-        gs, rs = _cmp(k, s1[k], used), _cmp(k, acc[k], used)
+        gs, rs = compared(k, s1[k], used), compared(k, acc[k], used)
         assert np.abs(gs - rs).max() < 2e-3 * np.abs(rs).max() + 1e-9, k
     for k in ROW_TABLES:
         keep = ~used[k]
@@ -294,17 +294,17 @@ def test_adagrad_with_bf16_tables(kind):
     2e-3 of the step) of the reference's value and representable in bf16, unused rows keep their bits, two runs leave the
     same bits."""
     cfg = make_config(U=300, I=450, C=20, d=64, regulation_rate=1e-3, max_gradient_norm=0.05, optimizer=kind)
-    p = _p32(random_params(cfg, seed=75))
+    p = p32(random_params(cfg, seed=75))
     for k in BF16_TABLES:
-        p[k] = _bf16_round(p[k]).astype(np.float64)
+        p[k] = bf16_round(p[k]).astype(np.float64)
     acc = ref.random_accumulators(p, kind, 76)
     acc0 = {k: v.copy() for k, v in acc.items()}
     b, cat = random_batch(cfg, B=36, Sn=3, seed=751)
     loss, q, info, used = ref.restricted_adagrad_step(dict(p), acc, cat, b, cfg, LR, kind, 0.05)
     outs = []
     for rep in range(2):
-        m = _model(cfg, cat, p, [acc0], table_dtype="bf16")
-        l = m.train(None, _tuple(b), LR)
+        m = model(cfg, cat, p, [acc0], table_dtype="bf16")
+        l = m.train(None, batch_tuple(b), LR)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss))
         outs.append((m.get_params(), m.get_slots()[0]))
     got, s1 = outs[0]
@@ -314,19 +314,19 @@ def test_adagrad_with_bf16_tables(kind):
         if k.endswith("_b2"):
             continue
         full = np.asarray(got[k], np.float64).reshape(q[k].shape)
-        a, r = _cmp(k, full, used), _cmp(k, q[k], used)
+        a, r = compared(k, full, used), compared(k, q[k], used)
         if k in BF16_TABLES:
             ulp = 2.0 ** (np.floor(np.log2(np.maximum(np.abs(r), 1e-30))) - 7)
             assert (np.abs(a - r) <= ulp * 1.001 + 2e-3 * np.abs(r - p[k]).max()).all(), k
-            assert np.array_equal(a.astype(np.float32), _bf16_round(a)), k
+            assert np.array_equal(a.astype(np.float32), bf16_round(a)), k
         else:
-            step = np.abs(r - _cmp(k, p[k], used)).max()
+            step = np.abs(r - compared(k, p[k], used)).max()
             assert np.abs(a - r).max() < 2e-3 * step + 1e-7, k
         if k in used:
             keep = ~used[k]
             assert np.array_equal(full[keep], np.asarray(p[k])[keep]), k
             assert np.array_equal(np.asarray(s1[k], np.float32)[keep], np.asarray(acc0[k], np.float32)[keep]), k
-        gs, rs = _cmp(k, s1[k], used), _cmp(k, acc[k], used)
+        gs, rs = compared(k, s1[k], used), compared(k, acc[k], used)
         assert np.abs(gs - rs).max() < 2e-3 * np.abs(rs).max() + 1e-9, k
 
 
@@ -336,18 +336,18 @@ def test_adagrad_sum_of_squares_and_scale(kind, table_dtype):
     and two runs agree bit for bit in losses, parameters and accumulators."""
     import torch
     cfg = make_config(U=3000, I=4000, C=40, d=64, regulation_rate=0.05, max_gradient_norm=13.5, optimizer=kind)
-    p = _p32(random_params(cfg, seed=1401))
+    p = p32(random_params(cfg, seed=1401))
     if table_dtype == "bf16":
         for k in BF16_TABLES:
-            p[k] = _bf16_round(p[k]).astype(np.float64)
+            p[k] = bf16_round(p[k]).astype(np.float64)
     acc = ref.random_accumulators(p, kind, 1402)
     _, cat = random_batch(cfg, B=8, Sn=2, seed=1400)
     shapes = [(64, 1), (5, 3), (40, 5), (1, 2), (64, 4), (17, 1)]
-    batches = [_tuple(random_batch(cfg, B=B, Sn=Sn, seed=1410 + k)[0]) for k, (B, Sn) in enumerate(shapes)]
-    probe = _tuple(random_batch(cfg, B=9, Sn=2, seed=1420)[0])
+    batches = [batch_tuple(random_batch(cfg, B=B, Sn=Sn, seed=1410 + k)[0]) for k, (B, Sn) in enumerate(shapes)]
+    probe = batch_tuple(random_batch(cfg, B=9, Sn=2, seed=1420)[0])
     runs = []
     for rep in range(2):
-        m = _model(cfg, cat, p, [acc], table_dtype=table_dtype)
+        m = model(cfg, cat, p, [acc], table_dtype=table_dtype)
         losses = [m.train(None, b, LR) for b in batches]
         m.grads(probe)                     # (folds the last step's records)
         St = float(m.state[32:40].view(torch.float64).item())
@@ -367,28 +367,28 @@ def test_rowwise_adagrad_on_large_tables():
     the reference."""
     kind = ROWWISE
     cfg = make_config(U=300_000, I=150_000, C=40, d=64, regulation_rate=1e-3, max_gradient_norm=0.05, optimizer=kind)
-    p = _p32(random_params(cfg, seed=85))
+    p = p32(random_params(cfg, seed=85))
     acc = ref.initial_accumulators(p, kind)
     _, cat = random_batch(cfg, B=4, Sn=2, seed=0)
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     q = dict(p)
     amb = np.zeros(cfg["item_count"], bool)
     for s in range(2):
         b = random_batch(cfg, B=48, Sn=2 + s, seed=850 + s)[0]
         loss, q, info, used = ref.restricted_adagrad_step(q, acc, cat, b, cfg, LR, kind, 0.05)
         amb |= used["item_b_amb"]
-        l = m.train(None, _tuple(b), LR)
+        l = m.train(None, batch_tuple(b), LR)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss))
-        _sync_amb(m, q, acc, used)
+        sync_amb(m, q, acc, used)
     got = m.get_params()
     s1 = m.get_slots()[0]
     used = {"item_b_amb": amb}
     for k in q:
         if k.endswith("_b2"):
             continue
-        a, r = _cmp(k, np.asarray(got[k]).reshape(q[k].shape), used), _cmp(k, q[k], used)
-        assert np.abs(a - r).max() < 2e-3 * 2 * np.abs(r - _cmp(k, p[k], used)).max() + 1e-7, k
-        gs, rs = _cmp(k, s1[k], used), _cmp(k, acc[k], used)
+        a, r = compared(k, np.asarray(got[k]).reshape(q[k].shape), used), compared(k, q[k], used)
+        assert np.abs(a - r).max() < 2e-3 * 2 * np.abs(r - compared(k, p[k], used)).max() + 1e-7, k
+        gs, rs = compared(k, s1[k], used), compared(k, acc[k], used)
         assert np.abs(gs - rs).max() < 2e-3 * np.abs(rs).max() + 1e-9, k
 
 

@@ -16,7 +16,6 @@
 Plus the driver's resume flow (train.py:71-76,124-127) and the captured-graph workspace.
 """
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -24,18 +23,11 @@ import torch
 
 from oracle import tlsan_oracle as orc
 from tests.helpers import fixture_batch, make_config
+from tests.ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 LOGIT_TOL = 1e-4
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 # ------------------------------------------------------------------------------------------- C3
@@ -270,216 +262,178 @@ def _c4_cfg():
     return synth.make_config("movies_tv", Ls=90)
 
 
-def _c4_worker(rank, world, port, ret):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from tlsan_amd import synth
-        from tlsan_amd.dist import ShardedModel
-        from tlsan_amd.model import Model
-        cfg = _c4_cfg()
-        icl = synth.item_cate_list(cfg)
-        B = 1024
-        per_step = [[synth.make_batches(cfg, 1, B, seed=300 + 10 * s + r)[0] for r in range(world)] for s in range(2)]
+def _c4_worker(rank, world):
+    from tlsan_amd import synth
+    from tlsan_amd.dist import ShardedModel
+    from tlsan_amd.model import Model
+    cfg = _c4_cfg()
+    icl = synth.item_cate_list(cfg)
+    B = 1024
+    per_step = [[synth.make_batches(cfg, 1, B, seed=300 + 10 * s + r)[0] for r in range(world)] for s in range(2)]
 
-        def run():
-            m = ShardedModel(cfg, icl, device="cuda:0", l2_mode="lazy")
-            losses = []
-            for per in per_step:
-                m.train_async(per[rank], 1.0)
-                losses.append(float(m.last_loss.item()))
-            return m, losses, m.gather_params()
-        m1, l1, p1 = run()
-        m2, l2, p2 = run()
-        assert l1 == l2
-        for k in p1:
-            assert np.array_equal(p1[k], p2[k]), k                  # bitwise reproducible across runs
+    def run():
+        m = ShardedModel(cfg, icl, device="cuda:0", l2_mode="lazy")
+        losses = []
+        for per in per_step:
+            m.train_async(per[rank], 1.0)
+            losses.append(float(m.last_loss.item()))
+        return m, losses, m.gather_params()
+    m1, l1, p1 = run()
+    m2, l2, p2 = run()
+    assert l1 == l2
+    for k in p1:
+        assert np.array_equal(p1[k], p2[k]), k                  # bitwise reproducible across runs
 
-        # the configuration as BASELINE.json names it: static-shape exchanges with bf16 rows on the wire (fp32 weights at
-        # the owners) -- reproducible bit for bit, and close to the fp32 exchange (the forward sees bf16-rounded tables)
-        def run_wire():
-            m = ShardedModel(cfg, icl, device="cuda:0", l2_mode="lazy", static_rows=True, wire_dtype="bf16")
-            dbs = [m.device_batch(per[rank]) for per in per_step]
-            losses = []
-            for s, db in enumerate(dbs):
-                m.train_async(db, 1.0, next_batch=dbs[s + 1] if s + 1 < len(dbs) else None)
-                losses.append(float(m.last_loss.item()))
-            m.check_static_overflow()
-            return losses, m.gather_params()
-        lw1, pw1 = run_wire()
-        lw2, pw2 = run_wire()
-        assert lw1 == lw2
-        for k in pw1:
-            assert np.array_equal(pw1[k], pw2[k]), k
-        assert np.allclose(lw1, l1, rtol=2e-3), (lw1, l1)
-        p00 = Model.init_params(cfg, 1234)
-        for k in pw1:
-            du = np.asarray(pw1[k], np.float64) - np.asarray(p00[k], np.float64).reshape(np.shape(pw1[k]))
-            dr = np.asarray(p1[k], np.float64) - np.asarray(p00[k], np.float64).reshape(np.shape(p1[k]))
-            assert np.abs(du - dr).max() < 0.15 * (np.abs(dr).max() + 1e-12) + 1e-6, (k, float(np.abs(du - dr).max()), float(np.abs(dr).max()))   # (sanity; the semantics are pinned by test_bf16_rows_on_the_wire)
-        if rank == 0:
-            # the same two global batches (2048 sequences) through the single-GPU model
-            def cat2(per):
-                Sn = max(np.asarray(b[4]).shape[1] for b in per)
-                cols = []
-                for c in range(9):
-                    parts = [np.asarray(b[c]) for b in per]
-                    if c == 4:
-                        parts = [np.pad(x, ((0, 0), (0, Sn - x.shape[1]))) for x in parts]
-                    cols.append(np.concatenate(parts, 0))
-                return tuple(cols)
-            ms = Model(cfg, icl, l2_mode="lazy")
-            ls = [ms.train(None, cat2(per), 1.0) for per in per_step]
-            ps = ms.get_params()
-            assert np.allclose(l1, ls, rtol=3e-6, atol=0), (l1, ls)
-            p0 = Model.init_params(cfg, 1234)
-            # ... and directly against the fp64 oracle on the concatenated batches (round 6: the oracle holds Movies-TV's tables)
-            q = {k: np.asarray(v, np.float64) for k, v in p0.items()}
-            lo = []
-            for per in per_step:
-                l, q, _ = orc.train_step(q, icl, orc.as_batch(cat2(per)), 8, cfg["regulation_rate"], lr=1.0)
-                lo.append(l)
-            assert np.allclose(l1, lo, rtol=2e-5, atol=0), (l1, lo)
-            for k in q:
-                du = np.asarray(p1[k], np.float64).reshape(q[k].shape) - np.asarray(p0[k], np.float64)
-                dr = q[k] - np.asarray(p0[k], np.float64)
-                assert np.abs(du - dr).max() < 5e-4 * (np.abs(dr).max() + 1e-12) + 5e-7, ("oracle", k, float(np.abs(du - dr).max()), float(np.abs(dr).max()))
-            for k in ps:
-                du = np.asarray(p1[k], np.float64).reshape(np.shape(ps[k])) - np.asarray(p0[k], np.float64)
-                dr = np.asarray(ps[k], np.float64) - np.asarray(p0[k], np.float64)
-                assert np.abs(du - dr).max() < 5e-4 * (np.abs(dr).max() + 1e-12) + 5e-7, (k, float(np.abs(du - dr).max()), float(np.abs(dr).max()))
-        ret[rank] = "ok"
-    except Exception:
-        import traceback
-        ret[rank] = "FAIL: " + traceback.format_exc()
-    finally:
-        dist.destroy_process_group()
+    # the configuration as BASELINE.json names it: static-shape exchanges with bf16 rows on the wire (fp32 weights at
+    # the owners) -- reproducible bit for bit, and close to the fp32 exchange (the forward sees bf16-rounded tables)
+    def run_wire():
+        m = ShardedModel(cfg, icl, device="cuda:0", l2_mode="lazy", static_rows=True, wire_dtype="bf16")
+        dbs = [m.device_batch(per[rank]) for per in per_step]
+        losses = []
+        for s, db in enumerate(dbs):
+            m.train_async(db, 1.0, next_batch=dbs[s + 1] if s + 1 < len(dbs) else None)
+            losses.append(float(m.last_loss.item()))
+        m.check_static_overflow()
+        return losses, m.gather_params()
+    lw1, pw1 = run_wire()
+    lw2, pw2 = run_wire()
+    assert lw1 == lw2
+    for k in pw1:
+        assert np.array_equal(pw1[k], pw2[k]), k
+    assert np.allclose(lw1, l1, rtol=2e-3), (lw1, l1)
+    p00 = Model.init_params(cfg, 1234)
+    for k in pw1:
+        du = np.asarray(pw1[k], np.float64) - np.asarray(p00[k], np.float64).reshape(np.shape(pw1[k]))
+        dr = np.asarray(p1[k], np.float64) - np.asarray(p00[k], np.float64).reshape(np.shape(p1[k]))
+        assert np.abs(du - dr).max() < 0.15 * (np.abs(dr).max() + 1e-12) + 1e-6, (k, float(np.abs(du - dr).max()), float(np.abs(dr).max()))   # (sanity; the semantics are pinned by test_bf16_rows_on_the_wire)
+    if rank == 0:
+        # the same two global batches (2048 sequences) through the single-GPU model
+        def cat2(per):
+            Sn = max(np.asarray(b[4]).shape[1] for b in per)
+            cols = []
+            for c in range(9):
+                parts = [np.asarray(b[c]) for b in per]
+                if c == 4:
+                    parts = [np.pad(x, ((0, 0), (0, Sn - x.shape[1]))) for x in parts]
+                cols.append(np.concatenate(parts, 0))
+            return tuple(cols)
+        ms = Model(cfg, icl, l2_mode="lazy")
+        ls = [ms.train(None, cat2(per), 1.0) for per in per_step]
+        ps = ms.get_params()
+        assert np.allclose(l1, ls, rtol=3e-6, atol=0), (l1, ls)
+        p0 = Model.init_params(cfg, 1234)
+        # ... and directly against the fp64 oracle on the concatenated batches (round 6: the oracle holds Movies-TV's tables)
+        q = {k: np.asarray(v, np.float64) for k, v in p0.items()}
+        lo = []
+        for per in per_step:
+            l, q, _ = orc.train_step(q, icl, orc.as_batch(cat2(per)), 8, cfg["regulation_rate"], lr=1.0)
+            lo.append(l)
+        assert np.allclose(l1, lo, rtol=2e-5, atol=0), (l1, lo)
+        for k in q:
+            du = np.asarray(p1[k], np.float64).reshape(q[k].shape) - np.asarray(p0[k], np.float64)
+            dr = q[k] - np.asarray(p0[k], np.float64)
+            assert np.abs(du - dr).max() < 5e-4 * (np.abs(dr).max() + 1e-12) + 5e-7, ("oracle", k, float(np.abs(du - dr).max()), float(np.abs(dr).max()))
+        for k in ps:
+            du = np.asarray(p1[k], np.float64).reshape(np.shape(ps[k])) - np.asarray(p0[k], np.float64)
+            dr = np.asarray(ps[k], np.float64) - np.asarray(p0[k], np.float64)
+            assert np.abs(du - dr).max() < 5e-4 * (np.abs(dr).max() + 1e-12) + 5e-7, (k, float(np.abs(du - dr).max()), float(np.abs(dr).max()))
 
 
 def test_c4_movies_tv_window_90_sharded_over_two_ranks():
-    import torch.multiprocessing as mp
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    ret = ctx.Manager().dict()
-    procs = [ctx.Process(target=_c4_worker, args=(r, world, port, ret)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(600)
-    assert all(ret.get(r) == "ok" for r in range(world)), dict(ret)
+    run_ranks(_c4_worker, 2, timeout=600)
 
 
 # ------------------------------------------------------------------------------------------- C5, sharded
-def _c5_sharded_worker(rank, world, port, ret):
+def _c5_sharded_worker(rank, world):
     import gc
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from tlsan_amd import synth
-        from tlsan_amd.dist import ShardedModel
-        cfg = synth.make_config("electronics", Ls=90, hidden_units=256, itemid_embedding_size=128, userid_embedding_size=128,
-                                cateid_embedding_size=128, user_count=10_000_000, item_count=5_000_000, cate_count=10_000)
-        icl = synth.item_cate_list(cfg)
-        B = 1024
-        per_step = [[synth.make_batches(cfg, 1, B, seed=500 + 10 * s + r)[0] for r in range(world)] for s in range(3)]
+    from tlsan_amd import synth
+    from tlsan_amd.dist import ShardedModel
+    cfg = synth.make_config("electronics", Ls=90, hidden_units=256, itemid_embedding_size=128, userid_embedding_size=128,
+                            cateid_embedding_size=128, user_count=10_000_000, item_count=5_000_000, cate_count=10_000)
+    icl = synth.item_cate_list(cfg)
+    B = 1024
+    per_step = [[synth.make_batches(cfg, 1, B, seed=500 + 10 * s + r)[0] for r in range(world)] for s in range(3)]
 
-        def run(static):
-            m = ShardedModel(cfg, icl, device="cuda:0", l2_mode="lazy", static_rows=static, init="device", seed=11)
-            dbs = [m.device_batch(per[rank]) for per in per_step]
-            rows0 = m.shard[:4096].clone()
-            losses = []
-            for s, db in enumerate(dbs):
-                kw = dict(after_next=dbs[s + 2] if s + 2 < len(dbs) else None) if static else {}
-                m.train_async(db, 1.0, next_batch=dbs[s + 1] if s + 1 < len(dbs) else None, **kw)
-                losses.append(float(m.last_loss.item()))
-            if static:
-                m.check_static_overflow()
-            changed = int((m.shard[:4096] != rows0).any(dim=1).sum().item())   # (before the fold, which rescales every row)
-            m.fold_scale()
-            torch.cuda.synchronize()
-            # (the shard stays on the device: 7.5 M rows of 220 floats per rank -- compare digests, keep a slice)
-            digest = [float(m.shard.double().sum().item()), float(m.shard.double().pow(2).sum().item()),
-                      float(m.cate_emb.double().sum().item()), float(m.dense.double().sum().item())]
-            head = m.shard[:4096].cpu().numpy().copy()
-            del m, dbs
-            gc.collect()
-            torch.cuda.empty_cache()
-            return losses, digest, head, changed
-        l1, d1, h1, c1 = run(False)
-        l2, d2, h2, c2 = run(False)
-        assert l1 == l2 and d1 == d2 and np.array_equal(h1, h2)          # bitwise reproducible
-        l3, d3, h3, c3 = run(True)
-        assert l3 == l1 and d3 == d1 and np.array_equal(h3, h1)          # static-shape exchanges: the same step, bit for bit
-        assert np.isfinite(l1).all() and l1[0] > 100.0                   # the L2 term of 10^7 usert rows at -1
-        assert 0 < c1 < 4096                                             # lazy L2: only rows that received a gradient moved
-        ret[rank] = "ok"
-    except Exception:
-        import traceback
-        ret[rank] = "FAIL: " + traceback.format_exc()
-    finally:
-        dist.destroy_process_group()
-
-
-def _c5_sharded_oracle_worker(rank, world, port, ret):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from tests.helpers import compact_problem
-        from tlsan_amd import synth
-        from tlsan_amd.dist import ShardedModel
-        cfg = synth.make_config("electronics", Ls=90, hidden_units=256, itemid_embedding_size=128, userid_embedding_size=128,
-                                cateid_embedding_size=128, user_count=10_000_000, item_count=5_000_000, cate_count=10_000)
-        icl = synth.item_cate_list(cfg)
-        B, di, Ls, G = 1024, 128, 90, world
-        per = [synth.make_batches(cfg, 1, B, seed=700 + r)[0] for r in range(world)]      # (every rank can build every part)
-        Sn = max(np.asarray(b[4]).shape[1] for b in per)
-        gb = tuple(np.concatenate([np.pad(np.asarray(b[c]), ((0, 0), (0, Sn - np.asarray(b[c]).shape[1]))) if c == 4 else np.asarray(b[c])
-                                   for b in per], 0) for c in range(9))
-        cp = compact_problem(gb, icl)
-        m = ShardedModel(cfg, icl, device="cuda:0", l2_mode="lazy", init="device", seed=13)
-        dev = m.device
-
-        def mine(ids, base):      # the touched rows this rank owns (ModPartition: id % G, local row id // G), as fused shard rows
-            own = ids[ids % G == rank]
-            return own, m.shard[torch.as_tensor(base + own // G, device=dev)].double().cpu().numpy()
-
-        def collect():
-            parts = [None] * world
-            dist.all_gather_object(parts, (mine(cp["items"], 0), mine(cp["users"], m.cI)))
-            it = np.zeros((len(cp["items"]), m.W)); us = np.zeros((len(cp["users"]), m.W))
-            for (ii, ir), (ui, ur) in parts:
-                it[np.searchsorted(cp["items"], ii)] = ir
-                us[np.searchsorted(cp["users"], ui)] = ur
-            q = dict(item_emb=it[:, :di].copy(), item_b=it[:, di].copy(), user_emb=us[:, :di].copy(), usert_emb=us[:, di:di + Ls].copy(),
-                     cate_emb=m.cate_emb[torch.as_tensor(cp["cates"], device=dev)].double().cpu().numpy())
-            q.update({k: np.asarray(v, np.float64) for k, v in m.unpack_dense(m.dense.cpu().numpy()).items()})
-            return q
-
-        q0 = collect()
-        # sum of squares of the regularised tables over ALL ranks (chunked fp64 on the device), minus the compact part
-        ssq = torch.tensor([_sumsq64(m.shard[:m.cI, :di]) + _sumsq64(m.shard[m.cI:, :di + Ls])], dtype=torch.float64)
-        dist.all_reduce(ssq)
-        extra = float(ssq.item()) + _sumsq64(m.cate_emb) - sum(float((q0[k] ** 2).sum()) for k in orc.REG_TABLES)
-        m.train_async(per[rank], 1.0)
-        loss, norm = float(m.last_loss.item()), float(m.last_gnorm.item())
+    def run(static):
+        m = ShardedModel(cfg, icl, device="cuda:0", l2_mode="lazy", static_rows=static, init="device", seed=11)
+        dbs = [m.device_batch(per[rank]) for per in per_step]
+        rows0 = m.shard[:4096].clone()
+        losses = []
+        for s, db in enumerate(dbs):
+            kw = dict(after_next=dbs[s + 2] if s + 2 < len(dbs) else None) if static else {}
+            m.train_async(db, 1.0, next_batch=dbs[s + 1] if s + 1 < len(dbs) else None, **kw)
+            losses.append(float(m.last_loss.item()))
+        if static:
+            m.check_static_overflow()
+        changed = int((m.shard[:4096] != rows0).any(dim=1).sum().item())   # (before the fold, which rescales every row)
         m.fold_scale()
-        q1 = collect()
-        if rank == 0:
-            lo, newp, info = orc.train_step(q0, cp["item_cate"], orc.as_batch(cp["batch"]), 8, cfg["regulation_rate"], lr=1.0, l2_extra=extra)
-            assert abs(loss - lo) < 3e-6 * abs(lo) + 1e-4, (loss, lo)
-            assert abs(norm - info["norm"]) < 3e-4 * info["norm"], (norm, info["norm"])
-            for k in newp:
-                du, dr = q1[k].reshape(q0[k].shape) - q0[k], newp[k] - q0[k]
-                assert np.abs(du - dr).max() < 5e-4 * (np.abs(dr).max() + 1e-9) + 5e-7, (k, float(np.abs(du - dr).max()), float(np.abs(dr).max()))
-        ret[rank] = "ok"
-    except Exception:
-        import traceback
-        ret[rank] = "FAIL: " + traceback.format_exc()
-    finally:
-        dist.destroy_process_group()
+        torch.cuda.synchronize()
+        # (the shard stays on the device: 7.5 M rows of 220 floats per rank -- compare digests, keep a slice)
+        digest = [float(m.shard.double().sum().item()), float(m.shard.double().pow(2).sum().item()),
+                  float(m.cate_emb.double().sum().item()), float(m.dense.double().sum().item())]
+        head = m.shard[:4096].cpu().numpy().copy()
+        del m, dbs
+        gc.collect()
+        torch.cuda.empty_cache()
+        return losses, digest, head, changed
+    l1, d1, h1, c1 = run(False)
+    l2, d2, h2, c2 = run(False)
+    assert l1 == l2 and d1 == d2 and np.array_equal(h1, h2)          # bitwise reproducible
+    l3, d3, h3, c3 = run(True)
+    assert l3 == l1 and d3 == d1 and np.array_equal(h3, h1)          # static-shape exchanges: the same step, bit for bit
+    assert np.isfinite(l1).all() and l1[0] > 100.0                   # the L2 term of 10^7 usert rows at -1
+    assert 0 < c1 < 4096                                             # lazy L2: only rows that received a gradient moved
+
+
+def _c5_sharded_oracle_worker(rank, world):
+    import torch.distributed as dist
+    from tests.helpers import compact_problem
+    from tlsan_amd import synth
+    from tlsan_amd.dist import ShardedModel
+    cfg = synth.make_config("electronics", Ls=90, hidden_units=256, itemid_embedding_size=128, userid_embedding_size=128,
+                            cateid_embedding_size=128, user_count=10_000_000, item_count=5_000_000, cate_count=10_000)
+    icl = synth.item_cate_list(cfg)
+    B, di, Ls, G = 1024, 128, 90, world
+    per = [synth.make_batches(cfg, 1, B, seed=700 + r)[0] for r in range(world)]      # (every rank can build every part)
+    Sn = max(np.asarray(b[4]).shape[1] for b in per)
+    gb = tuple(np.concatenate([np.pad(np.asarray(b[c]), ((0, 0), (0, Sn - np.asarray(b[c]).shape[1]))) if c == 4 else np.asarray(b[c])
+                               for b in per], 0) for c in range(9))
+    cp = compact_problem(gb, icl)
+    m = ShardedModel(cfg, icl, device="cuda:0", l2_mode="lazy", init="device", seed=13)
+    dev = m.device
+
+    def mine(ids, base):      # the touched rows this rank owns (ModPartition: id % G, local row id // G), as fused shard rows
+        own = ids[ids % G == rank]
+        return own, m.shard[torch.as_tensor(base + own // G, device=dev)].double().cpu().numpy()
+
+    def collect():
+        parts = [None] * world
+        dist.all_gather_object(parts, (mine(cp["items"], 0), mine(cp["users"], m.cI)))
+        it = np.zeros((len(cp["items"]), m.W)); us = np.zeros((len(cp["users"]), m.W))
+        for (ii, ir), (ui, ur) in parts:
+            it[np.searchsorted(cp["items"], ii)] = ir
+            us[np.searchsorted(cp["users"], ui)] = ur
+        q = dict(item_emb=it[:, :di].copy(), item_b=it[:, di].copy(), user_emb=us[:, :di].copy(), usert_emb=us[:, di:di + Ls].copy(),
+                 cate_emb=m.cate_emb[torch.as_tensor(cp["cates"], device=dev)].double().cpu().numpy())
+        q.update({k: np.asarray(v, np.float64) for k, v in m.unpack_dense(m.dense.cpu().numpy()).items()})
+        return q
+
+    q0 = collect()
+    # sum of squares of the regularised tables over ALL ranks (chunked fp64 on the device), minus the compact part
+    ssq = torch.tensor([_sumsq64(m.shard[:m.cI, :di]) + _sumsq64(m.shard[m.cI:, :di + Ls])], dtype=torch.float64)
+    dist.all_reduce(ssq)
+    extra = float(ssq.item()) + _sumsq64(m.cate_emb) - sum(float((q0[k] ** 2).sum()) for k in orc.REG_TABLES)
+    m.train_async(per[rank], 1.0)
+    loss, norm = float(m.last_loss.item()), float(m.last_gnorm.item())
+    m.fold_scale()
+    q1 = collect()
+    if rank == 0:
+        lo, newp, info = orc.train_step(q0, cp["item_cate"], orc.as_batch(cp["batch"]), 8, cfg["regulation_rate"], lr=1.0, l2_extra=extra)
+        assert abs(loss - lo) < 3e-6 * abs(lo) + 1e-4, (loss, lo)
+        assert abs(norm - info["norm"]) < 3e-4 * info["norm"], (norm, info["norm"])
+        for k in newp:
+            du, dr = q1[k].reshape(q0[k].shape) - q0[k], newp[k] - q0[k]
+            assert np.abs(du - dr).max() < 5e-4 * (np.abs(dr).max() + 1e-9) + 5e-7, (k, float(np.abs(du - dr).max()), float(np.abs(dr).max()))
 
 
 def test_c5_sharded_step_matches_oracle_at_size():
@@ -487,16 +441,7 @@ def test_c5_sharded_step_matches_oracle_at_size():
     cuda:0, gloo), tables of 10 M users / 5 M items row-sharded by id % 2, one lazy step of 2 x 1024 sequences.  The rows
     the global batch touches are collected from their owners' shards (before and after the step), the other rows enter the
     oracle through their sum of squares -- the id compaction of `_one_step_against_oracle_at_size`."""
-    import torch.multiprocessing as mp
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    ret = ctx.Manager().dict()
-    procs = [ctx.Process(target=_c5_sharded_oracle_worker, args=(r, world, port, ret)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(1500)
-    assert all(ret.get(r) == "ok" for r in range(world)), dict(ret)
+    run_ranks(_c5_sharded_oracle_worker, 2, timeout=1500)
 
 
 def test_c5_tables_sharded_over_two_ranks():
@@ -505,62 +450,42 @@ def test_c5_tables_sharded_over_two_ranks():
     sequences per rank and step.  Properties (the oracle cannot run this size): bitwise reproducible; the static-shape
     step (fixed-size exchanges, plans two batches ahead) equals the sized one bit for bit; lazy L2 leaves rows without
     a gradient alone."""
-    import torch.multiprocessing as mp
-    world, port = 2, _free_port()
-    ctx = mp.get_context("spawn")
-    ret = ctx.Manager().dict()
-    procs = [ctx.Process(target=_c5_sharded_worker, args=(r, world, port, ret)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(1500)
-    assert all(ret.get(r) == "ok" for r in range(world)), dict(ret)
+    run_ranks(_c5_sharded_worker, 2, timeout=1500)
 
 
 # ------------------------------------------------------------------------------------------- multi-GPU over RCCL
-def _nccl_worker(rank, world, port, ret):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    torch.cuda.set_device(rank)
-    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda:%d" % rank))
-    try:
-        from tests.helpers import random_batch, random_params
-        from tlsan_amd.dist import ShardedModel
-        cfg = make_config(U=61, I=83, C=9, d=128, regulation_rate=1e-3)
-        p = {k: np.asarray(v, np.float32).astype(np.float64) for k, v in random_params(cfg, seed=17).items()}
-        _, cat = random_batch(cfg, B=4, Sn=2, seed=0)
-        tup = lambda b: (b["u"], b["i"], b["y"], b["hist_i"], b["hist_i_new"], b["hist_t"], b["sl"], b["sl_new"], b["u_cate"])
-        steps = [[random_batch(cfg, B=24, Sn=3, seed=1000 + 10 * s + r)[0] for r in range(world)] for s in range(3)]
-        # static: fixed-size exchanges, nothing through the host; coalesce: its two exchanges behind the kernels as one RCCL group
-        for lazy, static, coalesce in ((False, False, False), (True, False, False), (True, True, False), (True, True, True)):
-            m = ShardedModel(cfg, cat, device="cuda:%d" % rank, l2_mode="lazy" if lazy else "dense", static_rows=static,
-                             coalesce=coalesce)
-            m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-            dbs = [m.device_batch(tup(per[rank])) for per in steps]
-            losses = []
-            for k, db in enumerate(dbs):
-                m.train_async(db, 0.8, next_batch=dbs[k + 1] if k + 1 < len(dbs) else None)
-                losses.append(float(m.last_loss.item()))
-            got = m.gather_params()
-            if rank == 0:
-                q, ref = dict(p), []
-                for per in steps:
-                    Sn = max(b["hist_i_new"].shape[1] for b in per)
-                    g = {k: np.concatenate([np.pad(b[k], ((0, 0), (0, Sn - b[k].shape[1]))) if k == "hist_i_new" else b[k]
-                                            for b in per], 0) for k in per[0]}
-                    l, q, _ = orc.train_step(q, cat, g, 8, cfg["regulation_rate"], lr=0.8)
-                    ref.append(l)
-                assert np.allclose(losses, ref, rtol=2e-4, atol=1e-5), (losses, ref)
-                for k in q:
-                    du = np.asarray(got[k], np.float64).reshape(q[k].shape) - p[k]
-                    dr = q[k] - p[k]
-                    assert np.abs(du - dr).max() < 5e-4 * (np.abs(dr).max() + 1e-9) + 5e-7, (lazy, static, coalesce, k)
-        ret[rank] = "ok"
-    except Exception:
-        import traceback
-        ret[rank] = "FAIL: " + traceback.format_exc()
-    finally:
-        dist.destroy_process_group()
+def _nccl_worker(rank, world):
+    from tests.helpers import random_batch, random_params
+    from tlsan_amd.dist import ShardedModel
+    cfg = make_config(U=61, I=83, C=9, d=128, regulation_rate=1e-3)
+    p = {k: np.asarray(v, np.float32).astype(np.float64) for k, v in random_params(cfg, seed=17).items()}
+    _, cat = random_batch(cfg, B=4, Sn=2, seed=0)
+    tup = lambda b: (b["u"], b["i"], b["y"], b["hist_i"], b["hist_i_new"], b["hist_t"], b["sl"], b["sl_new"], b["u_cate"])
+    steps = [[random_batch(cfg, B=24, Sn=3, seed=1000 + 10 * s + r)[0] for r in range(world)] for s in range(3)]
+    # static: fixed-size exchanges, nothing through the host; coalesce: its two exchanges behind the kernels as one RCCL group
+    for lazy, static, coalesce in ((False, False, False), (True, False, False), (True, True, False), (True, True, True)):
+        m = ShardedModel(cfg, cat, device="cuda:%d" % rank, l2_mode="lazy" if lazy else "dense", static_rows=static,
+                         coalesce=coalesce)
+        m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
+        dbs = [m.device_batch(tup(per[rank])) for per in steps]
+        losses = []
+        for k, db in enumerate(dbs):
+            m.train_async(db, 0.8, next_batch=dbs[k + 1] if k + 1 < len(dbs) else None)
+            losses.append(float(m.last_loss.item()))
+        got = m.gather_params()
+        if rank == 0:
+            q, ref = dict(p), []
+            for per in steps:
+                Sn = max(b["hist_i_new"].shape[1] for b in per)
+                g = {k: np.concatenate([np.pad(b[k], ((0, 0), (0, Sn - b[k].shape[1]))) if k == "hist_i_new" else b[k]
+                                        for b in per], 0) for k in per[0]}
+                l, q, _ = orc.train_step(q, cat, g, 8, cfg["regulation_rate"], lr=0.8)
+                ref.append(l)
+            assert np.allclose(losses, ref, rtol=2e-4, atol=1e-5), (losses, ref)
+            for k in q:
+                du = np.asarray(got[k], np.float64).reshape(q[k].shape) - p[k]
+                dr = q[k] - p[k]
+                assert np.abs(du - dr).max() < 5e-4 * (np.abs(dr).max() + 1e-9) + 5e-7, (lazy, static, coalesce, k)
 
 
 @pytest.mark.parametrize("world", [2, 8])
@@ -569,16 +494,7 @@ def test_sharded_step_over_rccl(world):
     Needs `world` GPUs in the box (the 1-GPU boxes of the test pool skip it; the 8-GPU node runs it)."""
     if torch.cuda.device_count() < world:
         pytest.skip("needs %d GPUs, found %d" % (world, torch.cuda.device_count()))
-    import torch.multiprocessing as mp
-    port = _free_port()
-    ctx = mp.get_context("spawn")
-    ret = ctx.Manager().dict()
-    procs = [ctx.Process(target=_nccl_worker, args=(r, world, port, ret)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(900)
-    assert all(ret.get(r) == "ok" for r in range(world)), dict(ret)
+    run_ranks(_nccl_worker, world, backend="nccl", timeout=900, env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"})
 
 
 # ------------------------------------------------------------------------------------------- driver + graph

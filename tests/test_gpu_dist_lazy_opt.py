@@ -1,5 +1,5 @@
 """Lazy Adam / RMSProp / Adadelta on the row-sharded step (ShardedModel(l2_mode="lazy"), tlsan_shard_apply_lazy_opt)
-against the restricted oracle of tests/test_gpu_lazy_opt.py on the concatenated batch: the dense optimizer's step with
+against the restricted oracle of tests/lazy_opt_ref.py on the concatenated batch: the dense optimizer's step with
 every row the GLOBAL batch did not use put back, in W and both slots.  Two processes share cuda:0 and talk over gloo, as
 in tests/test_gpu_dist.py."""
 import os
@@ -8,19 +8,18 @@ import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
-from tests.helpers import make_config, random_batch, random_params
+from tests.helpers import batch_tuple, concat_batches, make_config, p32, random_batch, random_params, sharded
+from tests.lazy_opt_ref import (LR, ROW_TABLES, check_step, cover_all_batch, driver_worker, random_slots, restricted_step,
+                                sync_amb, used_rows)
+from tests.ranks import run_ranks
 from tests.shard_ref import _np_opt_elem
-from tests.test_gpu_dist import _concat, _driver_worker, _free_port
-from tests.test_gpu_lazy_opt import (LR, ROW_TABLES, _check, _cover_all_batch, _p32, _sync_amb, _tuple, random_slots,
-                                     restricted_step, used_rows)
 
 pytestmark = pytest.mark.gpu
 
 
 class _AsModel:
-    """what _check and _sync_amb ask of a model, answered by a ShardedModel (collectives: every rank calls them)"""
+    """what check_step and sync_amb ask of a model, answered by a ShardedModel (collectives: every rank calls them)"""
 
     def __init__(self, m):
         self.m = m
@@ -34,37 +33,6 @@ class _AsModel:
     @property
     def item_b(self):
         return torch.as_tensor(self.m.gather_params()["item_b"])
-
-
-def _sharded(cfg, cat, p=None, slots=None, l2_mode="lazy", **kw):
-    from tlsan_amd.dist import ShardedModel
-    m = ShardedModel(cfg, cat, device="cuda:0", l2_mode=l2_mode, **kw)
-    if p is not None:
-        m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-    if slots is not None:
-        m._set_slots([{k: np.asarray(v, np.float32) for k, v in s.items()} for s in slots])
-    return m
-
-
-def _worker(rank, world, port, ret, name, *args):
-    """globals()[name](rank, world, *args) inside a gloo group, its outcome in ret[rank]"""
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        globals()[name](rank, world, *args)
-        ret[rank] = "ok"
-    except Exception:
-        import traceback
-        ret[rank] = "FAIL: " + traceback.format_exc()
-    finally:
-        dist.destroy_process_group()
-
-
-def _spawn(fn, world, *args):
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), ret, fn.__name__) + args, nprocs=world, join=True)
-    assert all(v == "ok" for v in dict(ret).values()) and len(ret) == world, dict(ret)
 
 
 def _oracle_batches(cfg, world):
@@ -90,10 +58,10 @@ def _oracle_run(rank, world, optimizer, reg, ckpt):
     cfg = make_config(U=300, I=450, C=20, d=64, regulation_rate=reg, max_gradient_norm=0.05,
                       optimizer="lazy_" + optimizer, model_dir=ckpt)
     lr = LR[optimizer]
-    p = _p32(random_params(cfg, seed=71))
+    p = p32(random_params(cfg, seed=71))
     st = random_slots(p, optimizer, 72)
     cat = np.random.RandomState(70).randint(0, 17, cfg["item_count"]).astype(np.int32)
-    m = _sharded(cfg, cat, p, [st["slot1"], st["slot2"]])
+    m = sharded(cfg, cat, p, [st["slot1"], st["slot2"]])
     q = dict(p)
     losses, prefix = [], None
     for n, per in enumerate(_oracle_batches(cfg, world)):
@@ -105,21 +73,21 @@ def _oracle_run(rank, world, optimizer, reg, ckpt):
                 assert (u0[k] & u1[k]).any() and (u0[k] ^ u1[k]).any(), k
         before = (m.gather_params(), m.gather_slots())
         prev = q
-        loss, q, info, used = restricted_step(q, st, cat, _concat(per), cfg, lr, optimizer, clip)
+        loss, q, info, used = restricted_step(q, st, cat, concat_batches(per), cfg, lr, optimizer, clip)
         assert (info["coef"] < 1.0) == (n < 5)
         for k in ROW_TABLES:
             assert not used[k].all(), k
-        m.train_async(_tuple(per[rank]), lr)
+        m.train_async(batch_tuple(per[rank]), lr)
         l = float(m.last_loss.item())
         losses.append(l)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss)), (n, l, loss)
-        _check(_AsModel(m), q, st, prev, used, n + 1, exact_unused=before)
-        _sync_amb(_AsModel(m), q, st, used)
+        check_step(_AsModel(m), q, st, prev, used, n + 1, exact_unused=before)
+        sync_amb(_AsModel(m), q, st, used)
         if n == 2:       # checkpoint round trips in the middle of the run: the per-rank files, and the gathered single file
             want = (m.gather_params(), m.gather_slots())
             prefix = m.save()
             for path in (prefix, m.save(sharded=False) + ".npz"):
-                m2 = _sharded(dict(cfg), cat, seed=99)
+                m2 = sharded(dict(cfg), cat, seed=99)
                 m2.restore(None, path)
                 assert m2.global_step.eval() == 3
                 back = (m2.gather_params(), m2.gather_slots())
@@ -136,7 +104,7 @@ def _oracle_run(rank, world, optimizer, reg, ckpt):
     m.restore(None, prefix)
     m.clip = 0.05
     for n, per in list(enumerate(_oracle_batches(cfg, world)))[3:5]:
-        m.train_async(_tuple(per[rank]), lr)
+        m.train_async(batch_tuple(per[rank]), lr)
         assert float(m.last_loss.item()) == losses[n], (n, float(m.last_loss.item()), losses[n])
     return out
 
@@ -177,27 +145,27 @@ def test_sharded_lazy_optimizers_track_the_restricted_oracle(world, optimizer, t
     """Tables much larger than a batch, non-zero slots everywhere: five clipped steps and one unclipped one.  Loss, used
     rows, dense weights and their slots follow the restricted oracle on the concatenated batch within the single-GPU
     test's bounds; rows no rank used keep W and both slots bit for bit; both checkpoint formats restore the state."""
-    _spawn((_oracle_case), world, optimizer, 1e-3, str(tmp_path), 1)
+    run_ranks(_oracle_case, world, optimizer, 1e-3, str(tmp_path), 1)
 
 
 def test_sharded_lazy_adam_is_bitwise_reproducible(tmp_path):
     """The two-rank Adam run done twice: identical losses, parameters and slots."""
-    _spawn((_oracle_case), 2, "adam", 1e-3, str(tmp_path), 2)
+    run_ranks(_oracle_case, 2, "adam", 1e-3, str(tmp_path), 2)
 
 
 def test_sharded_lazy_running_sums_of_squares(tmp_path):
     """regulation_rate = 0.05, where the L2 term carries the loss: the oracle parity of the six steps still holds, and
     the running sums (_sq) equal the sums of squares of the gathered tables to 1e-6 (checked in _oracle_case)."""
-    _spawn((_oracle_case), 2, "adam", 0.05, str(tmp_path), 1)
+    run_ranks(_oracle_case, 2, "adam", 0.05, str(tmp_path), 1)
 
 
 def _one_rank_categories(rank, world):
     cfg = make_config(U=300, I=450, C=64, d=64, regulation_rate=1e-3, max_gradient_norm=0.05, optimizer="lazy_adam")
     rng = np.random.RandomState(5)
     cat = rng.choice(np.arange(10), cfg["item_count"]).astype(np.int32)
-    p = _p32(random_params(cfg, seed=91))
+    p = p32(random_params(cfg, seed=91))
     st = random_slots(p, "adam", 92)
-    m = _sharded(cfg, cat, p, [st["slot1"], st["slot2"]])
+    m = sharded(cfg, cat, p, [st["slot1"], st["slot2"]])
     names = ("cate_s1", "cate_s2")
     start = [m.cate_emb.cpu().numpy()] + [m.slots[k].cpu().numpy() for k in names]
     for s in range(2):
@@ -206,7 +174,7 @@ def _one_rank_categories(rank, world):
         if s == 0:     # every category of the rank's range is named at least once
             own = np.arange(10, 15) if rank == 0 else np.arange(15, 18)
             b["u_cate"][:len(own)] = own
-        m.train_async(_tuple(b), 0.05)
+        m.train_async(batch_tuple(b), 0.05)
     end = [m.cate_emb.cpu().numpy()] + [m.slots[k].cpu().numpy() for k in names]
     for a, b0 in zip(end, start):
         assert np.array_equal(a[18:], b0[18:])                       # nobody's categories: bit for bit
@@ -222,22 +190,22 @@ def _one_rank_categories(rank, world):
 def test_sharded_lazy_categories_seen_by_one_rank_only():
     """Item categories 0..9, rank 0's u_cate 10..14, rank 1's 15..17, 64 categories: rows 18..63 of cate_emb and of both
     slots keep their bits, rows 10..17 move on BOTH ranks, and the replicated state is bitwise the same on both."""
-    _spawn((_one_rank_categories), 2)
+    run_ranks(_one_rank_categories, 2)
 
 
 def _equals_dense(rank, world):
     base = make_config(U=40, I=60, C=7, d=64, regulation_rate=1e-3, max_gradient_norm=0.05)
     _, cat = random_batch(base, B=8, Sn=3, seed=1)
-    full = _cover_all_batch(base, 740)
+    full = cover_all_batch(base, 740)
     B = len(full["u"])
     mine = {k: v[rank * B // world:(rank + 1) * B // world] for k, v in full.items()}
     for optimizer in ("adam", "rmsprop", "adadelta"):
-        p = _p32(random_params(base, seed=73))
+        p = p32(random_params(base, seed=73))
         st = random_slots(p, optimizer, 74)
         out = []
         for name, l2 in ((optimizer, "dense"), ("lazy_" + optimizer, "lazy")):
-            m = _sharded(dict(base, optimizer=name), cat, p, [st["slot1"], st["slot2"]], l2_mode=l2)
-            m.train_async(_tuple(mine), LR[optimizer])
+            m = sharded(dict(base, optimizer=name), cat, p, [st["slot1"], st["slot2"]], l2_mode=l2)
+            m.train_async(batch_tuple(mine), LR[optimizer])
             out.append((float(m.last_loss.item()), m.gather_params(), m.gather_slots()))
         (ld, pd, sd), (ll, pl, sl) = out
         assert abs(ld - ll) <= 1e-6 * max(1.0, abs(ld)), (optimizer, ld, ll)
@@ -251,17 +219,14 @@ def _equals_dense(rank, world):
 def test_sharded_lazy_equals_sharded_dense_when_every_row_is_used():
     """One global batch that uses every row of every table, split over two ranks: sharded lazy_X and sharded X from the
     same parameters and slots agree to fp32 rounding."""
-    _spawn((_equals_dense), 2)
+    run_ranks(_equals_dense, 2)
 
 
 def test_sharded_train_driver_with_lazy_adam(tmp_path):
     """python -m tlsan_amd.train --sharded 1 --optimizer lazy_adam over two ranks against the single-GPU driver with
     the same flags (40 steps, batch 33, the bounds of test_sharded_train_driver_matches_single_gpu)."""
-    mgr = mp.Manager()
-    ret = mgr.dict()
     extra = ("--optimizer", "lazy_adam", "--learning_rate", "0.01")
-    mp.spawn(_driver_worker, args=(2, _free_port(), ret, str(tmp_path), extra), nprocs=2, join=True)
-    assert all(v == "ok" for v in dict(ret).values()) and len(ret) == 2, dict(ret)
+    run_ranks(driver_worker, 2, str(tmp_path), extra)
 
 
 # (di, Ls, dc, ranks): the four row-width forms of the kernel (64 NCH floats per row, NCH = 1..4), and more ranks than it
@@ -401,4 +366,4 @@ def _refusals(rank, world):
 def test_sharded_lazy_refusals():
     """The static-shape step (and with it graph capture and bf16 rows on the wire) has no lazy optimizer, and the default
     l2_mode has none either: NotImplementedError at construction."""
-    _spawn((_refusals), 1)
+    run_ranks(_refusals, 1)

@@ -10,36 +10,14 @@ import numpy as np
 import pytest
 
 from oracle import tlsan_oracle as orc
-from tests.helpers import make_config, random_batch, random_params
+from tests.helpers import BF16_TABLES, batch_tuple, bf16_round, make_config, model, p32, random_batch, random_params
+from tests.ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 
 LOGIT_TOL = 1e-4
 PAIRS = [(64, 4), (128, 16), (128, 4)]
-BF16_TABLES = ("item_emb", "user_emb", "cate_emb")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _model(cfg, cat, p=None, **kw):
-    from tlsan_amd.model import Model
-    m = Model(cfg, cat, **kw)
-    if p is not None:
-        m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-    return m
-
-
-def _tuple(b, test=False):
-    return (b["u"], b["i"], b["j"] if test else b["y"], b["hist_i"], b["hist_i_new"], b["hist_t"],
-            b["sl"], b["sl_new"], b["u_cate"])
-
-
-def _p32(p):
-    return {k: np.asarray(v, np.float32).astype(np.float64) for k, v in p.items()}
-
-
-def _bf16_round(a):
-    import torch
-    return torch.as_tensor(np.asarray(a, np.float32)).to(torch.bfloat16).float().numpy()
 
 
 def _check_update(got, p, newp, tol, floor, what=""):
@@ -53,29 +31,29 @@ def _check_update(got, p, newp, tol, floor, what=""):
 @pytest.mark.parametrize("B,Sn", [(1, 0), (37, 3), (300, 18)])
 def test_forward_logits(d, H, B, Sn):
     cfg = make_config(U=70, I=90, C=11, d=d, H=H)
-    p = _p32(random_params(cfg, seed=d + H + B))
+    p = p32(random_params(cfg, seed=d + H + B))
     b, cat = random_batch(cfg, B=B, Sn=Sn, seed=B + Sn, test=True)
-    m = _model(cfg, cat, p)
-    li, lj, ut, _ = m.forward(_tuple(b, True), is_test=True, want_u_t=True)
+    m = model(cfg, cat, p)
+    li, lj, ut, _ = m.forward(batch_tuple(b, True), is_test=True, want_u_t=True)
     ref = orc.forward(p, cat, b, H)
     bn = dict(b); bn["i"] = b["j"]
     refj = orc.forward(p, cat, bn, H)
     assert np.abs(li.cpu().numpy() - ref["logits"]).max() < LOGIT_TOL
     assert np.abs(lj.cpu().numpy() - refj["logits"]).max() < LOGIT_TOL
     assert np.abs(ut.cpu().numpy() - ref["u_t"]).max() < LOGIT_TOL
-    auc = m.eval_auc(None, _tuple(b, True))
+    auc = m.eval_auc(None, batch_tuple(b, True))
     assert auc == pytest.approx(float(np.mean(ref["logits"] - refj["logits"] > 0)), abs=1e-6)
 
 
 @pytest.mark.parametrize("d,H", PAIRS)
 def test_gradients_both_norm_modes(d, H):
     cfg = make_config(U=30, I=50, C=7, d=d, H=H)
-    p = _p32(random_params(cfg, seed=3 * d + H))
+    p = p32(random_params(cfg, seed=3 * d + H))
     b, cat = random_batch(cfg, B=45, Sn=4, seed=d * 7 + H)
     reg = cfg["regulation_rate"]
     loss, logits, g, sparse = orc.backward(p, cat, b, H, reg)
-    m = _model(cfg, cat, p)
-    out = m.grads(_tuple(b))
+    m = model(cfg, cat, p)
+    out = m.grads(batch_tuple(b))
     assert np.abs(out["logits"] - logits).max() < LOGIT_TOL
     assert abs(out["loss"] - loss) < 1e-4 * max(1.0, abs(loss))
     for k in g:
@@ -84,7 +62,7 @@ def test_gradients_both_norm_modes(d, H):
         assert err < 2e-4 * np.abs(g[k]).max() + 1e-6, (k, err, np.abs(g[k]).max())
     n18 = orc.global_norm(p, g, sparse, reg, "tf18")
     assert abs(out["gnorm"] - n18) < 2e-4 * n18
-    out2 = _model(cfg, cat, p, norm_mode="dedup").grads(_tuple(b))
+    out2 = model(cfg, cat, p, norm_mode="dedup").grads(batch_tuple(b))
     nd = orc.global_norm(p, g, sparse, reg, "dedup")
     assert abs(out2["gnorm"] - nd) < 2e-4 * nd
 
@@ -94,12 +72,12 @@ def test_gradients_both_norm_modes(d, H):
 @pytest.mark.parametrize("clip", [5.0, 0.02])
 def test_train_step_matches_oracle(d, H, l2_mode, clip):
     cfg = make_config(U=40, I=60, C=9, d=d, H=H, max_gradient_norm=clip, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=11 + H))
+    p = p32(random_params(cfg, seed=11 + H))
     b, cat = random_batch(cfg, B=48, Sn=4, seed=12)
     loss, newp, info = orc.train_step(p, cat, b, H, cfg["regulation_rate"], lr=0.7, clip=clip)
     assert (info["coef"] < 1.0) == (clip < 1)
-    m = _model(cfg, cat, p, l2_mode=l2_mode)
-    l = m.train(None, _tuple(b), 0.7)
+    m = model(cfg, cat, p, l2_mode=l2_mode)
+    l = m.train(None, batch_tuple(b), 0.7)
     assert abs(l - loss) < 1e-4 * max(1.0, abs(loss))
     assert abs(m.last_gnorm() - info["norm"]) < 2e-4 * info["norm"]
     got = m.get_params()
@@ -111,13 +89,13 @@ def test_train_step_matches_oracle(d, H, l2_mode, clip):
 @pytest.mark.parametrize("l2_mode", ["dense", "lazy"])
 def test_three_steps_track_oracle_and_are_bitwise_reproducible(d, H, l2_mode):
     cfg = make_config(U=25, I=35, C=5, d=d, H=H, regulation_rate=5e-5)
-    p = _p32(random_params(cfg, seed=21 + H))
+    p = p32(random_params(cfg, seed=21 + H))
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=40, Sn=1 + s, seed=100 + s)[0] for s in range(3)]
     runs = []
     for rep in range(2):
-        m = _model(cfg, cat, p, l2_mode=l2_mode)
-        losses = [m.train(None, _tuple(b), 0.5) for b in batches]
+        m = model(cfg, cat, p, l2_mode=l2_mode)
+        losses = [m.train(None, batch_tuple(b), 0.5) for b in batches]
         runs.append((losses, m.get_params()))
     assert runs[0][0] == runs[1][0]
     for k in runs[0][1]:
@@ -137,7 +115,7 @@ def test_three_steps_track_oracle_and_are_bitwise_reproducible(d, H, l2_mode):
 @pytest.mark.parametrize("Ls,B,Sn", [(33, 50, 3), (90, 37, 5)])
 def test_long_windows_streamed(d, H, Ls, B, Sn):
     cfg = make_config(U=50, I=150, C=8, d=d, H=H, Ls=Ls, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=Ls + d + H))
+    p = p32(random_params(cfg, seed=Ls + d + H))
     b, cat = random_batch(cfg, B=B, Sn=Sn, seed=Ls)
     b["sl"][:4] = [Ls, 1, Ls - 1, min(Ls, 11)]
     ar = np.arange(Ls)[None, :]
@@ -145,13 +123,13 @@ def test_long_windows_streamed(d, H, Ls, B, Sn):
     b["hist_t"] = np.where(ar < b["sl"][:, None], (1.0 / np.random.RandomState(3).randint(1, 13, (B, Ls))), 0).astype(np.float32)
     ref = orc.forward(p, cat, b, H)
     tb = dict(b); tb["j"] = b["i"][::-1].copy()
-    li, lj, ut, _ = _model(cfg, cat, p).forward(_tuple(tb, True), is_test=True, want_u_t=True)
+    li, lj, ut, _ = model(cfg, cat, p).forward(batch_tuple(tb, True), is_test=True, want_u_t=True)
     assert np.abs(li.cpu().numpy() - ref["logits"]).max() < LOGIT_TOL
     assert np.abs(ut.cpu().numpy() - ref["u_t"]).max() < LOGIT_TOL
     loss, newp, info = orc.train_step(p, cat, b, H, cfg["regulation_rate"], lr=0.6)
     for l2 in ("dense", "lazy"):
-        m = _model(cfg, cat, p, l2_mode=l2)
-        l = m.train(None, _tuple(b), 0.6)
+        m = model(cfg, cat, p, l2_mode=l2)
+        l = m.train(None, batch_tuple(b), 0.6)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss)), l2
         assert abs(m.last_gnorm() - info["norm"]) < 3e-4 * info["norm"], l2
         _check_update(m.get_params(), p, newp, 3e-4, 5e-7, l2)
@@ -162,11 +140,11 @@ def test_long_windows_streamed(d, H, Ls, B, Sn):
 def test_attention_weights_match_oracle(d, H, Ls, Sn):
     B = 37
     cfg = make_config(U=50, I=80, C=8, d=d, H=H, Ls=Ls)
-    p = _p32(random_params(cfg, seed=d + Ls + H))
+    p = p32(random_params(cfg, seed=d + Ls + H))
     b, cat = random_batch(cfg, B=B, Sn=Sn, seed=Ls + B, test=True)
     b["sl"][:3] = [Ls, 1, max(1, Ls - 1)]
-    m = _model(cfg, cat, p)
-    li, _, _, _ = m.forward(_tuple(b, test=True), is_test=True, want_att=True)
+    m = model(cfg, cat, p)
+    li, _, _, _ = m.forward(batch_tuple(b, test=True), is_test=True, want_att=True)
     ref = orc.forward(p, cat, dict(b, y=np.zeros(B)), H)
     assert np.abs(li.cpu().numpy() - ref["logits"]).max() < LOGIT_TOL
     for got, want, T, length in ((m.att0, ref["att0"], Ls, b["sl"]), (m.att1, ref["att1"], Sn + 1, b["sl_new"] + 1)):
@@ -184,23 +162,23 @@ def test_attention_weights_match_oracle(d, H, Ls, Sn):
 def test_dropout_training_matches_oracle(d, H, Ls):
     rate = 0.3
     cfg = make_config(U=40, I=60, C=9, d=d, H=H, regulation_rate=1e-3, dropout=rate, Ls=Ls)
-    p = _p32(random_params(cfg, seed=91 + H))
+    p = p32(random_params(cfg, seed=91 + H))
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=37, Sn=2 + s, seed=910 + s)[0] for s in range(2)]
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     q = dict(p)
     for n, b in enumerate(batches):
         seed = m.dropout_seed()
         loss, newq, info = orc.train_step(q, cat, b, H, cfg["regulation_rate"], lr=0.6, dropout=(rate, seed))
         plain = orc.loss_fn(q, cat, b, H, cfg["regulation_rate"])
         assert abs(plain - loss) > 1e-5
-        l = m.train(None, _tuple(b), 0.6)
+        l = m.train(None, batch_tuple(b), 0.6)
         assert abs(l - loss) < 1e-4 * max(1.0, abs(loss)), (n, l, loss, plain)
         assert abs(m.last_gnorm() - info["norm"]) < 2e-4 * info["norm"]
         got = m.get_params()
         _check_update(got, q, newq, 3e-4, 3e-7, n)
         q = {k: np.asarray(got[k], np.float64).reshape(newq[k].shape) for k in newq}
-    li, _, _, _ = m.forward(_tuple(batches[0]), is_test=False)
+    li, _, _, _ = m.forward(batch_tuple(batches[0]), is_test=False)
     assert np.abs(li.cpu().numpy() - orc.forward(q, cat, batches[0], H)["logits"]).max() < LOGIT_TOL
 
 
@@ -210,14 +188,14 @@ def test_bf16_tables(d, H, l2_mode, Ls):
     """bf16 tables: forward and gradients equal the oracle on the stored parameters; a step lands every table element on
     a bf16 neighbour of the exact update, the rest follows the oracle, and a second run repeats it bitwise."""
     cfg = make_config(U=60, I=90, C=9, d=d, H=H, Ls=Ls, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=81 + H))
+    p = p32(random_params(cfg, seed=81 + H))
     for k in BF16_TABLES:
-        p[k] = _bf16_round(p[k]).astype(np.float64)
+        p[k] = bf16_round(p[k]).astype(np.float64)
     b, cat = random_batch(cfg, B=64, Sn=4, seed=82)
-    m = _model(cfg, cat, p, l2_mode=l2_mode, table_dtype="bf16")
-    li, _, _, _ = m.forward(_tuple(b), is_test=False)
+    m = model(cfg, cat, p, l2_mode=l2_mode, table_dtype="bf16")
+    li, _, _, _ = m.forward(batch_tuple(b), is_test=False)
     assert np.abs(li.cpu().numpy() - orc.forward(p, cat, b, H)["logits"]).max() < 1e-4
-    g = m.grads(_tuple(b))
+    g = m.grads(batch_tuple(b))
     _, _, ref_g, _ = orc.backward(p, cat, b, H, cfg["regulation_rate"])
     for k in ref_g:
         a, r = np.asarray(g["grads"][k], np.float64).reshape(ref_g[k].shape), ref_g[k]
@@ -225,8 +203,8 @@ def test_bf16_tables(d, H, l2_mode, Ls):
     loss, q, info = orc.train_step(p, cat, b, H, cfg["regulation_rate"], lr=0.7)
     runs = []
     for rep in range(2):
-        mm = _model(cfg, cat, p, l2_mode=l2_mode, table_dtype="bf16")
-        l = mm.train(None, _tuple(b), 0.7)
+        mm = model(cfg, cat, p, l2_mode=l2_mode, table_dtype="bf16")
+        l = mm.train(None, batch_tuple(b), 0.7)
         assert abs(l - loss) < 1e-4 * max(1.0, abs(loss))
         runs.append(mm.get_params())
     for k in q:
@@ -239,7 +217,7 @@ def test_bf16_tables(d, H, l2_mode, Ls):
             ratio = np.abs(a - r) / ulp
             w = np.unravel_index(np.argmax(ratio), ratio.shape)
             assert (np.abs(a - r) <= ulp * (nround + 1e-3) + 1e-12).all(), (k, ratio[w], a[w], r[w], p[k][w])
-            assert np.array_equal(a.astype(np.float32), _bf16_round(a)), k
+            assert np.array_equal(a.astype(np.float32), bf16_round(a)), k
         else:
             du, dr = a - p[k], r - p[k]
             assert np.abs(du - dr).max() < 2e-4 * (np.abs(dr).max() + 1e-9) + 2e-7, k
@@ -253,17 +231,17 @@ def test_bf16_matrix_products(d, H, table_dtype, Ls, rate):
     """bf16 matrix operands, at test_bf16_matrix_products' tolerances (logits 1.5e-3 of their scale, gradients 15 % of
     their norm, loss 5e-4); with dropout, the step follows the oracle's under the same pattern to the same tolerances."""
     cfg = make_config(U=300, I=400, C=17, d=d, H=H, Ls=Ls, regulation_rate=1e-3, dropout=rate)
-    p = _p32(random_params(cfg, seed=7 + H))
+    p = p32(random_params(cfg, seed=7 + H))
     if table_dtype == "bf16":
         for k in BF16_TABLES:
-            p[k] = _bf16_round(p[k]).astype(np.float64)
+            p[k] = bf16_round(p[k]).astype(np.float64)
     b, cat = random_batch(cfg, B=96, Sn=4, seed=8)
     if rate > 0:
         outs = []
         for rep in range(2):
-            m = _model(cfg, cat, p, table_dtype=table_dtype, matrix_dtype="bf16")
+            m = model(cfg, cat, p, table_dtype=table_dtype, matrix_dtype="bf16")
             seed = m.dropout_seed()
-            outs.append((m.train(None, _tuple(b), 0.6), m.get_params()))
+            outs.append((m.train(None, batch_tuple(b), 0.6), m.get_params()))
         loss, newq, _ = orc.train_step(p, cat, b, H, cfg["regulation_rate"], lr=0.6, dropout=(rate, seed))
         plain = orc.loss_fn(p, cat, b, H, cfg["regulation_rate"])
         l, got = outs[0]
@@ -278,7 +256,7 @@ def test_bf16_matrix_products(d, H, table_dtype, Ls, rate):
     ref = orc.forward(p, cat, b, H)
     loss, _, ref_g, _ = orc.backward(p, cat, b, H, cfg["regulation_rate"])
     scale = np.abs(ref["logits"]).max()
-    outs = [_model(cfg, cat, p, table_dtype=table_dtype, matrix_dtype="bf16").grads(_tuple(b)) for _ in range(2)]
+    outs = [model(cfg, cat, p, table_dtype=table_dtype, matrix_dtype="bf16").grads(batch_tuple(b)) for _ in range(2)]
     g = outs[0]
     err = np.abs(g["logits"] - ref["logits"]).max()
     assert 1e-5 < err < 1.5e-3 * scale + 1e-3, (err, scale)
@@ -296,13 +274,13 @@ def test_bf16_matrix_products(d, H, table_dtype, Ls, rate):
 def test_category_segments(d, H):
     """Tables of thousands of categories: the category half of the gradient rows goes to per-category segments (CSEG)."""
     cfg = make_config(U=70, I=2600, C=2100, d=d, H=H, Ls=10, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=91 + H))
+    p = p32(random_params(cfg, seed=91 + H))
     cat = np.random.RandomState(5).randint(0, 2100, 2600).astype(np.int32)
     b, _ = random_batch(cfg, B=41, Sn=3, seed=900)
     loss, newp, _ = orc.train_step(p, cat, b, H, cfg["regulation_rate"], lr=0.6)
     for l2 in ("dense", "lazy"):
-        m = _model(cfg, cat, p, l2_mode=l2)
-        l = m.train(None, _tuple(b), 0.6)
+        m = model(cfg, cat, p, l2_mode=l2)
+        l = m.train(None, batch_tuple(b), 0.6)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss)), l2
         _check_update(m.get_params(), p, newp, 3e-4, 5e-7, l2)
 
@@ -312,16 +290,16 @@ def test_category_segments(d, H):
 def test_other_optimizers_and_checkpoints(d, H, optimizer, lr, tmp_path):
     cfg = make_config(U=30, I=45, C=7, d=d, H=H, regulation_rate=1e-3, max_gradient_norm=0.05, optimizer=optimizer,
                       model_dir=str(tmp_path))
-    p = _p32(random_params(cfg, seed=61 + H))
+    p = p32(random_params(cfg, seed=61 + H))
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=36, Sn=1 + s % 3, seed=600 + s)[0] for s in range(4)]
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     q, st = dict(p), orc.init_opt_state(p, optimizer)
     for n, b in enumerate(batches):
         prev = q
         loss, q, info = orc.train_step(q, cat, b, H, cfg["regulation_rate"], lr=lr, clip=0.05, optimizer=optimizer,
                                        opt_state=st)
-        l = m.train(None, _tuple(b), lr)
+        l = m.train(None, batch_tuple(b), lr)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss))
         got = m.get_params()
         for k in q:
@@ -331,35 +309,35 @@ def test_other_optimizers_and_checkpoints(d, H, optimizer, lr, tmp_path):
             assert np.abs(np.asarray(got[k], np.float64).reshape(q[k].shape) - q[k]).max() < 2e-3 * step * (n + 1) + 1e-7, (n, k)
         if n == 1:
             path = m.save()
-            m = _model(cfg, cat, None)
+            m = model(cfg, cat, None)
             m.restore(None, path)
 
 
 @pytest.mark.parametrize("d,H", PAIRS)
 def test_save_restore_round_trip(d, H, tmp_path):
     cfg = make_config(U=30, I=45, C=7, d=d, H=H, regulation_rate=1e-3, model_dir=str(tmp_path))
-    p = _p32(random_params(cfg, seed=71 + H))
+    p = p32(random_params(cfg, seed=71 + H))
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     b1, _ = random_batch(cfg, B=36, Sn=2, seed=700)
     b2, _ = random_batch(cfg, B=36, Sn=3, seed=701)
-    m = _model(cfg, cat, p, l2_mode="lazy")
-    m.train(None, _tuple(b1), 0.5)
+    m = model(cfg, cat, p, l2_mode="lazy")
+    m.train(None, batch_tuple(b1), 0.5)
     path = m.save()
-    m2 = _model(cfg, cat, None, l2_mode="lazy")
+    m2 = model(cfg, cat, None, l2_mode="lazy")
     m2.restore(None, path)
     a, c = m.get_params(), m2.get_params()
     for k in a:
         assert np.array_equal(a[k], c[k]), k
-    assert m.train(None, _tuple(b2), 0.5) == m2.train(None, _tuple(b2), 0.5)
+    assert m.train(None, batch_tuple(b2), 0.5) == m2.train(None, batch_tuple(b2), 0.5)
 
 
 @pytest.mark.parametrize("d,H", PAIRS)
 def test_eval_ranks_and_metrics(d, H):
     cfg = make_config(U=60, I=333, C=13, d=d, H=H)
-    p = _p32(random_params(cfg, seed=31 + H))
+    p = p32(random_params(cfg, seed=31 + H))
     b, cat = random_batch(cfg, B=77, Sn=3, seed=32, test=True)
-    m = _model(cfg, cat, p)
-    ranks = m.label_ranks(_tuple(b, True)).cpu().numpy()
+    m = model(cfg, cat, p)
+    ranks = m.label_ranks(batch_tuple(b, True)).cpu().numpy()
     ref = orc.forward(p, cat, b, H)
     scores = orc.all_item_scores(p, cat, ref["u_t"])
     rr = orc.label_ranks(scores, b["i"])
@@ -369,8 +347,8 @@ def test_eval_ranks_and_metrics(d, H):
     assert clear.sum() > 60
     assert np.array_equal(ranks[clear], rr[clear])
     assert np.abs(ranks - rr).max() <= 2
-    pr = m.eval_prec(None, _tuple(b, True))
-    rc = m.eval_recall(None, _tuple(b, True))
+    pr = m.eval_prec(None, batch_tuple(b, True))
+    rc = m.eval_recall(None, batch_tuple(b, True))
     hits = orc.hits_at_k(scores, b["i"])
     for i, k in enumerate((1, 10, 20, 30, 40, 50)):
         assert abs(pr[i] - hits[i] / (k * 77)) <= 2 / (k * 77) + 1e-9
@@ -403,52 +381,34 @@ def test_train_driver_with_four_heads(tmp_path):
     assert len(res["prec"]) == 6 and 0.0 <= res["recall"][-1] <= 1.0
 
 
-def _shard_worker(rank, world, port, ret):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from tlsan_amd.dist import ShardedModel
-        d, H = 128, 4
-        cfg = make_config(U=61, I=83, C=9, d=d, H=H, regulation_rate=1e-3)
-        p = _p32(random_params(cfg, seed=17))
-        _, cat = random_batch(cfg, B=4, Sn=2, seed=0)
-        steps = [[random_batch(cfg, B=24, Sn=3, seed=1000 + 10 * s + r)[0] for r in range(world)] for s in range(3)]
-        m = ShardedModel(cfg, cat, device="cuda:0", l2_mode="lazy")
-        m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-        losses = []
+def _shard_worker(rank, world):
+    from tlsan_amd.dist import ShardedModel
+    d, H = 128, 4
+    cfg = make_config(U=61, I=83, C=9, d=d, H=H, regulation_rate=1e-3)
+    p = p32(random_params(cfg, seed=17))
+    _, cat = random_batch(cfg, B=4, Sn=2, seed=0)
+    steps = [[random_batch(cfg, B=24, Sn=3, seed=1000 + 10 * s + r)[0] for r in range(world)] for s in range(3)]
+    m = ShardedModel(cfg, cat, device="cuda:0", l2_mode="lazy")
+    m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
+    losses = []
+    for per in steps:
+        m.train_async(batch_tuple(per[rank]), 0.8)
+        losses.append(float(m.last_loss.item()))
+    got = m.gather_params()
+    if rank == 0:
+        q = dict(p)
+        ref = []
         for per in steps:
-            m.train_async(_tuple(per[rank]), 0.8)
-            losses.append(float(m.last_loss.item()))
-        got = m.gather_params()
-        if rank == 0:
-            q = dict(p)
-            ref = []
-            for per in steps:
-                glob = {k: np.concatenate([b[k] for b in per], 0) for k in per[0]}
-                l, q, _ = orc.train_step(q, cat, glob, H, cfg["regulation_rate"], lr=0.8)
-                ref.append(l)
-            assert np.allclose(losses, ref, rtol=2e-4, atol=1e-5), (losses, ref)
-            for k in q:
-                g = np.asarray(got[k], np.float64).reshape(q[k].shape)
-                du, dr = g - p[k], q[k] - p[k]
-                assert np.abs(du - dr).max() < 5e-4 * (np.abs(dr).max() + 1e-9) + 5e-7, k
-        ret[rank] = "ok"
-    except Exception:
-        import traceback
-        ret[rank] = "FAIL: " + traceback.format_exc()
-    finally:
-        dist.destroy_process_group()
+            glob = {k: np.concatenate([b[k] for b in per], 0) for k in per[0]}
+            l, q, _ = orc.train_step(q, cat, glob, H, cfg["regulation_rate"], lr=0.8)
+            ref.append(l)
+        assert np.allclose(losses, ref, rtol=2e-4, atol=1e-5), (losses, ref)
+        for k in q:
+            g = np.asarray(got[k], np.float64).reshape(q[k].shape)
+            du, dr = g - p[k], q[k] - p[k]
+            assert np.abs(du - dr).max() < 5e-4 * (np.abs(dr).max() + 1e-9) + 5e-7, k
 
 
 def test_sharded_step_with_four_heads_at_d128():
     """The row-sharded step (tlsan_amd.dist) at 128/4: two processes sharing the GPU over gloo, three steps."""
-    import socket
-    import torch.multiprocessing as mp
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    ret = mp.Manager().dict()
-    mp.spawn(_shard_worker, args=(2, port, ret), nprocs=2, join=True)
-    assert len(ret) == 2 and all(v == "ok" for v in dict(ret).values()), dict(ret)
+    run_ranks(_shard_worker, 2)

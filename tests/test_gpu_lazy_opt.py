@@ -11,137 +11,13 @@ import numpy as np
 import pytest
 
 from oracle import tlsan_oracle as orc
-from tests.helpers import make_config, random_batch, random_params
+from tests.helpers import BF16_TABLES, batch_tuple, bf16_round, make_config, model, p32, random_batch, random_params
+from tests.lazy_opt_ref import (LR, ROW_TABLES, SPARSE_CATEGORY_CASES, check_step, compared, random_slots, restricted_step,
+                                sync_amb, cover_all_batch)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BF16_TABLES = ("item_emb", "user_emb", "cate_emb")
-ROW_TABLES = ("item_emb", "item_b", "user_emb", "usert_emb", "cate_emb")
-LR = {"adam": 0.05, "rmsprop": 0.02, "adadelta": 1.0}
-
-
-def _model(cfg, cat, p=None, slots=None, **kw):
-    from tlsan_amd.model import Model
-    m = Model(cfg, cat, **kw)
-    if p is not None:
-        m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-    if slots is not None:
-        m.set_slots([{k: np.asarray(v, np.float32) for k, v in s.items()} for s in slots])
-    return m
-
-
-def _tuple(b):
-    return (b["u"], b["i"], b["y"], b["hist_i"], b["hist_i_new"], b["hist_t"], b["sl"], b["sl_new"], b["u_cate"])
-
-
-def _p32(p):
-    return {k: np.asarray(v, np.float32).astype(np.float64) for k, v in p.items()}
-
-
-def _bf16_round(a):
-    import torch
-    return torch.as_tensor(np.asarray(a, np.float32)).to(torch.bfloat16).float().numpy()
-
-
-def used_rows(b, cat, cfg):
-    """Boolean masks of the rows a batch uses, per table (the index's used-row records)."""
-    U, I, Cn, Ls = cfg["user_count"], cfg["item_count"], cfg["cate_count"], cfg["Ls"]
-    uu = np.zeros(U, bool)
-    uu[b["u"]] = True
-    ui = np.zeros(I, bool)
-    ui[b["i"]] = True
-    Sn = b["hist_i_new"].shape[1]
-    ui[b["hist_i"][np.arange(Ls)[None, :] < b["sl"][:, None]]] = True
-    if Sn:
-        ui[b["hist_i_new"][np.arange(Sn)[None, :] < b["sl_new"][:, None]]] = True
-    uc = np.zeros(Cn, bool)
-    uc[np.asarray(cat)[ui]] = True
-    uc[b["u_cate"]] = True
-    ub = np.zeros(I, bool)
-    ub[b["i"]] = True
-    return {"user_emb": uu, "usert_emb": uu, "item_emb": ui, "item_b": ub, "cate_emb": uc}
-
-
-def restricted_step(q, st, cat, b, cfg, lr, optimizer, clip):
-    """The lazy step's reference: the dense oracle step, with every unused row of W and both slots put back."""
-    q0, s0 = copy.deepcopy(q), copy.deepcopy(st)
-    loss, newq, info = orc.train_step(q, cat, b, cfg["num_heads"], cfg["regulation_rate"], lr=lr, clip=clip,
-                                      optimizer=optimizer, opt_state=st)
-    used = used_rows(b, cat, cfg)
-    # item_b moves where its fp32 gradient is non-zero: a candidate whose sigmoid saturates to exactly its label in fp32
-    # has gradient 0 there (and keeps its slots, as under the dense RMSProp / Adadelta) while the fp64 oracle still sees a
-    # tiny one -- such rows are compared nowhere (`amb`: every use of the item as a candidate near saturation)
-    near = np.abs(np.asarray(info["logits"], np.float64).reshape(-1)) > 15.0
-    amb = np.zeros_like(used["item_b"])
-    amb[np.asarray(b["i"])[near]] = True
-    amb[np.asarray(b["i"])[~near]] = False
-    used = dict(used, item_b_amb=amb)
-    for k, mask in used.items():
-        if k == "item_b_amb":
-            continue
-        newq[k] = np.where(mask.reshape((-1,) + (1,) * (q0[k].ndim - 1)), newq[k], q0[k])
-        for s in ("slot1", "slot2"):
-            st[s][k] = np.where(mask.reshape((-1,) + (1,) * (q0[k].ndim - 1)), st[s][k], s0[s][k])
-    return loss, newq, info, used
-
-
-def random_slots(p, optimizer, seed):
-    """Non-zero slots on every row (a sweep over unused rows would show), valid for the optimizer (v, rms >= 0)."""
-    rng = np.random.RandomState(seed)
-    st = orc.init_opt_state(p, optimizer)
-    for k in p:
-        sh = np.shape(p[k])
-        if optimizer == "adam":
-            st["slot1"][k] = rng.uniform(-0.01, 0.01, sh)
-            st["slot2"][k] = rng.uniform(1e-5, 1e-4, sh)
-        elif optimizer == "rmsprop":
-            st["slot1"][k] = rng.uniform(0.5, 1.5, sh)
-            st["slot2"][k] = np.zeros(sh)                 # (momentum 0: the slot is recomputed, never decayed)
-        else:
-            st["slot1"][k] = rng.uniform(1e-5, 1e-3, sh)
-            st["slot2"][k] = rng.uniform(1e-6, 1e-4, sh)
-        for s in ("slot1", "slot2"):
-            st[s][k] = np.asarray(st[s][k], np.float32).astype(np.float64)
-    return st
-
-
-def _cmp(k, a, used):
-    """the rows of parameter k that are compared (item_b: not the saturated candidates, see restricted_step)"""
-    a = np.asarray(a, np.float64)
-    return a[~used["item_b_amb"]] if k == "item_b" else a
-
-
-def _sync_amb(m, q, st, used):
-    """carry the device's item_b (and its slots) of the saturated candidates into the reference for the next steps"""
-    amb = used["item_b_amb"]
-    if amb.any():
-        q["item_b"] = np.where(amb, np.asarray(m.item_b.cpu().numpy(), np.float64), q["item_b"])
-        for j, s in enumerate(m.get_slots()):
-            st["slot%d" % (j + 1)]["item_b"] = np.where(amb, np.asarray(s["item_b"], np.float64),
-                                                        st["slot%d" % (j + 1)]["item_b"])
-
-
-def _check(m, q, st, p_prev, used, tol_n, skip_b2=True, exact_unused=None):
-    got = m.get_params()
-    s1, s2 = m.get_slots()
-    for k in q:
-        if skip_b2 and k.endswith("_b2"):
-            continue      # (gradient = rounding noise, see test_gpu_parity.test_other_optimizers_track_oracle)
-        a = _cmp(k, np.asarray(got[k], np.float64).reshape(np.shape(q[k])), used)
-        r, r0 = _cmp(k, q[k], used), _cmp(k, p_prev[k], used)
-        step = np.abs(r - r0).max()
-        assert np.abs(a - r).max() < 2e-3 * step * tol_n + 1e-7, k
-        for gs, ref in ((s1[k], st["slot1"][k]), (s2[k], st["slot2"][k])):
-            gs, ref = _cmp(k, np.asarray(gs).reshape(np.shape(ref)), used), _cmp(k, ref, used)
-            assert np.abs(gs - ref).max() < 2e-3 * np.abs(ref).max() + 1e-9, k
-    if exact_unused is not None:
-        P0, S0 = exact_unused
-        for k in ROW_TABLES:
-            keep = ~used[k]
-            assert np.array_equal(np.asarray(got[k], np.float32)[keep], np.asarray(P0[k], np.float32)[keep]), k
-            assert np.array_equal(np.asarray(s1[k], np.float32)[keep], np.asarray(S0[0][k], np.float32)[keep]), k
-            assert np.array_equal(np.asarray(s2[k], np.float32)[keep], np.asarray(S0[1][k], np.float32)[keep]), k
 
 
 @pytest.mark.parametrize("optimizer", ["adam", "rmsprop", "adadelta"])
@@ -152,11 +28,11 @@ def test_lazy_optimizers_track_the_restricted_oracle(optimizer, tmp_path):
     cfg = make_config(U=300, I=450, C=20, d=64, regulation_rate=1e-3, max_gradient_norm=0.05,
                       optimizer="lazy_" + optimizer, model_dir=str(tmp_path))
     lr = LR[optimizer]
-    p = _p32(random_params(cfg, seed=71))
+    p = p32(random_params(cfg, seed=71))
     st = random_slots(p, optimizer, 72)
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=16 + 4 * s, Sn=1 + s % 3, seed=700 + s)[0] for s in range(6)]
-    m = _model(cfg, cat, p, [st["slot1"], st["slot2"]])
+    m = model(cfg, cat, p, [st["slot1"], st["slot2"]])
     q = dict(p)
     for n, b in enumerate(batches):
         clip = 0.05 if n < 5 else 1e3
@@ -165,28 +41,16 @@ def test_lazy_optimizers_track_the_restricted_oracle(optimizer, tmp_path):
         prev = q
         loss, q, info, used = restricted_step(q, st, cat, b, cfg, lr, optimizer, clip)
         assert (info["coef"] < 1.0) == (n < 5)
-        l = m.train(None, _tuple(b), lr)
+        l = m.train(None, batch_tuple(b), lr)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss)), (n, l, loss)
         assert not used["user_emb"].all() and not used["item_emb"].all()
-        _check(m, q, st, prev, used, n + 1, exact_unused=before)
-        _sync_amb(m, q, st, used)
+        check_step(m, q, st, prev, used, n + 1, exact_unused=before)
+        sync_amb(m, q, st, used)
         if n == 2:                                # checkpoint round trip in the middle of the run
             path = m.save()
-            m = _model(cfg, cat, None)
+            m = model(cfg, cat, None)
             m.restore(None, path)
     assert m.table_scale() == 1.0
-
-
-def _cover_all_batch(cfg, seed):
-    """One batch whose candidates cover every item, users every user and u_cate every category."""
-    I, U, Cn = cfg["item_count"], cfg["user_count"], cfg["cate_count"]
-    B = max(I, U, Cn)
-    b, _ = random_batch(cfg, B=B, Sn=2, seed=seed)
-    rng = np.random.RandomState(seed + 1)
-    b["i"] = rng.permutation(np.arange(B) % I).astype(np.int64)
-    b["u"] = rng.permutation(np.arange(B) % U).astype(np.int64)
-    b["u_cate"] = rng.permutation(np.arange(B) % Cn).astype(np.int64)
-    return b
 
 
 @pytest.mark.parametrize("optimizer,dropout,matrix_dtype", [("adam", 0.0, "f32"), ("rmsprop", 0.0, "f32"),
@@ -197,14 +61,14 @@ def test_lazy_equals_dense_when_every_row_is_used(optimizer, dropout, matrix_dty
     rounding, with dropout and bf16 matrix products as well (the same keep / drop pattern and products in both)."""
     cfg = make_config(U=40, I=60, C=7, d=64, regulation_rate=1e-3, max_gradient_norm=0.05, dropout=dropout)
     lr = LR[optimizer]
-    p = _p32(random_params(cfg, seed=73))
+    p = p32(random_params(cfg, seed=73))
     st = random_slots(p, optimizer, 74)
     _, cat = random_batch(cfg, B=8, Sn=3, seed=1)
-    b = _cover_all_batch(cfg, 740)
+    b = cover_all_batch(cfg, 740)
     out = []
     for name in (optimizer, "lazy_" + optimizer):
-        m = _model(dict(cfg, optimizer=name), cat, p, [st["slot1"], st["slot2"]], matrix_dtype=matrix_dtype)
-        l = m.train(None, _tuple(b), lr)
+        m = model(dict(cfg, optimizer=name), cat, p, [st["slot1"], st["slot2"]], matrix_dtype=matrix_dtype)
+        l = m.train(None, batch_tuple(b), lr)
         out.append((l, m.get_params(), m.get_slots()))
     (ld, pd, sd), (ll, pl, sl) = out
     assert abs(ld - ll) <= 1e-6 * max(1.0, abs(ld))
@@ -219,20 +83,20 @@ def _row_form_run(d, Ls, C, optimizer, B=24, Sn=3, steps=2, seed=80, U=200, I=30
     cfg = make_config(U=U, I=I, C=C, d=d, Ls=Ls, regulation_rate=1e-3, max_gradient_norm=clip,
                       optimizer="lazy_" + optimizer)
     lr = LR[optimizer]
-    p = _p32(random_params(cfg, seed=seed))
+    p = p32(random_params(cfg, seed=seed))
     st = random_slots(p, optimizer, seed + 1)
     _, cat = random_batch(cfg, B=8, Sn=2, seed=seed + 2)
-    m = _model(cfg, cat, p, [st["slot1"], st["slot2"]], table_dtype=table_dtype)
+    m = model(cfg, cat, p, [st["slot1"], st["slot2"]], table_dtype=table_dtype)
     q = dict(p)
     for s in range(steps):
         b = random_batch(cfg, B=B, Sn=Sn, seed=seed + 10 + s)[0]
         before = (m.get_params(), m.get_slots())
         prev = q
         loss, q, info, used = restricted_step(q, st, cat, b, cfg, lr, optimizer, clip)
-        l = m.train(None, _tuple(b), lr)
+        l = m.train(None, batch_tuple(b), lr)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss)), (s, l, loss)
-        _check(m, q, st, prev, used, s + 1, exact_unused=before)
-        _sync_amb(m, q, st, used)
+        check_step(m, q, st, prev, used, s + 1, exact_unused=before)
+        sync_amb(m, q, st, used)
 
 
 @pytest.mark.parametrize("d,Ls,C,optimizer", [(64, 10, 20, "adam"), (128, 10, 20, "rmsprop"), (256, 10, 20, "adadelta"),
@@ -248,15 +112,15 @@ def test_lazy_row_forms(d, Ls, C, optimizer):
 def _sparse_category_run(optimizer, C, item_cates, ucate_cates, B, d=64, Ls=10, steps=2, seed=120):
     """A batch uses a small part of the category table: the items belong to `item_cates` only and u_cate names
     `ucate_cates` only, so some categories are reached only through items, some named only by u_cate, and the rest are
-    unused -- those keep W and both slots bit for bit (_check), the others follow the restricted oracle."""
+    unused -- those keep W and both slots bit for bit (check_step), the others follow the restricted oracle."""
     cfg = make_config(U=300, I=450, C=C, d=d, Ls=Ls, regulation_rate=1e-3, max_gradient_norm=0.05,
                       optimizer="lazy_" + optimizer)
     lr = LR[optimizer]
     rng = np.random.RandomState(seed)
     cat = rng.choice(np.asarray(item_cates), cfg["item_count"]).astype(np.int32)
-    p = _p32(random_params(cfg, seed=seed + 1))
+    p = p32(random_params(cfg, seed=seed + 1))
     st = random_slots(p, optimizer, seed + 2)
-    m = _model(cfg, cat, p, [st["slot1"], st["slot2"]])
+    m = model(cfg, cat, p, [st["slot1"], st["slot2"]])
     q = dict(p)
     only_items = only_ucate = unused = 0
     for s in range(steps):
@@ -265,10 +129,10 @@ def _sparse_category_run(optimizer, C, item_cates, ucate_cates, B, d=64, Ls=10, 
         before = (m.get_params(), m.get_slots())
         prev = q
         loss, q, info, used = restricted_step(q, st, cat, b, cfg, lr, optimizer, 0.05)
-        l = m.train(None, _tuple(b), lr)
+        l = m.train(None, batch_tuple(b), lr)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss)), (s, l, loss)
-        _check(m, q, st, prev, used, s + 1, exact_unused=before)
-        _sync_amb(m, q, st, used)
+        check_step(m, q, st, prev, used, s + 1, exact_unused=before)
+        sync_amb(m, q, st, used)
         by_item = np.zeros(C, bool)
         by_item[cat[used["item_emb"]]] = True
         by_ucate = np.zeros(C, bool)
@@ -277,11 +141,6 @@ def _sparse_category_run(optimizer, C, item_cates, ucate_cates, B, d=64, Ls=10, 
         only_ucate += int((by_ucate & ~by_item).sum())
         unused += int((~used["cate_emb"]).sum())
     assert only_items > 0 and only_ucate > 0 and unused > 0, (only_items, only_ucate, unused)
-
-
-SPARSE_CATEGORY_CASES = [("adam", 400, range(0, 10), range(200, 400), 16, 64),       # one category per workgroup
-                         ("adadelta", 1000, range(0, 20), range(500, 1000), 16, 128),  # wide rows
-                         ("adam", 6, [0, 1], [2], 96, 64)]                              # shared categories (Rc64)
 
 
 @pytest.mark.parametrize("optimizer,C,item_cates,ucate_cates,B,d", SPARSE_CATEGORY_CASES)
@@ -296,7 +155,8 @@ from tests.test_gpu_lazy_opt import _row_form_run
 for opt in ("adam", "adadelta"):
     _row_form_run(64, 10, 40, opt, B=32, seed=90)
     _row_form_run(128, 24, 40, opt, B=32, seed=91)
-from tests.test_gpu_lazy_opt import SPARSE_CATEGORY_CASES, _sparse_category_run
+from tests.lazy_opt_ref import SPARSE_CATEGORY_CASES
+from tests.test_gpu_lazy_opt import _sparse_category_run
 for optimizer, C, item_cates, ucate_cates, B, d in SPARSE_CATEGORY_CASES:
     _sparse_category_run(optimizer, C, item_cates, ucate_cates, B, d=d, seed=140)
 print("ok")
@@ -315,14 +175,14 @@ def test_lazy_step_on_a_scaled_state():
     """A C caller may run lazy-L2 SGD steps on the state first, so that the table scale P is not 1: the lazy optimizer's
     step then acts on the true values P * stored (as the forward pass and the loss do) and leaves P as it is."""
     cfg = make_config(U=300, I=450, C=20, d=64, regulation_rate=0.05, max_gradient_norm=0.05, optimizer="lazy_adam")
-    p = _p32(random_params(cfg, seed=131))
+    p = p32(random_params(cfg, seed=131))
     st = random_slots(p, "adam", 132)
     _, cat = random_batch(cfg, B=8, Sn=3, seed=133)
-    m = _model(cfg, cat, p, [st["slot1"], st["slot2"]])
+    m = model(cfg, cat, p, [st["slot1"], st["slot2"]])
     copt, m._copt = m._copt, None            # two unclipped lazy-L2 SGD steps (tlsan_train_step): P = (1 - lr reg)^2
     cfg["max_gradient_norm"] = 1e3
     for s in range(2):
-        m.train(None, _tuple(random_batch(cfg, B=16, Sn=2, seed=134 + s)[0]), 1.0)
+        m.train(None, batch_tuple(random_batch(cfg, B=16, Sn=2, seed=134 + s)[0]), 1.0)
     m._copt = copt
     cfg["max_gradient_norm"] = 0.05
     P = m.table_scale()
@@ -333,7 +193,7 @@ def test_lazy_step_on_a_scaled_state():
     st["t"] = 2                              # (Adam's step count: the model's two steps so far)
     b = random_batch(cfg, B=20, Sn=2, seed=136)[0]
     loss, q, info, used = restricted_step(dict(q0), st, cat, b, cfg, 0.05, "adam", 0.05)
-    l = m.train(None, _tuple(b), 0.05)
+    l = m.train(None, batch_tuple(b), 0.05)
     assert abs(l - loss) < 2e-4 * max(1.0, abs(loss)), (l, loss)
     assert m.table_scale() == P
     stored = m.get_params()
@@ -342,10 +202,10 @@ def test_lazy_step_on_a_scaled_state():
     for k in q:
         if k.endswith("_b2"):
             continue
-        a, r, r0 = (_cmp(k, np.asarray(x).reshape(np.shape(q[k])), used) for x in (got[k], q[k], q0[k]))
+        a, r, r0 = (compared(k, np.asarray(x).reshape(np.shape(q[k])), used) for x in (got[k], q[k], q0[k]))
         assert np.abs(a - r).max() < 2e-3 * np.abs(r - r0).max() + 1e-6, k
         for gs, ref in ((s1[k], st["slot1"][k]), (s2[k], st["slot2"][k])):
-            gs, ref = _cmp(k, np.asarray(gs).reshape(np.shape(ref)), used), _cmp(k, ref, used)
+            gs, ref = compared(k, np.asarray(gs).reshape(np.shape(ref)), used), compared(k, ref, used)
             assert np.abs(gs - ref).max() < 2e-3 * np.abs(ref).max() + 1e-9, k
     for k in ROW_TABLES:
         keep = ~used[k]
@@ -358,17 +218,17 @@ def test_lazy_sum_of_squares_and_scale(table_dtype):
     and two runs agree bit for bit in losses, parameters and slots."""
     import torch
     cfg = make_config(U=3000, I=4000, C=40, d=64, regulation_rate=0.05, max_gradient_norm=13.5, optimizer="lazy_adam")
-    p = _p32(random_params(cfg, seed=1401))
+    p = p32(random_params(cfg, seed=1401))
     if table_dtype == "bf16":
         for k in BF16_TABLES:
-            p[k] = _bf16_round(p[k]).astype(np.float64)
+            p[k] = bf16_round(p[k]).astype(np.float64)
     _, cat = random_batch(cfg, B=8, Sn=2, seed=1400)
     shapes = [(64, 1), (5, 3), (40, 5), (1, 2), (64, 4), (17, 1)]
-    batches = [_tuple(random_batch(cfg, B=B, Sn=Sn, seed=1410 + k)[0]) for k, (B, Sn) in enumerate(shapes)]
-    probe = _tuple(random_batch(cfg, B=9, Sn=2, seed=1420)[0])
+    batches = [batch_tuple(random_batch(cfg, B=B, Sn=Sn, seed=1410 + k)[0]) for k, (B, Sn) in enumerate(shapes)]
+    probe = batch_tuple(random_batch(cfg, B=9, Sn=2, seed=1420)[0])
     runs = []
     for rep in range(2):
-        m = _model(cfg, cat, p, table_dtype=table_dtype)
+        m = model(cfg, cat, p, table_dtype=table_dtype)
         losses = [m.train(None, b, 0.01) for b in batches]
         m.grads(probe)                     # (folds the last step's records)
         St = float(m.state[32:40].view(torch.float64).item())
@@ -389,17 +249,17 @@ def test_lazy_optimizers_with_bf16_tables(optimizer):
     neighbours of the oracle's value, unused rows keep their bits, two runs leave the same bits."""
     cfg = make_config(U=300, I=450, C=20, d=64, regulation_rate=1e-3, max_gradient_norm=0.05, optimizer="lazy_" + optimizer)
     lr = {"adam": 0.01, "rmsprop": 0.01, "adadelta": 1.0}[optimizer]
-    p = _p32(random_params(cfg, seed=75))
+    p = p32(random_params(cfg, seed=75))
     for k in BF16_TABLES:
-        p[k] = _bf16_round(p[k]).astype(np.float64)
+        p[k] = bf16_round(p[k]).astype(np.float64)
     st = random_slots(p, optimizer, 76)
     b, cat = random_batch(cfg, B=36, Sn=3, seed=751)
     st0 = copy.deepcopy(st)
     loss, q, info, used = restricted_step(dict(p), st, cat, b, cfg, lr, optimizer, 0.05)
     outs = []
     for rep in range(2):
-        m = _model(cfg, cat, p, [st0["slot1"], st0["slot2"]], table_dtype="bf16")
-        l = m.train(None, _tuple(b), lr)
+        m = model(cfg, cat, p, [st0["slot1"], st0["slot2"]], table_dtype="bf16")
+        l = m.train(None, batch_tuple(b), lr)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss))
         outs.append((m.get_params(), m.get_slots()))
     got, (s1, s2) = outs[0]
@@ -413,15 +273,15 @@ def test_lazy_optimizers_with_bf16_tables(optimizer):
         if k in BF16_TABLES:
             ulp = 2.0 ** (np.floor(np.log2(np.maximum(np.abs(r), 1e-30))) - 7)
             assert (np.abs(a - r) <= ulp * 1.001 + 2e-3 * np.abs(r - p[k]).max()).all(), k
-            assert np.array_equal(a.astype(np.float32), _bf16_round(a)), k
+            assert np.array_equal(a.astype(np.float32), bf16_round(a)), k
         else:
-            step = np.abs(r - _cmp(k, p[k], used)).max()
+            step = np.abs(r - compared(k, p[k], used)).max()
             assert np.abs(a - r).max() < 2e-3 * step + 1e-7, k
         if k in used:
             keep = ~used[k]
             assert np.array_equal(a[keep], np.asarray(p[k])[keep]), k
         for gs, ref in ((s1[k], st["slot1"][k]), (s2[k], st["slot2"][k])):
-            gs, ref = _cmp(k, np.asarray(gs).reshape(ref.shape), used), _cmp(k, ref, used)
+            gs, ref = compared(k, np.asarray(gs).reshape(ref.shape), used), compared(k, ref, used)
             assert np.abs(gs - ref).max() < 2e-3 * np.abs(ref).max() + 1e-9, k
 
 
@@ -429,19 +289,19 @@ def test_lazy_adam_on_large_tables():
     """300 k users / 150 k items: the two-level scan and the sorted-user index; two steps against the restricted oracle."""
     cfg = make_config(U=300_000, I=150_000, C=40, d=64, regulation_rate=1e-3, max_gradient_norm=0.05,
                       optimizer="lazy_adam")
-    p = _p32(random_params(cfg, seed=85))
+    p = p32(random_params(cfg, seed=85))
     st = orc.init_opt_state(p, "adam")
     _, cat = random_batch(cfg, B=4, Sn=2, seed=0)
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     q = dict(p)
     amb_all = []
     for s in range(2):
         b = random_batch(cfg, B=48, Sn=2 + s, seed=850 + s)[0]
         loss, q, info, used = restricted_step(q, st, cat, b, cfg, 0.05, "adam", 0.05)
         amb_all.append(used)
-        l = m.train(None, _tuple(b), 0.05)
+        l = m.train(None, batch_tuple(b), 0.05)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss))
-        _sync_amb(m, q, st, used)
+        sync_amb(m, q, st, used)
     got = m.get_params()
     s1, s2 = m.get_slots()
     amb = np.zeros(cfg["item_count"], bool)
@@ -451,10 +311,10 @@ def test_lazy_adam_on_large_tables():
     for k in q:
         if k.endswith("_b2"):
             continue
-        a, r = _cmp(k, np.asarray(got[k]).reshape(q[k].shape), used), _cmp(k, q[k], used)
-        assert np.abs(a - r).max() < 2e-3 * 2 * np.abs(r - _cmp(k, p[k], used)).max() + 1e-7, k
+        a, r = compared(k, np.asarray(got[k]).reshape(q[k].shape), used), compared(k, q[k], used)
+        assert np.abs(a - r).max() < 2e-3 * 2 * np.abs(r - compared(k, p[k], used)).max() + 1e-7, k
         for gs, ref in ((s1[k], st["slot1"][k]), (s2[k], st["slot2"][k])):
-            gs, ref = _cmp(k, np.asarray(gs).reshape(ref.shape), used), _cmp(k, ref, used)
+            gs, ref = compared(k, np.asarray(gs).reshape(ref.shape), used), compared(k, ref, used)
             assert np.abs(gs - ref).max() < 2e-3 * np.abs(ref).max() + 1e-9, k
 
 

@@ -8,29 +8,12 @@ import numpy as np
 import pytest
 
 from oracle import tlsan_oracle as orc
-from tests.helpers import fixture_batch, make_config, random_batch, random_params
+from tests.helpers import (BF16_TABLES, batch_tuple, bf16_round, fixture_batch, make_config, model, p32, random_batch,
+                           random_params)
 
 pytestmark = pytest.mark.gpu
 
 LOGIT_TOL = 1e-4
-
-
-def _model(cfg, cat, p=None, **kw):
-    from tlsan_amd.model import Model
-    m = Model(cfg, cat, **kw)
-    if p is not None:
-        m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-    return m
-
-
-def _tuple(b, test=False):
-    return (b["u"], b["i"], b["j"] if test else b["y"], b["hist_i"], b["hist_i_new"], b["hist_t"],
-            b["sl"], b["sl_new"], b["u_cate"])
-
-
-def _p32(p):
-    """oracle params rounded to fp32 (what the device holds), kept in fp64 for the oracle."""
-    return {k: np.asarray(v, np.float32).astype(np.float64) for k, v in p.items()}
 
 
 def _relerr(a, b):
@@ -41,29 +24,29 @@ def _relerr(a, b):
                                     (64, 200, 12), (128, 300, 18)])
 def test_forward_logits(d, B, Sn):
     cfg = make_config(U=70, I=90, C=11, d=d)
-    p = _p32(random_params(cfg, seed=d + B))
+    p = p32(random_params(cfg, seed=d + B))
     b, cat = random_batch(cfg, B=B, Sn=Sn, seed=B + Sn, test=True)
-    m = _model(cfg, cat, p)
-    li, lj, ut, _ = m.forward(_tuple(b, True), is_test=True, want_u_t=True)
+    m = model(cfg, cat, p)
+    li, lj, ut, _ = m.forward(batch_tuple(b, True), is_test=True, want_u_t=True)
     ref = orc.forward(p, cat, b, 8)
     bn = dict(b); bn["i"] = b["j"]
     refj = orc.forward(p, cat, bn, 8)
     assert np.abs(li.cpu().numpy() - ref["logits"]).max() < LOGIT_TOL
     assert np.abs(lj.cpu().numpy() - refj["logits"]).max() < LOGIT_TOL
     assert np.abs(ut.cpu().numpy() - ref["u_t"]).max() < LOGIT_TOL
-    auc = m.eval_auc(None, _tuple(b, True))
+    auc = m.eval_auc(None, batch_tuple(b, True))
     assert auc == pytest.approx(float(np.mean(ref["logits"] - refj["logits"] > 0)), abs=1e-6)
 
 
 @pytest.mark.parametrize("d,B,Sn", [(64, 45, 4), (128, 40, 3), (128, 33, 9), (256, 18, 2), (128, 1, 0)])
 def test_gradients(d, B, Sn):
     cfg = make_config(U=30, I=50, C=7, d=d)  # small tables -> many duplicate ids
-    p = _p32(random_params(cfg, seed=3 * d + B))
+    p = p32(random_params(cfg, seed=3 * d + B))
     b, cat = random_batch(cfg, B=B, Sn=Sn, seed=B * 7 + Sn)
     reg = cfg["regulation_rate"]
     loss, logits, g, sparse = orc.backward(p, cat, b, 8, reg)
-    m = _model(cfg, cat, p)
-    out = m.grads(_tuple(b))
+    m = model(cfg, cat, p)
+    out = m.grads(batch_tuple(b))
     assert np.abs(out["logits"] - logits).max() < LOGIT_TOL
     assert abs(out["loss"] - loss) < 1e-4 * max(1.0, abs(loss))
     for k in g:
@@ -73,8 +56,8 @@ def test_gradients(d, B, Sn):
         assert err < 2e-4 * np.abs(g[k]).max() + 1e-6, (k, err, np.abs(g[k]).max())
     n18 = orc.global_norm(p, g, sparse, reg, "tf18")
     assert abs(out["gnorm"] - n18) < 2e-4 * n18
-    m2 = _model(cfg, cat, p, norm_mode="dedup")
-    out2 = m2.grads(_tuple(b))
+    m2 = model(cfg, cat, p, norm_mode="dedup")
+    out2 = m2.grads(batch_tuple(b))
     nd = orc.global_norm(p, g, sparse, reg, "dedup")
     assert abs(out2["gnorm"] - nd) < 2e-4 * nd
 
@@ -83,14 +66,14 @@ def test_gradients(d, B, Sn):
 @pytest.mark.parametrize("clip", [5.0, 0.02])
 def test_train_step_matches_oracle(norm_mode, clip):
     cfg = make_config(U=40, I=60, C=9, d=128, max_gradient_norm=clip, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=11))
+    p = p32(random_params(cfg, seed=11))
     b, cat = random_batch(cfg, B=48, Sn=4, seed=12)
     loss, newp, info = orc.train_step(p, cat, b, 8, cfg["regulation_rate"], lr=0.7, clip=clip,
                                       norm_mode=norm_mode)
     if clip < 1:
         assert info["coef"] < 1.0
-    m = _model(cfg, cat, p, norm_mode=norm_mode)
-    l = m.train(None, _tuple(b), 0.7)
+    m = model(cfg, cat, p, norm_mode=norm_mode)
+    l = m.train(None, batch_tuple(b), 0.7)
     assert abs(l - loss) < 1e-4 * max(1.0, abs(loss))
     assert abs(m.last_gnorm() - info["norm"]) < 2e-4 * info["norm"]
     got = m.get_params()
@@ -110,23 +93,23 @@ def test_category_segments_match_oracle(d, Ls, l2_mode):
     category blocks of the apply pass sum that segment instead of walking the category's items.  Same numbers as the
     oracle: gradients, three training steps (window in registers and streamed, dense and lazy L2), bitwise reproducible."""
     cfg = make_config(U=70, I=2600, C=2100, d=d, Ls=Ls, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=91))
+    p = p32(random_params(cfg, seed=91))
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=41, Sn=2 + s, seed=900 + s)[0] for s in range(3)]
     for b in batches:          # (several uses per item and per category: ids folded onto 150 items; u_cate hits their categories)
         for k in ("hist_i", "hist_i_new", "i"):
             b[k] %= 150
         b["u_cate"][:] = cat[b["i"]]
-    m = _model(cfg, cat, p, l2_mode=l2_mode)
-    g = m.grads(_tuple(batches[0]))
+    m = model(cfg, cat, p, l2_mode=l2_mode)
+    g = m.grads(batch_tuple(batches[0]))
     _, _, ref_g, _ = orc.backward(p, cat, batches[0], 8, cfg["regulation_rate"])
     for k in ref_g:
         a, r = np.asarray(g["grads"][k], np.float64).reshape(ref_g[k].shape), ref_g[k]
         assert np.abs(a - r).max() < 2e-4 * np.abs(r).max() + 1e-6, k
     runs = []
     for rep in range(2):
-        mm = _model(cfg, cat, p, l2_mode=l2_mode)
-        losses = [mm.train(None, _tuple(b), 0.6) for b in batches]
+        mm = model(cfg, cat, p, l2_mode=l2_mode)
+        losses = [mm.train(None, batch_tuple(b), 0.6) for b in batches]
         runs.append((losses, mm.get_params()))
     assert runs[0][0] == runs[1][0]
     for k in runs[0][1]:
@@ -147,11 +130,11 @@ def test_category_segments_with_many_uses_per_category():
     workgroups.  A category segment is never split (round 3's advisor: `category_split` ran with `cseg` set and the
     split kernel then summed the first C/16 categories only, silently): one lazy step against the oracle."""
     cfg = make_config(U=70, I=2600, C=2100, d=64, Ls=90, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=93))
+    p = p32(random_params(cfg, seed=93))
     b, cat = random_batch(cfg, B=12000, Sn=3, seed=931)
     assert b["u"].shape[0] * (cfg["Ls"] + 3 + 2) // cfg["cate_count"] > 512
-    m = _model(cfg, cat, p, l2_mode="lazy")
-    loss = m.train(None, _tuple(b), 0.6)
+    m = model(cfg, cat, p, l2_mode="lazy")
+    loss = m.train(None, batch_tuple(b), 0.6)
     lo, q, _ = orc.train_step(p, cat, b, 8, cfg["regulation_rate"], lr=0.6)
     assert abs(loss - lo) < 2e-4 * max(1.0, abs(lo))
     got = m.get_params()
@@ -163,13 +146,13 @@ def test_category_segments_with_many_uses_per_category():
 
 def test_multi_step_tracks_oracle_and_is_deterministic():
     cfg = make_config(U=25, I=35, C=5, d=64, regulation_rate=5e-5)
-    p = _p32(random_params(cfg, seed=21))
+    p = p32(random_params(cfg, seed=21))
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=40, Sn=1 + s % 4, seed=100 + s)[0] for s in range(6)]
     runs = []
     for rep in range(2):
-        m = _model(cfg, cat, p)
-        losses = [m.train(None, _tuple(b), 0.5) for b in batches]
+        m = model(cfg, cat, p)
+        losses = [m.train(None, batch_tuple(b), 0.5) for b in batches]
         runs.append((losses, m.get_params()))
     # bitwise reproducible (deterministic scatter-add and reductions)
     assert runs[0][0] == runs[1][0]
@@ -191,10 +174,10 @@ def test_real_fixture_batches(name):
     """Real batches from the reference's input.py, reference default shapes (d=64, B=32/128)."""
     batch, (U, I, C), icl = fixture_batch(name)
     cfg = make_config(U=U, I=I, C=C, d=64)
-    p = _p32(orc.init_params(cfg, seed=1234))
+    p = p32(orc.init_params(cfg, seed=1234))
     rng = np.random.RandomState(5)
     p["item_b"] = rng.uniform(-0.1, 0.1, p["item_b"].shape).astype(np.float32).astype(np.float64)
-    m = _model(cfg, icl, p)
+    m = model(cfg, icl, p)
     b = orc.as_batch(batch)
     loss, newp, info = orc.train_step(p, icl, b, 8, cfg["regulation_rate"], 1.0)
     l = m.train(None, batch, 1.0)
@@ -206,7 +189,7 @@ def test_real_fixture_batches(name):
         assert np.abs(du - dr).max() < 3e-4 * (np.abs(dr).max() + 1e-9) + 2e-7, k
     tb, _, _ = fixture_batch(name, "DataInputTest", 128, 10, 0)
     tbd = orc.as_batch(tb, is_test=True)
-    q = _p32(got)
+    q = p32(got)
     auc_ref, r1, r2 = orc.eval_auc_batch(q, icl, tbd, 8)
     assert m.eval_auc(None, tb) == pytest.approx(auc_ref, abs=1.0 / 128 + 1e-9)
     li, lj, _, _ = m.forward(tb, is_test=True)
@@ -216,10 +199,10 @@ def test_real_fixture_batches(name):
 @pytest.mark.parametrize("d", [64, 128])
 def test_eval_ranks_and_metrics(d):
     cfg = make_config(U=60, I=333, C=13, d=d)
-    p = _p32(random_params(cfg, seed=31))
+    p = p32(random_params(cfg, seed=31))
     b, cat = random_batch(cfg, B=77, Sn=3, seed=32, test=True)
-    m = _model(cfg, cat, p)
-    ranks = m.label_ranks(_tuple(b, True)).cpu().numpy()
+    m = model(cfg, cat, p)
+    ranks = m.label_ranks(batch_tuple(b, True)).cpu().numpy()
     ref = orc.forward(p, cat, b, 8)
     scores = orc.all_item_scores(p, cat, ref["u_t"])
     rr = orc.label_ranks(scores, b["i"])
@@ -231,14 +214,14 @@ def test_eval_ranks_and_metrics(d):
     assert clear.sum() > 60
     assert np.array_equal(ranks[clear], rr[clear])
     assert np.abs(ranks - rr).max() <= 2
-    pr = m.eval_prec(None, _tuple(b, True))
-    rc = m.eval_recall(None, _tuple(b, True))
+    pr = m.eval_prec(None, batch_tuple(b, True))
+    rc = m.eval_recall(None, batch_tuple(b, True))
     hits = orc.hits_at_k(scores, b["i"])
     for i, k in enumerate((1, 10, 20, 30, 40, 50)):
         assert abs(pr[i] - hits[i] / (k * 77)) <= 2 / (k * 77) + 1e-9
         assert abs(rc[i] - hits[i] / 77) <= 2 / 77 + 1e-9
     # cumulative semantics (reference never resets the streaming counters)
-    pr2 = m.eval_prec(None, _tuple(b, True))
+    pr2 = m.eval_prec(None, batch_tuple(b, True))
     assert np.allclose(pr2, pr)
     assert m.prec_10.eval() == pytest.approx(pr2[1])
 
@@ -246,21 +229,21 @@ def test_eval_ranks_and_metrics(d):
 def test_exact_ties_follow_topk_order():
     """Two items with bit-identical rows and biases: the lower id ranks first (tf.nn.top_k)."""
     cfg = make_config(U=20, I=64, C=4, d=64)
-    p = _p32(random_params(cfg, seed=41))
+    p = p32(random_params(cfg, seed=41))
     b, cat = random_batch(cfg, B=16, Sn=2, seed=42, test=True)
     p["item_emb"][9] = p["item_emb"][5]
     p["item_b"][9] = p["item_b"][5]
     cat[9] = cat[5]
     b["i"][:8] = 5
     b["i"][8:] = 9
-    m = _model(cfg, cat, p)
-    ranks = m.label_ranks(_tuple(b, True)).cpu().numpy()
+    m = model(cfg, cat, p)
+    ranks = m.label_ranks(batch_tuple(b, True)).cpu().numpy()
     ref = orc.forward(p, cat, b, 8)
     scores = orc.all_item_scores(p, cat, ref["u_t"]).astype(np.float32)
     # label 9 must count item 5 as ahead of it, label 5 must not count item 9
-    m2 = _model(cfg, cat, p)
+    m2 = model(cfg, cat, p)
     b2 = dict(b); b2["i"] = np.where(b["i"] == 5, 9, 5)
-    ranks2 = m2.label_ranks(_tuple(b2, True)).cpu().numpy()
+    ranks2 = m2.label_ranks(batch_tuple(b2, True)).cpu().numpy()
     assert np.array_equal(ranks2[:8], ranks[:8] + 1)
     assert np.array_equal(ranks2[8:], ranks[8:] - 1)
 
@@ -277,7 +260,7 @@ def test_errors():
     cfg = make_config(d=64)
     m = Model(cfg, np.zeros(cfg["item_count"], np.int32))
     b, _ = random_batch(cfg, B=4, Sn=2, seed=1)
-    bad = list(_tuple(b)); bad[3] = bad[3][:, :5]
+    bad = list(batch_tuple(b)); bad[3] = bad[3][:, :5]
     with pytest.raises(ValueError):
         m.train(None, tuple(bad), 1.0)
 
@@ -287,13 +270,13 @@ def test_lazy_l2_matches_dense_oracle(clip):
     """l2_mode='lazy' (scaled representation, only used rows touched) is the reference's dense-L2
     update up to fp32 rounding: several steps against the (dense) oracle, clip active and not."""
     cfg = make_config(U=300, I=200, C=9, d=128, max_gradient_norm=clip, regulation_rate=2e-2)  # big reg: decay visible
-    p = _p32(random_params(cfg, seed=51))
+    p = p32(random_params(cfg, seed=51))
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=24, Sn=1 + s % 3, seed=300 + s)[0] for s in range(5)]
-    m = _model(cfg, cat, p, l2_mode="lazy")
+    m = model(cfg, cat, p, l2_mode="lazy")
     q = dict(p)
     for b in batches:
-        l = m.train(None, _tuple(b), 0.9)
+        l = m.train(None, batch_tuple(b), 0.9)
         lo, q, info = orc.train_step(q, cat, b, 8, cfg["regulation_rate"], lr=0.9, clip=clip)
         assert abs(l - lo) < 2e-4 * max(1.0, abs(lo))
         assert abs(m.last_gnorm() - info["norm"]) < 3e-4 * info["norm"]
@@ -301,10 +284,10 @@ def test_lazy_l2_matches_dense_oracle(clip):
     assert P < (0.95 if clip > 1 else 1.0)  # the decay really lives in the scale
     # evaluation uses the scale on the fly
     tb, _ = random_batch(cfg, B=20, Sn=2, seed=99, test=True)
-    li, lj, ut, _ = m.forward(_tuple(tb, True), is_test=True, want_u_t=True)
+    li, lj, ut, _ = m.forward(batch_tuple(tb, True), is_test=True, want_u_t=True)
     ref = orc.forward(q, cat, tb, 8)
     assert np.abs(li.cpu().numpy() - ref["logits"]).max() < 3e-4
-    ranks = m.label_ranks(_tuple(tb, True)).cpu().numpy()
+    ranks = m.label_ranks(batch_tuple(tb, True)).cpu().numpy()
     rr = orc.label_ranks(orc.all_item_scores(q, cat, ref["u_t"]), tb["i"])
     assert np.abs(ranks - rr).max() <= 2
     got = m.get_params()  # folds the scale
@@ -314,20 +297,20 @@ def test_lazy_l2_matches_dense_oracle(clip):
         assert np.abs(g - q[k]).max() < 5e-4 * np.abs(q[k]).max() + 1e-6, k
     # training continues correctly after the fold
     b = batches[0]
-    l = m.train(None, _tuple(b), 0.9)
+    l = m.train(None, batch_tuple(b), 0.9)
     lo, q, _ = orc.train_step(q, cat, b, 8, cfg["regulation_rate"], lr=0.9, clip=clip)
     assert abs(l - lo) < 2e-4 * max(1.0, abs(lo))
 
 
 def test_lazy_is_deterministic_and_untouched_rows_are_not_written():
     cfg = make_config(U=400, I=300, C=7, d=64, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=61))
+    p = p32(random_params(cfg, seed=61))
     b, cat = random_batch(cfg, B=16, Sn=2, seed=62)
     outs = []
     for rep in range(2):
-        m = _model(cfg, cat, p, l2_mode="lazy")
+        m = model(cfg, cat, p, l2_mode="lazy")
         before = m.user_emb.clone()
-        m.train(None, _tuple(b), 1.0)
+        m.train(None, batch_tuple(b), 1.0)
         touched = np.zeros(cfg["user_count"], bool)
         touched[b["u"]] = True
         same = (m.user_emb == before).all(dim=1).cpu().numpy()
@@ -341,7 +324,7 @@ def test_long_sessions_and_short_window():
     """Sessions longer than one prefetch chunk (32 ids at d=128, 16 at d=64) and Ls < 10."""
     for d, Ls, Sn in ((128, 6, 40), (64, 4, 37), (128, 10, 70)):
         cfg = make_config(U=40, I=120, C=6, d=d, Ls=Ls)
-        p = _p32(random_params(cfg, seed=d + Sn))
+        p = p32(random_params(cfg, seed=d + Sn))
         b, cat = random_batch(cfg, B=19, Sn=Sn, seed=Sn)
         b["sl_new"][:3] = [Sn, Sn - 1, 33 if Sn > 33 else Sn]
         ar = np.arange(Sn)[None, :]
@@ -349,8 +332,8 @@ def test_long_sessions_and_short_window():
         b["hist_i_new"] = np.where(ar < b["sl_new"][:, None], rng.randint(0, 120, (19, Sn)), 0)
         loss, newp, info = orc.train_step(p, cat, b, 8, cfg["regulation_rate"], lr=0.5)
         for l2 in ("dense", "lazy"):
-            m = _model(cfg, cat, p, l2_mode=l2)
-            l = m.train(None, _tuple(b), 0.5)
+            m = model(cfg, cat, p, l2_mode=l2)
+            l = m.train(None, batch_tuple(b), 0.5)
             assert abs(l - loss) < 2e-4 * max(1.0, abs(loss)), (d, Ls, Sn, l2)
             got = m.get_params()
             for k in newp:
@@ -361,21 +344,21 @@ def test_long_sessions_and_short_window():
     from tlsan_amd._lib import TlsanError
     cfg = make_config(U=10, I=20, C=3, d=64)
     b, cat = random_batch(cfg, B=4, Sn=100, seed=1)
-    m = _model(cfg, cat)
+    m = model(cfg, cat)
     with pytest.raises(TlsanError):
-        m.train(None, _tuple(b), 1.0)
+        m.train(None, batch_tuple(b), 1.0)
 
 
 def test_graph_replay_equals_eager():
     cfg = make_config(U=200, I=150, C=9, d=128)
-    p = _p32(random_params(cfg, seed=71))
+    p = p32(random_params(cfg, seed=71))
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=64, Sn=3, seed=400 + s)[0] for s in range(3)]
     outs = []
     for mode in ("eager", "graph"):
-        m = _model(cfg, cat, p, l2_mode="lazy")
+        m = model(cfg, cat, p, l2_mode="lazy")
         if mode == "graph":
-            graphs = [m.capture_step(_tuple(b), 0.7) for b in batches]
+            graphs = [m.capture_step(batch_tuple(b), 0.7) for b in batches]
             # capture_step runs one warm step per batch: rebuild the same starting point
             m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
             for rep in range(2):
@@ -384,7 +367,7 @@ def test_graph_replay_equals_eager():
         else:
             for rep in range(2):
                 for b in batches:
-                    m.train_async(_tuple(b), 0.7)
+                    m.train_async(batch_tuple(b), 0.7)
         outs.append(m.get_params())
     for k in outs[0]:
         assert np.array_equal(outs[0][k], outs[1][k]), k
@@ -399,7 +382,7 @@ def test_full_size_batch_matches_oracle(C, l2_mode):
     cfg = synth.make_config("electronics", user_count=3000, item_count=2000, cate_count=C)
     icl = synth.item_cate_list(cfg)
     batch = synth.make_batches(cfg, 1, 4096, seed=5)[0]
-    m = _model(cfg, icl, l2_mode=l2_mode)
+    m = model(cfg, icl, l2_mode=l2_mode)
     p = {k: np.asarray(v, np.float64) for k, v in m.get_params().items()}
     b = orc.as_batch(batch)
     loss, newp, info = orc.train_step(p, icl, b, 8, cfg["regulation_rate"], lr=1.0)
@@ -474,22 +457,22 @@ def test_long_windows_streamed(d, Ls, Sn, B):
     (The larger batches: several workgroup passes, a last one that is not full, the samples ranked by window length and
     dealt out to the passes, each pass's windows walked as one list whose runs are merged through the LDS.)"""
     cfg = make_config(U=50, I=150, C=8, d=d, Ls=Ls, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=Ls + d))
+    p = p32(random_params(cfg, seed=Ls + d))
     b, cat = random_batch(cfg, B=B, Sn=Sn, seed=Ls)
     b["sl"][:4] = [Ls, 1, Ls - 1, min(Ls, 11)]
     ar = np.arange(Ls)[None, :]
     b["hist_i"] = np.where(ar < b["sl"][:, None], np.random.RandomState(2).randint(0, 150, (B, Ls)), 0)
     b["hist_t"] = np.where(ar < b["sl"][:, None], (1.0 / np.random.RandomState(3).randint(1, 13, (B, Ls))), 0).astype(np.float32)
     ref = orc.forward(p, cat, b, 8)
-    m0 = _model(cfg, cat, p)
+    m0 = model(cfg, cat, p)
     tb = dict(b); tb["j"] = b["i"][::-1].copy()
-    li, lj, ut, _ = m0.forward(_tuple(tb, True), is_test=True, want_u_t=True)
+    li, lj, ut, _ = m0.forward(batch_tuple(tb, True), is_test=True, want_u_t=True)
     assert np.abs(li.cpu().numpy() - ref["logits"]).max() < LOGIT_TOL
     assert np.abs(ut.cpu().numpy() - ref["u_t"]).max() < LOGIT_TOL
     loss, newp, info = orc.train_step(p, cat, b, 8, cfg["regulation_rate"], lr=0.6)
     for l2 in ("dense", "lazy"):
-        m = _model(cfg, cat, p, l2_mode=l2)
-        l = m.train(None, _tuple(b), 0.6)
+        m = model(cfg, cat, p, l2_mode=l2)
+        l = m.train(None, batch_tuple(b), 0.6)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss)), l2
         assert abs(m.last_gnorm() - info["norm"]) < 3e-4 * info["norm"], l2
         got = m.get_params()
@@ -504,19 +487,19 @@ def test_bf16_tables_with_streamed_windows(d, Ls, Sn, B):
     """bf16 table storage with Ls > 10 (the Movies-TV configuration asks for both): forward and gradients equal the
     fp64 oracle evaluated on the stored (bf16-rounded) tables, and a training step runs and is reproducible."""
     cfg = make_config(U=50, I=150, C=8, d=d, Ls=Ls, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=Ls + d))
+    p = p32(random_params(cfg, seed=Ls + d))
     for k in BF16_TABLES:
-        p[k] = _bf16_round(p[k]).astype(np.float64)
+        p[k] = bf16_round(p[k]).astype(np.float64)
     b, cat = random_batch(cfg, B=B, Sn=Sn, seed=Ls)
     b["sl"][:4] = [Ls, 1, Ls - 1, min(Ls, 11)]
     ar = np.arange(Ls)[None, :]
     b["hist_i"] = np.where(ar < b["sl"][:, None], np.random.RandomState(2).randint(0, 150, (B, Ls)), 0)
     b["hist_t"] = np.where(ar < b["sl"][:, None], (1.0 / np.random.RandomState(3).randint(1, 13, (B, Ls))), 0).astype(np.float32)
-    m = _model(cfg, cat, p, l2_mode="lazy", table_dtype="bf16")
+    m = model(cfg, cat, p, l2_mode="lazy", table_dtype="bf16")
     ref = orc.forward(p, cat, b, 8)
-    li, _, _, _ = m.forward(_tuple(b), is_test=False)
+    li, _, _, _ = m.forward(batch_tuple(b), is_test=False)
     assert np.abs(li.cpu().numpy() - ref["logits"]).max() < LOGIT_TOL
-    g = m.grads(_tuple(b))
+    g = m.grads(batch_tuple(b))
     _, _, ref_g, _ = orc.backward(p, cat, b, 8, cfg["regulation_rate"])
     for k in ref_g:
         a, r = np.asarray(g["grads"][k], np.float64).reshape(ref_g[k].shape), ref_g[k]
@@ -524,8 +507,8 @@ def test_bf16_tables_with_streamed_windows(d, Ls, Sn, B):
     loss = orc.train_step(p, cat, b, 8, cfg["regulation_rate"], lr=0.6)[0]
     outs = []
     for rep in range(2):
-        mm = _model(cfg, cat, p, l2_mode="lazy", table_dtype="bf16")
-        l = mm.train(None, _tuple(b), 0.6)
+        mm = model(cfg, cat, p, l2_mode="lazy", table_dtype="bf16")
+        l = mm.train(None, batch_tuple(b), 0.6)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss))
         outs.append(mm.get_params())
     for k in outs[0]:
@@ -536,17 +519,16 @@ _BF16_CLIP_DUMP = r'''
 import sys
 import numpy as np
 sys.path.insert(0, %r)
-from tests.helpers import make_config, random_batch, random_params
-from tests.test_gpu_parity import BF16_TABLES, _bf16_round, _p32, _tuple
+from tests.helpers import BF16_TABLES, batch_tuple, bf16_round, make_config, p32, random_batch, random_params
 from tlsan_amd.model import Model
 cfg = make_config(U=40, I=60, C=9, d=128, max_gradient_norm=0.02, regulation_rate=1e-3)
-p = _p32(random_params(cfg, seed=41))
+p = p32(random_params(cfg, seed=41))
 for k in BF16_TABLES:
-    p[k] = _bf16_round(p[k]).astype(np.float64)
+    p[k] = bf16_round(p[k]).astype(np.float64)
 b, cat = random_batch(cfg, B=48, Sn=4, seed=42)
 m = Model(cfg, cat, l2_mode="lazy", table_dtype="bf16")
 m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-loss = m.train(None, _tuple(b), 0.7)
+loss = m.train(None, batch_tuple(b), 0.7)
 np.savez(sys.argv[1], loss=loss, gnorm=m.last_gnorm(), **m.get_params())
 '''
 
@@ -561,9 +543,9 @@ def test_bf16_tables_clipped_step_in_the_one_pass_form(tmp_path):
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cfg = make_config(U=40, I=60, C=9, d=128, max_gradient_norm=0.02, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=41))
+    p = p32(random_params(cfg, seed=41))
     for k in BF16_TABLES:
-        p[k] = _bf16_round(p[k]).astype(np.float64)
+        p[k] = bf16_round(p[k]).astype(np.float64)
     b, cat = random_batch(cfg, B=48, Sn=4, seed=42)
     loss, newp, info = orc.train_step(p, cat, b, 8, cfg["regulation_rate"], lr=0.7, clip=0.02)
     _, spec, _ = orc.train_step(p, cat, b, 8, cfg["regulation_rate"], lr=0.7, clip=1e30)      # what coefficient 1 writes first
@@ -625,12 +607,12 @@ def test_prefetched_index_equals_inline(case):
     prefetching call plans from the dims and the batch alone and the step reads one or two steps later."""
     shape, kw, B0 = _PREFETCH_CASES[case]
     cfg = make_config(**dict(dict(U=60, I=80, C=9, regulation_rate=1e-3), **shape))
-    p = _p32(random_params(cfg, seed=31))
+    p = p32(random_params(cfg, seed=31))
     _, cat = random_batch(cfg, B=8, Sn=2, seed=0)
-    batches = [_tuple(random_batch(cfg, B=B0 + 7 * (s % 3), Sn=1 + s % 4, seed=300 + s)[0]) for s in range(7)]
+    batches = [batch_tuple(random_batch(cfg, B=B0 + 7 * (s % 3), Sn=1 + s % 4, seed=300 + s)[0]) for s in range(7)]
     runs = []
     for prefetch in (0, 1, 2, 3):     # none / one step ahead / two steps ahead / two ahead, announced irregularly
-        m = _model(cfg, cat, p, **kw)
+        m = model(cfg, cat, p, **kw)
         dbs = [m.device_batch(b) for b in batches]
         for s, db in enumerate(dbs):
             nxt = dbs[s + 1] if (prefetch and s + 1 < len(dbs)) else None
@@ -641,7 +623,7 @@ def test_prefetched_index_equals_inline(case):
         for k in runs[0]:
             assert np.array_equal(runs[0][k], r[k]), k
     # announcing a batch and then training another one is an error (its uses are already counted)
-    m = _model(cfg, cat, p, **kw)
+    m = model(cfg, cat, p, **kw)
     dbs = [m.device_batch(b) for b in batches[:3]]
     m.train_async(dbs[0], 0.6, next_batch=dbs[1])
     with pytest.raises(RuntimeError):
@@ -667,7 +649,7 @@ def test_full_scale_properties():
     batches = synth.make_batches(cfg, 3, 4096, seed=77)
     runs = {}
     for mode in ("lazy", "lazy", "dense"):
-        m = _model(cfg, icl, l2_mode=mode)
+        m = model(cfg, icl, l2_mode=mode)
         p0 = m.get_params()
         before_user = m.user_emb.clone()
         losses, norms = [], []
@@ -693,7 +675,7 @@ def test_full_scale_properties():
         assert np.abs(a - d_).max() <= 2e-6 * np.abs(d_).max() + 1e-9, k
     # checksum of the step: item_b moves by -step * (sum of the per-use bias gradients) and its
     # total change is -step * sum_b dl_b, where sum_b dl_b = mean(sigmoid(logit) - y)
-    m = _model(cfg, icl, l2_mode="lazy")
+    m = model(cfg, icl, l2_mode="lazy")
     b = batches[0]
     db = m.device_batch(b)
     li, _, _, _ = m.forward(b, is_test=False)
@@ -726,7 +708,7 @@ def test_full_scale_bf16(matrix_dtype):
     reg = cfg["regulation_rate"]
     runs = {}
     for mode in ("lazy", "lazy", "dense"):
-        m = _model(cfg, icl, l2_mode=mode, table_dtype="bf16", matrix_dtype=matrix_dtype)
+        m = model(cfg, icl, l2_mode=mode, table_dtype="bf16", matrix_dtype=matrix_dtype)
         assert m.item_emb.dtype == torch.bfloat16
         before_user = m.user_emb.clone()
         losses = [m.train(None, b, 1.0) for b in batches[:3]]
@@ -755,8 +737,8 @@ def test_full_scale_bf16(matrix_dtype):
     assert runs["lazy"]["losses"] == runs["lazy2"]["losses"]
     assert np.allclose(runs["lazy"]["losses"][:3], runs["dense"]["losses"], rtol=2e-3, atol=0)
     # (the lazy run took one step more than the dense one above: compare fresh runs of three steps each)
-    pl = _model(cfg, icl, l2_mode="lazy", table_dtype="bf16", matrix_dtype=matrix_dtype)
-    pd = _model(cfg, icl, l2_mode="dense", table_dtype="bf16", matrix_dtype=matrix_dtype)
+    pl = model(cfg, icl, l2_mode="lazy", table_dtype="bf16", matrix_dtype=matrix_dtype)
+    pd = model(cfg, icl, l2_mode="dense", table_dtype="bf16", matrix_dtype=matrix_dtype)
     for b in batches[:3]:
         pl.train_async(b, 1.0)
         pd.train_async(b, 1.0)
@@ -779,17 +761,17 @@ def test_periodic_scale_fold_in_long_lazy_runs():
     """lazy L2 folds the table scale into the tables on a fixed schedule (Model.renorm_every) so that
     P never underflows; folding must not change what is trained."""
     cfg = make_config(U=40, I=60, C=9, d=64, regulation_rate=2e-2)
-    p = _p32(random_params(cfg, seed=71))
+    p = p32(random_params(cfg, seed=71))
     _, cat = random_batch(cfg, B=8, Sn=2, seed=0)
     batches = [random_batch(cfg, B=30, Sn=3, seed=700 + s)[0] for s in range(7)]
     q = dict(p)
     for b in batches:
         _, q, _ = orc.train_step(q, cat, b, 8, cfg["regulation_rate"], lr=1.0)
     for every in (0, 3):
-        m = _model(cfg, cat, p, l2_mode="lazy")
+        m = model(cfg, cat, p, l2_mode="lazy")
         m.renorm_every = every
         for b in batches:
-            m.train_async(_tuple(b), 1.0)
+            m.train_async(batch_tuple(b), 1.0)
         if every:
             assert m.table_scale() > 0.97     # folded at step 6, one step since
         else:
@@ -798,15 +780,6 @@ def test_periodic_scale_fold_in_long_lazy_runs():
         for k in q:
             g = np.asarray(got[k], np.float64).reshape(q[k].shape)
             assert np.abs(g - q[k]).max() < 5e-4 * np.abs(q[k]).max() + 1e-6, (every, k)
-
-
-def _bf16_round(a):
-    """round-to-nearest-even to bfloat16, back to float32 (what Model.set_params stores)"""
-    import torch
-    return torch.as_tensor(np.asarray(a, np.float32)).to(torch.bfloat16).float().numpy()
-
-
-BF16_TABLES = ("item_emb", "user_emb", "cate_emb")
 
 
 @pytest.mark.parametrize("l2_mode", ["dense", "lazy"])
@@ -820,20 +793,20 @@ def test_bf16_tables(l2_mode):
       * the L2 / clip-norm bookkeeping follows the STORED values (loss of the next step matches the
         oracle evaluated on the stored parameters)."""
     cfg = make_config(U=60, I=90, C=9, d=128, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=81))
+    p = p32(random_params(cfg, seed=81))
     for k in BF16_TABLES:
-        p[k] = _bf16_round(p[k]).astype(np.float64)
+        p[k] = bf16_round(p[k]).astype(np.float64)
     b, cat = random_batch(cfg, B=64, Sn=4, seed=82)
     b2, _ = random_batch(cfg, B=64, Sn=3, seed=83)
-    m = _model(cfg, cat, p, l2_mode=l2_mode, table_dtype="bf16")
+    m = model(cfg, cat, p, l2_mode=l2_mode, table_dtype="bf16")
     got0 = m.get_params()
     for k in p:
         assert np.array_equal(np.asarray(got0[k], np.float64).reshape(p[k].shape), p[k]), k   # stored exactly
     # forward + gradients on the stored parameters
     out = orc.forward(p, cat, b, 8)
-    li, _, _, _ = m.forward(_tuple(b), is_test=False)
+    li, _, _, _ = m.forward(batch_tuple(b), is_test=False)
     assert np.abs(li.cpu().numpy() - out["logits"]).max() < 1e-4
-    g = m.grads(_tuple(b))
+    g = m.grads(batch_tuple(b))
     _, _, ref_g, _ = orc.backward(p, cat, b, 8, cfg["regulation_rate"])
     for k in ref_g:
         a, r = np.asarray(g["grads"][k], np.float64).reshape(ref_g[k].shape), ref_g[k]
@@ -842,14 +815,14 @@ def test_bf16_tables(l2_mode):
     loss, q, info = orc.train_step(p, cat, b, 8, cfg["regulation_rate"], lr=0.7)
     runs = []
     for rep in range(2):
-        mm = _model(cfg, cat, p, l2_mode=l2_mode, table_dtype="bf16")
-        l = mm.train(None, _tuple(b), 0.7)
+        mm = model(cfg, cat, p, l2_mode=l2_mode, table_dtype="bf16")
+        l = mm.train(None, batch_tuple(b), 0.7)
         assert abs(l - loss) < 1e-4 * max(1.0, abs(loss))
-        l2 = mm.train(None, _tuple(b2), 0.7)           # second step: its loss carries the L2 term of the STORED tables
+        l2 = mm.train(None, batch_tuple(b2), 0.7)           # second step: its loss carries the L2 term of the STORED tables
         runs.append((mm.get_params(), l2))
         if rep == 0:
-            m1 = _model(cfg, cat, p, l2_mode=l2_mode, table_dtype="bf16")
-            m1.train(None, _tuple(b), 0.7)
+            m1 = model(cfg, cat, p, l2_mode=l2_mode, table_dtype="bf16")
+            m1.train(None, batch_tuple(b), 0.7)
             stored = {k: np.asarray(v, np.float64) for k, v in m1.get_params().items()}
             for k in q:
                 a, r = stored[k].reshape(q[k].shape), q[k]
@@ -858,7 +831,7 @@ def test_bf16_tables(l2_mode):
                     # (lazy: reading the parameters folds the table scale in, a second stochastic rounding)
                     nround = 2 if l2_mode == "lazy" else 1
                     assert (np.abs(a - r) <= ulp * (nround + 1e-3) + 1e-12).all(), k
-                    assert np.array_equal(a.astype(np.float32), _bf16_round(a)), k        # representable in bf16
+                    assert np.array_equal(a.astype(np.float32), bf16_round(a)), k        # representable in bf16
                     bias = ((a - r) / ulp).mean()
                     assert abs(bias) < 0.06, (k, bias)                                    # unbiased: E[stored] = exact
                 else:
@@ -882,18 +855,18 @@ def test_bf16_matrix_products(d, table_dtype, Ls):
     tolerance is part of the interface; the arithmetic is still deterministic (bitwise equal on a second run),
     and training at the reference's protocol reaches the same AUC (scripts/readme_band.py --matrix_dtype bf16)."""
     cfg = make_config(U=300, I=400, C=17, d=d, Ls=Ls, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=7))
+    p = p32(random_params(cfg, seed=7))
     if table_dtype == "bf16":
         for k in BF16_TABLES:
-            p[k] = _bf16_round(p[k]).astype(np.float64)
+            p[k] = bf16_round(p[k]).astype(np.float64)
     b, cat = random_batch(cfg, B=96, Sn=4, seed=8)
     ref = orc.forward(p, cat, b, 8)
     loss, _, ref_g, _ = orc.backward(p, cat, b, 8, cfg["regulation_rate"])
     scale = np.abs(ref["logits"]).max()          # (Ls > 10: the streamed-window kernels)
     outs = []
     for rep in range(2):
-        m = _model(cfg, cat, p, table_dtype=table_dtype, matrix_dtype="bf16")
-        g = m.grads(_tuple(b))
+        m = model(cfg, cat, p, table_dtype=table_dtype, matrix_dtype="bf16")
+        g = m.grads(batch_tuple(b))
         outs.append(g)
     g = outs[0]
     err = np.abs(g["logits"] - ref["logits"]).max()
@@ -907,8 +880,8 @@ def test_bf16_matrix_products(d, table_dtype, Ls):
     for k in outs[0]["grads"]:
         assert np.array_equal(outs[0]["grads"][k], outs[1]["grads"][k]), k
     # a train step: lazy == dense to fp32 rounding in this mode too
-    ms = [_model(cfg, cat, p, l2_mode=l2, table_dtype=table_dtype, matrix_dtype="bf16") for l2 in ("dense", "lazy")]
-    ls = [m.train(None, _tuple(b), 0.5) for m in ms]
+    ms = [model(cfg, cat, p, l2_mode=l2, table_dtype=table_dtype, matrix_dtype="bf16") for l2 in ("dense", "lazy")]
+    ls = [m.train(None, batch_tuple(b), 0.5) for m in ms]
     assert abs(ls[0] - ls[1]) < 1e-5 * max(1.0, abs(ls[0]))
     pa, pb = ms[0].get_params(), ms[1].get_params()
     for k in pa:
@@ -924,16 +897,16 @@ def test_dropout_with_bf16_matrix_products(d, table_dtype, rate, Ls):
     to the bf16 tolerances of test_bf16_matrix_products (loss 5e-4, parameter changes to 15 % of their norm), far
     inside the distance to the step WITHOUT the pattern; a second model repeats it bitwise."""
     cfg = make_config(U=60, I=80, C=9, d=d, regulation_rate=1e-3, dropout=rate, Ls=Ls)
-    p = _p32(random_params(cfg, seed=97))
+    p = p32(random_params(cfg, seed=97))
     if table_dtype == "bf16":
         for k in BF16_TABLES:
-            p[k] = _bf16_round(p[k]).astype(np.float64)
+            p[k] = bf16_round(p[k]).astype(np.float64)
     b, cat = random_batch(cfg, B=45, Sn=3, seed=98)
     outs = []
     for rep in range(2):
-        m = _model(cfg, cat, p, table_dtype=table_dtype, matrix_dtype="bf16")
+        m = model(cfg, cat, p, table_dtype=table_dtype, matrix_dtype="bf16")
         seed = m.dropout_seed()
-        l = m.train(None, _tuple(b), 0.6)
+        l = m.train(None, batch_tuple(b), 0.6)
         outs.append((l, m.get_params()))
     loss, newq, info = orc.train_step(p, cat, b, 8, cfg["regulation_rate"], lr=0.6, dropout=(rate, seed))
     plain = orc.loss_fn(p, cat, b, 8, cfg["regulation_rate"])
@@ -958,17 +931,17 @@ def test_other_optimizers_track_oracle(optimizer, lr, tmp_path):
     The step counter / accumulators survive save + restore."""
     cfg = make_config(U=30, I=45, C=7, d=64, regulation_rate=1e-3, max_gradient_norm=0.05, optimizer=optimizer,
                       model_dir=str(tmp_path))
-    p = _p32(random_params(cfg, seed=61))
+    p = p32(random_params(cfg, seed=61))
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=36, Sn=1 + s % 3, seed=600 + s)[0] for s in range(5)]
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     q, st = dict(p), orc.init_opt_state(p, optimizer)
     for n, b in enumerate(batches):
         prev = q
         loss, q, info = orc.train_step(q, cat, b, 8, cfg["regulation_rate"], lr=lr, clip=0.05, optimizer=optimizer,
                                        opt_state=st)
         assert info["coef"] < 1.0                 # the clip is active
-        l = m.train(None, _tuple(b), lr)
+        l = m.train(None, batch_tuple(b), lr)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss))
         got = m.get_params()
         for k in q:
@@ -980,7 +953,7 @@ def test_other_optimizers_track_oracle(optimizer, lr, tmp_path):
             assert np.abs(np.asarray(got[k], np.float64).reshape(q[k].shape) - q[k]).max() < 2e-3 * step * (n + 1) + 1e-7, (n, k)
         if n == 2:                                # checkpoint round trip in the middle of the run
             path = m.save()
-            m = _model(cfg, cat, None)
+            m = model(cfg, cat, None)
             m.restore(None, path)
     s1, s2 = m.get_slots()
     for k in q:
@@ -990,7 +963,7 @@ def test_other_optimizers_track_oracle(optimizer, lr, tmp_path):
             assert np.abs(np.asarray(got, np.float64).reshape(ref.shape) - ref).max() < 2e-3 * np.abs(ref).max() + 1e-9, k
     assert np.array_equal(m.dense_KT.cpu().numpy(), m.get_params()["dense_K"].T)
     with pytest.raises(NotImplementedError):
-        _model(cfg, cat, p, l2_mode="lazy")
+        model(cfg, cat, p, l2_mode="lazy")
 
 
 @pytest.mark.parametrize("l2_mode", ["lazy", "dense"])
@@ -999,14 +972,14 @@ def test_large_tables_take_the_two_level_scan(l2_mode):
     (k_scan_block_sums + k_index_scan) instead of the single launch; the step must not notice.
     Two steps on 300k users / 150k items against the oracle."""
     cfg = make_config(U=300_000, I=150_000, C=40, d=64, regulation_rate=1e-3, max_gradient_norm=5.0)
-    p = _p32(random_params(cfg, seed=81))
+    p = p32(random_params(cfg, seed=81))
     _, cat = random_batch(cfg, B=4, Sn=2, seed=0)
     batches = [random_batch(cfg, B=48, Sn=2 + s, seed=810 + s)[0] for s in range(2)]
-    m = _model(cfg, cat, p, l2_mode=l2_mode)
+    m = model(cfg, cat, p, l2_mode=l2_mode)
     q = dict(p)
     for b in batches:
         loss, newq, info = orc.train_step(q, cat, b, 8, cfg["regulation_rate"], lr=0.9)
-        l = m.train(None, _tuple(b), 0.9)
+        l = m.train(None, batch_tuple(b), 0.9)
         assert abs(l - loss) < 1e-4 * max(1.0, abs(loss))
         assert abs(m.last_gnorm() - info["norm"]) < 2e-4 * info["norm"]
         q = newq
@@ -1023,17 +996,17 @@ def test_dropout_training_matches_oracle(d, rate, Ls):
     both attention blocks, train steps only.  With the same keep / drop pattern (a hash of seed, sample,
     block, position, map, channel) three train steps follow the oracle; evaluation does not drop."""
     cfg = make_config(U=40, I=60, C=9, d=d, regulation_rate=1e-3, dropout=rate, Ls=Ls)   # (Ls > 10: streamed window)
-    p = _p32(random_params(cfg, seed=91))
+    p = p32(random_params(cfg, seed=91))
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=37, Sn=2 + s, seed=910 + s)[0] for s in range(3)]
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     q = dict(p)
     for n, b in enumerate(batches):
         seed = m.dropout_seed()
         loss, newq, info = orc.train_step(q, cat, b, 8, cfg["regulation_rate"], lr=0.6, dropout=(rate, seed))
         plain = orc.loss_fn(q, cat, b, 8, cfg["regulation_rate"])
         assert abs(plain - loss) > 1e-5                        # the pattern matters
-        l = m.train(None, _tuple(b), 0.6)
+        l = m.train(None, batch_tuple(b), 0.6)
         assert abs(l - loss) < 1e-4 * max(1.0, abs(loss)), (n, l, loss, plain)
         assert abs(m.last_gnorm() - info["norm"]) < 2e-4 * info["norm"]
         got = m.get_params()
@@ -1043,7 +1016,7 @@ def test_dropout_training_matches_oracle(d, rate, Ls):
             assert np.abs(du - dr).max() < 3e-4 * (np.abs(dr).max() + 1e-9) + 3e-7, (n, k)
         q = {k: np.asarray(got[k], np.float64).reshape(newq[k].shape) for k in newq}   # follow the device
     # forward / evaluation: no dropout
-    li, _, _, _ = m.forward(_tuple(batches[0]), is_test=False)
+    li, _, _, _ = m.forward(batch_tuple(batches[0]), is_test=False)
     ref = orc.forward(q, cat, batches[0], 8)["logits"]
     assert np.abs(li.cpu().numpy() - ref).max() < LOGIT_TOL
 
@@ -1055,7 +1028,7 @@ def test_empty_histories(d, Ls):
     softmax is uniform over rows that are all zero -> the long summary is exactly 0 and nothing flows back
     into the window.  Mixed with ordinary samples, forward and one train step against the oracle."""
     cfg = make_config(U=30, I=50, C=7, d=d, Ls=Ls, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=95))
+    p = p32(random_params(cfg, seed=95))
     b, cat = random_batch(cfg, B=41, Sn=3, seed=96)
     b["sl"][::3] = 0
     if Ls > 10:
@@ -1064,11 +1037,11 @@ def test_empty_histories(d, Ls):
     b["hist_i"] = np.where(ar < b["sl"][:, None], b["hist_i"], 0)
     b["hist_t"] = np.where(ar < b["sl"][:, None], b["hist_t"], 0).astype(np.float32)
     ref = orc.forward(p, cat, b, 8)
-    m = _model(cfg, cat, p)
-    li, _, _, _ = m.forward(_tuple(b), is_test=False)
+    m = model(cfg, cat, p)
+    li, _, _, _ = m.forward(batch_tuple(b), is_test=False)
     assert np.abs(li.cpu().numpy() - ref["logits"]).max() < LOGIT_TOL
     loss, newp, info = orc.train_step(p, cat, b, 8, cfg["regulation_rate"], lr=0.5)
-    l = m.train(None, _tuple(b), 0.5)
+    l = m.train(None, batch_tuple(b), 0.5)
     assert abs(l - loss) < 1e-4 * max(1.0, abs(loss))
     got = m.get_params()
     for k in newp:
@@ -1087,7 +1060,7 @@ def test_one_hot_row_takes_every_use(l2_mode, C, clip):
     the one-pass form throughout, whose hot-row workgroup updates the row itself -- with coefficient 1, and corrected by
     k_spec_commit when the step is clipped (clip 0.02)."""
     cfg = make_config(U=9, I=31, C=C, d=128, regulation_rate=1e-3, max_gradient_norm=clip)
-    p = _p32(random_params(cfg, seed=97))
+    p = p32(random_params(cfg, seed=97))
     b, cat = random_batch(cfg, B=256, Sn=2, seed=98, full=True)
     b["u"][:] = cfg["user_count"] - 1
     b["hist_i"][:] = 7
@@ -1098,8 +1071,8 @@ def test_one_hot_row_takes_every_use(l2_mode, C, clip):
     assert (info["coef"] < 1.0) == (clip < 1.0)
     outs = []
     for rep in range(2):
-        m = _model(cfg, cat, p, l2_mode=l2_mode)
-        l = m.train(None, _tuple(b), 0.5)
+        m = model(cfg, cat, p, l2_mode=l2_mode)
+        l = m.train(None, batch_tuple(b), 0.5)
         assert abs(l - loss) < 1e-4 * max(1.0, abs(loss))
         assert abs(m.last_gnorm() - info["norm"]) < 2e-4 * info["norm"]
         outs.append(m.get_params())
@@ -1258,16 +1231,16 @@ def test_unequal_embedding_widths(d, di, Ls):
     other test takes the two halves equal.  Forward logits and one train step (lazy and dense L2) against the oracle with
     the concatenated row split anywhere a 16-byte piece allows (rows wider than 64 floats take the wide row workgroups)."""
     cfg = make_config(U=60, I=80, C=9, d=d, Ls=Ls, di=di, regulation_rate=1e-3)
-    p = _p32(random_params(cfg, seed=d + di))
+    p = p32(random_params(cfg, seed=d + di))
     b, cat = random_batch(cfg, B=45, Sn=4, seed=di)
     ref = orc.forward(p, cat, b, 8)
     loss, newp, info = orc.train_step(p, cat, b, 8, cfg["regulation_rate"], lr=0.7)
     for l2 in ("lazy", "dense"):
-        m = _model(cfg, cat, p, l2_mode=l2)
-        li, _, ut, _ = m.forward(_tuple(b), is_test=False, want_u_t=True)
+        m = model(cfg, cat, p, l2_mode=l2)
+        li, _, ut, _ = m.forward(batch_tuple(b), is_test=False, want_u_t=True)
         assert np.abs(li.cpu().numpy() - ref["logits"]).max() < LOGIT_TOL, l2
         assert np.abs(ut.cpu().numpy() - ref["u_t"]).max() < LOGIT_TOL, l2
-        got_loss = m.train(None, _tuple(b), 0.7)
+        got_loss = m.train(None, batch_tuple(b), 0.7)
         assert abs(got_loss - loss) < 1e-4 * max(1.0, abs(loss)), l2
         assert abs(m.last_gnorm() - info["norm"]) < 2e-4 * info["norm"], l2
         got = m.get_params()
@@ -1319,7 +1292,7 @@ def test_shared_categories_in_the_one_pass_form(d, Ls, C, clip):
     and wider (d = 128 with a 90-entry window: two passes of the narrow form), categories of 100-250 items (shared by
     item) and of 62 (C = 8: shared by use position), bitwise reproducible."""
     cfg = make_config(U=300, I=500, C=C, d=d, Ls=Ls, regulation_rate=1e-3, max_gradient_norm=clip)
-    p = _p32(random_params(cfg, seed=131))
+    p = p32(random_params(cfg, seed=131))
     b, cat = random_batch(cfg, B=640, Sn=3, seed=132)
     for k in ("hist_i", "hist_i_new"):     # (some hot rows)
         b[k][::3] %= 5
@@ -1328,8 +1301,8 @@ def test_shared_categories_in_the_one_pass_form(d, Ls, C, clip):
     assert (info["coef"] < 1.0) == (clip < 1.0)
     outs = []
     for rep in range(2):
-        m = _model(cfg, cat, p, l2_mode="lazy")
-        l = m.train(None, _tuple(b), 0.5)
+        m = model(cfg, cat, p, l2_mode="lazy")
+        l = m.train(None, batch_tuple(b), 0.5)
         assert abs(l - loss) < 1e-4 * max(1.0, abs(loss))
         assert abs(m.last_gnorm() - info["norm"]) < 2e-4 * info["norm"]
         outs.append(m.get_params())
@@ -1371,17 +1344,17 @@ def test_lazy_sum_of_squares_tracks_the_tables(d, table_dtype):
     import torch
     clip = {64: 13.5, 128: 17.0}[d]     # (above the norm of the later steps, below that of the first: profiled with the oracle)
     cfg = make_config(U=3000, I=4000, C=40, d=d, regulation_rate=0.05, max_gradient_norm=clip)
-    p = _p32(random_params(cfg, seed=1301))
+    p = p32(random_params(cfg, seed=1301))
     if table_dtype == "bf16":
         for k in BF16_TABLES:
-            p[k] = _bf16_round(p[k]).astype(np.float64)
+            p[k] = bf16_round(p[k]).astype(np.float64)
     _, cat = random_batch(cfg, B=8, Sn=2, seed=1300)
     shapes = [(64, 1), (5, 3), (40, 5), (1, 2), (64, 4), (17, 1)]
-    batches = [_tuple(random_batch(cfg, B=B, Sn=Sn, seed=1310 + k)[0]) for k, (B, Sn) in enumerate(shapes)]
-    probe = _tuple(random_batch(cfg, B=9, Sn=2, seed=1320)[0])
+    batches = [batch_tuple(random_batch(cfg, B=B, Sn=Sn, seed=1310 + k)[0]) for k, (B, Sn) in enumerate(shapes)]
+    probe = batch_tuple(random_batch(cfg, B=9, Sn=2, seed=1320)[0])
     runs = []
     for every_step in (False, True):
-        m = _model(cfg, cat, p, l2_mode="lazy", table_dtype=table_dtype)
+        m = model(cfg, cat, p, l2_mode="lazy", table_dtype=table_dtype)
         m.renorm_every = 3
         losses, gnorms = [], []
         for b in batches:
@@ -1454,13 +1427,13 @@ def test_dropout_with_bf16_tables(d, Ls):
     at the stored (bf16-rounded) tables under the same keep / drop pattern, and a training step is reproducible."""
     rate = 0.3
     cfg = make_config(U=40, I=60, C=9, d=d, regulation_rate=1e-3, dropout=rate, Ls=Ls)
-    p = _p32(random_params(cfg, seed=95))
+    p = p32(random_params(cfg, seed=95))
     for k in BF16_TABLES:
-        p[k] = _bf16_round(p[k]).astype(np.float64)
+        p[k] = bf16_round(p[k]).astype(np.float64)
     b, cat = random_batch(cfg, B=37, Sn=3, seed=951)
-    m = _model(cfg, cat, p, l2_mode="lazy", table_dtype="bf16")
+    m = model(cfg, cat, p, l2_mode="lazy", table_dtype="bf16")
     seed = m.dropout_seed()
-    g = m.grads(_tuple(b))
+    g = m.grads(batch_tuple(b))
     loss, _, ref_g, _ = orc.backward(p, cat, b, 8, cfg["regulation_rate"], dropout=(rate, seed))
     plain = orc.loss_fn(p, cat, b, 8, cfg["regulation_rate"])
     assert abs(plain - loss) > 1e-5                        # the pattern matters
@@ -1470,8 +1443,8 @@ def test_dropout_with_bf16_tables(d, Ls):
         assert np.abs(a - r).max() < 3e-4 * np.abs(r).max() + 1e-6, k
     outs = []
     for rep in range(2):
-        mm = _model(cfg, cat, p, l2_mode="lazy", table_dtype="bf16")
-        mm.train(None, _tuple(b), 0.6)
+        mm = model(cfg, cat, p, l2_mode="lazy", table_dtype="bf16")
+        mm.train(None, batch_tuple(b), 0.6)
         outs.append(mm.get_params())
     for k in outs[0]:
         assert np.array_equal(outs[0][k], outs[1][k]), k
@@ -1484,11 +1457,11 @@ def test_attention_weights_match_oracle(d, Ls, B, Sn):
     [H*B, Ls, d/H] and [H*B, 1+Sn, d/H], row h*B + b -- windows in registers and streamed, sessions of every length
     including none, exactly 0 on masked positions."""
     cfg = make_config(U=50, I=80, C=8, d=d, Ls=Ls)
-    p = _p32(random_params(cfg, seed=d + Ls))
+    p = p32(random_params(cfg, seed=d + Ls))
     b, cat = random_batch(cfg, B=B, Sn=Sn, seed=Ls + B, test=True)
     b["sl"][:3] = [Ls, 1, max(1, Ls - 1)]
-    m = _model(cfg, cat, p)
-    li, lj, _, _ = m.forward(_tuple(b, test=True), is_test=True, want_att=True)
+    m = model(cfg, cat, p)
+    li, lj, _, _ = m.forward(batch_tuple(b, test=True), is_test=True, want_att=True)
     ref = orc.forward(p, cat, dict(b, y=np.zeros(B)), 8)
     assert np.abs(li.cpu().numpy() - ref["logits"]).max() < LOGIT_TOL
     H = 8
@@ -1509,16 +1482,16 @@ def test_other_optimizers_with_bf16_tables(optimizer, lr):
     the oracle's updated value (stochastic rounding on the write-back); the fp32-kept parameters match as usual; two runs
     leave the same bits."""
     cfg = make_config(U=30, I=45, C=7, d=64, regulation_rate=1e-3, max_gradient_norm=0.05, optimizer=optimizer)
-    p = _p32(random_params(cfg, seed=63))
+    p = p32(random_params(cfg, seed=63))
     for k in BF16_TABLES:
-        p[k] = _bf16_round(p[k]).astype(np.float64)
+        p[k] = bf16_round(p[k]).astype(np.float64)
     b, cat = random_batch(cfg, B=36, Sn=3, seed=631)
     st = orc.init_opt_state(p, optimizer)
     loss, q, info = orc.train_step(p, cat, b, 8, cfg["regulation_rate"], lr=lr, clip=0.05, optimizer=optimizer, opt_state=st)
     outs = []
     for rep in range(2):
-        m = _model(cfg, cat, p, table_dtype="bf16")
-        l = m.train(None, _tuple(b), lr)
+        m = model(cfg, cat, p, table_dtype="bf16")
+        l = m.train(None, batch_tuple(b), lr)
         assert abs(l - loss) < 2e-4 * max(1.0, abs(loss))
         outs.append((m.get_params(), m.get_slots()))
     got, (s1, s2) = outs[0]
@@ -1530,7 +1503,7 @@ def test_other_optimizers_with_bf16_tables(optimizer, lr):
         if k in BF16_TABLES:
             ulp = 2.0 ** (np.floor(np.log2(np.maximum(np.abs(r), 1e-30))) - 7)
             assert (np.abs(a - r) <= ulp * 1.001 + 2e-3 * np.abs(r - p[k]).max()).all(), k
-            assert np.array_equal(a.astype(np.float32), _bf16_round(a)), k
+            assert np.array_equal(a.astype(np.float32), bf16_round(a)), k
         else:
             step = np.abs(r - p[k]).max()
             assert np.abs(a - r).max() < 2e-3 * step + 1e-7, k
@@ -1569,7 +1542,7 @@ def test_nonfinite_inputs_give_nonfinite_loss(d, Ls, mm):
     time, and require a non-finite loss AND global norm from the train step, lazy and dense L2; after a step with a NaN
     norm the clip coefficient (clip_coef, tlsan_common.h) has handed it on to the parameters, as TF's clip_by_global_norm does."""
     cfg = make_config(U=30, I=50, C=7, d=d, Ls=Ls)
-    p0 = _p32(random_params(cfg, seed=5 * d + Ls))
+    p0 = p32(random_params(cfg, seed=5 * d + Ls))
     b, cat = random_batch(cfg, B=40, Sn=3, seed=d + 1)
     it, us = int(b["hist_i"][0, 0]), int(b["u"][3])          # (sl >= 1: position 0 is a valid window entry)
     for key, idx in (("item_emb", (it, 5)), ("user_emb", (us, 2)), ("fwa1_W2", (1, 2))):
@@ -1577,14 +1550,14 @@ def test_nonfinite_inputs_give_nonfinite_loss(d, Ls, mm):
             for l2 in ("lazy", "dense"):
                 p = {k: v.copy() for k, v in p0.items()}
                 p[key][idx] = bad
-                m = _model(cfg, cat, p, l2_mode=l2, matrix_dtype=mm)
-                loss = m.train(None, _tuple(b), 1.0)
+                m = model(cfg, cat, p, l2_mode=l2, matrix_dtype=mm)
+                loss = m.train(None, batch_tuple(b), 1.0)
                 assert not np.isfinite(loss), (key, bad, l2, loss)
                 assert not np.isfinite(m.last_gnorm()), (key, bad, l2, m.last_gnorm())
                 if np.isnan(m.last_gnorm()):   # (a NaN norm poisons every clipped gradient, as TF's min(1 / norm, 1 / clip) does;
                     got = m.get_params()       #  a +Inf norm clips to coefficient 0: finite gradients then move nothing)
                     assert not np.isfinite(got["dense_K"]).all(), (key, bad, l2)
     # ... and a healthy step stays finite (the check is not vacuous)
-    m = _model(cfg, cat, p0, l2_mode="lazy", matrix_dtype=mm)
-    assert np.isfinite(m.train(None, _tuple(b), 1.0)) and np.isfinite(m.last_gnorm())
+    m = model(cfg, cat, p0, l2_mode="lazy", matrix_dtype=mm)
+    assert np.isfinite(m.train(None, batch_tuple(b), 1.0)) and np.isfinite(m.last_gnorm())
 

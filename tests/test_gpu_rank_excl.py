@@ -3,14 +3,14 @@ ShardedModel .label_ranks(exclude=, return_eligible=), the SeenItems form of `ex
 against the fp64 oracle, exact where the candidate composition is not, list hygiene, sharded against single-GPU."""
 import ctypes as C
 import os
-import traceback
 
 import numpy as np
 import pytest
 
 from oracle import tlsan_oracle as orc
-from tests.helpers import make_config, random_batch, random_params
-from tests.test_gpu_candidates import _free_port, _history_sets, _host, _lazy_model, _model, _p32, _tuple
+from tests.helpers import (batch_tuple, history_sets, host, lazy_model, make_config, model, p32, random_batch,
+                           random_params)
+from tests.ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -23,14 +23,14 @@ def test_filtered_ranks_match_oracle(d, H):
     the fp64 scores, counting the items ahead of the label in tf.nn.top_k's order over the items that are not excluded."""
     I = 333
     cfg = make_config(U=60, I=I, C=13, d=d, H=H)
-    p = _p32(random_params(cfg, seed=31))
+    p = p32(random_params(cfg, seed=31))
     b, cat = random_batch(cfg, B=77, Sn=3, seed=32, test=True)
     b["hist_i"][:6, 0] = b["i"][:6]
-    m = _model(cfg, cat, p)
-    got, elig = (_host(t) for t in m.label_ranks(_tuple(b), exclude="history", return_eligible=True))
+    m = model(cfg, cat, p)
+    got, elig = (host(t) for t in m.label_ranks(batch_tuple(b, True), exclude="history", return_eligible=True))
     assert got.dtype == np.int32 and elig.dtype == np.int32
     scores = orc.all_item_scores(p, cat, orc.forward(p, cat, b, H)["u_t"])
-    hist = _history_sets(b)
+    hist = history_sets(b)
     ids = np.arange(I)
     want, want_elig, excl_ahead = np.zeros(77, np.int64), np.zeros(77, np.int64), np.zeros(77, np.int64)
     for r in range(77):
@@ -53,7 +53,7 @@ def test_filtered_ranks_match_oracle(d, H):
     assert (excl_ahead > 0).sum() >= 60
     assert sum(int(b["i"][r]) in hist[r] for r in range(77)) >= 6
     # the unfiltered call is untouched, and it is the filtered rank plus what was taken out
-    plain = _host(m.label_ranks(_tuple(b)))
+    plain = host(m.label_ranks(batch_tuple(b, True)))
     assert np.all(plain >= got) and np.array_equal((plain - got)[clear], excl_ahead[clear])
 
 
@@ -64,21 +64,21 @@ def test_exact_where_composition_is_not(form, table_dtype):
     composition from candidate scores is allowed 2 bad rows here: test_full_candidate_list_gives_label_rank); with
     empty lists it is label_ranks' result bit for bit."""
     I = 2000 if form == "dense" else 270000          # gather: I * d * 4 B > 256 MB
-    cfg, m = _lazy_model(I, table_dtype, 31)
+    cfg, m = lazy_model(I, table_dtype, 31)
     B = 64 if form == "dense" else 16
     b, _ = random_batch(cfg, B=B, Sn=3, seed=33, test=True)
-    plain = _host(m.label_ranks(_tuple(b)))
+    plain = host(m.label_ranks(batch_tuple(b, True)))
     assert plain.max() > 0
     everything = [np.arange(I)] * B                   # (the label is inside the list: it is never excluded)
-    r, e = (_host(t) for t in m.label_ranks(_tuple(b), exclude=everything, return_eligible=True))
+    r, e = (host(t) for t in m.label_ranks(batch_tuple(b, True), exclude=everything, return_eligible=True))
     assert np.array_equal(r, np.zeros(B, np.int32)), r
     assert np.array_equal(e, np.zeros(B, np.int32)), e
-    r, e = (_host(t) for t in m.label_ranks(_tuple(b), exclude=[[]] * B, return_eligible=True))
+    r, e = (host(t) for t in m.label_ranks(batch_tuple(b, True), exclude=[[]] * B, return_eligible=True))
     assert np.array_equal(r, plain) and np.all(e == I - 1)
     # half of the items: the two halves' counts add up to the whole
     lo, hi = [np.arange(I // 2)] * B, [np.arange(I // 2, I)] * B
-    rl, el = (_host(t) for t in m.label_ranks(_tuple(b), exclude=lo, return_eligible=True))
-    rh, eh = (_host(t) for t in m.label_ranks(_tuple(b), exclude=hi, return_eligible=True))
+    rl, el = (host(t) for t in m.label_ranks(batch_tuple(b, True), exclude=lo, return_eligible=True))
+    rh, eh = (host(t) for t in m.label_ranks(batch_tuple(b, True), exclude=hi, return_eligible=True))
     assert np.array_equal((plain - rl) + (plain - rh), plain) and np.all(el + eh == I - 1)
 
 
@@ -94,44 +94,44 @@ def _raw_excl(m, batch, off, ids):
     L.check(m.lib.tlsan_eval_ranks_excl(C.byref(m.dims), C.byref(m.cparams), ut.data_ptr(), db.i.data_ptr(), db.B,
                                         toff.data_ptr(), tids.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
                                         out[2].data_ptr(), ws.data_ptr(), ws.numel(), m._stream()), "tlsan_eval_ranks_excl")
-    return [_host(t) for t in out]
+    return [host(t) for t in out]
 
 
 def test_list_hygiene():
     I, B = 900, 53
     cfg = make_config(U=40, I=I, C=11, d=128)
-    p = _p32(random_params(cfg, seed=71))
+    p = p32(random_params(cfg, seed=71))
     b, cat = random_batch(cfg, B=B, Sn=3, seed=72, test=True)
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     rng = np.random.RandomState(73)
     clean = [np.sort(rng.choice(I, rng.randint(1, 200), replace=False)) for _ in range(B)]
     for r in (3, 17, 52):
         clean[r] = np.zeros(0, np.int64)                                  # rows with empty lists
     clean = [c[c != b["i"][r]] for r, c in enumerate(clean)]
-    want, want_e = (_host(t) for t in m.label_ranks(_tuple(b), exclude=clean, return_eligible=True))
+    want, want_e = (host(t) for t in m.label_ranks(batch_tuple(b, True), exclude=clean, return_eligible=True))
     assert np.array_equal(want_e, I - 1 - np.array([len(c) for c in clean]))
-    plain = _host(m.label_ranks(_tuple(b)))
+    plain = host(m.label_ranks(batch_tuple(b, True)))
     assert (plain - want).sum() > 100 and (want >= 0).all()
     # repeats, ids outside the table, the label, any order, python lists
     dirty = []
     for r, c in enumerate(clean):
         x = np.concatenate([c, c[:len(c) // 2], [-1, -5, I, I + 7, 10 ** 6], [b["i"][r]] * 2]) if r % 4 else c
         dirty.append(rng.permutation(x).tolist())
-    got, got_e = (_host(t) for t in m.label_ranks(_tuple(b), exclude=dirty, return_eligible=True))
+    got, got_e = (host(t) for t in m.label_ranks(batch_tuple(b, True), exclude=dirty, return_eligible=True))
     assert np.array_equal(got, want) and np.array_equal(got_e, want_e)
     # a row's result does not depend on the other rows' lists, nor on the rows it shares a launch with
     other = [clean[r] if r % 2 else np.arange(I) for r in range(B)]
-    got = _host(m.label_ranks(_tuple(b), exclude=other))
+    got = host(m.label_ranks(batch_tuple(b, True), exclude=other))
     assert np.array_equal(got[1::2], want[1::2]) and np.all(got[0::2] == 0)
     sub = {k: v[20:41] for k, v in b.items()}
-    assert np.array_equal(_host(m.label_ranks(_tuple(sub), exclude=clean[20:41])), want[20:41])
+    assert np.array_equal(host(m.label_ranks(batch_tuple(sub, True), exclude=clean[20:41])), want[20:41])
     # the C entry point itself on a CSR of uneven rows: ascending with repeats, ids past the table, the label
     rows = []
     for r, c in enumerate(clean):
         x = np.concatenate([c, c[::3], [b["i"][r]], [I, I + 1, 2 ** 31 - 1] if r % 3 else []]).astype(np.int64)
         rows.append(np.sort(x))
     off = np.concatenate([[0], np.cumsum([len(x) for x in rows])])
-    ranks, ahead, held = _raw_excl(m, _tuple(b), off, np.concatenate(rows))
+    ranks, ahead, held = _raw_excl(m, batch_tuple(b, True), off, np.concatenate(rows))
     assert np.array_equal(ranks, plain)
     assert np.array_equal(ranks - ahead, want) and np.array_equal(I - 1 - held, want_e)
     from tlsan_amd import _lib as L
@@ -161,35 +161,35 @@ def test_seen_form():
     from tlsan_amd.model import SeenItems
     I, B = 1200, 96
     cfg = make_config(U=50, I=I, C=11, d=64)
-    p = _p32(random_params(cfg, seed=81))
+    p = p32(random_params(cfg, seed=81))
     b, cat = random_batch(cfg, B=B, Sn=3, seed=82, test=True)
     b["u"][:3] = [47, 48, 49]                          # users without a training sample: the row's input alone
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     ts, seen = _seen_case(cfg, 83)
     holder = SeenItems.from_train_set(ts, cfg["user_count"], m.device)
     assert holder.max_len == max(len(s) for s in seen)
-    hist = _history_sets(b)
+    hist = history_sets(b)
     lists = [sorted(seen[int(b["u"][r])] | hist[r]) for r in range(B)]
     assert sum(not hist[r] <= seen[int(b["u"][r])] for r in range(B)) > B // 2      # the union matters
-    got, got_e = (_host(t) for t in m.label_ranks(_tuple(b), exclude=holder, return_eligible=True))
-    want, want_e = (_host(t) for t in m.label_ranks(_tuple(b), exclude=lists, return_eligible=True))
+    got, got_e = (host(t) for t in m.label_ranks(batch_tuple(b, True), exclude=holder, return_eligible=True))
+    want, want_e = (host(t) for t in m.label_ranks(batch_tuple(b, True), exclude=lists, return_eligible=True))
     assert np.array_equal(got, want) and np.array_equal(got_e, want_e)
     assert np.array_equal(got_e, [I - 1 - len(set(lists[r]) - {int(b["i"][r])}) for r in range(B)])
-    assert (got < _host(m.label_ranks(_tuple(b), exclude="history"))).sum() > 0
-    ids, _ = (_host(t) for t in m.recommend(_tuple(b), 50, exclude=holder))
+    assert (got < host(m.label_ranks(batch_tuple(b, True), exclude="history"))).sum() > 0
+    ids, _ = (host(t) for t in m.recommend(batch_tuple(b, True), 50, exclude=holder))
     for r in range(B):
         assert not set(ids[r].tolist()) & set(lists[r]), r
     # the other callers of exclusion_csr take the form as well
-    neg = _host(m.sample_negatives(_tuple(b), 80, exclude=holder))
+    neg = host(m.sample_negatives(batch_tuple(b, True), 80, exclude=holder))
     for r in range(B):
         assert not set(neg[r].tolist()) & (set(lists[r]) | {int(b["i"][r])}), r
-    assert np.array_equal(_host(m.sampled_ranks(_tuple(b), 80, exclude=holder)),
-                          _host(m.sampled_ranks(_tuple(b), 80, exclude=lists)))
+    assert np.array_equal(host(m.sampled_ranks(batch_tuple(b, True), 80, exclude=holder)),
+                          host(m.sampled_ranks(batch_tuple(b, True), 80, exclude=lists)))
 
 
 def _case():
     cfg = make_config(U=61, I=1501, C=9, d=128)
-    p = _p32(random_params(cfg, seed=91))
+    p = p32(random_params(cfg, seed=91))
     b, cat = random_batch(cfg, B=48, Sn=3, seed=92, test=True)
     b["hist_i"][:5, 0] = b["i"][:5]
     ts, seen = _seen_case(cfg, 93)
@@ -209,48 +209,39 @@ class _Recorder:
         return self.fn(hist, *a, **k)
 
 
-def _shard_worker(rank, world, port, ret, out_dir):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from tlsan_amd.dist import ShardedModel
-        from tlsan_amd.model import SeenItems
-        from tlsan_amd import train as T
-        cfg, p, b, cat, ts, lists = _case()
-        m = ShardedModel(cfg, cat, device="cuda:0")
-        m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-        holder = SeenItems.from_train_set(ts, cfg["user_count"], m.device)
-        n = len(b["u"]) // world
-        part = _tuple({k: v[rank * n:(rank + 1) * n] for k, v in b.items()})
-        res = {}
-        for name, ex in (("history", "history"), ("seen", holder), ("lists", lists[rank * n:(rank + 1) * n])):
-            r, e = m.label_ranks(part, exclude=ex, return_eligible=True)
-            res["r_" + name], res["e_" + name] = _host(r), _host(e)
-        res["plain"] = _host(m.label_ranks(part))
-        ids, _ = m.recommend(part, 20, exclude=holder)
-        res["rec_seen"] = _host(ids)
-        np.savez(os.path.join(out_dir, "rank%d.npz" % rank), **res)
-        # the drivers: no training, the full-ranking metrics of the same model over the clothing test set
-        ds = os.path.join(ROOT, "tests", "golden", "packed_clothing.npz")
-        argv = ["--dataset", ds, "--max_epochs", "0", "--quiet", "--eval_rank_exclude", "seen", "--eval_topk", "0",
-                "--model_dir", os.path.join(out_dir, "r%d" % rank), "--device_input", "0"]
-        rec = T.full_ranking_metrics = _Recorder(T.full_ranking_metrics)
-        res = T.train_sharded(T.parse(argv + ["--sharded", "1"]))
-        if rank == 0:
-            h_sharded = rec.hists[-1]
-            one = T.train(T.parse(argv))
-            h_one = rec.hists[-1]
-            assert set(res) - {"world"} == set(one) and set(res["full_ranking"]) == set(one["full_ranking"])
-            assert h_sharded.sum() == h_one.sum() == 2010
-            moved = int(np.abs(h_sharded - h_one).sum()) // 2
-            print("rows whose filtered rank differs between the drivers: %d" % moved)
-            assert moved <= 2, moved
-        ret[rank] = "ok"
-    except Exception:
-        ret[rank] = "FAIL: " + traceback.format_exc()
-    finally:
-        dist.destroy_process_group()
+def _shard_worker(rank, world, out_dir):
+    from tlsan_amd.dist import ShardedModel
+    from tlsan_amd.model import SeenItems
+    from tlsan_amd import train as T
+    cfg, p, b, cat, ts, lists = _case()
+    m = ShardedModel(cfg, cat, device="cuda:0")
+    m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
+    holder = SeenItems.from_train_set(ts, cfg["user_count"], m.device)
+    n = len(b["u"]) // world
+    part = batch_tuple({k: v[rank * n:(rank + 1) * n] for k, v in b.items()}, True)
+    res = {}
+    for name, ex in (("history", "history"), ("seen", holder), ("lists", lists[rank * n:(rank + 1) * n])):
+        r, e = m.label_ranks(part, exclude=ex, return_eligible=True)
+        res["r_" + name], res["e_" + name] = host(r), host(e)
+    res["plain"] = host(m.label_ranks(part))
+    ids, _ = m.recommend(part, 20, exclude=holder)
+    res["rec_seen"] = host(ids)
+    np.savez(os.path.join(out_dir, "rank%d.npz" % rank), **res)
+    # the drivers: no training, the full-ranking metrics of the same model over the clothing test set
+    ds = os.path.join(ROOT, "tests", "golden", "packed_clothing.npz")
+    argv = ["--dataset", ds, "--max_epochs", "0", "--quiet", "--eval_rank_exclude", "seen", "--eval_topk", "0",
+            "--model_dir", os.path.join(out_dir, "r%d" % rank), "--device_input", "0"]
+    rec = T.full_ranking_metrics = _Recorder(T.full_ranking_metrics)
+    res = T.train_sharded(T.parse(argv + ["--sharded", "1"]))
+    if rank == 0:
+        h_sharded = rec.hists[-1]
+        one = T.train(T.parse(argv))
+        h_one = rec.hists[-1]
+        assert set(res) - {"world"} == set(one) and set(res["full_ranking"]) == set(one["full_ranking"])
+        assert h_sharded.sum() == h_one.sum() == 2010
+        moved = int(np.abs(h_sharded - h_one).sum()) // 2
+        print("rows whose filtered rank differs between the drivers: %d" % moved)
+        assert moved <= 2, moved
 
 
 def test_sharded_filtered_ranks_match_model(tmp_path):
@@ -258,28 +249,24 @@ def test_sharded_filtered_ranks_match_model(tmp_path):
     filtered ranks and the eligible counts are equal as integers; the two DRIVERS launch different batch sizes (the
     forward's u_t can differ in its last bits with the launch's batch size), so their rank histograms are
     compared with the 2-row allowance the tree's tests give near-ties."""
-    import torch.multiprocessing as mp
     from tlsan_amd.model import SeenItems
     world = 2
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_shard_worker, args=(world, _free_port(), ret, str(tmp_path)), nprocs=world, join=True)
-    assert all(v == "ok" for v in dict(ret).values()) and len(ret) == world, dict(ret)
+    run_ranks(_shard_worker, world, str(tmp_path))
     cfg, p, b, cat, ts, lists = _case()
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     holder = SeenItems.from_train_set(ts, cfg["user_count"], m.device)
     got = [np.load(str(tmp_path / ("rank%d.npz" % r))) for r in range(world)]
     cat_ = lambda k: np.concatenate([g[k] for g in got])
     n = len(b["u"]) // world
-    parts = [_tuple({k: v[r * n:(r + 1) * n] for k, v in b.items()}) for r in range(world)]
+    parts = [batch_tuple({k: v[r * n:(r + 1) * n] for k, v in b.items()}, True) for r in range(world)]
     for name, ex in (("history", lambda r: "history"), ("seen", lambda r: holder), ("lists", lambda r: lists[r * n:(r + 1) * n])):
         want = [m.label_ranks(parts[r], exclude=ex(r), return_eligible=True) for r in range(world)]
-        assert np.array_equal(cat_("r_" + name), np.concatenate([_host(w[0]) for w in want])), name
-        assert np.array_equal(cat_("e_" + name), np.concatenate([_host(w[1]) for w in want])), name
+        assert np.array_equal(cat_("r_" + name), np.concatenate([host(w[0]) for w in want])), name
+        assert np.array_equal(cat_("e_" + name), np.concatenate([host(w[1]) for w in want])), name
         assert cat_("r_" + name).dtype == np.int32 and cat_("r_" + name).min() >= 0
-    assert np.array_equal(cat_("plain"), np.concatenate([_host(m.label_ranks(parts[r])) for r in range(world)]))
+    assert np.array_equal(cat_("plain"), np.concatenate([host(m.label_ranks(parts[r])) for r in range(world)]))
     assert (cat_("plain") - cat_("r_seen")).sum() > 0
-    rec = np.concatenate([_host(m.recommend(parts[r], 20, exclude=holder)[0]) for r in range(world)])
+    rec = np.concatenate([host(m.recommend(parts[r], 20, exclude=holder)[0]) for r in range(world)])
     assert np.array_equal(cat_("rec_seen"), rec)
 
 

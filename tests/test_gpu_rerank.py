@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from tests import rerank_ref as ref
-from tests.helpers import make_config, random_batch, random_params
+from tests.helpers import batch_tuple, bits, host, make_config, random_batch, random_params
 
 pytestmark = pytest.mark.gpu
 
@@ -22,10 +22,6 @@ B = 37
 SPECIAL = (5, 6, 7, 8, 9)       # tail of -1 / -inf; all scores equal; two identical vectors; a zero vector; a NaN score
 CASES = [(64, 16, 16, 0, 0.5), (64, 64, 20, 2, 0.3), (128, 200, 100, 3, 0.5), (256, 256, 256, 0, 0.7),
          (128, 256, 10, 1, 1.0), (64, 40, 40, 1, 0.0)]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.int32)
 
 
 def make_pools(d, N, seed, rows=B):
@@ -77,7 +73,7 @@ def check_rows(pool, ids, sc, K, m, theta, d):
         worst = max([worst] + regret.tolist())
         assert np.all(regret <= ref.tau(d)), (r, float(regret.max()), ref.tau(d))
         assert len(picks) == K or not more, (r, len(picks))          # a list ends early only when nothing is eligible
-        assert np.array_equal(_bits(sc[r, :len(picks)]), _bits(row[1][picks])), r
+        assert np.array_equal(bits(sc[r, :len(picks)]), bits(row[1][picks])), r
         assert np.all(sc[r, len(picks):] == -np.inf), r
         if len(picks) < K:
             short.append(r)
@@ -102,15 +98,15 @@ def test_rerank_against_the_reference(d, N, K, m, theta):
     short = check_rows(pool, ids, sc, K, m, theta, d)
     if theta == 0.0:                                                 # integer logic only: the reference's ids
         want_ids, want_sc = reference_lists(pool, K, m, theta)
-        assert np.array_equal(ids, want_ids) and np.array_equal(_bits(sc), _bits(want_sc))
+        assert np.array_equal(ids, want_ids) and np.array_equal(bits(sc), bits(want_sc))
     if m > 0 and 12 * m < K:                                         # the cap ends every row short
         assert len(short) == B
     assert 5 in short or K <= N - max(1, N // 4)                     # the row with the -1 tail
     # bits: the same call again, and the special rows as a batch of their own
     ids2, sc2 = run(pool, K, m, theta)
-    assert np.array_equal(ids, ids2) and np.array_equal(_bits(sc), _bits(sc2))
+    assert np.array_equal(ids, ids2) and np.array_equal(bits(sc), bits(sc2))
     ids5, sc5 = run(pool, K, m, theta, rows=SPECIAL)
-    assert np.array_equal(ids5, ids[list(SPECIAL)]) and np.array_equal(_bits(sc5), _bits(sc[list(SPECIAL)]))
+    assert np.array_equal(ids5, ids[list(SPECIAL)]) and np.array_equal(bits(sc5), bits(sc[list(SPECIAL)]))
 
 
 @pytest.mark.parametrize("d,N,K", [(64, 16, 16), (128, 200, 100), (256, 256, 256), (64, 64, 7)])
@@ -123,20 +119,12 @@ def test_rerank_identity(d, N, K):
     plain = [r for r in range(B) if r != 9 or N // 2 >= K]
     assert len(plain) >= B - 1
     assert np.array_equal(ids[plain], pool["ids"][plain, :K])
-    assert np.array_equal(_bits(sc[plain]), _bits(pool["s"][plain, :K]))
+    assert np.array_equal(bits(sc[plain]), bits(pool["s"][plain, :K]))
     want_ids, want_sc = reference_lists(pool, K, 0, 0.0)
-    assert np.array_equal(ids, want_ids) and np.array_equal(_bits(sc), _bits(want_sc))
+    assert np.array_equal(ids, want_ids) and np.array_equal(bits(sc), bits(want_sc))
 
 
 # ---- through Model
-def _tuple(b):
-    return (b["u"], b["i"], b["j"], b["hist_i"], b["hist_i_new"], b["hist_t"], b["sl"], b["sl_new"], b["u_cate"])
-
-
-def _host(t):
-    return t.cpu().numpy()
-
-
 @pytest.fixture(scope="module")
 def model_case():
     from tlsan_amd.model import Model
@@ -150,25 +138,25 @@ def model_case():
 
 def test_recommend_defaults_keep_the_plain_path(model_case):
     m, b, _ = model_case
-    a = [_host(t) for t in m.recommend(_tuple(b), 10)]
-    c = [_host(t) for t in m.recommend(_tuple(b), 10, diversity=0.0, per_category=0)]
-    e = [_host(t) for t in m.recommend(_tuple(b), 10, exclude="history", diversity=0.0, per_category=0, pool=None)]
-    f = [_host(t) for t in m.recommend(_tuple(b), 10, exclude="history")]
-    assert np.array_equal(a[0], c[0]) and np.array_equal(_bits(a[1]), _bits(c[1]))
-    assert np.array_equal(e[0], f[0]) and np.array_equal(_bits(e[1]), _bits(f[1]))
+    a = [host(t) for t in m.recommend(batch_tuple(b, True), 10)]
+    c = [host(t) for t in m.recommend(batch_tuple(b, True), 10, diversity=0.0, per_category=0)]
+    e = [host(t) for t in m.recommend(batch_tuple(b, True), 10, exclude="history", diversity=0.0, per_category=0, pool=None)]
+    f = [host(t) for t in m.recommend(batch_tuple(b, True), 10, exclude="history")]
+    assert np.array_equal(a[0], c[0]) and np.array_equal(bits(a[1]), bits(c[1]))
+    assert np.array_equal(e[0], f[0]) and np.array_equal(bits(e[1]), bits(f[1]))
     for kw in (dict(pool=300, diversity=0.5), dict(pool=5, diversity=0.5), dict(diversity=2), dict(pool=64),
                dict(per_category=-1)):
         with pytest.raises(ValueError):
-            m.recommend(_tuple(b), 10, **kw)
+            m.recommend(batch_tuple(b, True), 10, **kw)
 
 
 def test_recommend_cap_equals_the_capped_ranking_over_all_items(model_case):
     """pool = 256 holds all 200 items: the list is the brute-force capped ranking of score_candidates' scores."""
     m, b, cat = model_case
     I, n = 200, len(b["u"])
-    sc_all = _host(m.score_candidates(_tuple(b), np.tile(np.arange(I), (n, 1))))
+    sc_all = host(m.score_candidates(batch_tuple(b, True), np.tile(np.arange(I), (n, 1))))
     for exclude in (None, "history"):
-        ids, sc = (_host(t) for t in m.recommend(_tuple(b), 10, exclude=exclude, per_category=2, pool=256))
+        ids, sc = (host(t) for t in m.recommend(batch_tuple(b, True), 10, exclude=exclude, per_category=2, pool=256))
         for r in range(n):
             ok = np.ones(I, bool)
             if exclude:
@@ -176,7 +164,7 @@ def test_recommend_cap_equals_the_capped_ranking_over_all_items(model_case):
                 ok[b["hist_i_new"][r, :b["sl_new"][r]]] = False
             want = ref.capped_ranking(sc_all[r], cat, 10, 2, ok)
             assert len(want) == 10 and ids[r].tolist() == want, (exclude, r)
-            assert np.array_equal(_bits(sc[r]), _bits(sc_all[r, want])), (exclude, r)
+            assert np.array_equal(bits(sc[r]), bits(sc_all[r, want])), (exclude, r)
 
 
 @pytest.mark.parametrize("pool,N", [(None, 40), (32, 32)])
@@ -186,16 +174,16 @@ def test_recommend_diversity_passes_the_teacher_forced_check(model_case, pool, N
     import torch
     from tlsan_amd import model as M
     m, b, cat = model_case
-    ids, sc = (_host(t) for t in m.recommend(_tuple(b), 10, exclude="history", diversity=0.5, pool=pool))
-    pid, psc = m.recommend(_tuple(b), N, exclude="history")
+    ids, sc = (host(t) for t in m.recommend(batch_tuple(b, True), 10, exclude="history", diversity=0.5, pool=pool))
+    pid, psc = m.recommend(batch_tuple(b, True), N, exclude="history")
     vec, inv = M.item_vectors(m.lib, m.dims, m.cparams, pid.reshape(-1).contiguous(), 1, 0, m._stream())
     torch.cuda.synchronize()
     n = len(b["u"])
-    pid_h = _host(pid)
-    pl = dict(ids=pid_h, s=_host(psc), w=_host(vec).reshape(n, N, -1), inv=_host(inv).reshape(n, N),
+    pid_h = host(pid)
+    pl = dict(ids=pid_h, s=host(psc), w=host(vec).reshape(n, N, -1), inv=host(inv).reshape(n, N),
               cate=np.asarray(cat)[np.maximum(pid_h, 0)])
     assert check_rows(pl, ids, sc, 10, 0, 0.5, 64) == []
-    plain = _host(m.recommend(_tuple(b), 10, exclude="history")[0])
+    plain = host(m.recommend(batch_tuple(b, True), 10, exclude="history")[0])
     assert np.array_equal(ids[:, 0], plain[:, 0]) and not np.array_equal(ids, plain)     # the penalty moved something
 
 

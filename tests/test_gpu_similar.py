@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from tests import similar_ref as ref
-from tests.helpers import make_config, random_batch, random_params
+from tests.helpers import bits, make_config, model, random_batch, random_params, sharded
+from tests.ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -27,9 +28,8 @@ def _params(cfg, seed, **tables):
 
 
 def _model(cfg, cat, p, **kw):
-    from tlsan_amd.model import Model
-    m = Model(cfg, cat, **kw)
-    m.set_params(p)
+    m = model(cfg, cat, **kw)
+    m.set_params(p)          # (float32 as _params made them, handed over unconverted: helpers.model would convert)
     return m
 
 
@@ -44,10 +44,6 @@ def _stored(m, cat):
 
 def _host(pair):
     return pair[0].cpu().numpy(), pair[1].cpu().numpy()
-
-
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.int32)
 
 
 def _check(m, w, qids, k, metric, exclude=None, P=1.0, got=None):
@@ -113,8 +109,8 @@ def test_duplicate_rows_under_cosine():
     for r, q in enumerate(qids):
         copies = [n for n in range(90) if n % 6 == q % 6 and n != q]
         assert ids[r, :14].tolist() == copies                # 14 bit-identical rows: ascending id, never the query
-        assert len(set(_bits(sc[r, :14]).tolist())) == 1
-    assert np.array_equal(ids[1], ids[3]) and np.array_equal(_bits(sc[1]), _bits(sc[3]))
+        assert len(set(bits(sc[r, :14]).tolist())) == 1
+    assert np.array_equal(ids[1], ids[3]) and np.array_equal(bits(sc[1]), bits(sc[3]))
 
 
 def test_scores_rising_with_the_id_overflow_the_buffers():
@@ -161,7 +157,7 @@ def test_eligibility():
     for metric in METRICS:
         for k in (5, 64, 256):
             ids, sc = _check(m, w, qids, k, metric, exclude=excl)
-            assert np.array_equal(ids[0], ids[2]) and np.array_equal(_bits(sc[0]), _bits(sc[2]))   # the same query twice
+            assert np.array_equal(ids[0], ids[2]) and np.array_equal(bits(sc[0]), bits(sc[2]))   # the same query twice
             assert ids[3].tolist() == [-1] * k               # everything but the query excluded
         with pytest.raises(ValueError):
             m.similar_items([3, I], 5, metric=metric)
@@ -173,7 +169,7 @@ def test_eligibility():
         m.similar_items([3, 4], 5, exclude=[[1]])
     # the zero row: inv = 0, every score +0.0, ids ascending
     ids, sc = _host(m.similar_items([17], 8, metric="cosine"))
-    assert ids[0].tolist() == list(range(8)) and np.array_equal(_bits(sc), np.zeros((1, 8), np.int32))
+    assert ids[0].tolist() == list(range(8)) and np.array_equal(bits(sc), np.zeros((1, 8), np.int32))
     # a padding query and an id past the table, through the C call; foreign and repeated ids in the CSR itself
     off = torch.tensor([0, 4, 4, 4, 7], dtype=torch.int32, device=m.device)
     xid = torch.tensor([5, 5, 9, 2 ** 31 - 1, 8, 8, 1 << 20], dtype=torch.int32, device=m.device)
@@ -196,13 +192,13 @@ def test_independence_and_symmetry():
     for metric in METRICS:
         many = _host(m.similar_items(qids, 20, metric=metric))
         again = _host(m.similar_items(qids, 20, metric=metric))
-        assert np.array_equal(many[0], again[0]) and np.array_equal(_bits(many[1]), _bits(again[1]))
+        assert np.array_equal(many[0], again[0]) and np.array_equal(bits(many[1]), bits(again[1]))
         for r in (0, 16, 32):
             one = _host(m.similar_items(qids[r:r + 1], 20, metric=metric))
-            assert np.array_equal(one[0][0], many[0][r]) and np.array_equal(_bits(one[1][0]), _bits(many[1][r]))
+            assert np.array_equal(one[0][0], many[0][r]) and np.array_equal(bits(one[1][0]), bits(many[1][r]))
         ids, sc = _host(m.similar_items(np.arange(I), 256, metric=metric))      # every pair, both ways round
         S = np.zeros((I, I), np.int32)
-        S[np.arange(I)[:, None], ids] = _bits(sc)
+        S[np.arange(I)[:, None], ids] = bits(sc)
         assert np.all(np.sort(ids, 1) == np.delete(np.tile(np.arange(I), (I, 1)), np.arange(I) * (I + 1)).reshape(I, I - 1))
         assert np.array_equal(S, S.T)
 
@@ -263,7 +259,7 @@ def test_bf16_tables():
     cat = _cat(cfg)
     m = _model(cfg, cat, _params(cfg, seed=81), table_dtype="bf16")
     w = _stored(m, cat)
-    assert np.array_equal(_bits(w.astype(np.float32)) & 0xFFFF, np.zeros(w.shape, np.int32))
+    assert np.array_equal(bits(w.astype(np.float32)) & 0xFFFF, np.zeros(w.shape, np.int32))
     for Q in (1, 33):
         for k in (16, 65):
             for metric in METRICS:
@@ -302,29 +298,14 @@ def test_gathering_form_at_d256():
 
 
 # ---- 8. sharded
-def _worker(rank, world, port, ret, *args):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        _sharded_case(rank, world, *args)
-        ret[rank] = "ok"
-    except Exception:
-        import traceback
-        ret[rank] = "FAIL: " + traceback.format_exc()
-    finally:
-        dist.destroy_process_group()
-
-
 def _sharded_case(rank, world):
-    from tests.test_gpu_dist_lazy_opt import _sharded
     I = 257                                                  # not a multiple of the world size
     cfg = make_config(U=20, I=I, C=5, d=128, H=8)
     cat = _cat(cfg)
     p = _params(cfg, seed=101)
     p["item_emb"][::3, ::5] = -0.0
     p["cate_emb"][1, :7] = -0.0
-    sm = _sharded(cfg, cat, p, l2_mode="dense")
+    sm = sharded(cfg, cat, p, l2_mode="dense")
     m = _model(cfg, cat, {k: np.asarray(v, np.float32) for k, v in sm.gather_params().items()})
     assert np.signbit(m.item_emb.cpu().numpy()[0, 0]) and np.signbit(m.cate_emb.cpu().numpy()[1, 0])
     qids = np.random.RandomState(102).randint(0, I, 33)
@@ -335,17 +316,13 @@ def _sharded_case(rank, world):
             want = _host(m.similar_items(qids, k, metric=metric, exclude=ex))
             got = _host(sm.similar_items(qids, k, metric=metric, exclude=ex))
             assert np.array_equal(got[0], want[0]), (metric, k)
-            assert np.array_equal(_bits(got[1]), _bits(want[1])), (metric, k)
+            assert np.array_equal(bits(got[1]), bits(want[1])), (metric, k)
             _check(m, w, qids, k, metric, exclude=ex, got=got)
 
 
 @pytest.mark.parametrize("world", [1, 2])
 def test_sharded_similar_items_equal_the_model_bit_for_bit(world):
-    import torch.multiprocessing as mp
-    from tests.test_gpu_dist_lazy_opt import _free_port
-    ret = mp.Manager().dict()
-    mp.spawn(_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
-    assert all(v == "ok" for v in dict(ret).values()) and len(ret) == world, dict(ret)
+    run_ranks(_sharded_case, world)
 
 
 # ---- 9. the driver
@@ -373,31 +350,17 @@ def _check_file(path, ds):
     assert np.all(np.abs(sc) <= 1 + 1e-5)                    # cosine
 
 
-def _sharded_driver_worker(rank, world, port, ret, out):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from tlsan_amd import train as T
-        ds = os.path.join(ROOT, "tests", "golden", "packed_clothing.npz")
-        T.train_sharded(T.parse(["--dataset", ds, "--max_steps", "5", "--eval_freq", "1000", "--quiet", "--train_batch_size", "33",
-                                 "--model_dir", os.path.join(out, "r%d" % rank), "--device_input", "0", "--l2_mode", "lazy",
-                                 "--static_rows", "1", "--similar_k", "5", "--sharded", "1"]))
-        path = os.path.join(out, "r%d" % rank, "similar-5.npz")
-        assert os.path.exists(path) == (rank == 0)           # rank 0 writes
-        if rank == 0:
-            _check_file(path, ds)
-        ret[rank] = "ok"
-    except Exception:
-        import traceback
-        ret[rank] = "FAIL: " + traceback.format_exc()
-    finally:
-        dist.destroy_process_group()
+def _sharded_driver_worker(rank, world, out):
+    from tlsan_amd import train as T
+    ds = os.path.join(ROOT, "tests", "golden", "packed_clothing.npz")
+    T.train_sharded(T.parse(["--dataset", ds, "--max_steps", "5", "--eval_freq", "1000", "--quiet", "--train_batch_size", "33",
+                             "--model_dir", os.path.join(out, "r%d" % rank), "--device_input", "0", "--l2_mode", "lazy",
+                             "--static_rows", "1", "--similar_k", "5", "--sharded", "1"]))
+    path = os.path.join(out, "r%d" % rank, "similar-5.npz")
+    assert os.path.exists(path) == (rank == 0)           # rank 0 writes
+    if rank == 0:
+        _check_file(path, ds)
 
 
 def test_sharded_driver_writes_similar_items(tmp_path):
-    import torch.multiprocessing as mp
-    from tests.test_gpu_dist_lazy_opt import _free_port
-    ret = mp.Manager().dict()
-    mp.spawn(_sharded_driver_worker, args=(2, _free_port(), ret, str(tmp_path)), nprocs=2, join=True)
-    assert all(v == "ok" for v in dict(ret).values()) and len(ret) == 2, dict(ret)
+    run_ranks(_sharded_driver_worker, 2, str(tmp_path))

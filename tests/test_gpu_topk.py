@@ -1,41 +1,21 @@
 """GPU tests of the top-K recommendation over all items (tlsan_eval_topk / tlsan_topk_merge, Model.recommend,
 ShardedModel.recommend, the driver's --recommend_k): against the fp64 oracle, bit for bit against the rank path, and
 the order's corner cases (exact ties, NaN, exclusion, rows with fewer than K eligible items)."""
-import ctypes as C
 import os
-import socket
 import subprocess
 import sys
-import traceback
 
 import numpy as np
 import pytest
 
 from oracle import tlsan_oracle as orc
-from tests.helpers import make_config, random_batch, random_params
+from tests.helpers import (batch_tuple, history_sets, host, label_scores, make_config, model, p32, random_batch,
+                           random_params)
+from tests.ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _p32(p):
-    return {k: np.asarray(v, np.float32).astype(np.float64) for k, v in p.items()}
-
-
-def _model(cfg, cat, p, **kw):
-    from tlsan_amd.model import Model
-    m = Model(cfg, cat, **kw)
-    m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-    return m
-
-
-def _tuple(b):
-    return (b["u"], b["i"], b["j"], b["hist_i"], b["hist_i_new"], b["hist_t"], b["sl"], b["sl_new"], b["u_cate"])
-
-
-def _host(t):
-    return t.cpu().numpy()
 
 
 def _check_order(ids, scores):
@@ -62,13 +42,13 @@ def _oracle_topk(scores, k):
 @pytest.mark.parametrize("d,H", [(64, 8), (128, 8), (256, 8), (64, 4), (128, 16), (128, 4)])
 def test_topk_matches_oracle(d, H):
     cfg = make_config(U=60, I=700, C=13, d=d, H=H)
-    p = _p32(random_params(cfg, seed=51))
+    p = p32(random_params(cfg, seed=51))
     b, cat = random_batch(cfg, B=77, Sn=3, seed=52, test=True)
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     ref = orc.forward(p, cat, b, H)
     scores = orc.all_item_scores(p, cat, ref["u_t"])
     for k in (1, 20, 100):
-        ids, sc = (_host(t) for t in m.recommend(_tuple(b), k))
+        ids, sc = (host(t) for t in m.recommend(batch_tuple(b, True), k))
         want, ws, clear = _oracle_topk(scores, k)
         assert ids.shape == (77, k) and sc.dtype == np.float32
         assert clear.sum() > (60 if k < 100 else 15), clear.sum()
@@ -77,15 +57,6 @@ def test_topk_matches_oracle(d, H):
         assert np.abs(sc - got_s).max() < 1e-4          # the returned score is the returned item's
         assert np.abs(sc - ws).max() < 1e-4
         _check_order(ids, sc)
-
-
-def _label_scores(m, db, ut):
-    from tlsan_amd import _lib as L
-    out = __import__("torch").empty(db.B, dtype=__import__("torch").float32, device=m.device)
-    ws = m._workspace(db.B, db.Sn)
-    L.check(m.lib.tlsan_eval_label_scores(C.byref(m.dims), C.byref(m.cparams), ut.data_ptr(), db.i.data_ptr(), db.B,
-                                          out.data_ptr(), ws.data_ptr(), ws.numel(), m._stream()), "label scores")
-    return _host(out)
 
 
 @pytest.mark.parametrize("form,table_dtype", [("dense", "f32"), ("dense", "bf16"), ("gather", "f32"), ("gather", "bf16")])
@@ -97,20 +68,20 @@ def test_topk_consistent_with_label_ranks(form, table_dtype):
     p = random_params(cfg, seed=61)
     tb, cat = random_batch(cfg, B=256, Sn=3, seed=62)
     b, _ = random_batch(cfg, B=512, Sn=3, seed=63, test=True)
-    m = _model(cfg, cat, p, l2_mode="lazy", table_dtype=table_dtype)
+    m = model(cfg, cat, p, l2_mode="lazy", table_dtype=table_dtype)
     for _ in range(2):
         m.train(None, (tb["u"], tb["i"], tb["y"], tb["hist_i"], tb["hist_i_new"], tb["hist_t"], tb["sl"], tb["sl_new"],
                        tb["u_cate"]), 1.0)
     assert m.table_scale() != 1.0
     K = 50
     # labels: every other row takes an item of its own list (u_t does not depend on the label), the rest stay random
-    first = _host(m.recommend(_tuple(b), K)[0])
+    first = host(m.recommend(batch_tuple(b, True), K)[0])
     b["i"][::2] = first[np.arange(0, 512, 2), np.arange(256) % K]
     b["i"][::6] = first[::6, K - 1]
-    ranks = _host(m.label_ranks(_tuple(b)))
-    _, _, ut, db = m.forward(_tuple(b), is_test=True, want_u_t=True)
-    slab = _label_scores(m, db, ut)
-    ids, sc = (_host(t) for t in m.recommend(_tuple(b), K))
+    ranks = host(m.label_ranks(batch_tuple(b, True)))
+    _, _, ut, db = m.forward(batch_tuple(b, True), is_test=True, want_u_t=True)
+    slab = label_scores(m, db, ut)
+    ids, sc = (host(t) for t in m.recommend(batch_tuple(b, True), K))
     _check_order(ids, sc)
     assert (ranks < K).sum() >= 256
     pos = np.array([list(r).index(l) if l in r else K for r, l in zip(ids, b["i"])])
@@ -129,21 +100,21 @@ def test_topk_consistent_with_label_ranks(form, table_dtype):
 
 def test_topk_exact_ties():
     cfg = make_config(U=20, I=300, C=5, d=64)
-    p = _p32(random_params(cfg, seed=71))
+    p = p32(random_params(cfg, seed=71))
     b, cat = random_batch(cfg, B=16, Sn=2, seed=72, test=True)
     tied = np.arange(100, 300, 5)[:40]             # 40 items, bit-identical rows, far ahead of the rest
     p["item_emb"][tied] = p["item_emb"][tied[0]]
     p["item_b"][tied] = 1000.0
     cat[tied] = cat[tied[0]]
-    m = _model(cfg, cat, p)
-    ids, sc = (_host(t) for t in m.recommend(_tuple(b), 10))
+    m = model(cfg, cat, p)
+    ids, sc = (host(t) for t in m.recommend(batch_tuple(b, True), 10))
     assert np.all(ids == tied[:10][None, :])
     assert np.all(sc == sc[:, :1])
     # a tie straddling the K boundary: 5 distinct leaders, then the tied group -> its 5 lowest ids
     lead = np.array([3, 17, 41, 77, 99])
     p["item_b"][lead] = 2000.0 + 100.0 * np.arange(5)
     m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-    ids, sc = (_host(t) for t in m.recommend(_tuple(b), 10))
+    ids, sc = (host(t) for t in m.recommend(batch_tuple(b, True), 10))
     assert np.all(ids[:, :5] == lead[::-1][None, :])
     assert np.all(ids[:, 5:] == tied[:5][None, :])
     _check_order(ids, sc)
@@ -151,42 +122,35 @@ def test_topk_exact_ties():
 
 def test_topk_deterministic_and_batch_independent():
     cfg = make_config(U=300, I=9000, C=40, d=128)
-    p = _p32(random_params(cfg, seed=81))
+    p = p32(random_params(cfg, seed=81))
     b, cat = random_batch(cfg, B=4096, Sn=3, seed=82, test=True)
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     from tlsan_amd.model import eval_topk, exclusion_csr
-    _, _, ut, db = m.forward(_tuple(b), is_test=True, want_u_t=True)
+    _, _, ut, db = m.forward(batch_tuple(b, True), is_test=True, want_u_t=True)
     sub = {key: v[100:116] for key, v in b.items()}
-    _, _, ut_s, db_s = m.forward(_tuple(sub), is_test=True, want_u_t=True)
+    _, _, ut_s, db_s = m.forward(batch_tuple(sub, True), is_test=True, want_u_t=True)
     ut_s.copy_(ut[100:116])     # (the forward's own last bits may follow the launch's batch; the selection's may not)
     for k in (10, 256):
-        a = [_host(t) for t in m.recommend(_tuple(b), k)]
-        a2 = [_host(t) for t in m.recommend(_tuple(b), k)]
+        a = [host(t) for t in m.recommend(batch_tuple(b, True), k)]
+        a2 = [host(t) for t in m.recommend(batch_tuple(b, True), k)]
         assert np.array_equal(a[0], a2[0]) and np.array_equal(a[1].view(np.int32), a2[1].view(np.int32))
         _check_order(*a)
         # a batch of 16 (36 item slices) and one of 4096 (8 slices), the same u_t rows
-        run = lambda u, d: [_host(t) for t in eval_topk(m.lib, m.dims, m.cparams, u, d.B, k, exclusion_csr(d, "history", 9000),
+        run = lambda u, d: [host(t) for t in eval_topk(m.lib, m.dims, m.cparams, u, d.B, k, exclusion_csr(d, "history", 9000),
                                                         1, 0, m._topk_workspace, m._stream())]
         s, full = run(ut_s, db_s), run(ut, db)
         assert np.array_equal(s[0], full[0][100:116]) and np.array_equal(s[1].view(np.int32), full[1][100:116].view(np.int32))
         # end to end (each batch through its own forward): the same items
-        e2e = _host(m.recommend(_tuple(sub), k, exclude="history")[0])
+        e2e = host(m.recommend(batch_tuple(sub, True), k, exclude="history")[0])
         assert np.array_equal(e2e, full[0][100:116])
-
-
-def _history_sets(b):
-    out = []
-    for r in range(len(b["u"])):
-        out.append(set(b["hist_i"][r, :b["sl"][r]].tolist()) | set(b["hist_i_new"][r, :b["sl_new"][r]].tolist()))
-    return out
 
 
 def test_topk_exclusion():
     cfg = make_config(U=60, I=800, C=13, d=128)
-    p = _p32(random_params(cfg, seed=91))
+    p = p32(random_params(cfg, seed=91))
     b, cat = random_batch(cfg, B=64, Sn=4, seed=92, test=True)
     # histories drawn from the best items, so that exclusion changes the lists
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     ref = orc.forward(p, cat, b, 8)
     best = orc.topk_ids(orc.all_item_scores(p, cat, ref["u_t"]), 12)
     b["hist_i"][:, :6] = best[:, ::2]
@@ -196,12 +160,12 @@ def test_topk_exclusion():
     b["hist_t"] = np.where(np.arange(cfg["Ls"])[None, :] < b["sl"][:, None], b["hist_t"], 0).astype(np.float32)
     ref = orc.forward(p, cat, b, 8)
     scores = orc.all_item_scores(p, cat, ref["u_t"])
-    hist = _history_sets(b)
+    hist = history_sets(b)
     rng = np.random.RandomState(93)
     lists = [np.concatenate([best[r, 1::3], rng.randint(-5, 900, 7), best[r, 1:2]]) for r in range(64)]  # repeats, out of range
     for exclude, sets in (("history", hist), (lists, [set(x[(x >= 0) & (x < 800)].tolist()) for x in lists])):
         k = 20
-        ids, sc = (_host(t) for t in m.recommend(_tuple(b), k, exclude=exclude))
+        ids, sc = (host(t) for t in m.recommend(batch_tuple(b, True), k, exclude=exclude))
         for r in range(64):
             assert not (set(ids[r].tolist()) & sets[r]), r
         masked = scores.copy()
@@ -213,11 +177,11 @@ def test_topk_exclusion():
         _check_order(ids, sc)
     # fewer eligible items than K
     cfg = make_config(U=20, I=30, C=3, d=64)
-    p = _p32(random_params(cfg, seed=94))
+    p = p32(random_params(cfg, seed=94))
     b, cat = random_batch(cfg, B=16, Sn=2, seed=95, test=True)
-    m = _model(cfg, cat, p)
-    ids, sc = (_host(t) for t in m.recommend(_tuple(b), 40, exclude="history"))
-    for r, h in enumerate(_history_sets(b)):
+    m = model(cfg, cat, p)
+    ids, sc = (host(t) for t in m.recommend(batch_tuple(b, True), 40, exclude="history"))
+    for r, h in enumerate(history_sets(b)):
         n = 30 - len(h)
         assert np.all(ids[r, n:] == -1) and np.all(sc[r, n:] == -np.inf)
         assert set(ids[r, :n].tolist()) == set(range(30)) - h
@@ -225,8 +189,8 @@ def test_topk_exclusion():
     # the padding of the windows (item 0 past sl / sl_new) is not history: item 0, made the best item, stays first
     p["item_b"][0] = 1000.0
     m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-    ids, _ = (_host(t) for t in m.recommend(_tuple(b), 5, exclude="history"))
-    padded = [r for r, h in enumerate(_history_sets(b)) if 0 not in h and b["sl"][r] < cfg["Ls"]]
+    ids, _ = (host(t) for t in m.recommend(batch_tuple(b, True), 5, exclude="history"))
+    padded = [r for r, h in enumerate(history_sets(b)) if 0 not in h and b["sl"][r] < cfg["Ls"]]
     assert padded
     assert np.all(ids[padded, 0] == 0)
 
@@ -239,79 +203,58 @@ def _avoid(b, item):
 
 def test_topk_nan_item_never_selected():
     cfg = make_config(U=20, I=400, C=7, d=128)
-    p = _p32(random_params(cfg, seed=101))
+    p = p32(random_params(cfg, seed=101))
     b, cat = random_batch(cfg, B=48, Sn=2, seed=102, test=True)
     _avoid(b, 7)
     p["item_emb"][7] = np.nan
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     for k in (1, 50, 256):
-        ids, sc = (_host(t) for t in m.recommend(_tuple(b), k))
+        ids, sc = (host(t) for t in m.recommend(batch_tuple(b, True), k))
         assert not np.any(ids == 7) and np.all(np.isfinite(sc))
         _check_order(ids, sc)
     # with fewer finite items than K the NaN item comes last, before the padding
     cfg = make_config(U=20, I=20, C=3, d=64)
-    p = _p32(random_params(cfg, seed=103))
+    p = p32(random_params(cfg, seed=103))
     b, cat = random_batch(cfg, B=16, Sn=2, seed=104, test=True)
     _avoid(b, 7)
     p["item_emb"][7] = np.nan
-    m = _model(cfg, cat, p)
-    ids, sc = (_host(t) for t in m.recommend(_tuple(b), 25))
+    m = model(cfg, cat, p)
+    ids, sc = (host(t) for t in m.recommend(batch_tuple(b, True), 25))
     assert np.all(ids[:, 19] == 7) and np.all(np.isnan(sc[:, 19]))
     assert np.all(ids[:, 20:] == -1)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _case():
     cfg = make_config(U=61, I=1501, C=9, d=128)
-    p = _p32(random_params(cfg, seed=111))
+    p = p32(random_params(cfg, seed=111))
     b, cat = random_batch(cfg, B=48, Sn=3, seed=112, test=True)
     return cfg, p, b, cat
 
 
-def _shard_worker(rank, world, port, ret, out_dir):
-    import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        from tlsan_amd.dist import ShardedModel
-        cfg, p, b, cat = _case()
-        m = ShardedModel(cfg, cat, device="cuda:0")
-        m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-        n = len(b["u"]) // world
-        part = {k: v[rank * n:(rank + 1) * n] for k, v in b.items()}
-        lists = [np.array([r, 3 * r + 1, 1400, 1400, -2]) for r in range(rank * n, (rank + 1) * n)]
-        res = {}
-        for name, ex in (("none", None), ("history", "history"), ("lists", lists)):
-            ids, sc = m.recommend(_tuple(part), 30, exclude=ex)
-            res[name + "_ids"], res[name + "_sc"] = _host(ids), _host(sc)
-        np.savez(os.path.join(out_dir, "rank%d.npz" % rank), **res)
-        ret[rank] = "ok"
-    except Exception:
-        ret[rank] = "FAIL: " + traceback.format_exc()
-    finally:
-        dist.destroy_process_group()
+def _shard_worker(rank, world, out_dir):
+    from tlsan_amd.dist import ShardedModel
+    cfg, p, b, cat = _case()
+    m = ShardedModel(cfg, cat, device="cuda:0")
+    m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
+    n = len(b["u"]) // world
+    part = {k: v[rank * n:(rank + 1) * n] for k, v in b.items()}
+    lists = [np.array([r, 3 * r + 1, 1400, 1400, -2]) for r in range(rank * n, (rank + 1) * n)]
+    res = {}
+    for name, ex in (("none", None), ("history", "history"), ("lists", lists)):
+        ids, sc = m.recommend(batch_tuple(part, True), 30, exclude=ex)
+        res[name + "_ids"], res[name + "_sc"] = host(ids), host(sc)
+    np.savez(os.path.join(out_dir, "rank%d.npz" % rank), **res)
 
 
 def test_sharded_recommend_matches_model(tmp_path):
-    import torch.multiprocessing as mp
     world = 2
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_shard_worker, args=(world, _free_port(), ret, str(tmp_path)), nprocs=world, join=True)
-    assert all(v == "ok" for v in dict(ret).values()) and len(ret) == world, dict(ret)
+    run_ranks(_shard_worker, world, str(tmp_path))
     cfg, p, b, cat = _case()
-    m = _model(cfg, cat, p)
+    m = model(cfg, cat, p)
     lists = [np.array([r, 3 * r + 1, 1400, 1400, -2]) for r in range(len(b["u"]))]
     got = [np.load(str(tmp_path / ("rank%d.npz" % r))) for r in range(world)]
     for name, ex in (("none", None), ("history", "history"), ("lists", lists)):
-        ids, sc = (_host(t) for t in m.recommend(_tuple(b), 30, exclude=ex))
+        ids, sc = (host(t) for t in m.recommend(batch_tuple(b, True), 30, exclude=ex))
         gi = np.concatenate([g[name + "_ids"] for g in got])
         gs = np.concatenate([g[name + "_sc"] for g in got])
         assert np.array_equal(gi, ids), name

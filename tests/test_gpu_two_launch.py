@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 from oracle import tlsan_oracle as orc
-from tests.helpers import make_config, random_batch, random_params
+from tests.helpers import batch_tuple, make_config, model, p32, random_batch, random_params
 
 pytestmark = pytest.mark.gpu
 
@@ -30,36 +30,24 @@ LR, REG = 0.9, 2e-2        # (test_lazy_l2_matches_dense_oracle's: the decay is 
 NO_CLIP, CLIP = 1e6, 0.02
 
 
-def _tuple(b, test=False):
-    return (b["u"], b["i"], b["j"] if test else b["y"], b["hist_i"], b["hist_i_new"], b["hist_t"],
-            b["sl"], b["sl_new"], b["u_cate"])
-
-
-def _p32(p):
-    return {k: np.asarray(v, np.float32).astype(np.float64) for k, v in p.items()}
-
-
 def _problem(d, B):
     big = B > 32
     cfg = make_config(U=3000 if big else 300, I=2000 if big else 200, C=400 if big else 9, d=d,
                       max_gradient_norm=NO_CLIP, regulation_rate=REG)
-    p = _p32(random_params(cfg, seed=7 * d + B))
+    p = p32(random_params(cfg, seed=7 * d + B))
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=B, Sn=1 + s % 3, seed=900 + 13 * s + B)[0] for s in range(STEPS)]
     return cfg, p, cat, batches
 
 
-def _model(cfg, cat, p):
-    from tlsan_amd.model import Model
-    m = Model(dict(cfg), cat, l2_mode="lazy")
-    m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})
-    return m
+def _model(cfg, cat, p):       # (helpers.model with this file's two constants: the lazy-L2 step, and a copy of cfg for the model)
+    return model(dict(cfg), cat, p, l2_mode="lazy")
 
 
 def _run(m, batches, clips, ahead):
     """The steps, each with its own clip norm; ahead: the index of the next two batches is built while a step runs, so a step
     starts with the fused kernel (and makes a clipped predecessor's correction at its head).  -> losses, global norms"""
-    dbs = [m.device_batch(_tuple(b)) for b in batches]
+    dbs = [m.device_batch(batch_tuple(b)) for b in batches]
     losses, norms = [], []
     for t, db in enumerate(dbs):
         m.config["max_gradient_norm"] = clips[t]
@@ -173,7 +161,7 @@ def test_planted_nonfinite_row_poisons_this_step_and_the_next(d, ahead):
     """test_nonfinite_inputs_give_nonfinite_loss's plants (a NaN and a +Inf in a gathered item row, a gathered user row):
     the step's loss is non-finite, and so is the next step's -- the NaN coefficient takes the correcting pass."""
     cfg = make_config(U=30, I=50, C=7, d=d, Ls=10)
-    p0 = _p32(random_params(cfg, seed=5 * d + 10))
+    p0 = p32(random_params(cfg, seed=5 * d + 10))
     b, cat = random_batch(cfg, B=40, Sn=3, seed=d + 1)
     it, us = int(b["hist_i"][0, 0]), int(b["u"][3])
     for key, idx in (("item_emb", (it, 5)), ("user_emb", (us, 2))):
@@ -191,14 +179,14 @@ def test_planted_nonfinite_row_poisons_this_step_and_the_next(d, ahead):
 
 def test_graph_replays_of_a_clipped_step_equal_eager():
     cfg = make_config(U=200, I=150, C=9, d=128, max_gradient_norm=CLIP, regulation_rate=REG)
-    p = _p32(random_params(cfg, seed=71))
+    p = p32(random_params(cfg, seed=71))
     _, cat = random_batch(cfg, B=8, Sn=3, seed=0)
     batches = [random_batch(cfg, B=64, Sn=3, seed=400 + s)[0] for s in range(3)]
     outs = []
     for mode in ("eager", "graph"):
         m = _model(cfg, cat, p)
         if mode == "graph":
-            graphs = [m.capture_step(_tuple(b), 0.7) for b in batches]
+            graphs = [m.capture_step(batch_tuple(b), 0.7) for b in batches]
             m.set_params({k: np.asarray(v, np.float32) for k, v in p.items()})   # (capture_step ran a warm step per batch)
             for rep in range(2):
                 for g in graphs:
@@ -206,7 +194,7 @@ def test_graph_replays_of_a_clipped_step_equal_eager():
         else:
             for rep in range(2):
                 for b in batches:
-                    m.train_async(_tuple(b), 0.7)
+                    m.train_async(batch_tuple(b), 0.7)
         assert m.last_gnorm() > CLIP       # (the steps are clipped)
         outs.append(m.get_params())
     for k in outs[0]:
@@ -216,7 +204,7 @@ def test_graph_replays_of_a_clipped_step_equal_eager():
 def test_evaluation_directly_after_a_clipped_step():
     import torch
     cfg = make_config(U=300, I=200, C=9, d=128, max_gradient_norm=CLIP, regulation_rate=REG)
-    p = _p32(random_params(cfg, seed=51))
+    p = p32(random_params(cfg, seed=51))
     b, cat = random_batch(cfg, B=24, Sn=2, seed=300)
     tb, _ = random_batch(cfg, B=200, Sn=2, seed=99, test=True)
     _, q, info = orc.train_step(dict(p), cat, b, 8, REG, lr=LR, clip=CLIP)
@@ -224,12 +212,12 @@ def test_evaluation_directly_after_a_clipped_step():
     res = []
     for explicit in (False, True):
         m = _model(cfg, cat, p)
-        m.train_async(_tuple(b), LR)
+        m.train_async(batch_tuple(b), LR)
         if explicit:
             m._flush()
             torch.cuda.synchronize()
-        auc = m.eval_auc(None, _tuple(tb, True))
-        li, lj, _, _ = m.forward(_tuple(tb, True), is_test=True)
+        auc = m.eval_auc(None, batch_tuple(tb, True))
+        li, lj, _, _ = m.forward(batch_tuple(tb, True), is_test=True)
         res.append((auc, li.cpu().numpy(), lj.cpu().numpy()))
     assert res[0][0] == res[1][0]
     assert np.array_equal(res[0][1], res[1][1]) and np.array_equal(res[0][2], res[1][2])
