@@ -142,7 +142,8 @@ def _fwa_forward(x, length, W1, b1, W2, b2, H, k1=None, k2=None):
     m1 = np.maximum(z1, 0.0)               # relu :405
     m2 = (m1 if k2 is None else m1 * k2) @ W2 + b2   # :382
     mask = (np.arange(L)[None, :] < length[:, None])            # sequence_mask :376
-    m2m = m2 + (1.0 - mask[:, :, None, None]) * VERY_NEGATIVE_NUMBER  # :384, 480-483
+    # (the mask term in x's own dtype: a float64 one would quietly lift a float32 run's softmax to float64)
+    m2m = m2 + (1.0 - mask[:, :, None, None]).astype(x.dtype) * VERY_NEGATIVE_NUMBER  # :384, 480-483
     mx = m2m.max(axis=1, keepdims=True)
     e = np.exp(m2m - mx)
     soft = e / e.sum(axis=1, keepdims=True)  # :386
