@@ -552,6 +552,38 @@ int tlsan_rerank(const int32_t* pool_ids, const float* pool_scores, const float*
                  const int32_t* cate, int32_t B, int32_t N, int32_t d, int32_t K, float diversity, int32_t per_category,
                  int32_t* ids, float* scores, void* stream);
 
+/* List metrics: what a recommendation list looks like beside its accuracy.  A row is a list of K entries (1 <= K <= 256):
+ * ids [B, K] global item ids, -1 = no entry, ANYWHERE in the row (a caller-given list need not be a tlsan_eval_topk list);
+ * at flattened position b * K + j the entry's stored vector (vec [B * K, d], d = 64, 128 or 256) and inverse norm (inv
+ * [B * K]) -- both what tlsan_item_vectors wrote for the flattened ids, so an id -1 has zeros and a zero row has inv 0 --
+ * and its category (cate [B * K]).  Like tlsan_rerank the call reads no table: one form serves a whole table and a
+ * sharded one, with the same bits.  Per row, over its VALID entries (id >= 0) in position order:
+ *   n_valid [B]     their number n.
+ *   pair_cos [B]    the sum over valid i < j of cos(i, j) = fl((w_i . w_j) * fl(inv_i * inv_j)), tlsan_rerank's cosine (the
+ *     fp32 dot in one fixed order that depends on d and the lane only; a zero vector has cosine 0 against everything),
+ *     accumulated in double in ONE order: c_j = ((0 + cos(i0, j)) + cos(i1, j)) + ... over the valid i < j ascending, then
+ *     pair_cos = ((0 + c_0) + c_1) + ... over j ascending (c_j = 0 for an entry that is not valid).  Exactly 0.0 for n < 2.
+ *     The intra-list diversity is ILD = 1 - pair_cos / (n (n - 1) / 2), formed by the caller (NaN for n < 2, not clamped).
+ *   n_cate [B]      distinct categories among the valid entries.
+ *   max_cate [B]    the largest number of valid entries that share one category, 0 for an empty row: a list made with
+ *     tlsan_rerank's per_category = m shows max_cate <= m.
+ *   hit_pos [B]     the first position j (a position in the list, holes counted) with a valid ids[b, j] == labels[b] where
+ *     labels[b] >= 0; -1 when the label is absent or negative, or labels is NULL.
+ *   weight_sum [B]  ((0 + weight[b K + j0]) + weight[b K + j1]) + ... in double over the valid j ascending; 0 when weight
+ *     is NULL.  The novelty hook: the caller passes each entry's self-information.
+ *   exposure [n_items] (nullable)  exposure[g] += 1 for every valid entry with g < n_items (integer atomics: the result
+ *     does not depend on the order); ids >= n_items are skipped.  The call adds to the array and never clears it.
+ * A row's outputs depend on its own list only: not on B, the other rows, the launch geometry or a second run; there are
+ * no floating-point atomics.
+ * Refused before any launch, with the function's name in tlsan_last_error: B < 1 or B * K >= 2^31, K outside 1..256,
+ * exposure given with n_items < 1, NULL among ids / vec / inv / cate or the six per-row outputs ("tlsan_list_metrics:
+ * NULL argument") (TLSAN_E_BADARG), d not 64 / 128 / 256 (TLSAN_E_UNSUPPORTED).  An addition: nothing else in the ABI
+ * changed (TLSAN_ABI_VERSION stays 14). */
+int tlsan_list_metrics(const int32_t* ids, const float* vec, const float* inv, const int32_t* cate,
+                       const int32_t* labels, const float* weight, int32_t B, int32_t K, int32_t d, int32_t* n_valid,
+                       double* pair_cos, int32_t* n_cate, int32_t* max_cate, int32_t* hit_pos, double* weight_sum,
+                       uint32_t* exposure, int32_t n_items, void* stream);
+
 /* Scores of caller-given candidates (a re-ranking of a retrieval stage's items, or a sampled evaluation):
  *   scores[b, c] = u_t[b] . [item_emb || cate_emb[item_cate]][g] + item_b[g],  g = cand[b, c] (global id),
  * for u_t [B, d], cand [B, C] int32, scores [B, C] float32.  Each score equals tlsan_eval_label_scores' for the

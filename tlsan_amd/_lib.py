@@ -19,6 +19,7 @@ INDEX_SLOTS = 3   # TLSAN_INDEX_SLOTS (csrc/tlsan_state.h): destination-index sl
 SN_CAP = 96     # TLSAN_SN_CAP (csrc/tlsan_common.h): longest session of a training batch
 TOPK_MAX = 256  # TOPK_MAX (csrc/tlsan_topk.h): largest K of tlsan_eval_topk
 RERANK_MAX = 256  # RERANK_MAX (csrc/tlsan_rerank.h): largest pool of tlsan_rerank
+LISTM_MAX = 256   # LISTM_MAX (csrc/tlsan_listm.h): longest list of tlsan_list_metrics
 SIM_DOT, SIM_COSINE = 0, 1   # TLSAN_SIM_DOT / TLSAN_SIM_COSINE (include/tlsan.h): the metrics of tlsan_similar_topk
 NEG_MAX = 1024  # NEG_MAX (csrc/tlsan_cand.h): largest N of tlsan_sample_negatives
 
@@ -29,7 +30,7 @@ EXPORTS = [
     "tlsan_train_step", "tlsan_train_step_opt", "tlsan_batch_pack", "tlsan_batch_index", "tlsan_grads", "tlsan_eval_ranks", "tlsan_eval_label_scores", "tlsan_eval_counts_shard",
     "tlsan_eval_ranks_excl", "tlsan_eval_counts_shard_excl",
     "tlsan_topk_workspace_bytes", "tlsan_eval_topk", "tlsan_topk_merge",
-    "tlsan_item_vectors", "tlsan_similar_workspace_bytes", "tlsan_similar_topk", "tlsan_rerank",
+    "tlsan_item_vectors", "tlsan_similar_workspace_bytes", "tlsan_similar_topk", "tlsan_rerank", "tlsan_list_metrics",
     "tlsan_score_candidates", "tlsan_candidate_ranks", "tlsan_sample_negatives", "tlsan_profile_enable", "tlsan_profile_stride",
     "tlsan_profile_collect", "tlsan_debug_stamps", "tlsan_rows_apply_workspace", "tlsan_rows_apply", "tlsan_scan_compact",
     "tlsan_route_plan", "tlsan_shard_gather", "tlsan_shard_summary", "tlsan_shard_apply_workspace", "tlsan_shard_apply",
@@ -216,6 +217,9 @@ def load():
     lib.tlsan_similar_topk.restype = C.c_int
     lib.tlsan_rerank.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.tlsan_rerank.restype = C.c_int
+    if hasattr(lib, "tlsan_list_metrics"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
+        lib.tlsan_list_metrics.argtypes = [C.c_void_p] * 6 + [C.c_int32] * 3 + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]
+        lib.tlsan_list_metrics.restype = C.c_int
     lib.tlsan_score_candidates.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                            C.c_int32, C.c_void_p, C.c_void_p]
     lib.tlsan_score_candidates.restype = C.c_int

@@ -31,7 +31,7 @@ from .dist_comm import (ExchangePlan, KeyRouter, ModPartition, RowExchange, _sta
 from .dist_step import DynamicStep, FlatLayout, StaticStep, fused_params
 from .model import (LAZY_ADAGRAD_OPTIMIZERS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer, candidate_tensor, eval_topk,
                     exclusion_csr, grow_workspace, hits_and_rows, pack_dense, read_checkpoint, sample_negatives, sampled_ranks,
-                    score_candidates, item_vectors, rerank, rerank_chunk, rerank_pool, similar_queries, similar_topk, topk_merge, unpack_dense, write_checkpoint)
+                    score_candidates, item_vectors, list_metric_inputs, list_metrics, list_metrics_chunks, rerank, rerank_chunk, rerank_pool, similar_queries, similar_topk, topk_merge, unpack_dense, write_checkpoint)
 
 
 def _ru4(x):
@@ -440,33 +440,59 @@ class ShardedModel:
         +0); the categories come from the replicated map; tlsan_rerank picks.  A chunk's all-gathered vectors stay
         within model.RERANK_STAGING bytes."""
         B, N = pid.shape
-        st, W, d = self._stream(), self.world, self.d
+        st = self._stream()
         ids = torch.empty(B, k, dtype=torch.int32, device=self.device)
         scores = torch.empty(B, k, dtype=torch.float32, device=self.device)
-        nloc, ldims, lp = self._item_shard()
-        rows = rerank_chunk(N, d, W)
+        shard = self._item_shard()
+        rows = rerank_chunk(N, self.d, self.world)
         for r0 in range(0, B, rows):
-            flat = pid[r0:r0 + rows].reshape(-1)
-            Q = int(flat.shape[0])
-            asked = allgather_rows(flat, self.group)           # rank r's entries at [r Q, (r + 1) Q)
-            if nloc > 0:
-                vec, inv = item_vectors(self.lib, ldims, lp, asked, W, self.rank, st)
-            else:
-                vec = torch.zeros(W * Q, d, dtype=torch.float32, device=self.device)
-                inv = torch.zeros(W * Q, dtype=torch.float32, device=self.device)
-            if W > 1:
-                # block s of what arrives is rank s's reading of this rank's entries
-                gvec, ginv = torch.empty_like(vec), torch.empty_like(inv)
-                a2a(gvec, vec, None, None, self.group)
-                a2a(ginv, inv, None, None, self.group)
-                owner = torch.where(flat >= 0, flat % W, torch.zeros_like(flat)).long()
-                vec = torch.gather(gvec.view(W, Q, d), 0, owner[None, :, None].expand(1, Q, d))[0].contiguous()
-                inv = torch.gather(ginv.view(W, Q), 0, owner[None])[0].contiguous()
-            g = flat.clamp(min=0).long()
-            cate = self.cate_by_key[(g % W) * self.router.R + g // W]      # (the replicated item -> category map)
+            vec, inv, cate, _ = self._fetch_entries(pid[r0:r0 + rows].reshape(-1), shard, st)
             rerank(self.lib, pid[r0:r0 + rows], psc[r0:r0 + rows], vec, inv, cate, k, diversity, per_category,
                    ids[r0:r0 + rows], scores[r0:r0 + rows], st)
         return ids, scores
+
+    def _fetch_entries(self, flat, shard, st):
+        """The staging of _rerank and list_metrics (collective; the same Q on every rank): for this rank's Q flattened
+        global ids (-1: none) -> (vec [Q, d], inv [Q], cate [Q], g [Q] the ids clamped to 0, int64).  The ids are
+        all-gathered, every rank reads the stored vectors and inverse norms of the ids ITS item shard holds
+        (tlsan_item_vectors, zeros for the others), one all-to-all returns each rank's entries and every entry's are
+        SELECTED from the rank that holds its id, g % world; the categories come from the replicated map."""
+        W, d = self.world, self.d
+        nloc, ldims, lp = shard
+        Q = int(flat.shape[0])
+        asked = allgather_rows(flat, self.group)           # rank r's entries at [r Q, (r + 1) Q)
+        if nloc > 0:
+            vec, inv = item_vectors(self.lib, ldims, lp, asked, W, self.rank, st)
+        else:
+            vec = torch.zeros(W * Q, d, dtype=torch.float32, device=self.device)
+            inv = torch.zeros(W * Q, dtype=torch.float32, device=self.device)
+        if W > 1:
+            # block s of what arrives is rank s's reading of this rank's entries
+            gvec, ginv = torch.empty_like(vec), torch.empty_like(inv)
+            a2a(gvec, vec, None, None, self.group)
+            a2a(ginv, inv, None, None, self.group)
+            owner = torch.where(flat >= 0, flat % W, torch.zeros_like(flat)).long()
+            vec = torch.gather(gvec.view(W, Q, d), 0, owner[None, :, None].expand(1, Q, d))[0].contiguous()
+            inv = torch.gather(ginv.view(W, Q), 0, owner[None])[0].contiguous()
+        g = flat.clamp(min=0).long()
+        return vec, inv, self.cate_by_key[(g % W) * self.router.R + g // W], g      # (the replicated item -> category map)
+
+    def list_metrics(self, ids, labels=None, item_weight=None, exposure=None):
+        """Model.list_metrics for this rank's lists (collective: every rank calls it, with lists of the same shape
+        [B, K]): the entries' vectors and inverse norms are fetched from the ranks that hold them exactly as the second
+        stage of a diversified recommend fetches them (_fetch_entries), and tlsan_list_metrics reads no table, so the
+        ListMetrics equal Model.list_metrics' on the gathered parameters bit for bit.  exposure counts this rank's
+        lists only: the caller sums the ranks' counters."""
+        ids, labels, item_weight = list_metric_inputs(ids, labels, item_weight, exposure, self.I, self.device)
+        if self._static is not None:   # (plans announced ahead may be running on the side streams)
+            self._static.drain()
+        st, shard = self._stream(), self._item_shard()
+
+        def measure(sub, lab):
+            vec, inv, cate, g = self._fetch_entries(sub.reshape(-1), shard, st)
+            return list_metrics(self.lib, sub, vec, inv, cate, lab, None if item_weight is None else item_weight[g],
+                                exposure, st)
+        return list_metrics_chunks(ids, labels, rerank_chunk(ids.shape[1], self.d, self.world), measure)
 
     def similar_items(self, items, k, metric="cosine", exclude=None):
         """Model.similar_items, collective: every rank passes the same items (and k, metric, exclude) and every rank

@@ -185,6 +185,21 @@ def seen_items_csr(train_set, n_users):
     return off, key % span
 
 
+def item_self_information(train_set, n_items):
+    """Novelty weights from a training PackedSet -> [n_items] float32: item g's self-information
+    -log2((c_g + 1) / (T + n_items)), c_g the number of training samples whose positive is g (target g with label 1; a
+    target with label 0 is a sampled negative), T the number of training samples.  The add-one keeps an item that was
+    never a positive finite; a rarer item weighs more.  Computed in float64, rounded once."""
+    if train_set.is_test:
+        raise ValueError("item_self_information needs train tuples")
+    n_items = int(n_items)
+    pos = train_set.target[train_set.label == 1]
+    if pos.size and (pos.min() < 0 or pos.max() >= n_items):
+        raise ValueError("item_self_information: item id outside 0..%d" % (n_items - 1))
+    c = np.bincount(pos, minlength=n_items).astype(np.float64)
+    return (-np.log2((c + 1.0) / (float(len(train_set.u)) + n_items))).astype(np.float32)
+
+
 def load_packed(path):
     """Load a ``packed_<name>.npz`` export: (train PackedSet, test PackedSet, (U,I,C), item_cate_list)."""
     z = np.load(path)

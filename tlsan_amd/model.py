@@ -18,6 +18,7 @@ device memory and the stream.  There is no CPU fallback.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import json
 import os
@@ -362,6 +363,69 @@ def rerank(lib, pool_ids, pool_scores, vec, inv, cate, k, diversity, per_categor
                              scores.data_ptr(), stream), "tlsan_rerank")
 
 
+ListMetrics = collections.namedtuple("ListMetrics", "n pair_cos ild n_cate max_cate hit_pos weight_sum")
+ListMetrics.__doc__ = """Per-row measurements of lists (tlsan_list_metrics), [B] device tensors: n valid entries (int32),
+pair_cos the summed pairwise cosines (float64), ild = 1 - pair_cos / (n (n - 1) / 2) (float64, NaN where n < 2, not
+clamped), n_cate distinct categories, max_cate the most entries sharing one, hit_pos the label's position or -1 (int32),
+weight_sum the summed entry weights (float64)."""
+
+
+def list_metric_inputs(ids, labels, item_weight, exposure, item_count, device):
+    """Checks list_metrics' arguments (ValueError before any launch) -> (ids [B, K] int32, labels [B] int32 or None,
+    item_weight [item_count] float32 or None) contiguous device tensors."""
+    as_dev = lambda x, dt: (x.to(device=device, dtype=dt) if isinstance(x, torch.Tensor)
+                            else torch.as_tensor(np.asarray(x)).to(device=device, dtype=dt)).contiguous()
+    shape = tuple(ids.shape) if isinstance(ids, torch.Tensor) else np.shape(ids)
+    if len(shape) != 2 or shape[0] < 1:
+        raise ValueError("ids: want a [B, K] array of item ids, got shape %s" % (shape,))
+    if not 1 <= shape[1] <= L.LISTM_MAX:
+        raise ValueError("ids: K must be in 1..%d, got %d" % (L.LISTM_MAX, shape[1]))
+    if labels is not None:
+        lshape = tuple(labels.shape) if isinstance(labels, torch.Tensor) else np.shape(labels)
+        if lshape != (shape[0],):
+            raise ValueError("labels: want [%d] item ids, got shape %s" % (shape[0], lshape))
+    if item_weight is not None:
+        wshape = tuple(item_weight.shape) if isinstance(item_weight, torch.Tensor) else np.shape(item_weight)
+        if wshape != (item_count,):
+            raise ValueError("item_weight: want [%d] weights, one per item, got shape %s" % (item_count, wshape))
+    if exposure is not None:
+        if not isinstance(exposure, torch.Tensor) or exposure.dtype != torch.int32 or tuple(exposure.shape) != (item_count,) \
+                or not exposure.is_contiguous() or exposure.device.type != torch.device(device).type:
+            raise ValueError("exposure: want a contiguous [%d] int32 counter on %s" % (item_count, device))
+    ids = as_dev(ids, torch.int32)
+    if int(ids.max()) >= item_count:
+        raise ValueError("ids: item ids must be below %d (-1: no entry)" % item_count)
+    return (ids, None if labels is None else as_dev(labels, torch.int32),
+            None if item_weight is None else as_dev(item_weight, torch.float32))
+
+
+def list_metrics(lib, ids, vec, inv, cate, labels, weight, exposure, stream):
+    """tlsan_list_metrics on the lists ids [B, K] int32 with their entries' vectors [B * K, d], inverse norms and
+    categories [B * K] (item_vectors' / rerank's staging), labels [B] int32 or None, weight [B * K] float32 or None and
+    exposure, an int32 device counter over the items the call adds to, or None -> ListMetrics."""
+    B, K = ids.shape
+    dev = ids.device
+    i32 = lambda: torch.empty(B, dtype=torch.int32, device=dev)
+    f64 = lambda: torch.empty(B, dtype=torch.float64, device=dev)
+    n, n_cate, max_cate, hit_pos, pair_cos, weight_sum = i32(), i32(), i32(), i32(), f64(), f64()
+    ptr = lambda t: None if t is None else t.data_ptr()
+    L.check(lib.tlsan_list_metrics(ids.data_ptr(), vec.data_ptr(), inv.data_ptr(), cate.data_ptr(), ptr(labels), ptr(weight),
+                                   B, K, int(vec.shape[1]), n.data_ptr(), pair_cos.data_ptr(), n_cate.data_ptr(),
+                                   max_cate.data_ptr(), hit_pos.data_ptr(), weight_sum.data_ptr(), ptr(exposure),
+                                   0 if exposure is None else int(exposure.shape[0]), stream), "tlsan_list_metrics")
+    nd = n.to(torch.float64)
+    ild = 1.0 - pair_cos / (nd * (nd - 1.0) * 0.5)      # (n < 2: pair_cos is exactly 0 and so is the count of pairs -- 0 / 0, NaN)
+    return ListMetrics(n, pair_cos, ild, n_cate, max_cate, hit_pos, weight_sum)
+
+
+def list_metrics_chunks(ids, labels, rows, measure):
+    """ListMetrics of the lists ids [B, K], `rows` of them at a time (rerank_chunk: no staged matrix beyond
+    RERANK_STAGING): measure(ids_chunk, labels_chunk) -> ListMetrics of a chunk; the chunks' rows concatenated."""
+    parts = [measure(ids[r0:r0 + rows], None if labels is None else labels[r0:r0 + rows])
+             for r0 in range(0, int(ids.shape[0]), rows)]
+    return parts[0] if len(parts) == 1 else ListMetrics(*[torch.cat(f) for f in zip(*parts)])
+
+
 SIMILAR_METRICS = {"dot": L.SIM_DOT, "cosine": L.SIM_COSINE}
 SIMILAR_CHUNK = 4096   # queries per tlsan_similar_topk call: bounds the slices' lists in the workspace (Q x slices x K)
 
@@ -498,6 +562,81 @@ class TopKCounters:
         self.hits_r += hits
         self.n_r += n
         return [self.hits_r[i] / self.n_r for i in range(len(KS))]
+
+
+def exposure_stats(exposure, n_items):
+    """(coverage, gini) of an exposure counter over n_items items (array or tensor; int32 counters are read as the
+    uint32 the kernel adds to): the share of items with exposure > 0, and the Gini coefficient of the exposure over ALL
+    n_items items, sum_i (2 i - I - 1) x_(i) / (I sum x) over the ascending x_(1) <= ... <= x_(I) -- 0 when uniform,
+    (I - 1) / I when one item takes everything, NaN when nothing was exposed."""
+    x = exposure.detach().cpu().numpy() if isinstance(exposure, torch.Tensor) else np.asarray(exposure)
+    n_items = int(n_items)
+    x = np.sort(x.reshape(-1)[:n_items].astype(np.int64) & 0xFFFFFFFF)
+    if len(x) != n_items or n_items < 1:
+        raise ValueError("exposure: want a counter over %d items, got %d" % (n_items, len(x)))
+    total = int(x.sum())
+    if total == 0:
+        return 0.0, float("nan")
+    lead = int(((2 * np.arange(1, n_items + 1, dtype=np.int64) - n_items - 1) * x).sum())   # (exact: integers)
+    return float(int((x > 0).sum())) / n_items, float(lead) / (float(n_items) * float(total))
+
+
+class ListMetricCounters:
+    """Accumulates ListMetrics of batches of lists of one length K on the device; result() makes the one host read.
+    Integer quantities (rows, valid entries, categories, the histogram of hit positions) are summed exactly, the two
+    double sums (ILD over the rows with n >= 2, the weights) per batch and then over the batches: the result does not
+    depend on how the rows were split into batches beyond the rounding of those two sums (1e-12 relative)."""
+    N_INT = 6   # rows, short rows, sum n, rows n >= 1, sum n_cate, rows n >= 2; then [K + 1] rows by hit position + 1
+                # (0: no hit) and [K + 1] rows by max_cate -- counts, so that processes' states add up (reduce)
+
+    def __init__(self):
+        self.k = self._int = self._dbl = None
+
+    def add(self, metrics, k):
+        """Count a batch's ListMetrics (possibly of no rows); k: the length K of its lists (the same in every call)."""
+        k, m = int(k), metrics
+        if self.k is None:
+            self.k = k
+            self._int = torch.zeros(self.N_INT + 2 * (k + 1), dtype=torch.int64, device=m.n.device)
+            self._dbl = torch.zeros(2, dtype=torch.float64, device=m.n.device)
+        elif k != self.k:
+            raise ValueError("ListMetricCounters: lists of length %d after lists of length %d" % (k, self.k))
+        n, s, one = m.n.to(torch.int64), self._int, torch.ones_like(m.n, dtype=torch.int64)
+        s[:self.N_INT] += torch.stack([one.sum(), (n < k).sum(), n.sum(), (n >= 1).sum(),
+                                       m.n_cate.to(torch.int64).sum(), (n >= 2).sum()])     # (n_cate is 0 on an empty row)
+        s[self.N_INT:self.N_INT + k + 1].scatter_add_(0, m.hit_pos.to(torch.int64) + 1, one)
+        s[self.N_INT + k + 1:].scatter_add_(0, m.max_cate.to(torch.int64), one)
+        self._dbl += torch.stack([torch.where(m.n >= 2, m.ild, torch.zeros_like(m.ild)).sum(), m.weight_sum.sum()])
+
+    def reduce(self, total):
+        """Several processes' counters into one: total(tensor) -> the exact sum of an int64 / float64 tensor over them."""
+        self._int, self._dbl = total(self._int), total(self._dbl)
+
+    def result(self, exposure=None, n_items=None):
+        """-> {"ILD@K": mean ILD over the rows with n >= 2, "categories@K": mean n_cate over the rows with n >= 1,
+        "max_per_category": max of max_cate over the rows, "HR@K" / "NDCG@K" / "MRR@K": from the hit positions over ALL
+        rows with full_ranking_metrics' formulas (a hit at position p is worth 1, 1 / log2(p + 2), 1 / (p + 1)),
+        "novelty@K": sum weight_sum / sum n, "coverage@K" / "gini@K": exposure_stats of the exposure counter (NaN
+        without one), "rows", "short_rows": rows with n < K}, K the lists' length; a mean over no rows is NaN."""
+        if self.k is None:
+            raise ValueError("ListMetricCounters: nothing was added")
+        k = self.k
+        v = torch.cat([self._int, self._dbl.view(torch.int64)]).cpu().numpy()     # the one host read
+        ints, dbl = v[:-2], v[-2:].copy().view(np.float64)
+        rows, short, sum_n, rows1, sum_cate, rows2 = (int(x) for x in ints[:self.N_INT])
+        hits = ints[self.N_INT + 1:self.N_INT + k + 1]
+        by_max = np.nonzero(ints[self.N_INT + k + 1:])[0]
+        p = np.arange(k, dtype=np.float64)
+        ratio = lambda a, b: float(a) / b if b else float("nan")
+        cov, gini = (float("nan"), float("nan")) if exposure is None else \
+            exposure_stats(exposure, len(exposure) if n_items is None else n_items)
+        return {"ILD@%d" % k: ratio(dbl[0], rows2), "categories@%d" % k: ratio(sum_cate, rows1),
+                "max_per_category": int(by_max[-1]) if len(by_max) else 0,
+                "HR@%d" % k: ratio(int(hits.sum()), rows),
+                "NDCG@%d" % k: ratio(float((hits / np.log2(p + 2.0)).sum()), rows),
+                "MRR@%d" % k: ratio(float((hits / (p + 1.0)).sum()), rows),
+                "novelty@%d" % k: ratio(dbl[1], sum_n), "coverage@%d" % k: cov, "gini@%d" % k: gini,
+                "rows": rows, "short_rows": short}
 
 
 def hits_and_rows(ranks):
@@ -1276,6 +1415,29 @@ class Model(object):
             rerank(self.lib, pid[r0:r0 + rows], psc[r0:r0 + rows], vec, inv, cate, k, diversity, per_category,
                    ids[r0:r0 + rows], scores[r0:r0 + rows], st)
         return ids, scores
+
+    def list_metrics(self, ids, labels=None, item_weight=None, exposure=None):
+        """What the lists ids [B, K] (tensor or array of global item ids, -1 = no entry, anywhere; 1 <= K <= 256; for
+        instance what recommend returned) look like beside their accuracy -> ListMetrics, [B] device tensors
+        (tlsan_list_metrics): valid entries, summed pairwise cosines (similar_items' / recommend's cosine of
+        [item_emb || cate_emb[item_cate]]) and the intra-list diversity ILD, distinct categories and the most entries
+        sharing one (<= m for a list made with per_category=m), the position of labels [B] (None: -1 everywhere) and the
+        summed item_weight [item_count] of the entries (the novelty hook: input.item_self_information).  exposure: a
+        [item_count] int32 device counter; every valid entry adds 1 to its item's (never cleared here).  Rows go through
+        in rerank_chunk pieces, staged as recommend's second stage stages them.  Like similar_items it reads the tables as
+        stored: an owed lazy-L2 correction lands first, the scale is NOT folded -- parameters, scale and state keep their
+        bits.  A wrong shape, K outside 1..256 or an id >= item_count is a ValueError before any launch."""
+        ids, labels, item_weight = list_metric_inputs(ids, labels, item_weight, exposure, self.config["item_count"], self.device)
+        self._flush()
+        st = self._stream()
+
+        def measure(sub, lab):
+            flat = sub.reshape(-1)
+            vec, inv = item_vectors(self.lib, self.dims, self.cparams, flat, 1, 0, st)
+            g = flat.clamp(min=0).long()
+            return list_metrics(self.lib, sub, vec, inv, self.item_cate[g], lab,
+                                None if item_weight is None else item_weight[g], exposure, st)
+        return list_metrics_chunks(ids, labels, rerank_chunk(ids.shape[1], self.config["hidden_units"]), measure)
 
     def similar_items(self, items, k, metric="cosine", exclude=None):
         """The k nearest items of each item of `items` (a 1-D list, array or tensor of global ids; outside

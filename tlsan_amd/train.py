@@ -23,8 +23,9 @@ import time
 import numpy as np
 import torch
 
-from .input import DataInput, DataInputTest, PackedSet, load_packed
-from .model import KS, LAZY_ADAGRAD_OPTIMIZERS, Model, SeenItems, full_ranking_metrics, hits_and_rows, metrics_from_histogram
+from .input import DataInput, DataInputTest, PackedSet, item_self_information, load_packed
+from .model import (KS, LAZY_ADAGRAD_OPTIMIZERS, ListMetricCounters, ListMetrics, Model, SeenItems, full_ranking_metrics,
+                    hits_and_rows, metrics_from_histogram)
 
 FLAGS = [  # (name, type, default)  -- train.py:26-54
     ("hidden_units", int, 64), ("num_blocks", int, 1), ("num_heads", int, 8), ("Ls", int, 10),
@@ -83,6 +84,11 @@ def parse(argv=None):
     ap.add_argument("--recommend_pool", type=int, default=0,
                     help="with --recommend_diversity / --recommend_per_category: the best N items per row the list is picked "
                          "from, recommend_k <= N <= 256 (0 = min(256, max(4 K, 32)))")
+    ap.add_argument("--recommend_metrics", type=int, default=0, choices=[0, 1],
+                    help="with --recommend_k: 1 = measure the lists over the whole test set (Model.list_metrics: ILD, categories, "
+                         "the largest per-category count, HR / NDCG / MRR of the test positives, novelty by the training "
+                         "set's self-information, catalogue coverage and the Gini coefficient of the exposure), print them "
+                         "and write <model_dir>/recommend_top<K>_metrics.json")
     ap.add_argument("--similar_k", type=int, default=0,
                     help="at the end of training, write <model_dir>/similar-<K>.npz: the K nearest items of every item "
                          "(item [I], ids [I, K], scores [I, K]; 0 = off)")
@@ -101,7 +107,10 @@ def parse(argv=None):
                          "has not seen and report HR@k, NDCG@k (k = 1, 5, 10, 20) and MRR; what counts as seen: 'none' = "
                          "nothing, 'history' = the row's input, 'seen' = every item of the user's training samples and the "
                          "row's input (leave-one-out).  The label itself is never excluded.  'off' = no such evaluation")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.recommend_metrics and not args.recommend_k:
+        ap.error("--recommend_metrics measures the lists of --recommend_k: give --recommend_k")
+    return args
 
 
 def sampled_line(n, res):
@@ -112,6 +121,11 @@ def sampled_line(n, res):
 def full_ranking_line(mode, res):
     """The driver's line of full-ranking metrics (full_ranking_metrics' dict)."""
     return "Full ranking (exclude=%s): " % mode + " ".join("%s = %.4f" % (k, v) for k, v in res.items())
+
+
+def list_metrics_line(res):
+    """The driver's line of list metrics (ListMetricCounters.result's dict)."""
+    return "List metrics: " + " ".join(("%s = %d" if isinstance(v, int) else "%s = %.4f") % (k, v) for k, v in res.items())
 
 
 def exclude_arg(mode, seen):
@@ -138,6 +152,21 @@ def write_recommendations(model_dir, k, user, ids, scores, settings=None):
                                          pool=np.int64(settings["pool"] or 0))
     np.savez(path, user=np.asarray(user, np.int64), ids=np.asarray(ids, np.int32), scores=np.asarray(scores, np.float32),
              **extra)
+    return path
+
+
+def list_metrics_path(model_dir, k):
+    return os.path.join(model_dir, "recommend_top%d_metrics.json" % k)
+
+
+def write_list_metrics(model_dir, k, res, settings=None):
+    """The result dict of the lists' measurement beside the lists, with the diversity settings they were made with."""
+    path = list_metrics_path(model_dir, k)
+    s = settings or {}
+    out = dict(res, diversity=float(s.get("diversity", 0.0)), per_category=int(s.get("per_category", 0)),
+               pool=int(s.get("pool") or 0))
+    with open(path, "w") as f:
+        json.dump(out, f, indent=2)
     return path
 
 
@@ -352,13 +381,39 @@ def eval_prec_recall(model, test_set, config, rows=None, summary=True):
     return prec, recall
 
 
-def recommend_test_set(model, rows, k, exclude, **settings):
+class ListMeasurement:
+    """The measurement of --recommend_metrics: called with every launch's device lists as recommend_test_set makes
+    them, it counts their ListMetrics (labels: the test positives; weights: the training set's self-information) and one
+    exposure counter; result() sums both over the processes -> ListMetricCounters.result's dict, on every rank."""
+
+    def __init__(self, model, rows, k, train_set):
+        self.model, self.rows, self.k, self.items = model, rows, k, rows.config["item_count"]
+        self.weight = torch.as_tensor(item_self_information(train_set, self.items)).to(model.device)
+        self.exposure = torch.zeros(self.items, dtype=torch.int32, device=model.device)
+        self.counters = ListMetricCounters()
+
+    def __call__(self, db, ids, real):
+        ids = ids.clone()
+        ids[real:] = -1       # (rows past `real` pad a launch: measured with the others -- the call is collective -- as empty lists)
+        m = self.model.list_metrics(ids, labels=db.i, item_weight=self.weight, exposure=self.exposure)
+        self.counters.add(ListMetrics(*[f[:real] for f in m]), self.k)
+
+    def result(self):
+        self.counters.reduce(self.rows.sum)
+        return self.counters.result(self.rows.sum(self.exposure.to(torch.int64)), self.items)
+
+
+def recommend_test_set(model, rows, k, exclude, on_lists=None, **settings):
     """model.recommend over every test row (settings: its diversity keywords) -> (user, ids, scores) host arrays in
-    test-set order; None but on rank 0."""
+    test-set order; None but on rank 0.  on_lists(device batch, ids, real): called with every launch's device lists
+    [rows, k] before they leave the device (ListMeasurement)."""
     parts = []
     for batch, real, _ in rows.launches(True):
         db = model.device_batch(batch, is_test=True)
-        parts.append(rows.gather((db.u,) + tuple(model.recommend(db, k, exclude=exclude, **settings)), real))
+        ids, scores = model.recommend(db, k, exclude=exclude, **settings)
+        if on_lists is not None:
+            on_lists(db, ids, real)
+        parts.append(rows.gather((db.u, ids, scores), real))
     if parts[0] is not None:
         return tuple(torch.cat(x).cpu().numpy() for x in zip(*parts))
 
@@ -469,10 +524,18 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
     model.save(None)                                           # train.py:239
     if args.recommend_k:
         settings = recommend_settings(args)
-        rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen), **settings)
+        # (a DevicePackedSet keeps the host set it was made from: the novelty weights are counted on the host)
+        measure = ListMeasurement(model, rows, args.recommend_k, getattr(train_set, "ps", train_set)) \
+            if args.recommend_metrics else None
+        rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen), on_lists=measure,
+                                 **settings)
+        list_res = measure.result() if measure is not None else None       # (collective: every rank)
         if rec is not None:                                    # (rank 0 holds the rows)
             path = write_recommendations(args.model_dir, args.recommend_k, *rec, settings=settings)
             say("Recommendations: %s" % path)
+            if list_res is not None:
+                say(list_metrics_line(list_res))
+                say("List metrics: %s" % write_list_metrics(args.model_dir, args.recommend_k, list_res, settings))
     if args.similar_k:
         path = write_similar(model, args.model_dir, args.similar_k, args.similar_metric, rows.config["item_count"],
                              write=rows.rank in (None, 0))
@@ -496,6 +559,8 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
         res["sampled"] = final_sampled
     if final_full is not None:
         res["full_ranking"] = final_full
+    if args.recommend_k and list_res is not None:
+        res["list_metrics"] = list_res
     return res
 
 
