@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define TLSAN_ABI_VERSION 14
+#define TLSAN_ABI_VERSION 15
 
 enum {
   TLSAN_OK = 0,
@@ -385,6 +385,49 @@ int tlsan_batch_pack(const tlsan_packed* set, const int32_t* order, int32_t lo, 
 #define TLSAN_INDEX_FOR_LAZY_SGD 0x100
 int tlsan_batch_index(const tlsan_dims* dims, const tlsan_batch* b, const int32_t* item_cate, void* state, int32_t slot,
                       void* stream);
+
+/* For tests and tools (ABI 15): a read-only view of an index slot and of the form it is built in.  Host-only: both calls
+ * launch nothing and touch no device memory.  Nothing in the product calls them.
+ *
+ * tlsan_index_layout_of: where the destination index of slot `slot` (0 .. 2) lives inside the state buffer, as BYTE
+ * OFFSETS from the state's first byte (the caller slices its own buffer), from the one definition of the state's layout.
+ * All arrays are int32 but the records (four int32 each: row, first position, uses, 0):
+ *   cnt_item [I], cnt_uc [C], cnt_user [U]     use counters, zero at rest (a build adds, the consuming step counts back)
+ *   off_*    [n + 1]                           first sorted position of every row, off[n] = all uses
+ *   cur_*    [n]                               fill cursors (== off after a build; cur_uc is advanced by the category lists)
+ *   urec_item, urec_user                       records of the used rows, ascending by row
+ *   perm     [rank_cap]                        the batch's ranking for the fused kernel's workgroups (16 places per group)
+ *   uc_list  [uc_list_cap]                     the samples of every category, category c at [off_uc[c], off_uc[c + 1])
+ *   hot_list [ap_hot_cap]                      record slots (urec_item) of the item rows with more than ap_hot uses
+ *   flag_user [ceil(U / 256)]                  marks of the 256-row pieces of the user counters, zero at rest
+ *   scan_ticket [3]                            arrival counters of the scan, one per slot (the same offset for every slot), zero at rest
+ *   n_uniq, n_hot                              the header's words of the slot: used rows [item, user] (two int32), hot rows */
+typedef struct {
+  int64_t cnt_item, cnt_uc, cnt_user;
+  int64_t off_item, off_uc, off_user;
+  int64_t cur_item, cur_uc, cur_user;
+  int64_t urec_item, urec_user;
+  int64_t perm, uc_list, hot_list, flag_user;
+  int64_t scan_ticket;
+  int64_t n_uniq, n_hot;
+  int32_t rank_cap, uc_list_cap;
+  int32_t ap_hot, ap_hot_cap;
+} tlsan_index_layout;
+int tlsan_index_layout_of(const tlsan_dims* dims, int32_t slot, tlsan_index_layout* out);
+
+/* tlsan_index_plan_of: the form tlsan_batch_index builds the index in for a batch of B samples with Sn session columns;
+ * flags: 0 or TLSAN_INDEX_FOR_LAZY_SGD.  Reads only these numbers and the dims (and the library's environment switches). */
+typedef struct {
+  int32_t cseg;        /* category segments: item uses are counted into their item's category as well */
+  int32_t uc_list;     /* the samples of every category are listed */
+  int32_t usort;       /* the user side comes from a sort of the batch's ids: no user counters */
+  int32_t isort;       /* the item side comes from a partitioned counting sort: no item counters */
+  int32_t sparse;      /* bit t (0 item, 1 category, 2 user): off / cur of that table are written for the used rows only */
+  int32_t rank;        /* a ranking of the batch is written */
+  int32_t by_window;   /* ... keyed by window length (> 0) or by session and window (0) */
+  int32_t two_level;   /* the scan takes its two-launch form (a table of more than 16 chunks of 4096 rows) */
+} tlsan_index_plan;
+int tlsan_index_plan_of(const tlsan_dims* dims, int32_t B, int32_t Sn, int32_t flags, tlsan_index_plan* out);
 
 /* Gradients only (no update) -- what `tf.gradients(self.loss, trainables)` (model.py:198)
  * returns, with duplicate ids summed and reg*W added for the four regularised tables.

@@ -22,7 +22,7 @@ def test_adagrad_kinds_in_header_and_lib():
         assert m is not None, name
         assert int(m.group(1)) == val
     assert (L.OPT_ADAGRAD, L.OPT_ROWWISE_ADAGRAD) == (4, 5)
-    assert re.search(r"#define\s+TLSAN_ABI_VERSION\s+14\b", hdr)
+    assert re.search(r"#define\s+TLSAN_ABI_VERSION\s+15\b", hdr)
 
 
 def test_optimizer_table():

@@ -30,7 +30,7 @@ def test_candidate_symbols_declared_and_exported():
         assert name in declared and name in L.EXPORTS, name
         assert hasattr(lib, name), name
     assert L.NEG_MAX == 1024
-    assert lib.tlsan_abi_version() == 14
+    assert lib.tlsan_abi_version() == 15
 
 
 def test_candidate_bad_arguments_are_rejected_without_a_launch():

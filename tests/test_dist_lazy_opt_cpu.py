@@ -22,7 +22,7 @@ def test_header_declares_the_entry_points_and_the_abi_version_stays():
     for name in NAMES:
         assert re.search(r"\b%s\s*\(" % name, hdr), name
         assert name in L.EXPORTS and hasattr(lib, name)
-    assert lib.tlsan_abi_version() == 14
+    assert lib.tlsan_abi_version() == 15
 
 
 def test_workspace_query_is_positive_and_monotone():

@@ -20,8 +20,8 @@ def test_header_and_exports():
     hdr = open(os.path.join(ROOT, "include", "tlsan.h")).read()
     assert re.search(r"\bint\s+tlsan_list_metrics\(", hdr)
     assert "tlsan_list_metrics" in L.EXPORTS and hasattr(L.load(), "tlsan_list_metrics")
-    assert re.search(r"#define\s+TLSAN_ABI_VERSION\s+14\b", hdr)
-    assert L.ABI_VERSION == 14 and L.load().tlsan_abi_version() == 14
+    assert re.search(r"#define\s+TLSAN_ABI_VERSION\s+15\b", hdr)
+    assert L.ABI_VERSION == 15 and L.load().tlsan_abi_version() == 15
     assert L.LISTM_MAX == 256 == L.TOPK_MAX == L.RERANK_MAX
     from tlsan_amd import build
     assert "tlsan_listm.hip" in build.SOURCES

@@ -17,8 +17,8 @@ def test_header_and_exports():
     hdr = open(os.path.join(ROOT, "include", "tlsan.h")).read()
     assert re.search(r"\bint\s+tlsan_rerank\(", hdr)
     assert "tlsan_rerank" in L.EXPORTS and hasattr(L.load(), "tlsan_rerank")
-    assert re.search(r"#define\s+TLSAN_ABI_VERSION\s+14\b", hdr)
-    assert L.ABI_VERSION == 14 and L.load().tlsan_abi_version() == 14
+    assert re.search(r"#define\s+TLSAN_ABI_VERSION\s+15\b", hdr)
+    assert L.ABI_VERSION == 15 and L.load().tlsan_abi_version() == 15
     assert L.RERANK_MAX == 256 == L.TOPK_MAX
 
 

@@ -25,8 +25,8 @@ def test_header_and_exports():
         m = re.search(r"#define\s+%s\s+(\d+)" % name, hdr)
         assert m is not None and int(m.group(1)) == val, name
     assert (L.SIM_DOT, L.SIM_COSINE) == (0, 1)
-    assert re.search(r"#define\s+TLSAN_ABI_VERSION\s+14\b", hdr)
-    assert L.ABI_VERSION == 14 and L.load().tlsan_abi_version() == 14
+    assert re.search(r"#define\s+TLSAN_ABI_VERSION\s+15\b", hdr)
+    assert L.ABI_VERSION == 15 and L.load().tlsan_abi_version() == 15
 
 
 def test_arguments_are_refused_without_a_launch():

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # (TLSAN_LIB_PATH: a diagnostic build of the same library, e.g. the -DTLSAN_STAMPS=1 variant of scripts/stamps.py)
 LIB_PATH = os.environ.get("TLSAN_LIB_PATH") or os.path.join(HERE, "libtlsan_hip.so")
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 NORM_TF18, NORM_DEDUP = 0, 1
 TABLE_F32, TABLE_BF16 = 0, 1
 MATRIX_F32, MATRIX_BF16 = 0, 1
@@ -27,7 +27,7 @@ EXPORTS = [
     "tlsan_abi_version", "tlsan_last_error", "tlsan_dense_layout_of", "tlsan_workspace_bytes",
     "tlsan_state_bytes", "tlsan_state_init", "tlsan_state_reindex", "tlsan_state_recategorize", "tlsan_state_scale",
     "tlsan_state_renorm", "tlsan_state_flush", "tlsan_sync_derived", "tlsan_forward", "tlsan_forward_att",
-    "tlsan_train_step", "tlsan_train_step_opt", "tlsan_batch_pack", "tlsan_batch_index", "tlsan_grads", "tlsan_eval_ranks", "tlsan_eval_label_scores", "tlsan_eval_counts_shard",
+    "tlsan_train_step", "tlsan_train_step_opt", "tlsan_batch_pack", "tlsan_batch_index", "tlsan_index_layout_of", "tlsan_index_plan_of", "tlsan_grads", "tlsan_eval_ranks", "tlsan_eval_label_scores", "tlsan_eval_counts_shard",
     "tlsan_eval_ranks_excl", "tlsan_eval_counts_shard_excl",
     "tlsan_topk_workspace_bytes", "tlsan_eval_topk", "tlsan_topk_merge",
     "tlsan_item_vectors", "tlsan_similar_workspace_bytes", "tlsan_similar_topk", "tlsan_rerank", "tlsan_list_metrics",
@@ -62,6 +62,17 @@ class DenseLayout(C.Structure):
 class Batch(C.Structure):
     _fields_ = [("B", C.c_int32), ("Sn", C.c_int32)] + [(n, C.c_void_p) for n in
                 ("u", "i", "j", "y", "hist_i", "hist_i_new", "hist_t", "sl", "sl_new", "u_cate")]
+
+
+class IndexLayout(C.Structure):     # tlsan_index_layout (include/tlsan.h): byte offsets into the state, for tests and tools
+    _fields_ = [(n, C.c_int64) for n in
+                ("cnt_item", "cnt_uc", "cnt_user", "off_item", "off_uc", "off_user", "cur_item", "cur_uc", "cur_user",
+                 "urec_item", "urec_user", "perm", "uc_list", "hot_list", "flag_user", "scan_ticket", "n_uniq", "n_hot")] + \
+               [(n, C.c_int32) for n in ("rank_cap", "uc_list_cap", "ap_hot", "ap_hot_cap")]
+
+
+class IndexPlan(C.Structure):       # tlsan_index_plan (include/tlsan.h)
+    _fields_ = [(n, C.c_int32) for n in ("cseg", "uc_list", "usort", "isort", "sparse", "rank", "by_window", "two_level")]
 
 
 class Packed(C.Structure):
@@ -181,6 +192,10 @@ def load():
     lib.tlsan_batch_pack.restype = C.c_int
     lib.tlsan_batch_index.argtypes = [P(Dims), P(Batch), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.tlsan_batch_index.restype = C.c_int
+    lib.tlsan_index_layout_of.argtypes = [P(Dims), C.c_int32, P(IndexLayout)]
+    lib.tlsan_index_layout_of.restype = C.c_int
+    lib.tlsan_index_plan_of.argtypes = [P(Dims), C.c_int32, C.c_int32, C.c_int32, P(IndexPlan)]
+    lib.tlsan_index_plan_of.restype = C.c_int
     lib.tlsan_grads.argtypes = [P(Dims), P(Params), P(Batch), P(HParams), P(GradsOut), P(StepOut),
                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.tlsan_eval_ranks.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_void_p, C.c_int32,

@@ -199,14 +199,16 @@ void carve(const tlsan_dims* d, const Shape& s, int B, int Sn, char* base, Ws* w
   w->bytes = o;
 }
 
+// a table of more scan blocks (chunks of 4096 rows) than SCAN_TWO_LEVEL_BLOCKS: the scan's two-launch form
+static bool scan_two_level(const int32_t n[3]) {
+  for (int k = 0; k < 3; ++k)
+    if ((n[k] + 4095) / 4096 > SCAN_TWO_LEVEL_BLOCKS) return true;
+  return false;
+}
 // exclusive scans of up to three count arrays in one launch (two for large tables, see k_index_scan);
 // bsum: scratch of >= nscan packed sums, or NULL (then always the single launch)
 int launch_scan(ScanArgs& sa, int nscan, long long* bsum, hipStream_t hs) {
-  int big = 0;
-  for (int k = 0; k < 3; ++k) {
-    const int nb = (k < 2 ? sa.blk0[k + 1] : nscan) - sa.blk0[k];
-    if (nb > SCAN_TWO_LEVEL_BLOCKS) big = 1;
-  }
+  const bool big = scan_two_level(sa.n);
   sa.bsum = nullptr;
   if (big && bsum) {
     sa.bsum = bsum;
@@ -269,7 +271,8 @@ struct St {  // persistent state
 static void carve_state(const tlsan_dims* d, const Shape& shp, char* base, St* s) {
   const Capacity cap = plan_capacity(d, shp, 1);   // (the state's answers do not depend on the batch)
   size_t o = 0;
-  auto take = [&](size_t n) { char* p = base ? base + o : nullptr; o += al(n); return p; };
+  // (a NULL base leaves every pointer as its byte offset into the state: tlsan_state_bytes, tlsan_index_layout_of)
+  auto take = [&](size_t n) { char* p = base + o; o += al(n); return p; };
   s->nbI = (d->item_count + AP_ROWS_PB - 1) / AP_ROWS_PB;
   s->nbU = (d->user_count + AP_ROWS_PB - 1) / AP_ROWS_PB;
   s->nbC = d->cate_count;
@@ -631,6 +634,11 @@ int tlsan_forward_att(const tlsan_dims* d, const tlsan_params* p, const tlsan_ba
   return launch_fwd(s, false, fp, a, (hipStream_t)stream);
 }
 
+// rows per table [item, category, user] that the index scan walks: a side that comes from a sort of the batch's ids has none
+static void scanned_rows(const tlsan_dims* d, const IndexPlan& ix, int32_t n[3]) {
+  n[0] = ix.isort ? 0 : d->item_count; n[1] = d->cate_count; n[2] = ix.usort ? 0 : d->user_count;
+}
+
 // destination index of a batch into slot k: use counts per destination row -> first sorted position
 // of every row (+ records of the used rows)
 static int build_index(const tlsan_dims* d, const tlsan_batch* b, const IndexPlan& ix, const int32_t* item_cate, const St& st,
@@ -685,12 +693,11 @@ static int build_index(const tlsan_dims* d, const tlsan_batch* b, const IndexPla
   sa.cnt[0] = st.cnt_item[k]; sa.cnt[1] = st.cnt_uc[k]; sa.cnt[2] = st.cnt_user[k];
   sa.off[0] = st.off_item[k]; sa.off[1] = st.off_uc[k]; sa.off[2] = st.off_user[k];
   sa.cur[0] = st.cur_item[k]; sa.cur[1] = st.cur_uc[k]; sa.cur[2] = st.cur_user[k];
-  sa.n[0] = isort ? 0 : d->item_count; sa.n[1] = d->cate_count; sa.n[2] = d->user_count;
+  scanned_rows(d, ix, sa.n);
   sa.blk0[0] = 0;
   sa.blk0[1] = (sa.n[0] + 4095) / 4096;
   sa.blk0[2] = sa.blk0[1] + (sa.n[1] + 4095) / 4096;
   if (usort) {
-    sa.n[2] = 0;
     if (!isort) {   // (with the items sorted as well, k_isort_bucket's launch had it)
       sa.us.u = b->u; sa.us.B = b->B; sa.us.U = d->user_count;
       sa.us.cur = st.cur_user[k]; sa.us.off = st.off_user[k]; sa.us.urec = st.urec_user[k]; sa.us.n_uniq = &st.hdr->n_uniq[k][1];
@@ -901,6 +908,51 @@ int tlsan_batch_index(const tlsan_dims* d, const tlsan_batch* b, const int32_t* 
   if (!state) return fail(TLSAN_E_WORKSPACE, "state is NULL");
   carve_state(d, s, (char*)state, &st);
   return build_index(d, b, plan_index(d, s, b, lazy_sgd), item_cate, st, slot, (hipStream_t)stream);
+}
+
+// (for tests and tools: where an index slot lives in the state -- carve_state's own answers, as offsets from a null base)
+int tlsan_index_layout_of(const tlsan_dims* d, int32_t slot, tlsan_index_layout* out) {
+  Shape s; St st;
+  int rc = shape_of(d, &s);
+  if (rc) return rc;
+  if (!out) return fail(TLSAN_E_BADARG, "tlsan_index_layout_of: out is NULL");
+  if (slot < 0 || slot >= TLSAN_INDEX_SLOTS) return fail(TLSAN_E_BADARG, "index slot must be 0 .. %d", TLSAN_INDEX_SLOTS - 1);
+  carve_state(d, s, nullptr, &st);
+  auto at = [](const void* p) { return (int64_t)(uintptr_t)p; };
+  const Capacity cap = plan_capacity(d, s, 1);
+  memset(out, 0, sizeof(*out));
+  out->cnt_item = at(st.cnt_item[slot]); out->cnt_uc = at(st.cnt_uc[slot]); out->cnt_user = at(st.cnt_user[slot]);
+  out->off_item = at(st.off_item[slot]); out->off_uc = at(st.off_uc[slot]); out->off_user = at(st.off_user[slot]);
+  out->cur_item = at(st.cur_item[slot]); out->cur_uc = at(st.cur_uc[slot]); out->cur_user = at(st.cur_user[slot]);
+  out->urec_item = at(st.urec_item[slot]); out->urec_user = at(st.urec_user[slot]);
+  out->perm = at(st.perm[slot]); out->uc_list = at(st.uc_list[slot]); out->hot_list = at(st.hot_list[slot]);
+  out->flag_user = at(st.flag_user[slot]);
+  out->scan_ticket = at(st.scan_ticket);
+  out->n_uniq = at(st.hdr) + (int64_t)(offsetof(StateHdr, n_uniq) + sizeof(int32_t) * 2 * slot);
+  out->n_hot = at(st.hdr) + (int64_t)(offsetof(StateHdr, n_hot) + sizeof(int32_t) * slot);
+  out->rank_cap = cap.rank_cap; out->uc_list_cap = cap.uc_list_cap;
+  out->ap_hot = AP_HOT; out->ap_hot_cap = AP_HOT_CAP;
+  return TLSAN_OK;
+}
+
+// (for tests and tools: what plan_index decides for a batch of B samples with Sn session columns -- host fields only)
+int tlsan_index_plan_of(const tlsan_dims* d, int32_t B, int32_t Sn, int32_t flags, tlsan_index_plan* out) {
+  Shape s;
+  int rc = shape_of(d, &s);
+  if (rc) return rc;
+  if (!out || B < 1 || Sn < 0) return fail(TLSAN_E_BADARG, "tlsan_index_plan_of: bad arguments (B=%d, Sn=%d)", B, Sn);
+  if (flags & ~TLSAN_INDEX_FOR_LAZY_SGD) return fail(TLSAN_E_BADARG, "tlsan_index_plan_of: flags must be 0 or TLSAN_INDEX_FOR_LAZY_SGD");
+  tlsan_batch b;
+  memset(&b, 0, sizeof(b));
+  b.B = B; b.Sn = Sn;
+  const IndexPlan ix = plan_index(d, s, &b, (flags & TLSAN_INDEX_FOR_LAZY_SGD) != 0);
+  int32_t n[3];
+  scanned_rows(d, ix, n);
+  memset(out, 0, sizeof(*out));
+  out->cseg = ix.cseg; out->uc_list = ix.uc_list; out->usort = ix.usort; out->isort = ix.isort;
+  out->sparse = ix.sparse; out->rank = ix.rank; out->by_window = ix.by_window;
+  out->two_level = scan_two_level(n) ? 1 : 0;
+  return TLSAN_OK;
 }
 
 // (rows: the four tables of the set are [rows] floats -- TLSAN_OPT_ROWWISE_ADAGRAD -- whose strides are not looked at)
