@@ -565,6 +565,40 @@ int tlsan_similar_topk(const tlsan_dims* dims, const tlsan_params* p, const floa
                        const int32_t* excl_ids, int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws,
                        size_t ws_bytes, void* stream);
 
+/* Scoped lists: tlsan_eval_topk and tlsan_similar_topk over a SUBSET of the table's items, with an optional category
+ * wanted per row ("the best K within these items", "more from this department").  Everything the unscoped calls say
+ * about scores, order, K, the exclusion lists, padding rows, short rows and the item-sharded form holds unchanged; the
+ * scores of a (row, item) pair are theirs bit for bit, and so are tlsan_eval_label_scores' and tlsan_score_candidates'.
+ *   sub [nsub] / nsub: the scope, LOCAL item indices of this table (global id = sub[n] * id_mul + id_add), ascending
+ *     and distinct, 0 <= nsub <= item_count; sub NULL with nsub < 0: every item of the table.  Only the scope's items
+ *     are scored: the work is that of nsub items, not of item_count.  nsub == 0: every row comes back id -1, score -inf.
+ *     An index outside [0, item_count) is never read as a table row and never selected (the rest of the list counts as
+ *     if it were not there).  The order and distinctness of sub are the caller's to keep: they are not checked, and a
+ *     repeated index can appear twice in a list.
+ *   row_cate [B] (tlsan_similar_topk_scoped: [Q]) or NULL: row b selects item n only when row_cate[b] < 0 or
+ *     p->item_cate[n] == row_cate[b].  A category no item of the scope has gives an all -1 / -inf row.  The category
+ *     test narrows what is selected, not what is scored: without sub the whole table is still scanned.
+ *   No dense [item_count, d] matrix is built, whatever the table's size.
+ *   A row's result does not depend on B (Q), on the other rows, on the launch geometry or on the number of ranks: in
+ *     the item-sharded form every rank passes the scope's items ITS table holds and the ranks' lists merge with
+ *     tlsan_topk_merge.
+ * Neither call changes the parameters, P or any state.
+ * Workspace: tlsan_scope_workspace_bytes, for both calls (0, with tlsan_last_error set, for bad dims / K / B, or nsub >
+ * item_count).  Refused before any launch, with the function's name in tlsan_last_error: what the unscoped call refuses,
+ * with its code; sub NULL with nsub >= 0, sub given with nsub < 0, nsub > item_count (TLSAN_E_BADARG); a workspace that
+ * is NULL or too small (TLSAN_E_WORKSPACE).  The three functions are additions: nothing else in the ABI changed
+ * (TLSAN_ABI_VERSION stays 15). */
+size_t tlsan_scope_workspace_bytes(const tlsan_dims* dims, int32_t B, int32_t K, int32_t nsub);
+int tlsan_eval_topk_scoped(const tlsan_dims* dims, const tlsan_params* p, const float* u_t, int32_t B, int32_t K,
+                           const int32_t* excl_off, const int32_t* excl_ids, const int32_t* sub, int32_t nsub,
+                           const int32_t* row_cate, int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws,
+                           size_t ws_bytes, void* stream);
+int tlsan_similar_topk_scoped(const tlsan_dims* dims, const tlsan_params* p, const float* qvec, const float* qinv,
+                              const int32_t* qids, int32_t Q, int32_t K, int32_t metric, const int32_t* excl_off,
+                              const int32_t* excl_ids, const int32_t* sub, int32_t nsub, const int32_t* row_cate,
+                              int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws, size_t ws_bytes,
+                              void* stream);
+
 /* Diversified lists: the second stage behind tlsan_eval_topk.  From each row's POOL of N entries (1 <= K <= N <= 256, in
  * tlsan_eval_topk's order: higher score first, ties -> lower global id) pick K by greedy maximal marginal relevance
  * under a per-category cap.  Pool entry j of a row has a global id g_j and the model score s_j (pool_ids, pool_scores

@@ -1,12 +1,13 @@
 // tlsan_api_eval.hip -- the evaluation entry points of the C ABI (include/tlsan.h): ranks of the labels among all items,
-// top-K items, similar-items lists, diversified lists, caller-given candidates and negative sampling.  The kernels of tlsan_eval.h are compiled
-// here; the top-K, similar-items, re-ranking and candidate kernels in units of their own (tlsan_topk.hip, tlsan_similar.hip, tlsan_rerank.hip, tlsan_cand.hip).
+// top-K items, similar-items lists, scoped lists, diversified lists, caller-given candidates and negative sampling.  The kernels of tlsan_eval.h are compiled
+// here; the top-K, similar-items, scoped, re-ranking and candidate kernels in units of their own (tlsan_topk.hip, tlsan_similar.hip, tlsan_scope.hip, tlsan_rerank.hip, tlsan_cand.hip).
 #include <stdio.h>
 
 #include "tlsan_host.h"
 #include "tlsan_eval.h"
 #include "tlsan_topk.h"
 #include "tlsan_similar.h"
+#include "tlsan_scope.h"
 #include "tlsan_rerank.h"
 #include "tlsan_cand.h"
 
@@ -283,6 +284,123 @@ int tlsan_similar_topk(const tlsan_dims* d, const tlsan_params* p, const float* 
   if ((err = tlsan_launch_similar_topk(sa, s.D, nsl, hs)) != hipSuccess)
     return fail(TLSAN_E_LAUNCH, "k_similar_topk: %s", hipGetErrorString(err));
   if (nsl > 1 && (err = tlsan_launch_topk_merge(w.t.ids, w.t.scores, Q, nsl, K, ids, scores, hs)) != hipSuccess)
+    return fail(TLSAN_E_LAUNCH, "k_topk_merge: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+// ---- scoped lists (tlsan_scope.h) ----
+struct ScopeWs {
+  int32_t* ids;        // [B, nsl, K] the slices' lists (nsl > 1)
+  float* scores;
+  float* inv;          // [I] inv of the scope's items, by local item (the cosine form)
+  size_t bytes;
+  int nsl;
+};
+
+// positions of a scope: nsub, or the whole table (nsub < 0)
+static int scope_count(const tlsan_dims* d, int32_t nsub) { return nsub < 0 ? d->item_count : nsub; }
+
+static void carve_scope(const tlsan_dims* d, int B, int K, int32_t nsub, char* base, ScopeWs* w) {
+  size_t o = 0;
+  auto take = [&](size_t n) { char* p = base ? base + o : nullptr; o += al(n); return p; };
+  const int nsl = w->nsl = eval_slices((B + 15) / 16, ((scope_count(d, nsub) + 63) / 64 + 3) / 4);
+  const size_t nc = nsl > 1 ? (size_t)B * nsl * K : 0;
+  w->ids = (int32_t*)take(4 * nc);
+  w->scores = (float*)take(4 * nc);
+  w->inv = (float*)take(sizeof(float) * (size_t)d->item_count);
+  w->bytes = o;
+}
+
+// what both scoped entry points refuse about (B or Q, K, the exclusion lists, the id mapping, the scope, the workspace)
+static int scope_check(const char* fn, const tlsan_dims* d, int32_t B, int32_t K, const int32_t* excl_off,
+                       const int32_t* excl_ids, const int32_t* sub, int32_t nsub, int32_t id_mul, int32_t id_add, void* ws,
+                       size_t ws_bytes, ScopeWs* w) {
+  if (K < 1 || K > TOPK_MAX) return fail(TLSAN_E_BADARG, "%s: K must be in 1..%d (got %d)", fn, TOPK_MAX, K);
+  if (!excl_off != !excl_ids) return fail(TLSAN_E_BADARG, "%s: excl_off and excl_ids go together", fn);
+  if (!eval_ids_ok(d, id_mul, id_add))
+    return fail(TLSAN_E_BADARG, "%s: global ids n * id_mul + id_add must be non-negative int32", fn);
+  if (!sub != (nsub < 0))
+    return fail(TLSAN_E_BADARG, "%s: sub and nsub go together (sub NULL with nsub < 0: the whole table; got nsub %d)", fn, nsub);
+  if (nsub > d->item_count)
+    return fail(TLSAN_E_BADARG, "%s: nsub %d exceeds the table's %d items (sub holds distinct indices)", fn, nsub, d->item_count);
+  if (!ws) return fail(TLSAN_E_WORKSPACE, "%s: ws is NULL", fn);
+  carve_scope(d, B, K, nsub, (char*)ws, w);
+  if (w->bytes > ws_bytes) return fail(TLSAN_E_WORKSPACE, "%s: workspace too small: need %zu have %zu", fn, w->bytes, ws_bytes);
+  return TLSAN_OK;
+}
+
+size_t tlsan_scope_workspace_bytes(const tlsan_dims* d, int32_t B, int32_t K, int32_t nsub) {
+  static const char* fn = "tlsan_scope_workspace_bytes";
+  Shape s;
+  const int rc = shape_of(d, &s);
+  if (rc) { sim_named(fn, rc); return 0; }
+  if (K < 1 || K > TOPK_MAX) { fail(TLSAN_E_BADARG, "%s: K must be in 1..%d (got %d)", fn, TOPK_MAX, K); return 0; }
+  if (B < 1) { fail(TLSAN_E_BADARG, "%s: B must be >= 1 (got %d)", fn, B); return 0; }
+  if (nsub > d->item_count) { fail(TLSAN_E_BADARG, "%s: nsub %d exceeds the table's %d items", fn, nsub, d->item_count); return 0; }
+  ScopeWs w;
+  carve_scope(d, B, K, nsub, nullptr, &w);
+  return w.bytes;
+}
+
+int tlsan_eval_topk_scoped(const tlsan_dims* d, const tlsan_params* p, const float* u_t, int32_t B, int32_t K,
+                           const int32_t* excl_off, const int32_t* excl_ids, const int32_t* sub, int32_t nsub,
+                           const int32_t* row_cate, int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws,
+                           size_t ws_bytes, void* stream) {
+  static const char* fn = "tlsan_eval_topk_scoped";
+  Shape s;
+  int rc = shape_of(d, &s);
+  if (rc || (rc = check_params(p))) return sim_named(fn, rc);
+  if (!u_t || !ids || !scores || B < 1) return fail(TLSAN_E_BADARG, "%s: bad arguments", fn);
+  ScopeWs w;
+  if ((rc = scope_check(fn, d, B, K, excl_off, excl_ids, sub, nsub, id_mul, id_add, ws, ws_bytes, &w))) return rc;
+  hipStream_t hs = (hipStream_t)stream;
+  ScopedTopkArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  TopkArgs& ta = sa.t;
+  ta.e = eval_args(d, p, u_t, B, id_mul, id_add);      // (all_emb stays NULL: the gather form)
+  ta.K = K; ta.excl_off = excl_off; ta.excl_ids = excl_ids;
+  ta.ids = w.nsl > 1 ? w.ids : ids;
+  ta.scores = w.nsl > 1 ? w.scores : scores;
+  sa.s.sub = sub; sa.s.nsub = nsub < 0 ? 0 : nsub; sa.s.row_cate = row_cate;
+  hipError_t err = tlsan_launch_scoped_topk(sa, s.D, w.nsl, hs);
+  if (err != hipSuccess) return fail(TLSAN_E_LAUNCH, "k_scoped_topk: %s", hipGetErrorString(err));
+  if (w.nsl > 1 && (err = tlsan_launch_topk_merge(w.ids, w.scores, B, w.nsl, K, ids, scores, hs)) != hipSuccess)
+    return fail(TLSAN_E_LAUNCH, "k_topk_merge: %s", hipGetErrorString(err));
+  return TLSAN_OK;
+}
+
+int tlsan_similar_topk_scoped(const tlsan_dims* d, const tlsan_params* p, const float* qvec, const float* qinv,
+                              const int32_t* qids, int32_t Q, int32_t K, int32_t metric, const int32_t* excl_off,
+                              const int32_t* excl_ids, const int32_t* sub, int32_t nsub, const int32_t* row_cate,
+                              int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws, size_t ws_bytes,
+                              void* stream) {
+  static const char* fn = "tlsan_similar_topk_scoped";
+  Shape s;
+  int rc = shape_of(d, &s);
+  if (rc || (rc = check_params(p))) return sim_named(fn, rc);
+  if (metric != SIM_DOT && metric != SIM_COSINE)
+    return fail(TLSAN_E_BADARG, "%s: metric must be TLSAN_SIM_DOT or TLSAN_SIM_COSINE (got %d)", fn, metric);
+  if (!qvec || !qids || !ids || !scores || (metric == SIM_COSINE && !qinv)) return fail(TLSAN_E_BADARG, "%s: NULL argument", fn);
+  if (Q < 1) return fail(TLSAN_E_BADARG, "%s: Q must be >= 1 (got %d)", fn, Q);
+  ScopeWs w;
+  if ((rc = scope_check(fn, d, Q, K, excl_off, excl_ids, sub, nsub, id_mul, id_add, ws, ws_bytes, &w))) return rc;
+  hipStream_t hs = (hipStream_t)stream;
+  ScopedSimArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  TopkArgs& ta = sa.m.t;
+  ta.e = eval_args(d, p, qvec, Q, id_mul, id_add);     // (all_emb stays NULL: the gather form)
+  ta.K = K; ta.excl_off = excl_off; ta.excl_ids = excl_ids;
+  ta.ids = w.nsl > 1 ? w.ids : ids;
+  ta.scores = w.nsl > 1 ? w.scores : scores;
+  sa.m.qinv = qinv; sa.m.qids = qids; sa.m.inv = w.inv; sa.m.metric = metric;
+  sa.s.sub = sub; sa.s.nsub = nsub < 0 ? 0 : nsub; sa.s.row_cate = row_cate;
+  hipError_t err = hipSuccess;
+  const int count = scope_count(d, nsub);
+  if (metric == SIM_COSINE && count > 0 && (err = tlsan_launch_scope_inv(ta.e, sa.s, count, s.D, w.inv, hs)) != hipSuccess)
+    return fail(TLSAN_E_LAUNCH, "k_scope_inv: %s", hipGetErrorString(err));
+  if ((err = tlsan_launch_scoped_similar(sa, s.D, w.nsl, hs)) != hipSuccess)
+    return fail(TLSAN_E_LAUNCH, "k_scoped_similar: %s", hipGetErrorString(err));
+  if (w.nsl > 1 && (err = tlsan_launch_topk_merge(w.ids, w.scores, Q, w.nsl, K, ids, scores, hs)) != hipSuccess)
     return fail(TLSAN_E_LAUNCH, "k_topk_merge: %s", hipGetErrorString(err));
   return TLSAN_OK;
 }

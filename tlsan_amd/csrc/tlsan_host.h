@@ -14,6 +14,7 @@ struct TopkArgs;                                   // tlsan_topk.h
 struct CandArgs; struct NegArgs; struct ExclArgs;  // tlsan_cand.h
 struct EvalArgs;                                   // tlsan_eval.h
 struct SimArgs; struct VecArgs;                    // tlsan_similar.h
+struct ScopeArgs; struct ScopedTopkArgs; struct ScopedSimArgs;   // tlsan_scope.h
 
 #pragma GCC visibility push(hidden)
 
@@ -89,6 +90,10 @@ hipError_t tlsan_launch_topk_merge(const int32_t* cid, const float* csc, int B, 
 hipError_t tlsan_launch_sim_prep(const EvalArgs& e, int D, float* inv, hipStream_t hs);
 hipError_t tlsan_launch_similar_topk(const SimArgs& a, int D, int nslices, hipStream_t hs);
 hipError_t tlsan_launch_item_vectors(const VecArgs& a, int D, hipStream_t hs);
+// ---- scoped lists (tlsan_scope.hip): the selections over a subset of the items, the inv pass of the subset (count >= 1)
+hipError_t tlsan_launch_scoped_topk(const ScopedTopkArgs& a, int D, int nslices, hipStream_t hs);
+hipError_t tlsan_launch_scoped_similar(const ScopedSimArgs& a, int D, int nslices, hipStream_t hs);
+hipError_t tlsan_launch_scope_inv(const EvalArgs& e, const ScopeArgs& s, int count, int D, float* inv, hipStream_t hs);
 // ---- candidate scoring, candidate ranks, negative sampling (tlsan_cand.hip)
 hipError_t tlsan_launch_score_cand(const CandArgs& a, int D, hipStream_t hs);
 hipError_t tlsan_launch_cand_ranks(const int32_t* cand, const float* scores, int B, int C, int32_t* ranks, hipStream_t hs);

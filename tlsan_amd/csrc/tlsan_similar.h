@@ -122,5 +122,5 @@ template <int D, int KP, int BUF, bool DENSE>
 __global__ __launch_bounds__(256, 2) void k_similar_topk(SimArgs sa) {
   __shared__ TopkSmem<KP, BUF> sm;
   SimScore pol(sa);
-  topk_scan<D, KP, BUF, DENSE>(sm, sa.t, pol);
+  topk_scan<D, KP, BUF, DENSE>(sm, sa.t, pol, AllItems());
 }

@@ -199,8 +199,25 @@ __device__ __forceinline__ void topk_offer(TopkSmem<KP, BUF>& sm, const topk_key
 //   void col(acc, item)   takes in a tile: its accumulator and the local item of the lane's column
 //   float score(i)        row i's score of that column
 //   bool may(i, gn)       whether row i may select global item gn
-template <int D, int KP, int BUF, bool DENSE, class Policy>
-__device__ __forceinline__ void topk_scan(TopkSmem<KP, BUF>& sm, const TopkArgs& ta, Policy& pol) {
+// Which items the positions n = 0 .. count - 1 of the scan stand for is the item mapping's (AllItems: the table, position
+// n is local item n; tlsan_scope.h: a caller's subset of it):
+//   int count(a)          the number of positions
+//   int local(n)          the local item of position n < count, as the mapping holds it
+//   bool holds(loc)       whether that is an item of the table; if not, the column reads item 0 and is never selected
+// and one constant, `loaded`: whether local() reads memory.  A round's loaded locals are read a round ahead of the tiles
+// that need them and looked at (holds) only when their round comes, so neither the load nor a wait for it is on the
+// critical path of the tile's table loads.  Without it (AllItems) a local is arithmetic of the round itself, and the scan
+// is the one k_similar_topk has always run: no register is carried from round to round for it.
+// The global id of a column is local * id_mul + id_add.
+struct AllItems {
+  static constexpr bool loaded = false;
+  __device__ __forceinline__ int count(const EvalArgs& a) const { return a.I; }
+  __device__ __forceinline__ int local(int n) const { return n; }
+  __device__ __forceinline__ bool holds(int) const { return true; }
+};
+
+template <int D, int KP, int BUF, bool DENSE, class Policy, class Map>
+__device__ __forceinline__ void topk_scan(TopkSmem<KP, BUF>& sm, const TopkArgs& ta, Policy& pol, const Map& map) {
   const EvalArgs& a = ta.e;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
   const int u0 = blockIdx.x * 16;
@@ -219,24 +236,43 @@ __device__ __forceinline__ void topk_scan(TopkSmem<KP, BUF>& sm, const TopkArgs&
     thr[i] = 0ull;
   }
   __syncthreads();
+  const int cnt = map.count(a);
   const int step = gridDim.y * 256;
-  const int nround = (a.I + step - 1) / step;
+  const int nround = (cnt + step - 1) / step;
+  const int w0 = (blockIdx.y * 4 + wave) * 64;
+  // the locals of the lane's four columns of the round that starts at position n0 (positions past the count: the last one's)
+  auto locals = [&](int n0, int (&loc)[4]) {
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt) loc[tt] = map.local(min(n0 + 16 * tt + r, cnt - 1));
+  };
+  int nxt[4] = {0, 0, 0, 0};   // (loaded) the coming round's
+  if (Map::loaded && w0 < cnt) locals(w0, nxt);
   int ph = 0;
   for (int rd = 0; rd < nround; ++rd) {
-    const int n0 = rd * step + (blockIdx.y * 4 + wave) * 64;
+    const int n0 = rd * step + w0;
     topk_key_t key[16];
     unsigned pend = 0;
-    if (n0 < a.I) {
+    if (n0 < cnt) {
       int item[4];
+      bool held[4];
       f32x4 acc[4];
+      if (Map::loaded) {
 #pragma unroll
-      for (int tt = 0; tt < 4; ++tt) item[tt] = min(n0 + 16 * tt + r, a.I - 1);
+        for (int tt = 0; tt < 4; ++tt) {
+          held[tt] = map.holds(nxt[tt]);
+          item[tt] = held[tt] ? nxt[tt] : 0;
+        }
+        if (n0 < cnt - step) locals(n0 + step, nxt);
+      } else {
+        locals(n0, item);
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) held[tt] = true;
+      }
       score_tiles4<D, DENSE>(a, af, item, q, acc);
 #pragma unroll
       for (int tt = 0; tt < 4; ++tt) {
-        const int n = n0 + 16 * tt + r;
-        const bool vn = n < a.I;
-        const int gn = n * a.id_mul + a.id_add;  // global item id
+        const bool vn = n0 + 16 * tt + r < cnt && held[tt];
+        const int gn = item[tt] * a.id_mul + a.id_add;  // global item id
         pol.col(acc[tt], item[tt]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {

@@ -31,7 +31,7 @@ from .dist_comm import (ExchangePlan, KeyRouter, ModPartition, RowExchange, _sta
 from .dist_step import DynamicStep, FlatLayout, StaticStep, fused_params
 from .model import (LAZY_ADAGRAD_OPTIMIZERS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer, candidate_tensor, eval_topk,
                     exclusion_csr, grow_workspace, hits_and_rows, pack_dense, read_checkpoint, sample_negatives, sampled_ranks,
-                    score_candidates, item_vectors, list_metric_inputs, list_metrics, list_metrics_chunks, rerank, rerank_chunk, rerank_pool, similar_queries, similar_topk, topk_merge, unpack_dense, write_checkpoint)
+                    score_candidates, item_vectors, list_metric_inputs, list_metrics, list_metrics_chunks, rerank, rerank_chunk, rerank_pool, batch_rows, last_items, scope_categories, scope_within, scoped_similar_topk, scoped_topk, similar_queries, similar_topk, topk_merge, ItemScope, unpack_dense, write_checkpoint)
 
 
 def _ru4(x):
@@ -399,25 +399,49 @@ class ShardedModel:
         ldims = L.Dims(self.U, max(nloc, 1), self.C, self.d, self.di, self.dc, self.H, self.Ls)
         return nloc, ldims, fused_params(self, self.shard, self._icl_local)
 
-    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None):
+    def _item_cate(self, g):
+        """The categories of the global item ids g (an int64 device tensor), from the replicated map."""
+        return self.cate_by_key[(g % self.world) * self.router.R + g // self.world]
+
+    def item_scope(self, items=None, mask=None, categories=None):
+        """Model.item_scope: an ItemScope over the model's items (every rank builds the same one)."""
+        icl = None if categories is None else self._item_cate(torch.arange(self.I, device=self.device))
+        return ItemScope(self.I, self.device, items=items, mask=mask, categories=categories, item_cate=icl)
+
+    def last_item_categories(self, batch):
+        """Model.last_item_categories for this rank's rows (no collective: the map is replicated)."""
+        item = last_items(self.device_batch(batch, is_test=True))
+        return torch.where(item >= 0, self._item_cate(item.clamp(min=0)), -1).to(torch.int32)
+
+    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None):
         """Model.recommend for this rank's rows (every rank calls it, with the same k, exclusion mode and diversity
         settings): u_t and the exclusion lists are all-gathered, every rank selects the k best of ITS item shard for all
         rows (tlsan_eval_topk, global ids n * world + rank), each row's lists go to the rank that owns the row (one
         all-to-all) and are merged there (tlsan_topk_merge).  Same ids and scores as Model.recommend.
         diversity / per_category / pool (Model.recommend's second stage): the lists selected and merged are the pools
         of N entries; _rerank picks the k of each.  Same ids and score bits as Model.recommend on the gathered
-        parameters."""
+        parameters.
+        within / category (Model.recommend's; every rank passes the same scope, and its own rows' categories): each
+        rank scans the scope's items ITS shard holds, within.sub(world, rank, its count), for all rows; the rows'
+        categories are all-gathered with u_t.  The merge, the all-to-all and _rerank are unchanged."""
         N = rerank_pool(k, diversity, per_category, pool)
         want = int(k)
+        within = scope_within(within, self.I)
+        category = scope_categories(category, batch_rows(batch), self.C, self.device)
         with self._eval_forward(batch) as (db, _, _, _, ut):
             B, k, st = db.B, want if N is None else N, self._stream()
             ut_all = allgather_rows(ut, self.group)
             Bt = int(ut_all.shape[0])
             off, xid = self._gather_excl(*exclusion_csr(db, exclude, self.I), B)
             nloc, ldims, lp = self._item_shard()
-            if nloc > 0:
-                cid, csc = eval_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), self.world, self.rank,
-                                     lambda nbytes: grow_workspace(self, "_tws", nbytes), st)
+            tws = lambda nbytes: grow_workspace(self, "_tws", nbytes)
+            if nloc > 0 and (within is not None or category is not None):
+                sub = None if within is None else within.sub(self.world, self.rank, nloc)
+                cat_all = None if category is None else allgather_rows(category, self.group)
+                cid, csc = scoped_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), sub, cat_all, self.world, self.rank,
+                                       tws, st)
+            elif nloc > 0:
+                cid, csc = eval_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), self.world, self.rank, tws, st)
             else:
                 cid = torch.full((Bt, k), -1, dtype=torch.int32, device=self.device)
                 csc = torch.full((Bt, k), float("-inf"), dtype=torch.float32, device=self.device)
@@ -494,14 +518,15 @@ class ShardedModel:
                                 exposure, st)
         return list_metrics_chunks(ids, labels, rerank_chunk(ids.shape[1], self.d, self.world), measure)
 
-    def similar_items(self, items, k, metric="cosine", exclude=None):
-        """Model.similar_items, collective: every rank passes the same items (and k, metric, exclude) and every rank
+    def similar_items(self, items, k, metric="cosine", exclude=None, within=None, same_category=False):
+        """Model.similar_items, collective: every rank passes the same items (and k, metric, exclude, within, same_category) and every rank
         gets all Q lists.  Each rank reads the stored vectors and inverse norms of the queries ITS item shard holds
         (tlsan_item_vectors, zeros for the others); they are all-gathered and each query's are SELECTED from the one
         rank that holds it (a sum would turn -0 into +0); every rank selects the k nearest of its shard for all queries
         (tlsan_similar_topk, global ids n * world + rank), the lists are all-gathered and merged (tlsan_topk_merge).
         Same ids and score bits as Model.similar_items on the gathered parameters."""
         qids, mc, excl = similar_queries(items, self.I, metric, exclude, self.device)
+        within = scope_within(within, self.I)
         if self._static is not None:   # (plans announced ahead may be running on the side streams)
             self._static.drain()
         Q, k, st = int(qids.shape[0]), int(k), self._stream()
@@ -516,9 +541,15 @@ class ShardedModel:
             vec = torch.gather(allgather_rows(vec, self.group).view(self.world, Q, self.d), 0,
                                owner[None, :, None].expand(1, Q, self.d))[0].contiguous()
             inv = torch.gather(allgather_rows(inv, self.group).view(self.world, Q), 0, owner[None])[0].contiguous()
-        if nloc > 0:
-            cid, csc = similar_topk(self.lib, ldims, lp, vec, inv, qids, k, mc, excl, self.world, self.rank,
-                                    lambda nbytes: grow_workspace(self, "_tws", nbytes), st)
+        tws = lambda nbytes: grow_workspace(self, "_tws", nbytes)
+        if nloc > 0 and (within is not None or same_category):
+            # (each rank scans the scope's items ITS shard holds; the queries' categories come from the replicated map)
+            sub = None if within is None else within.sub(self.world, self.rank, nloc)
+            cate = self._item_cate(qids.long()).to(torch.int32).contiguous() if same_category else None
+            cid, csc = scoped_similar_topk(self.lib, ldims, lp, vec, inv, qids, k, mc, excl, sub, cate, self.world,
+                                           self.rank, tws, st)
+        elif nloc > 0:
+            cid, csc = similar_topk(self.lib, ldims, lp, vec, inv, qids, k, mc, excl, self.world, self.rank, tws, st)
         else:
             cid = torch.full((Q, k), -1, dtype=torch.int32, device=self.device)
             csc = torch.full((Q, k), float("-inf"), dtype=torch.float32, device=self.device)

@@ -242,6 +242,153 @@ class SeenItems:
         return torch.where(ok, self.ids[torch.where(ok, lo[:, None] + ar, 0)], pad).to(torch.int32)
 
 
+class ItemScope:
+    """A set of GLOBAL item ids held on the device, sorted and unique: the `within=` of recommend and similar_items,
+    single and sharded ("the best k within these items": in stock, this region, this department).  Built from exactly
+    one of items= (a sequence, array or tensor of ids, in any order, repeats allowed), mask= (bool [item_count]) or
+    categories= (category ids) with item_cate= (the model's item -> category map, [item_count]).  An id outside
+    [0, item_count) or a wrong shape is a ValueError; an empty scope is allowed (every list comes back -1 / -inf).
+    Only the scope's items are scored: a list costs what a table of `count` items costs."""
+
+    def __init__(self, item_count, device, items=None, mask=None, categories=None, item_cate=None):
+        if (items is not None) + (mask is not None) + (categories is not None) != 1:
+            raise ValueError("ItemScope: give exactly one of items=, mask= and categories=")
+        host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        I = int(item_count)
+        if items is not None:
+            ids = host(items)
+            if ids.ndim != 1 or (ids.size and ids.dtype.kind not in "iu"):
+                raise ValueError("ItemScope: items must be a 1-D sequence of item ids, got shape %s dtype %s" % (ids.shape, ids.dtype))
+            ids = np.unique(ids.astype(np.int64))
+            if ids.size and (ids[0] < 0 or ids[-1] >= I):
+                raise ValueError("ItemScope: item ids must be in [0, %d)" % I)
+        elif mask is not None:
+            m = host(mask)
+            if m.shape != (I,) or m.dtype != np.bool_:
+                raise ValueError("ItemScope: mask must be bool [%d], got shape %s dtype %s" % (I, m.shape, m.dtype))
+            ids = np.flatnonzero(m).astype(np.int64)
+        else:
+            if item_cate is None:
+                raise ValueError("ItemScope: categories= needs item_cate=, the model's item -> category map")
+            ic, want = host(item_cate), host(categories)
+            if ic.shape != (I,):
+                raise ValueError("ItemScope: item_cate must be [%d], got shape %s" % (I, ic.shape))
+            if want.ndim != 1 or (want.size and want.dtype.kind not in "iu"):
+                raise ValueError("ItemScope: categories must be a 1-D sequence of category ids")
+            ids = np.flatnonzero(np.isin(ic, want)).astype(np.int64)
+        self.item_count, self.device = I, device
+        self.count = int(ids.size)
+        self._host = ids
+        self.ids = torch.as_tensor(ids.astype(np.int32)).to(device)
+        self._local = {}
+
+    def local(self, id_mul, id_add, n_local):
+        """The ascending LOCAL indices of the scope's items that a table of n_local items with global ids
+        n * id_mul + id_add holds (a whole table: (1, 0, item_count); the item shard of rank r of W: (W, r, its count))
+        -> int32 device tensor; cached per table."""
+        buf, n = self.sub(id_mul, id_add, n_local)
+        return buf[:n]
+
+    def sub(self, id_mul, id_add, n_local):
+        """local() as tlsan_eval_topk_scoped takes it: (buffer, nsub) -- the indices are buffer[:nsub]; the buffer is one
+        element longer, so that an empty list still has an address."""
+        key = (int(id_mul), int(id_add), int(n_local))
+        if key not in self._local:
+            rel = self._host - key[1]
+            loc = rel[(rel >= 0) & (rel % key[0] == 0)] // key[0]
+            loc = loc[loc < key[2]]
+            self._local[key] = (torch.as_tensor(np.concatenate([loc, [0]]).astype(np.int32)).to(self.device), len(loc))
+        return self._local[key]
+
+
+def last_items(db):
+    """The last item of each row's input, on the device -> [B] int64: hist_i_new[b, sl_new[b] - 1] when the row has a
+    current session, else hist_i[b, sl[b] - 1], else -1 (no input)."""
+    last = lambda h, n: h.long().gather(1, (n - 1).clamp(min=0)[:, None])[:, 0]
+    sl = db.sl.long()
+    item = torch.where(sl > 0, last(db.hist_i, sl), -1)
+    if db.Sn > 0:
+        sn = db.sl_new.long()
+        item = torch.where(sn > 0, last(db.hist_i_new.reshape(db.B, db.Sn), sn), item)
+    return item
+
+
+def last_item_categories(db, item_cate):
+    """The category of the last item of each row's input (last_items), on the device -> [B] int32; -1 for a row without
+    input (any category).  The `category=` of "more from the department you are in".  db: a DeviceBatch
+    (Model.device_batch); item_cate: the model's [item_count] device map."""
+    item = last_items(db)
+    return torch.where(item >= 0, item_cate.long()[item.clamp(min=0)], -1).to(torch.int32)
+
+
+def batch_rows(batch):
+    """The number of rows of a batch as the models take it: the reference's tuple or a DeviceBatch."""
+    return batch.B if isinstance(batch, DeviceBatch) else len(batch[0])
+
+
+def scope_within(within, item_count):
+    """Checks a `within=` argument -> it (None: no scope)."""
+    if within is not None and (not isinstance(within, ItemScope) or within.item_count != item_count):
+        raise ValueError("within must be None or an ItemScope over the model's %d items" % item_count)
+    return within
+
+
+def scope_categories(category, B, cate_count, device):
+    """Checks a `category=` argument ([B] category ids, array or tensor; negative: the row is unrestricted) -> contiguous
+    int32 device tensor, or None.  An id >= cate_count or a wrong shape is a ValueError."""
+    if category is None:
+        return None
+    cat = category if isinstance(category, torch.Tensor) else torch.as_tensor(np.asarray(category))   # (an array: checked on the host)
+    if tuple(cat.shape) != (B,) or cat.dtype.is_floating_point or cat.dtype == torch.bool:
+        raise ValueError("category: want [%d] category ids, got shape %s dtype %s" % (B, tuple(cat.shape), cat.dtype))
+    if int(cat.max()) >= cate_count:
+        raise ValueError("category: ids must be below %d (negative: the row is unrestricted)" % cate_count)
+    return cat.to(device).clamp(min=-1).to(torch.int32).contiguous()
+
+
+def scoped_topk(lib, dims, cparams, ut, B, k, excl, sub, row_cate, id_mul, id_add, workspace, stream):
+    """tlsan_eval_topk_scoped on u_t [B, d]: eval_topk over the local items sub (ItemScope.sub's pair; None: every item)
+    with the rows' wanted categories row_cate ([B] int32 or None) -> (ids [B, k] int32, scores [B, k] float32)."""
+    k = int(k)
+    sub, nsub = (None, -1) if sub is None else sub
+    nws = lib.tlsan_scope_workspace_bytes(C.byref(dims), B, k, nsub)
+    if nws == 0:
+        raise L.TlsanError("tlsan_scope_workspace_bytes: %s" % lib.tlsan_last_error().decode())
+    ws = workspace(nws)
+    ids = torch.empty(B, k, dtype=torch.int32, device=ut.device)
+    scores = torch.empty(B, k, dtype=torch.float32, device=ut.device)
+    off, xid = excl
+    ptr = lambda t: None if t is None else t.data_ptr()
+    L.check(lib.tlsan_eval_topk_scoped(C.byref(dims), C.byref(cparams), ut.data_ptr(), B, k, ptr(off), ptr(xid), ptr(sub), nsub,
+                                       ptr(row_cate), id_mul, id_add, ids.data_ptr(), scores.data_ptr(), ws.data_ptr(),
+                                       ws.numel(), stream), "tlsan_eval_topk_scoped")
+    return ids, scores
+
+
+def scoped_similar_topk(lib, dims, cparams, vec, inv, qids, k, metric, excl, sub, row_cate, id_mul, id_add, workspace, stream):
+    """tlsan_similar_topk_scoped: similar_topk over the local items sub (ItemScope.sub's pair; None: every item) with the queries' wanted
+    categories row_cate ([Q] int32 or None), SIMILAR_CHUNK queries at a time."""
+    Q, k = int(qids.shape[0]), int(k)
+    sub, nsub = (None, -1) if sub is None else sub
+    ids = torch.empty(Q, k, dtype=torch.int32, device=qids.device)
+    scores = torch.empty(Q, k, dtype=torch.float32, device=qids.device)
+    off, xid = excl
+    ptr = lambda t: None if t is None else t.data_ptr()
+    for q0 in range(0, Q, SIMILAR_CHUNK):
+        n = min(SIMILAR_CHUNK, Q - q0)
+        nws = lib.tlsan_scope_workspace_bytes(C.byref(dims), n, k, nsub)
+        if nws == 0:
+            raise L.TlsanError("tlsan_scope_workspace_bytes: %s" % lib.tlsan_last_error().decode())
+        ws = workspace(nws)
+        # (a chunk's rows keep their offsets into the one id array: the offsets are absolute)
+        L.check(lib.tlsan_similar_topk_scoped(C.byref(dims), C.byref(cparams), vec[q0:].data_ptr(), inv[q0:].data_ptr(),
+                                              qids[q0:].data_ptr(), n, k, metric, None if off is None else off[q0:].data_ptr(),
+                                              ptr(xid), ptr(sub), nsub, None if row_cate is None else row_cate[q0:].data_ptr(),
+                                              id_mul, id_add, ids[q0:].data_ptr(), scores[q0:].data_ptr(), ws.data_ptr(),
+                                              ws.numel(), stream), "tlsan_similar_topk_scoped")
+    return ids, scores
+
+
 def _input_items(db, pad):
     """[B, Ls + Sn] int32: the items the row's input holds (hist_i[b, :sl[b]], hist_i_new[b, :sl_new[b]]), the rest
     `pad` (the padding past the lengths is item 0, a real item, so the lengths decide)."""
@@ -1380,7 +1527,16 @@ class Model(object):
         ranks = ranks - ahead
         return (ranks, (self.config["item_count"] - 1) - held) if return_eligible else ranks
 
-    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None):
+    def item_scope(self, items=None, mask=None, categories=None):
+        """An ItemScope over this model's items: from ids, a bool mask, or category ids (with the model's item_cate)."""
+        return ItemScope(self.config["item_count"], self.device, items=items, mask=mask, categories=categories,
+                         item_cate=None if categories is None else self.item_cate)
+
+    def last_item_categories(self, batch):
+        """last_item_categories of a batch (tuple or DeviceBatch) with this model's item -> category map."""
+        return last_item_categories(self.device_batch(batch, is_test=True), self.item_cate)
+
+    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None):
         """The k best items over ALL items for each row -- what tf.nn.top_k(eval_logits, k) gives the reference
         (model.py:140) -- without materialising the [B, I] scores.  Takes label_ranks' batches (the label and the
         negative are not used).  -> (ids [B, k] int32, scores [B, k] float32) device tensors, in tf.nn.top_k's
@@ -1397,14 +1553,29 @@ class Model(object):
         returned are the model's own, bit for bit, in selection order.  theta = 0 with m > 0 is exact whenever the row
         comes back full: it is the capped ranking over ALL eligible items (the pool is the exact score-order prefix); a
         short row means the pool was too small -- raise it.  With both left at 0 nothing changes: the plain top-k path,
-        the same launches and bits (pool alone is a ValueError)."""
+        the same launches and bits (pool alone is a ValueError).
+        within (an ItemScope) / category ([B] category ids, array or tensor; -1: the row is unrestricted; an id >=
+        cate_count is a ValueError): the k best WITHIN the scope's items and, per row, within that category
+        (last_item_categories gives "the department the row is in") -- tlsan_eval_topk_scoped.  Only the scope's items
+        are scored, so a list costs what a table of within.count items costs; the category-only form still scans the
+        whole table (there is no per-category index).  Same scores, bit for bit, as without them; both compose with
+        exclude= and with diversity / per_category / pool (the scoped list is the pool).  With both None the old entry
+        point runs: the same launches and bits.  label_ranks takes no scope."""
         N = rerank_pool(k, diversity, per_category, pool)
+        within = scope_within(within, self.config["item_count"])
+        category = scope_categories(category, batch_rows(batch), self.config["cate_count"], self.device)
         _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
         excl, st = exclusion_csr(db, exclude, self.config["item_count"]), self._stream()
+        if within is None and category is None:
+            topk = lambda n: eval_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, 1, 0, self._topk_workspace, st)
+        else:
+            sub = None if within is None else within.sub(1, 0, self.config["item_count"])
+            topk = lambda n: scoped_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, sub, category, 1, 0,
+                                         self._topk_workspace, st)
         if N is None:
-            return eval_topk(self.lib, self.dims, self.cparams, ut, db.B, k, excl, 1, 0, self._topk_workspace, st)
+            return topk(k)
         # (forward has landed an owed lazy-L2 correction; the vectors are read as stored, the scale not folded)
-        pid, psc = eval_topk(self.lib, self.dims, self.cparams, ut, db.B, N, excl, 1, 0, self._topk_workspace, st)
+        pid, psc = topk(N)
         ids = torch.empty(db.B, int(k), dtype=torch.int32, device=self.device)
         scores = torch.empty(db.B, int(k), dtype=torch.float32, device=self.device)
         rows = rerank_chunk(N, self.config["hidden_units"])
@@ -1439,7 +1610,7 @@ class Model(object):
                                 None if item_weight is None else item_weight[g], exposure, st)
         return list_metrics_chunks(ids, labels, rerank_chunk(ids.shape[1], self.config["hidden_units"]), measure)
 
-    def similar_items(self, items, k, metric="cosine", exclude=None):
+    def similar_items(self, items, k, metric="cosine", exclude=None, within=None, same_category=False):
         """The k nearest items of each item of `items` (a 1-D list, array or tensor of global ids; outside
         [0, item_count): ValueError) by the representation the model scores with, [item_emb || cate_emb[item_cate]]:
         metric "cosine" or "dot" (the product of the true vectors: the table scale enters twice); no bias, no user.
@@ -1447,12 +1618,21 @@ class Model(object):
         its own list, nor do the items of exclude (None, or a sequence of Q id sequences); rows with fewer than k
         eligible items end in -1 / -inf.  Selected inside the scoring kernel (tlsan_similar_topk): the [Q, I]
         similarities are never materialised.  Reads the tables as they are stored: an owed lazy-L2 correction lands
-        first, the scale is NOT folded -- parameters, scale and state keep their bits."""
+        first, the scale is NOT folded -- parameters, scale and state keep their bits.
+        within (an ItemScope): the nearest WITHIN the scope's items, of which alone the similarities are formed;
+        same_category: query q's list holds items of item_cate[q]'s category only (it still scans the scope, or the
+        whole table without one) -- tlsan_similar_topk_scoped, same score bits.  With neither the old entry point runs."""
         qids, mc, excl = similar_queries(items, self.config["item_count"], metric, exclude, self.device)
+        within = scope_within(within, self.config["item_count"])
         self._flush()
         st = self._stream()
         vec, inv = item_vectors(self.lib, self.dims, self.cparams, qids, 1, 0, st)
-        return similar_topk(self.lib, self.dims, self.cparams, vec, inv, qids, k, mc, excl, 1, 0, self._topk_workspace, st)
+        if within is None and not same_category:
+            return similar_topk(self.lib, self.dims, self.cparams, vec, inv, qids, k, mc, excl, 1, 0, self._topk_workspace, st)
+        sub = None if within is None else within.sub(1, 0, self.config["item_count"])
+        cate = self.item_cate[qids.long()].to(torch.int32).contiguous() if same_category else None
+        return scoped_similar_topk(self.lib, self.dims, self.cparams, vec, inv, qids, k, mc, excl, sub, cate, 1, 0,
+                                   self._topk_workspace, st)
 
     def score_candidates(self, batch, candidates):
         """Scores of caller-given items: candidates [B, C] global item ids (array or tensor; -1 = padding, which scores

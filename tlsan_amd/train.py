@@ -89,11 +89,19 @@ def parse(argv=None):
                          "the largest per-category count, HR / NDCG / MRR of the test positives, novelty by the training "
                          "set's self-information, catalogue coverage and the Gini coefficient of the exposure), print them "
                          "and write <model_dir>/recommend_top<K>_metrics.json")
+    ap.add_argument("--recommend_categories", default="",
+                    help="with --recommend_k: recommend within the items of these categories only, e.g. 3,7,12 (an ItemScope: "
+                         "only those items are scored)")
+    ap.add_argument("--recommend_same_category", type=int, default=0, choices=[0, 1],
+                    help="with --recommend_k: 1 = each row's list holds items of the category of the last item of the row's "
+                         "input only (last_item_categories)")
     ap.add_argument("--similar_k", type=int, default=0,
                     help="at the end of training, write <model_dir>/similar-<K>.npz: the K nearest items of every item "
                          "(item [I], ids [I, K], scores [I, K]; 0 = off)")
     ap.add_argument("--similar_metric", default="cosine", choices=["cosine", "dot"],
                     help="the similarity of --similar_k: cosine, or the dot product of the item vectors")
+    ap.add_argument("--similar_same_category", type=int, default=0, choices=[0, 1],
+                    help="with --similar_k: 1 = an item's list holds items of its own category only")
     ap.add_argument("--eval_negatives", type=int, default=0,
                     help="sampled evaluation at every evaluation point: rank each test label among N sampled negatives "
                          "and report HR@k, NDCG@k (k = 1, 5, 10, 20), MRR and AUC_N; 0 = off")
@@ -110,6 +118,16 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.recommend_metrics and not args.recommend_k:
         ap.error("--recommend_metrics measures the lists of --recommend_k: give --recommend_k")
+    if (args.recommend_categories or args.recommend_same_category) and not args.recommend_k:
+        ap.error("--recommend_categories / --recommend_same_category narrow the lists of --recommend_k: give --recommend_k")
+    if args.similar_same_category and not args.similar_k:
+        ap.error("--similar_same_category narrows the lists of --similar_k: give --similar_k")
+    try:
+        args.recommend_categories = [int(c) for c in args.recommend_categories.split(",") if c.strip()]
+    except ValueError:
+        ap.error("--recommend_categories: want category ids separated by commas, e.g. 3,7,12")
+    if any(c < 0 for c in args.recommend_categories):
+        ap.error("--recommend_categories: category ids are non-negative")
     return args
 
 
@@ -185,12 +203,14 @@ def similar_path(model_dir, k):
 SIMILAR_ROWS = 16384   # query items per similar_items call of write_similar
 
 
-def write_similar(model, model_dir, k, metric, item_count, write=True):
+def write_similar(model, model_dir, k, metric, item_count, write=True, same_category=False):
     """The k nearest items of EVERY item (model.similar_items; collective on a sharded model, where only the process
-    with write=True keeps the lists) -> the path of the .npz written: item [I], ids [I, k], scores [I, k]."""
+    with write=True keeps the lists) -> the path of the .npz written: item [I], ids [I, k], scores [I, k].
+    same_category: similar_items' (an item's list holds its own category only)."""
     ids, scores = [], []
+    scoped = dict(same_category=True) if same_category else {}
     for i0 in range(0, item_count, SIMILAR_ROWS):
-        a, b = model.similar_items(np.arange(i0, min(i0 + SIMILAR_ROWS, item_count)), k, metric=metric)
+        a, b = model.similar_items(np.arange(i0, min(i0 + SIMILAR_ROWS, item_count)), k, metric=metric, **scoped)
         if write:
             ids.append(a.cpu().numpy())
             scores.append(b.cpu().numpy())
@@ -403,13 +423,16 @@ class ListMeasurement:
         return self.counters.result(self.rows.sum(self.exposure.to(torch.int64)), self.items)
 
 
-def recommend_test_set(model, rows, k, exclude, on_lists=None, **settings):
-    """model.recommend over every test row (settings: its diversity keywords) -> (user, ids, scores) host arrays in
-    test-set order; None but on rank 0.  on_lists(device batch, ids, real): called with every launch's device lists
-    [rows, k] before they leave the device (ListMeasurement)."""
+def recommend_test_set(model, rows, k, exclude, on_lists=None, same_category=False, **settings):
+    """model.recommend over every test row (settings: its diversity keywords and within=) -> (user, ids, scores) host
+    arrays in test-set order; None but on rank 0.  on_lists(device batch, ids, real): called with every launch's device
+    lists [rows, k] before they leave the device (ListMeasurement).  same_category: every launch's rows get
+    category=model.last_item_categories(their batch)."""
     parts = []
     for batch, real, _ in rows.launches(True):
         db = model.device_batch(batch, is_test=True)
+        if same_category:
+            settings["category"] = model.last_item_categories(db)
         ids, scores = model.recommend(db, k, exclude=exclude, **settings)
         if on_lists is not None:
             on_lists(db, ids, real)
@@ -527,8 +550,9 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
         # (a DevicePackedSet keeps the host set it was made from: the novelty weights are counted on the host)
         measure = ListMeasurement(model, rows, args.recommend_k, getattr(train_set, "ps", train_set)) \
             if args.recommend_metrics else None
+        scope = dict(within=model.item_scope(categories=args.recommend_categories)) if args.recommend_categories else {}
         rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen), on_lists=measure,
-                                 **settings)
+                                 same_category=bool(args.recommend_same_category), **settings, **scope)
         list_res = measure.result() if measure is not None else None       # (collective: every rank)
         if rec is not None:                                    # (rank 0 holds the rows)
             path = write_recommendations(args.model_dir, args.recommend_k, *rec, settings=settings)
@@ -538,7 +562,7 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
                 say("List metrics: %s" % write_list_metrics(args.model_dir, args.recommend_k, list_res, settings))
     if args.similar_k:
         path = write_similar(model, args.model_dir, args.similar_k, args.similar_metric, rows.config["item_count"],
-                             write=rows.rank in (None, 0))
+                             write=rows.rank in (None, 0), same_category=bool(args.similar_same_category))
         if path is not None:
             say("Similar items: %s" % path)
     model.train_writer.flush()
