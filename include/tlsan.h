@@ -599,6 +599,43 @@ int tlsan_similar_topk_scoped(const tlsan_dims* dims, const tlsan_params* p, con
                               int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws, size_t ws_bytes,
                               void* stream);
 
+/* Indexed lists: the scoped lists over an INDEX of the table's items -- a caller's lists of local item indices, one per
+ * category (or per cell of any other partition) -- where every row names the few lists it wants.  Only those lists are
+ * scored: a row costs what its lists' items cost, where tlsan_eval_topk_scoped's row_cate still scans the whole scope.
+ *   list_off [nlists + 1], list_items: list c is list_items[list_off[c] .. list_off[c + 1]), LOCAL item indices of this
+ *     table (global id = index * id_mul + id_add); the lists are disjoint.  An entry outside [0, item_count) is never
+ *     read as a table row and never selected.  An empty list is allowed.
+ *   max_list: the longest list's length as the host knows it.  It sizes the launch (the slices of a list) and the
+ *     workspace, nothing else: a wrong value costs time, not correctness.  The workspace call and the list call take
+ *     the same (B, P, K, nlists, max_list).
+ *   row_lists [B, P] (tlsan_similar_topk_lists: [Q, P]), 1 <= P <= 8: the lists row b probes.  A negative entry, or one
+ *     >= nlists (never used to address list_off), is no probe; a list named twice in a row counts once.
+ *   Row b's result: the K best, in tlsan_eval_topk's order, of the union of its probed lists minus its exclusion list
+ *     (and, in the similar form, minus the query itself, as tlsan_similar_topk).  A row without a probe, or with empty
+ *     lists only, comes back id -1, score -inf.  The scores of a (row, item) pair are tlsan_eval_topk_scoped's /
+ *     tlsan_similar_topk_scoped's bit for bit.
+ *   A row's result depends on its own inputs only: not on B, on the other rows, on how the call groups the rows that
+ *     share a list (it does so on the device, in the workspace, without a host synchronisation, and the grouping may
+ *     differ from call to call), on the launch geometry or on the number of ranks.  In the item-sharded form every
+ *     rank passes the index of ITS table's items and the ranks' lists merge with tlsan_topk_merge.
+ * Neither call changes the parameters, P or any state; no dense [item_count, d] matrix is built.
+ * Workspace: tlsan_lists_workspace_bytes, for both calls (0, with tlsan_last_error set, on a refusal).  Refused before
+ * any launch, with the function's name in tlsan_last_error: bad dims or parameters (the unscoped call's codes); K outside
+ * 1..256, P outside 1..8, B (Q) or nlists outside 1..2^24, max_list < 0, a NULL pointer, excl_off without excl_ids, an id mapping
+ * that leaves int32, a metric that is none (TLSAN_E_BADARG); a workspace that is NULL or too small (TLSAN_E_WORKSPACE).
+ * The three functions are additions: nothing else in the ABI changed (TLSAN_ABI_VERSION stays 15). */
+size_t tlsan_lists_workspace_bytes(const tlsan_dims* dims, int32_t B, int32_t P, int32_t K, int32_t nlists, int32_t max_list);
+int tlsan_eval_topk_lists(const tlsan_dims* dims, const tlsan_params* p, const float* u_t, int32_t B, int32_t K,
+                          const int32_t* excl_off, const int32_t* excl_ids, const int32_t* list_off,
+                          const int32_t* list_items, int32_t nlists, int32_t max_list, const int32_t* row_lists, int32_t P,
+                          int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws, size_t ws_bytes,
+                          void* stream);
+int tlsan_similar_topk_lists(const tlsan_dims* dims, const tlsan_params* p, const float* qvec, const float* qinv,
+                             const int32_t* qids, int32_t Q, int32_t K, int32_t metric, const int32_t* excl_off,
+                             const int32_t* excl_ids, const int32_t* list_off, const int32_t* list_items, int32_t nlists,
+                             int32_t max_list, const int32_t* row_lists, int32_t P, int32_t id_mul, int32_t id_add,
+                             int32_t* ids, float* scores, void* ws, size_t ws_bytes, void* stream);
+
 /* Diversified lists: the second stage behind tlsan_eval_topk.  From each row's POOL of N entries (1 <= K <= N <= 256, in
  * tlsan_eval_topk's order: higher score first, ties -> lower global id) pick K by greedy maximal marginal relevance
  * under a per-category cap.  Pool entry j of a row has a global id g_j and the model score s_j (pool_ids, pool_scores

@@ -32,6 +32,7 @@ EXPORTS = [
     "tlsan_topk_workspace_bytes", "tlsan_eval_topk", "tlsan_topk_merge",
     "tlsan_item_vectors", "tlsan_similar_workspace_bytes", "tlsan_similar_topk", "tlsan_rerank", "tlsan_list_metrics",
     "tlsan_scope_workspace_bytes", "tlsan_eval_topk_scoped", "tlsan_similar_topk_scoped",
+    "tlsan_lists_workspace_bytes", "tlsan_eval_topk_lists", "tlsan_similar_topk_lists",
     "tlsan_score_candidates", "tlsan_candidate_ranks", "tlsan_sample_negatives", "tlsan_profile_enable", "tlsan_profile_stride",
     "tlsan_profile_collect", "tlsan_debug_stamps", "tlsan_rows_apply_workspace", "tlsan_rows_apply", "tlsan_scan_compact",
     "tlsan_route_plan", "tlsan_shard_gather", "tlsan_shard_summary", "tlsan_shard_apply_workspace", "tlsan_shard_apply",
@@ -242,6 +243,18 @@ def load():
                                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.tlsan_similar_topk_scoped.restype = C.c_int
+    if hasattr(lib, "tlsan_eval_topk_lists"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
+        lib.tlsan_lists_workspace_bytes.argtypes = [P(Dims)] + [C.c_int32] * 5
+        lib.tlsan_lists_workspace_bytes.restype = C.c_size_t
+        lib.tlsan_eval_topk_lists.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.tlsan_eval_topk_lists.restype = C.c_int
+        lib.tlsan_similar_topk_lists.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                 C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.tlsan_similar_topk_lists.restype = C.c_int
     lib.tlsan_rerank.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.tlsan_rerank.restype = C.c_int
     if hasattr(lib, "tlsan_list_metrics"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)

@@ -31,7 +31,7 @@ from .dist_comm import (ExchangePlan, KeyRouter, ModPartition, RowExchange, _sta
 from .dist_step import DynamicStep, FlatLayout, StaticStep, fused_params
 from .model import (LAZY_ADAGRAD_OPTIMIZERS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer, candidate_tensor, eval_topk,
                     exclusion_csr, grow_workspace, hits_and_rows, pack_dense, read_checkpoint, sample_negatives, sampled_ranks,
-                    score_candidates, item_vectors, list_metric_inputs, list_metrics, list_metrics_chunks, rerank, rerank_chunk, rerank_pool, batch_rows, last_items, scope_categories, scope_within, scoped_similar_topk, scoped_topk, similar_queries, similar_topk, topk_merge, ItemScope, unpack_dense, write_checkpoint)
+                    score_candidates, item_vectors, list_metric_inputs, list_metrics, list_metrics_chunks, rerank, rerank_chunk, rerank_pool, batch_rows, last_items, scope_categories, scope_within, scoped_similar_topk, scoped_topk, CategoryIndex, index_categories, indexed_topk, recommend_index, lists_similar_topk, similar_index, similar_queries, similar_topk, topk_merge, ItemScope, unpack_dense, write_checkpoint)
 
 
 def _ru4(x):
@@ -413,7 +413,12 @@ class ShardedModel:
         item = last_items(self.device_batch(batch, is_test=True))
         return torch.where(item >= 0, self._item_cate(item.clamp(min=0)), -1).to(torch.int32)
 
-    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None):
+    def category_index(self, within=None):
+        """Model.category_index: a CategoryIndex over the model's items or an ItemScope's (every rank builds the same one)."""
+        return CategoryIndex(self._item_cate(torch.arange(self.I, device=self.device)), self.C, self.device,
+                             within=scope_within(within, self.I))
+
+    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None, index=None):
         """Model.recommend for this rank's rows (every rank calls it, with the same k, exclusion mode and diversity
         settings): u_t and the exclusion lists are all-gathered, every rank selects the k best of ITS item shard for all
         rows (tlsan_eval_topk, global ids n * world + rank), each row's lists go to the rank that owns the row (one
@@ -423,11 +428,18 @@ class ShardedModel:
         parameters.
         within / category (Model.recommend's; every rank passes the same scope, and its own rows' categories): each
         rank scans the scope's items ITS shard holds, within.sub(world, rank, its count), for all rows; the rows'
-        categories are all-gathered with u_t.  The merge, the all-to-all and _rerank are unchanged."""
+        categories are all-gathered with u_t.  The merge, the all-to-all and _rerank are unchanged.
+        index (Model.recommend's; every rank passes the same index and the same P): each rank scans the lists of ITS
+        item shard, index.local(world, rank, its count), for all gathered rows (tlsan_eval_topk_lists); the rows'
+        category arrays are all-gathered with u_t, and the unrestricted rows among them run through the path without
+        an index on every rank."""
         N = rerank_pool(k, diversity, per_category, pool)
         want = int(k)
         within = scope_within(within, self.I)
-        category = scope_categories(category, batch_rows(batch), self.C, self.device)
+        if recommend_index(index, within, self.I, self.C) is not None:
+            category = index_categories(category, batch_rows(batch), self.C, self.device)
+        else:
+            category = scope_categories(category, batch_rows(batch), self.C, self.device)
         with self._eval_forward(batch) as (db, _, _, _, ut):
             B, k, st = db.B, want if N is None else N, self._stream()
             ut_all = allgather_rows(ut, self.group)
@@ -435,7 +447,10 @@ class ShardedModel:
             off, xid = self._gather_excl(*exclusion_csr(db, exclude, self.I), B)
             nloc, ldims, lp = self._item_shard()
             tws = lambda nbytes: grow_workspace(self, "_tws", nbytes)
-            if nloc > 0 and (within is not None or category is not None):
+            if nloc > 0 and index is not None:
+                cid, csc = indexed_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), index, allgather_rows(category, self.group),
+                                        self.world, self.rank, nloc, tws, st)
+            elif nloc > 0 and (within is not None or category is not None):
                 sub = None if within is None else within.sub(self.world, self.rank, nloc)
                 cat_all = None if category is None else allgather_rows(category, self.group)
                 cid, csc = scoped_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), sub, cat_all, self.world, self.rank,
@@ -518,15 +533,17 @@ class ShardedModel:
                                 exposure, st)
         return list_metrics_chunks(ids, labels, rerank_chunk(ids.shape[1], self.d, self.world), measure)
 
-    def similar_items(self, items, k, metric="cosine", exclude=None, within=None, same_category=False):
+    def similar_items(self, items, k, metric="cosine", exclude=None, within=None, same_category=False, index=None):
         """Model.similar_items, collective: every rank passes the same items (and k, metric, exclude, within, same_category) and every rank
         gets all Q lists.  Each rank reads the stored vectors and inverse norms of the queries ITS item shard holds
         (tlsan_item_vectors, zeros for the others); they are all-gathered and each query's are SELECTED from the one
         rank that holds it (a sum would turn -0 into +0); every rank selects the k nearest of its shard for all queries
         (tlsan_similar_topk, global ids n * world + rank), the lists are all-gathered and merged (tlsan_topk_merge).
-        Same ids and score bits as Model.similar_items on the gathered parameters."""
+        Same ids and score bits as Model.similar_items on the gathered parameters.  index (with same_category=True): every
+        rank scans the lists of its own item shard, index.local(world, rank, its count) (tlsan_similar_topk_lists)."""
         qids, mc, excl = similar_queries(items, self.I, metric, exclude, self.device)
         within = scope_within(within, self.I)
+        index = similar_index(index, within, same_category, self.I, self.C)
         if self._static is not None:   # (plans announced ahead may be running on the side streams)
             self._static.drain()
         Q, k, st = int(qids.shape[0]), int(k), self._stream()
@@ -542,7 +559,11 @@ class ShardedModel:
                                owner[None, :, None].expand(1, Q, self.d))[0].contiguous()
             inv = torch.gather(allgather_rows(inv, self.group).view(self.world, Q), 0, owner[None])[0].contiguous()
         tws = lambda nbytes: grow_workspace(self, "_tws", nbytes)
-        if nloc > 0 and (within is not None or same_category):
+        if nloc > 0 and index is not None:
+            cate = self._item_cate(qids.long()).to(torch.int32).reshape(-1, 1).contiguous()
+            cid, csc = lists_similar_topk(self.lib, ldims, lp, vec, inv, qids, k, mc, excl,
+                                          index.local(self.world, self.rank, nloc), cate, self.world, self.rank, tws, st)
+        elif nloc > 0 and (within is not None or same_category):
             # (each rank scans the scope's items ITS shard holds; the queries' categories come from the replicated map)
             sub = None if within is None else within.sub(self.world, self.rank, nloc)
             cate = self._item_cate(qids.long()).to(torch.int32).contiguous() if same_category else None

@@ -301,6 +301,171 @@ class ItemScope:
         return self._local[key]
 
 
+class CategoryIndex:
+    """The items by category: a partition of the GLOBAL item ids -- of all item_count of them, or of an ItemScope's when
+    within= is given -- into one list per category, held on the device: list_off [cate_count + 1] int32 and list_items
+    int32, ascending by (category, id); max_list, the longest list's length, stays on the host.  The `index=` of
+    recommend and similar_items, single and sharded (Model.category_index / ShardedModel.category_index build it): a
+    row that asks for a category scores that category's list and nothing else.  A category without items is an empty
+    list; an index over an empty scope is allowed (every list is empty).  item_cate: [item_count] category ids in
+    [0, cate_count) (array or tensor); device "cpu" works.  The index is a snapshot of item_cate: rebuild it when the
+    map changes."""
+
+    PROBES = 8    # LISTS_PMAX (csrc/tlsan_lists.h): most lists a row probes
+
+    def __init__(self, item_cate, cate_count, device, within=None):
+        ic = item_cate.detach().cpu().numpy() if isinstance(item_cate, torch.Tensor) else np.asarray(item_cate)
+        I, C = int(ic.shape[0]) if ic.ndim == 1 else -1, int(cate_count)
+        if I < 0 or C < 1 or ic.dtype.kind not in "iu" or (I and (ic.min() < 0 or ic.max() >= C)):
+            raise ValueError("CategoryIndex: item_cate must be a 1-D array of category ids in [0, %d)" % C)
+        if within is not None and (not isinstance(within, ItemScope) or within.item_count != I):
+            raise ValueError("CategoryIndex: within must be None or an ItemScope over the %d items" % I)
+        ids = np.arange(I, dtype=np.int64) if within is None else within._host
+        cat = ic[ids].astype(np.int64)
+        order = np.argsort(cat, kind="stable")                 # (ids ascend, so a stable sort keeps them ascending in a list)
+        self.item_count, self.cate_count, self.device, self.within = I, C, device, within
+        self._items, self._cats = ids[order], cat[order]
+        self.count = int(ids.size)
+        off = np.concatenate([[0], np.cumsum(np.bincount(self._cats, minlength=C))])
+        self.max_list = int(np.diff(off).max())
+        self.list_off = torch.as_tensor(off.astype(np.int32)).to(device)
+        self.list_items = torch.as_tensor(self._items.astype(np.int32)).to(device)
+        self._local = {}
+
+    def local(self, id_mul, id_add, n_local):
+        """The index of a table of n_local items whose local item n is global id n * id_mul + id_add (a whole table:
+        (1, 0, item_count); the item shard of rank r of W: (W, r, its count)) -> (list_off [cate_count + 1] int32,
+        list_items int32 LOCAL indices ascending by (category, index) -- one element longer than the lists, so that an
+        empty index still has an address -- and the longest list's length); cached per table."""
+        key = (int(id_mul), int(id_add), int(n_local))
+        if key not in self._local:
+            rel = self._items - key[1]
+            keep = (rel >= 0) & (rel % key[0] == 0) & (rel // key[0] < key[2])
+            off = np.concatenate([[0], np.cumsum(np.bincount(self._cats[keep], minlength=self.cate_count))])
+            items = np.concatenate([rel[keep] // key[0], [0]])
+            self._local[key] = (torch.as_tensor(off.astype(np.int32)).to(self.device),
+                                torch.as_tensor(items.astype(np.int32)).to(self.device), int(np.diff(off).max()))
+        return self._local[key]
+
+
+def index_of(index, item_count, cate_count):
+    """Checks an `index=` argument -> it (None: no index)."""
+    if index is not None and (not isinstance(index, CategoryIndex) or index.item_count != item_count or index.cate_count != cate_count):
+        raise ValueError("index must be None or a CategoryIndex over the model's %d items in %d categories" % (item_count, cate_count))
+    return index
+
+
+def recommend_index(index, within, item_count, cate_count):
+    """Checks recommend's `index=` -> it (None: no index): the scope belongs to the index, so it goes without within=."""
+    index = index_of(index, item_count, cate_count)
+    if index is not None and within is not None:
+        raise ValueError("within= and index= together: the scope belongs to the index, category_index(within=scope)")
+    return index
+
+
+def similar_index(index, within, same_category, item_count, cate_count):
+    """Checks similar_items' `index=` -> it (None: no index): it goes with same_category=True and without within=."""
+    index = index_of(index, item_count, cate_count)
+    if index is not None and not same_category:
+        raise ValueError("index= needs same_category=True: the index is by category")
+    if index is not None and within is not None:
+        raise ValueError("within= and index= together: the scope belongs to the index, category_index(within=scope)")
+    return index
+
+
+def index_categories(category, B, cate_count, device):
+    """Checks the `category=` that goes with an index ([B] or [B, P] category ids, P <= CategoryIndex.PROBES, array or
+    tensor; negative: no probe, a row of negatives only is unrestricted) -> contiguous int32 [B, P] device tensor.  None,
+    an id >= cate_count or a wrong shape is a ValueError."""
+    if category is None:
+        raise ValueError("index= needs category=: the categories each row asks for")
+    cat = category if isinstance(category, torch.Tensor) else torch.as_tensor(np.asarray(category))
+    shape = tuple(cat.shape)
+    if shape == (B,):
+        cat = cat.reshape(B, 1)
+    elif len(shape) != 2 or shape[0] != B or not 1 <= shape[1] <= CategoryIndex.PROBES:
+        raise ValueError("category: with an index want [%d] or [%d, P] category ids, P in 1..%d, got shape %s"
+                         % (B, B, CategoryIndex.PROBES, shape))
+    if cat.dtype.is_floating_point or cat.dtype == torch.bool:
+        raise ValueError("category: want category ids, got dtype %s" % cat.dtype)
+    if int(cat.max()) >= cate_count:
+        raise ValueError("category: ids must be below %d (negative: no probe)" % cate_count)
+    return cat.to(device).clamp(min=-1).to(torch.int32).contiguous()
+
+
+def lists_topk(lib, dims, cparams, ut, B, k, excl, lists, row_lists, id_mul, id_add, workspace, stream):
+    """tlsan_eval_topk_lists on u_t [B, d]: the k best of the union of the lists row_lists [B, P] int32 names, of the index
+    `lists` (CategoryIndex.local's triple) -> (ids [B, k] int32, scores [B, k] float32)."""
+    k, P = int(k), int(row_lists.shape[1])
+    off, items, max_list = lists
+    nl = int(off.shape[0]) - 1
+    nws = lib.tlsan_lists_workspace_bytes(C.byref(dims), B, P, k, nl, max_list)
+    if nws == 0:
+        raise L.TlsanError("tlsan_lists_workspace_bytes: %s" % lib.tlsan_last_error().decode())
+    ws = workspace(nws)
+    ids = torch.empty(B, k, dtype=torch.int32, device=ut.device)
+    scores = torch.empty(B, k, dtype=torch.float32, device=ut.device)
+    xoff, xid = excl
+    ptr = lambda t: None if t is None else t.data_ptr()
+    L.check(lib.tlsan_eval_topk_lists(C.byref(dims), C.byref(cparams), ut.data_ptr(), B, k, ptr(xoff), ptr(xid), off.data_ptr(),
+                                      items.data_ptr(), nl, max_list, row_lists.data_ptr(), P, id_mul, id_add, ids.data_ptr(),
+                                      scores.data_ptr(), ws.data_ptr(), ws.numel(), stream), "tlsan_eval_topk_lists")
+    return ids, scores
+
+
+def lists_similar_topk(lib, dims, cparams, vec, inv, qids, k, metric, excl, lists, row_lists, id_mul, id_add, workspace, stream):
+    """tlsan_similar_topk_lists: similar_topk over the lists row_lists [Q, P] int32 names, of the index `lists`
+    (CategoryIndex.local's triple), SIMILAR_CHUNK queries at a time."""
+    Q, k, P = int(qids.shape[0]), int(k), int(row_lists.shape[1])
+    off, items, max_list = lists
+    nl = int(off.shape[0]) - 1
+    ids = torch.empty(Q, k, dtype=torch.int32, device=qids.device)
+    scores = torch.empty(Q, k, dtype=torch.float32, device=qids.device)
+    xoff, xid = excl
+    for q0 in range(0, Q, SIMILAR_CHUNK):
+        n = min(SIMILAR_CHUNK, Q - q0)
+        nws = lib.tlsan_lists_workspace_bytes(C.byref(dims), n, P, k, nl, max_list)
+        if nws == 0:
+            raise L.TlsanError("tlsan_lists_workspace_bytes: %s" % lib.tlsan_last_error().decode())
+        ws = workspace(nws)
+        # (a chunk's rows keep their offsets into the one id array: the offsets are absolute)
+        L.check(lib.tlsan_similar_topk_lists(C.byref(dims), C.byref(cparams), vec[q0:].data_ptr(), inv[q0:].data_ptr(),
+                                             qids[q0:].data_ptr(), n, k, metric, None if xoff is None else xoff[q0:].data_ptr(),
+                                             None if xid is None else xid.data_ptr(), off.data_ptr(), items.data_ptr(), nl,
+                                             max_list, row_lists[q0:].data_ptr(), P, id_mul, id_add, ids[q0:].data_ptr(),
+                                             scores[q0:].data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                "tlsan_similar_topk_lists")
+    return ids, scores
+
+
+def excl_rows(excl, rows, B):
+    """The exclusion CSR (exclusion_csr's: every row a slot of the same width) of the rows `rows` of B alone."""
+    off, xid = excl
+    if off is None:
+        return excl
+    w = xid.numel() // B
+    vals = xid.view(B, w)[rows].contiguous()
+    return torch.arange(0, (vals.shape[0] + 1) * w, w, dtype=torch.int32, device=xid.device), vals.view(-1)
+
+
+def indexed_topk(lib, dims, cparams, ut, B, k, excl, index, row_lists, id_mul, id_add, n_local, workspace, stream):
+    """recommend's lists with an index on u_t [B, d]: the rows that probe a list go through lists_topk; the rows whose
+    entries are all negative are unrestricted -- they run through the path without an index (scoped_topk over the index's
+    scope, eval_topk without one) as a sub-batch and are scattered back.  One host read says whether there are any."""
+    ids, scores = lists_topk(lib, dims, cparams, ut, B, k, excl, index.local(id_mul, id_add, n_local), row_lists, id_mul, id_add,
+                             workspace, stream)
+    free = torch.nonzero((row_lists < 0).all(1))[:, 0]
+    if free.numel():
+        sub_ut, sub_excl, n = ut[free].contiguous(), excl_rows(excl, free, B), int(free.numel())
+        if index.within is None:
+            fid, fsc = eval_topk(lib, dims, cparams, sub_ut, n, k, sub_excl, id_mul, id_add, workspace, stream)
+        else:
+            fid, fsc = scoped_topk(lib, dims, cparams, sub_ut, n, k, sub_excl, index.within.sub(id_mul, id_add, n_local), None,
+                                   id_mul, id_add, workspace, stream)
+        ids[free], scores[free] = fid, fsc
+    return ids, scores
+
+
 def last_items(db):
     """The last item of each row's input, on the device -> [B] int64: hist_i_new[b, sl_new[b] - 1] when the row has a
     current session, else hist_i[b, sl[b] - 1], else -1 (no input)."""
@@ -1536,7 +1701,12 @@ class Model(object):
         """last_item_categories of a batch (tuple or DeviceBatch) with this model's item -> category map."""
         return last_item_categories(self.device_batch(batch, is_test=True), self.item_cate)
 
-    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None):
+    def category_index(self, within=None):
+        """A CategoryIndex over this model's items, or over an ItemScope's (within=), by the model's item_cate."""
+        return CategoryIndex(self.item_cate, self.config["cate_count"], self.device,
+                             within=scope_within(within, self.config["item_count"]))
+
+    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None, index=None):
         """The k best items over ALL items for each row -- what tf.nn.top_k(eval_logits, k) gives the reference
         (model.py:140) -- without materialising the [B, I] scores.  Takes label_ranks' batches (the label and the
         negative are not used).  -> (ids [B, k] int32, scores [B, k] float32) device tensors, in tf.nn.top_k's
@@ -1558,15 +1728,30 @@ class Model(object):
         cate_count is a ValueError): the k best WITHIN the scope's items and, per row, within that category
         (last_item_categories gives "the department the row is in") -- tlsan_eval_topk_scoped.  Only the scope's items
         are scored, so a list costs what a table of within.count items costs; the category-only form still scans the
-        whole table (there is no per-category index).  Same scores, bit for bit, as without them; both compose with
+        whole table, or the scope.  Same scores, bit for bit, as without them; both compose with
         exclude= and with diversity / per_category / pool (the scoped list is the pool).  With both None the old entry
-        point runs: the same launches and bits.  label_ranks takes no scope."""
+        point runs: the same launches and bits.  label_ranks takes no scope.
+        index (a CategoryIndex, category_index()): a row scores the lists of the categories it asks for and nothing
+        else -- tlsan_eval_topk_lists; the same ids and score bits as the category form without it.  category is then
+        required, [B] or [B, P] with P <= 8: a row gets the best of the UNION of its categories (a negative entry is no
+        probe, a repeated id counts once); a row of negatives only is unrestricted and runs through the path without
+        an index as a sub-batch (one host read finds such rows).  The scope belongs to the index
+        (category_index(within=scope)): within= beside index= is a ValueError, as are an index over another item or
+        category count, an id >= cate_count, P > 8 and a wrong shape, all before any launch.  exclude= and the second
+        stage compose as with the scope: the indexed list is the pool.  Worth it when a category is a small part of
+        the table (profiles/category_index.md); with index=None nothing changes."""
         N = rerank_pool(k, diversity, per_category, pool)
         within = scope_within(within, self.config["item_count"])
-        category = scope_categories(category, batch_rows(batch), self.config["cate_count"], self.device)
+        if recommend_index(index, within, self.config["item_count"], self.config["cate_count"]) is not None:
+            category = index_categories(category, batch_rows(batch), self.config["cate_count"], self.device)
+        else:
+            category = scope_categories(category, batch_rows(batch), self.config["cate_count"], self.device)
         _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
         excl, st = exclusion_csr(db, exclude, self.config["item_count"]), self._stream()
-        if within is None and category is None:
+        if index is not None:
+            topk = lambda n: indexed_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, category, 1, 0,
+                                          self.config["item_count"], self._topk_workspace, st)
+        elif within is None and category is None:
             topk = lambda n: eval_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, 1, 0, self._topk_workspace, st)
         else:
             sub = None if within is None else within.sub(1, 0, self.config["item_count"])
@@ -1610,7 +1795,7 @@ class Model(object):
                                 None if item_weight is None else item_weight[g], exposure, st)
         return list_metrics_chunks(ids, labels, rerank_chunk(ids.shape[1], self.config["hidden_units"]), measure)
 
-    def similar_items(self, items, k, metric="cosine", exclude=None, within=None, same_category=False):
+    def similar_items(self, items, k, metric="cosine", exclude=None, within=None, same_category=False, index=None):
         """The k nearest items of each item of `items` (a 1-D list, array or tensor of global ids; outside
         [0, item_count): ValueError) by the representation the model scores with, [item_emb || cate_emb[item_cate]]:
         metric "cosine" or "dot" (the product of the true vectors: the table scale enters twice); no bias, no user.
@@ -1621,12 +1806,20 @@ class Model(object):
         first, the scale is NOT folded -- parameters, scale and state keep their bits.
         within (an ItemScope): the nearest WITHIN the scope's items, of which alone the similarities are formed;
         same_category: query q's list holds items of item_cate[q]'s category only (it still scans the scope, or the
-        whole table without one) -- tlsan_similar_topk_scoped, same score bits.  With neither the old entry point runs."""
+        whole table without one) -- tlsan_similar_topk_scoped, same score bits.  With neither the old entry point runs.
+        index (a CategoryIndex) with same_category=True: query q scores the list of item_cate[q] and nothing else
+        (tlsan_similar_topk_lists), same ids and score bits; index= without same_category=True, or beside within=
+        (the scope belongs to the index), is a ValueError."""
         qids, mc, excl = similar_queries(items, self.config["item_count"], metric, exclude, self.device)
         within = scope_within(within, self.config["item_count"])
+        index = similar_index(index, within, same_category, self.config["item_count"], self.config["cate_count"])
         self._flush()
         st = self._stream()
         vec, inv = item_vectors(self.lib, self.dims, self.cparams, qids, 1, 0, st)
+        if index is not None:
+            cate = self.item_cate[qids.long()].to(torch.int32).reshape(-1, 1).contiguous()
+            return lists_similar_topk(self.lib, self.dims, self.cparams, vec, inv, qids, k, mc, excl,
+                                      index.local(1, 0, self.config["item_count"]), cate, 1, 0, self._topk_workspace, st)
         if within is None and not same_category:
             return similar_topk(self.lib, self.dims, self.cparams, vec, inv, qids, k, mc, excl, 1, 0, self._topk_workspace, st)
         sub = None if within is None else within.sub(1, 0, self.config["item_count"])

@@ -102,6 +102,10 @@ def parse(argv=None):
                     help="the similarity of --similar_k: cosine, or the dot product of the item vectors")
     ap.add_argument("--similar_same_category", type=int, default=0, choices=[0, 1],
                     help="with --similar_k: 1 = an item's list holds items of its own category only")
+    ap.add_argument("--category_index", type=int, default=0, choices=[0, 1],
+                    help="1 = build a per-category item index (Model.category_index; over the items of --recommend_categories "
+                         "when given) and pass it wherever --recommend_same_category / --similar_same_category apply: a row "
+                         "scores its category's items only.  The files written are the same")
     ap.add_argument("--eval_negatives", type=int, default=0,
                     help="sampled evaluation at every evaluation point: rank each test label among N sampled negatives "
                          "and report HR@k, NDCG@k (k = 1, 5, 10, 20), MRR and AUC_N; 0 = off")
@@ -122,6 +126,9 @@ def parse(argv=None):
         ap.error("--recommend_categories / --recommend_same_category narrow the lists of --recommend_k: give --recommend_k")
     if args.similar_same_category and not args.similar_k:
         ap.error("--similar_same_category narrows the lists of --similar_k: give --similar_k")
+    if args.category_index and not (args.recommend_categories or args.recommend_same_category or args.similar_same_category):
+        ap.error("--category_index serves --recommend_same_category / --similar_same_category (and --recommend_categories "
+                 "with them): give one of them")
     try:
         args.recommend_categories = [int(c) for c in args.recommend_categories.split(",") if c.strip()]
     except ValueError:
@@ -203,12 +210,15 @@ def similar_path(model_dir, k):
 SIMILAR_ROWS = 16384   # query items per similar_items call of write_similar
 
 
-def write_similar(model, model_dir, k, metric, item_count, write=True, same_category=False):
+def write_similar(model, model_dir, k, metric, item_count, write=True, same_category=False, index=None):
     """The k nearest items of EVERY item (model.similar_items; collective on a sharded model, where only the process
     with write=True keeps the lists) -> the path of the .npz written: item [I], ids [I, k], scores [I, k].
-    same_category: similar_items' (an item's list holds its own category only)."""
+    same_category: similar_items' (an item's list holds its own category only); index: its CategoryIndex, which goes
+    with same_category."""
     ids, scores = [], []
     scoped = dict(same_category=True) if same_category else {}
+    if same_category and index is not None:
+        scoped["index"] = index
     for i0 in range(0, item_count, SIMILAR_ROWS):
         a, b = model.similar_items(np.arange(i0, min(i0 + SIMILAR_ROWS, item_count)), k, metric=metric, **scoped)
         if write:
@@ -545,12 +555,18 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
     final_sampled = sampled_now() if args.eval_negatives else None
     final_full = full_now() if full_mode else None
     model.save(None)                                           # train.py:239
+    # --category_index: one index over the whole table for the lists that take one (recommend's, over its scope, below)
+    whole = model.category_index() if args.category_index and (
+        (args.similar_k and args.similar_same_category) or
+        (args.recommend_k and args.recommend_same_category and not args.recommend_categories)) else None
     if args.recommend_k:
         settings = recommend_settings(args)
         # (a DevicePackedSet keeps the host set it was made from: the novelty weights are counted on the host)
         measure = ListMeasurement(model, rows, args.recommend_k, getattr(train_set, "ps", train_set)) \
             if args.recommend_metrics else None
         scope = dict(within=model.item_scope(categories=args.recommend_categories)) if args.recommend_categories else {}
+        if args.category_index and args.recommend_same_category:   # (the scope belongs to the index)
+            scope = dict(index=model.category_index(**scope) if scope else whole)
         rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen), on_lists=measure,
                                  same_category=bool(args.recommend_same_category), **settings, **scope)
         list_res = measure.result() if measure is not None else None       # (collective: every rank)
@@ -562,7 +578,7 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
                 say("List metrics: %s" % write_list_metrics(args.model_dir, args.recommend_k, list_res, settings))
     if args.similar_k:
         path = write_similar(model, args.model_dir, args.similar_k, args.similar_metric, rows.config["item_count"],
-                             write=rows.rank in (None, 0), same_category=bool(args.similar_same_category))
+                             write=rows.rank in (None, 0), same_category=bool(args.similar_same_category), index=whole)
         if path is not None:
             say("Similar items: %s" % path)
     model.train_writer.flush()
