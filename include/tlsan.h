@@ -636,6 +636,39 @@ int tlsan_similar_topk_lists(const tlsan_dims* dims, const tlsan_params* p, cons
                              int32_t max_list, const int32_t* row_lists, int32_t P, int32_t id_mul, int32_t id_add,
                              int32_t* ids, float* scores, void* ws, size_t ws_bytes, void* stream);
 
+/* Clustered item index: the partition the indexed lists take, LEARNED from the item vectors (k-means over what
+ * tlsan_item_vectors writes), and the choice of the lists a query probes.  The three calls take dense fp32 matrices with
+ * d = 64, 128 or 256 (16-byte aligned rows), read no table and change no parameter or state; C is the number of
+ * centroids, 1 <= C <= 16384.
+ *   tlsan_cluster_assign: assign[n] = the centroid nearest to row n of x [N, d] in Euclidean distance, found as the argmax
+ *     over j of fl(x_n . c_j) - h_j, h_j = fl(|c_j|^2 / 2) (summed in double), the product on the evaluation scorers' fp32
+ *     MFMA chains; equal values -> the lower j; a row whose best value is NaN (or that has none above -inf) -> 0.
+ *     dist[n] (dist may be NULL) = max(|x_n|^2 - 2 best_n, 0), the norm summed in double: the row's term of the k-means
+ *     objective.  A row's result depends on that row and on cent only: not on N, the other rows or the launch geometry.
+ *     Workspace: C floats (tlsan_cluster_workspace_bytes).
+ *   tlsan_cluster_means: cent[j] = the mean of the rows x[order[p]], seg_off[j] <= p < seg_off[j + 1] (x [N, d], order [N],
+ *     seg_off [C + 1]), summed in double in the order given and rounded once.  An empty segment leaves cent[j] as it is; a
+ *     position or a row outside [0, N) is passed over.  No atomics: the result is a function of the inputs, bit for bit.
+ *   tlsan_cluster_probe: row_lists[b, 0 .. P) = the P lists of highest s_j = fl(fl((q_b . c_j) * scale_j) + bias_j) (two
+ *     roundings, as a score of tlsan_eval_topk; scale NULL: 1, bias NULL: 0) for q [B, d], 1 <= P <= 64, in
+ *     tlsan_eval_topk's order: higher first, equal -> lower list, NaN last.  With list_off [C + 1] given, a list with
+ *     list_off[j + 1] <= list_off[j] is passed over.  Slots left over (C < P, too few lists with items) hold -1.  A
+ *     row's lists depend on that row only.  Workspace: B * P floats.
+ *   tlsan_cluster_workspace_bytes(B, C, P): enough for tlsan_cluster_assign with C centroids and for tlsan_cluster_probe of
+ *     B rows and P probes (B or P 0: the assignment alone); 0, with tlsan_last_error set, on a refusal.
+ * Refused before any launch, with the function's name in tlsan_last_error: a NULL pointer among the required ones, N or B
+ * < 1 (N > 2^30, B > 2^24), C outside 1..16384, P outside 1..64 (TLSAN_E_BADARG); d not 64 / 128 / 256
+ * (TLSAN_E_UNSUPPORTED); a workspace that is NULL or too small (TLSAN_E_WORKSPACE).  The four functions are additions:
+ * nothing else in the ABI changed (TLSAN_ABI_VERSION stays 15). */
+size_t tlsan_cluster_workspace_bytes(int32_t B, int32_t C, int32_t P);
+int tlsan_cluster_assign(const float* x, int32_t N, int32_t d, const float* cent, int32_t C, int32_t* assign, float* dist,
+                         void* ws, size_t ws_bytes, void* stream);
+int tlsan_cluster_means(const float* x, int32_t N, const int32_t* order, const int32_t* seg_off, int32_t C, int32_t d,
+                        float* cent, void* stream);
+int tlsan_cluster_probe(const float* q, int32_t B, int32_t d, const float* cent, const float* scale, const float* bias,
+                        const int32_t* list_off, int32_t C, int32_t P, int32_t* row_lists, void* ws, size_t ws_bytes,
+                        void* stream);
+
 /* Diversified lists: the second stage behind tlsan_eval_topk.  From each row's POOL of N entries (1 <= K <= N <= 256, in
  * tlsan_eval_topk's order: higher score first, ties -> lower global id) pick K by greedy maximal marginal relevance
  * under a per-category cap.  Pool entry j of a row has a global id g_j and the model score s_j (pool_ids, pool_scores

@@ -21,6 +21,7 @@ TOPK_MAX = 256  # TOPK_MAX (csrc/tlsan_topk.h): largest K of tlsan_eval_topk
 RERANK_MAX = 256  # RERANK_MAX (csrc/tlsan_rerank.h): largest pool of tlsan_rerank
 LISTM_MAX = 256   # LISTM_MAX (csrc/tlsan_listm.h): longest list of tlsan_list_metrics
 SIM_DOT, SIM_COSINE = 0, 1   # TLSAN_SIM_DOT / TLSAN_SIM_COSINE (include/tlsan.h): the metrics of tlsan_similar_topk
+CLUSTER_CMAX, CLUSTER_PMAX = 16384, 64   # csrc/tlsan_cluster.h: most centroids of a call, most probes of a row
 NEG_MAX = 1024  # NEG_MAX (csrc/tlsan_cand.h): largest N of tlsan_sample_negatives
 
 EXPORTS = [
@@ -33,6 +34,7 @@ EXPORTS = [
     "tlsan_item_vectors", "tlsan_similar_workspace_bytes", "tlsan_similar_topk", "tlsan_rerank", "tlsan_list_metrics",
     "tlsan_scope_workspace_bytes", "tlsan_eval_topk_scoped", "tlsan_similar_topk_scoped",
     "tlsan_lists_workspace_bytes", "tlsan_eval_topk_lists", "tlsan_similar_topk_lists",
+    "tlsan_cluster_workspace_bytes", "tlsan_cluster_assign", "tlsan_cluster_means", "tlsan_cluster_probe",
     "tlsan_score_candidates", "tlsan_candidate_ranks", "tlsan_sample_negatives", "tlsan_profile_enable", "tlsan_profile_stride",
     "tlsan_profile_collect", "tlsan_debug_stamps", "tlsan_rows_apply_workspace", "tlsan_rows_apply", "tlsan_scan_compact",
     "tlsan_route_plan", "tlsan_shard_gather", "tlsan_shard_summary", "tlsan_shard_apply_workspace", "tlsan_shard_apply",
@@ -255,6 +257,18 @@ def load():
                                                  C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_size_t, C.c_void_p]
         lib.tlsan_similar_topk_lists.restype = C.c_int
+    if hasattr(lib, "tlsan_cluster_probe"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
+        lib.tlsan_cluster_workspace_bytes.argtypes = [C.c_int32] * 3
+        lib.tlsan_cluster_workspace_bytes.restype = C.c_size_t
+        lib.tlsan_cluster_assign.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.tlsan_cluster_assign.restype = C.c_int
+        lib.tlsan_cluster_means.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_void_p]
+        lib.tlsan_cluster_means.restype = C.c_int
+        lib.tlsan_cluster_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.tlsan_cluster_probe.restype = C.c_int
     lib.tlsan_rerank.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.tlsan_rerank.restype = C.c_int
     if hasattr(lib, "tlsan_list_metrics"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)

@@ -38,6 +38,14 @@ def _ru4(x):
     return (x + 3) // 4 * 4
 
 
+def refuse_clustered(index, probes=None):
+    """A ClusteredIndex (or its probes=) beside a ShardedModel: a ValueError before anything is gathered or launched."""
+    from .cluster import ClusteredIndex
+    if isinstance(index, ClusteredIndex) or probes is not None:
+        raise ValueError("ShardedModel: a ClusteredIndex is not supported on a row-sharded model (building and probing "
+                         "across ranks); use a CategoryIndex, or a Model")
+
+
 class ShardedModel:
     """Model surface (train / eval_auc / ...) over row-sharded tables; see module docstring."""
 
@@ -413,12 +421,17 @@ class ShardedModel:
         item = last_items(self.device_batch(batch, is_test=True))
         return torch.where(item >= 0, self._item_cate(item.clamp(min=0)), -1).to(torch.int32)
 
+    def cluster_index(self, *args, **kwargs):
+        """Model.cluster_index is not built across ranks: a ValueError (train and probe a ClusteredIndex on a Model)."""
+        raise ValueError("ShardedModel: a ClusteredIndex is not supported on a row-sharded model (building and probing across ranks)")
+
     def category_index(self, within=None):
         """Model.category_index: a CategoryIndex over the model's items or an ItemScope's (every rank builds the same one)."""
         return CategoryIndex(self._item_cate(torch.arange(self.I, device=self.device)), self.C, self.device,
                              within=scope_within(within, self.I))
 
-    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None, index=None):
+    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None, index=None,
+                  probes=None):
         """Model.recommend for this rank's rows (every rank calls it, with the same k, exclusion mode and diversity
         settings): u_t and the exclusion lists are all-gathered, every rank selects the k best of ITS item shard for all
         rows (tlsan_eval_topk, global ids n * world + rank), each row's lists go to the rank that owns the row (one
@@ -433,6 +446,7 @@ class ShardedModel:
         item shard, index.local(world, rank, its count), for all gathered rows (tlsan_eval_topk_lists); the rows'
         category arrays are all-gathered with u_t, and the unrestricted rows among them run through the path without
         an index on every rank."""
+        refuse_clustered(index, probes)
         N = rerank_pool(k, diversity, per_category, pool)
         want = int(k)
         within = scope_within(within, self.I)
@@ -533,7 +547,7 @@ class ShardedModel:
                                 exposure, st)
         return list_metrics_chunks(ids, labels, rerank_chunk(ids.shape[1], self.d, self.world), measure)
 
-    def similar_items(self, items, k, metric="cosine", exclude=None, within=None, same_category=False, index=None):
+    def similar_items(self, items, k, metric="cosine", exclude=None, within=None, same_category=False, index=None, probes=None):
         """Model.similar_items, collective: every rank passes the same items (and k, metric, exclude, within, same_category) and every rank
         gets all Q lists.  Each rank reads the stored vectors and inverse norms of the queries ITS item shard holds
         (tlsan_item_vectors, zeros for the others); they are all-gathered and each query's are SELECTED from the one
@@ -541,6 +555,7 @@ class ShardedModel:
         (tlsan_similar_topk, global ids n * world + rank), the lists are all-gathered and merged (tlsan_topk_merge).
         Same ids and score bits as Model.similar_items on the gathered parameters.  index (with same_category=True): every
         rank scans the lists of its own item shard, index.local(world, rank, its count) (tlsan_similar_topk_lists)."""
+        refuse_clustered(index, probes)
         qids, mc, excl = similar_queries(items, self.I, metric, exclude, self.device)
         within = scope_within(within, self.I)
         index = similar_index(index, within, same_category, self.I, self.C)

@@ -1706,7 +1706,15 @@ class Model(object):
         return CategoryIndex(self.item_cate, self.config["cate_count"], self.device,
                              within=scope_within(within, self.config["item_count"]))
 
-    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None, index=None):
+    def cluster_index(self, nlists, within=None, iters=10, seed=1234, train_size=None, max_list=None):
+        """A ClusteredIndex (cluster.py) over this model's items, or over an ItemScope's (within=): nlists lists learned by
+        k-means from the item vectors as stored -- the `index=` that goes with `probes=` in recommend and similar_items.
+        A snapshot of the parameters: rebuild it after training."""
+        from .cluster import fit
+        return fit(self, nlists, within=within, iters=iters, seed=seed, train_size=train_size, max_list=max_list)
+
+    def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None, index=None,
+                  probes=None):
         """The k best items over ALL items for each row -- what tf.nn.top_k(eval_logits, k) gives the reference
         (model.py:140) -- without materialising the [B, I] scores.  Takes label_ranks' batches (the label and the
         negative are not used).  -> (ids [B, k] int32, scores [B, k] float32) device tensors, in tf.nn.top_k's
@@ -1739,16 +1747,30 @@ class Model(object):
         (category_index(within=scope)): within= beside index= is a ValueError, as are an index over another item or
         category count, an id >= cate_count, P > 8 and a wrong shape, all before any launch.  exclude= and the second
         stage compose as with the scope: the indexed list is the pool.  Worth it when a category is a small part of
-        the table (profiles/category_index.md); with index=None nothing changes."""
+        the table (profiles/category_index.md); with index=None nothing changes.
+        index (a ClusteredIndex, cluster_index()) with probes=P, 1 <= P <= 64: an APPROXIMATE list over the whole
+        catalogue (or the index's scope) -- the row scores the P lists whose centroids score highest against it
+        (tlsan_cluster_probe, with the table scale and the lists' mean bias) and nothing else: tlsan_eval_topk_lists on
+        groups of 8 probes, merged.  Every returned score is the exact path's bit for bit and the list is the exact top k
+        of the probed lists' union minus the exclusions; with P >= the number of non-empty lists it equals recommend()
+        without an index.  Recall at fewer probes is not guaranteed (cluster.recall measures it).  category= or within=
+        beside it, probes= without it or outside 1..64, or an index over another item count: ValueError before any launch."""
+        from .cluster import clustered_probes, clustered_topk
         N = rerank_pool(k, diversity, per_category, pool)
+        probes = clustered_probes(index, probes, self.config["item_count"], category=category, within=within)
         within = scope_within(within, self.config["item_count"])
-        if recommend_index(index, within, self.config["item_count"], self.config["cate_count"]) is not None:
+        if probes is not None:
+            pass
+        elif recommend_index(index, within, self.config["item_count"], self.config["cate_count"]) is not None:
             category = index_categories(category, batch_rows(batch), self.config["cate_count"], self.device)
         else:
             category = scope_categories(category, batch_rows(batch), self.config["cate_count"], self.device)
         _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
         excl, st = exclusion_csr(db, exclude, self.config["item_count"]), self._stream()
-        if index is not None:
+        if probes is not None:
+            topk = lambda n: clustered_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, probes,
+                                            self._scale_vector(index.lists), self._topk_workspace, st)
+        elif index is not None:
             topk = lambda n: indexed_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, category, 1, 0,
                                           self.config["item_count"], self._topk_workspace, st)
         elif within is None and category is None:
@@ -1795,7 +1817,14 @@ class Model(object):
                                 None if item_weight is None else item_weight[g], exposure, st)
         return list_metrics_chunks(ids, labels, rerank_chunk(ids.shape[1], self.config["hidden_units"]), measure)
 
-    def similar_items(self, items, k, metric="cosine", exclude=None, within=None, same_category=False, index=None):
+    def _scale_vector(self, n):
+        """The table scale as the probe takes it: [n] float32 on the device, read from the state without a host round
+        trip; None where there is no scale (dense L2: 1)."""
+        if self.l2_mode != L.L2_LAZY:
+            return None
+        return self.state[:4].view(torch.float32).expand(n).contiguous()
+
+    def similar_items(self, items, k, metric="cosine", exclude=None, within=None, same_category=False, index=None, probes=None):
         """The k nearest items of each item of `items` (a 1-D list, array or tensor of global ids; outside
         [0, item_count): ValueError) by the representation the model scores with, [item_emb || cate_emb[item_cate]]:
         metric "cosine" or "dot" (the product of the true vectors: the table scale enters twice); no bias, no user.
@@ -1809,13 +1838,22 @@ class Model(object):
         whole table without one) -- tlsan_similar_topk_scoped, same score bits.  With neither the old entry point runs.
         index (a CategoryIndex) with same_category=True: query q scores the list of item_cate[q] and nothing else
         (tlsan_similar_topk_lists), same ids and score bits; index= without same_category=True, or beside within=
-        (the scope belongs to the index), is a ValueError."""
+        (the scope belongs to the index), is a ValueError.
+        index (a ClusteredIndex) with probes=P: the approximate form, as in recommend -- the query's vector picks its P
+        lists (cosine: against the normalised centroids; dot: the plain product; no bias), tlsan_similar_topk_lists on
+        groups of 8, merged; same_category= or within= beside it is a ValueError."""
+        from .cluster import clustered_probes, clustered_similar_topk
         qids, mc, excl = similar_queries(items, self.config["item_count"], metric, exclude, self.device)
+        probes = clustered_probes(index, probes, self.config["item_count"], same_category=same_category, within=within)
         within = scope_within(within, self.config["item_count"])
-        index = similar_index(index, within, same_category, self.config["item_count"], self.config["cate_count"])
+        if probes is None:
+            index = similar_index(index, within, same_category, self.config["item_count"], self.config["cate_count"])
         self._flush()
         st = self._stream()
         vec, inv = item_vectors(self.lib, self.dims, self.cparams, qids, 1, 0, st)
+        if probes is not None:
+            return clustered_similar_topk(self.lib, self.dims, self.cparams, vec, inv, qids, k, mc, excl, index, probes,
+                                          self._topk_workspace, st)
         if index is not None:
             cate = self.item_cate[qids.long()].to(torch.int32).reshape(-1, 1).contiguous()
             return lists_similar_topk(self.lib, self.dims, self.cparams, vec, inv, qids, k, mc, excl,

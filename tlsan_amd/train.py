@@ -106,6 +106,13 @@ def parse(argv=None):
                     help="1 = build a per-category item index (Model.category_index; over the items of --recommend_categories "
                          "when given) and pass it wherever --recommend_same_category / --similar_same_category apply: a row "
                          "scores its category's items only.  The files written are the same")
+    ap.add_argument("--cluster_index", type=int, default=0, metavar="NLISTS",
+                    help="with --recommend_k: build a clustered item index of NLISTS lists (Model.cluster_index: k-means over "
+                         "the item vectors; over the items of --recommend_categories when given) and write APPROXIMATE lists: "
+                         "each row scores the --cluster_probes lists nearest to it.  With --recommend_metrics 1 the recall@k "
+                         "of these lists against the exact ones over the test rows is printed.  0 = off")
+    ap.add_argument("--cluster_probes", type=int, default=8, metavar="P",
+                    help="with --cluster_index: lists a row probes, 1..64")
     ap.add_argument("--eval_negatives", type=int, default=0,
                     help="sampled evaluation at every evaluation point: rank each test label among N sampled negatives "
                          "and report HR@k, NDCG@k (k = 1, 5, 10, 20), MRR and AUC_N; 0 = off")
@@ -129,6 +136,12 @@ def parse(argv=None):
     if args.category_index and not (args.recommend_categories or args.recommend_same_category or args.similar_same_category):
         ap.error("--category_index serves --recommend_same_category / --similar_same_category (and --recommend_categories "
                  "with them): give one of them")
+    if args.cluster_index and not args.recommend_k:
+        ap.error("--cluster_index serves the lists of --recommend_k: give --recommend_k")
+    if args.cluster_index and (args.category_index or args.recommend_same_category):
+        ap.error("--cluster_index goes without --category_index / --recommend_same_category: a row's lists are chosen by the index")
+    if args.cluster_index < 0 or (args.cluster_index and not 1 <= args.cluster_probes <= 64):
+        ap.error("--cluster_index wants NLISTS >= 1 and --cluster_probes in 1..64")
     try:
         args.recommend_categories = [int(c) for c in args.recommend_categories.split(",") if c.strip()]
     except ValueError:
@@ -433,6 +446,29 @@ class ListMeasurement:
         return self.counters.result(self.rows.sum(self.exposure.to(torch.int64)), self.items)
 
 
+class RecallMeasurement:
+    """The recall of --cluster_index with --recommend_metrics: beside every launch's approximate lists it makes the exact
+    ones (the same call without the index) and counts, per real row, the exact list's valid ids the approximate list holds;
+    result() sums over the processes -> (recall@k, rows).  then: the ListMeasurement to call on as well (None: none)."""
+
+    def __init__(self, model, rows, k, exclude, exact_settings, then=None):
+        self.model, self.rows, self.k, self.exclude, self.settings, self.then = model, rows, k, exclude, exact_settings, then
+        self.sums = torch.zeros(2, dtype=torch.float64, device=model.device)      # summed per-row recall, rows counted
+
+    def __call__(self, db, ids, real):
+        exact = self.model.recommend(db, self.k, exclude=self.exclude, **self.settings)[0][:real]
+        n = (exact >= 0).sum(1)
+        hit = ((ids[:real, :, None] == exact[:, None, :]) & (exact[:, None, :] >= 0)).any(1).sum(1)
+        ok = n > 0
+        self.sums += torch.stack([(hit[ok] / n[ok]).to(torch.float64).sum(), ok.sum().to(torch.float64)])
+        if self.then is not None:
+            self.then(db, ids, real)
+
+    def result(self):
+        s = self.rows.sum(self.sums).cpu().numpy()
+        return (float(s[0] / s[1]) if s[1] else float("nan")), int(s[1])
+
+
 def recommend_test_set(model, rows, k, exclude, on_lists=None, same_category=False, **settings):
     """model.recommend over every test row (settings: its diversity keywords and within=) -> (user, ids, scores) host
     arrays in test-set order; None but on rank 0.  on_lists(device batch, ids, real): called with every launch's device
@@ -567,9 +603,21 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
         scope = dict(within=model.item_scope(categories=args.recommend_categories)) if args.recommend_categories else {}
         if args.category_index and args.recommend_same_category:   # (the scope belongs to the index)
             scope = dict(index=model.category_index(**scope) if scope else whole)
-        rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen), on_lists=measure,
-                                 same_category=bool(args.recommend_same_category), **settings, **scope)
+        recall_of = None
+        if args.cluster_index:                                     # (the scope belongs to the index)
+            cindex = model.cluster_index(args.cluster_index, **scope)
+            say("Clustered index: %d lists over %d items, max / mean list %d / %.1f, %d k-means iterations"
+                % (cindex.lists, cindex.count, cindex.max_list, cindex.mean_list, len(cindex.objective)))
+            if args.recommend_metrics:
+                recall_of = RecallMeasurement(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen),
+                                              dict(settings, **scope), then=measure)
+            scope = dict(index=cindex, probes=args.cluster_probes)
+        rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen),
+                                 on_lists=recall_of or measure, same_category=bool(args.recommend_same_category), **settings, **scope)
         list_res = measure.result() if measure is not None else None       # (collective: every rank)
+        if recall_of is not None:
+            say("Clustered index: recall@%d = %.4f against the exact lists over %d rows (%d probes)"
+                % ((args.recommend_k,) + recall_of.result() + (args.cluster_probes,)))
         if rec is not None:                                    # (rank 0 holds the rows)
             path = write_recommendations(args.model_dir, args.recommend_k, *rec, settings=settings)
             say("Recommendations: %s" % path)
