@@ -669,7 +669,31 @@ int tlsan_cluster_probe(const float* q, int32_t B, int32_t d, const float* cent,
                         const int32_t* list_off, int32_t C, int32_t P, int32_t* row_lists, void* ws, size_t ws_bytes,
                         void* stream);
 
-/* Diversified lists: the second stage behind tlsan_eval_topk.  From each row's POOL of N entries (1 <= K <= N <= 256, in
+/* Dense top-K: for each query vector q_i (q [Q, d], d = 64, 128 or 256, 16-byte aligned rows) the K rows of a dense fp32
+ * matrix x [N, d] of highest
+ *     score(i, n) = fl(fl(acc(q_i, x_n) * q_scale[i]) + q_bias[i])       (q_scale NULL: 1, q_bias NULL: 0; device vectors [Q])
+ * selected inside the scoring kernel: the [Q, N] matrix is never materialised, no table is read and no parameter or
+ * state changes.  acc is the fp32 MFMA chain of tlsan_eval_topk's tiles with the query in u_t's place; the products
+ * commute and the chain's k-order is the same, so with q_i an item's stored vector (tlsan_item_vectors), x_n a row's u_t,
+ * q_scale the table scale and q_bias the item's item_b, score(i, n) is tlsan_eval_topk's / tlsan_score_candidates' score
+ * of that (row, item) pair bit for bit: the audience of an item -- a user appears in it with exactly the score the item
+ * has in that user's list.  The global id of matrix row n is id_add + n (a caller that holds rows [row0, row0 + N) of a
+ * larger matrix passes row0 and merges the holders' lists with tlsan_topk_merge).  ids / scores [Q, K] in
+ * tlsan_eval_topk's order: higher score first, equal scores -> lower global row id, +0 == -0, NaN last; a query with
+ * fewer than K eligible rows ends in -1 / -inf.  excl_off [Q + 1] / excl_ids (both or neither): per-query global row ids,
+ * ascending, never selected; listed ids outside [id_add, id_add + N) match no row.
+ *   tlsan_dense_topk_workspace_bytes(Q, N, K): the room the slices' lists take, never less for a larger Q, N or K; 0, with
+ *     tlsan_last_error set, on sizes the call refuses.
+ * Refused before any launch, with the function's name in tlsan_last_error: a NULL q, x, ids or scores, excl_off without
+ * excl_ids or the reverse, Q < 1 (Q > 2^24), N < 1 (N > 2^30), id_add < 0 or id_add + N past int32, K outside 1..256
+ * (TLSAN_E_BADARG); d not 64 / 128 / 256 (TLSAN_E_UNSUPPORTED); a workspace that is NULL or too small
+ * (TLSAN_E_WORKSPACE).  The two functions are additions: nothing else in the ABI changed (TLSAN_ABI_VERSION stays 15). */
+size_t tlsan_dense_topk_workspace_bytes(int32_t Q, int32_t N, int32_t K);
+int tlsan_dense_topk(const float* q, int32_t Q, int32_t d, const float* x, int32_t N, const float* q_scale, const float* q_bias,
+                     const int32_t* excl_off, const int32_t* excl_ids, int32_t id_add, int32_t K, int32_t* ids, float* scores,
+                     void* ws, size_t ws_bytes, void* stream);
+
+/* Diversified lists: the second stage behind tlsan_eval_topk. From each row's POOL of N entries (1 <= K <= N <= 256, in
  * tlsan_eval_topk's order: higher score first, ties -> lower global id) pick K by greedy maximal marginal relevance
  * under a per-category cap.  Pool entry j of a row has a global id g_j and the model score s_j (pool_ids, pool_scores
  * [B, N]), and, at flattened position b * N + j, its stored vector w_j (vec [B * N, d], d = 64, 128 or 256), inv_j (inv

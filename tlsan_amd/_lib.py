@@ -35,6 +35,7 @@ EXPORTS = [
     "tlsan_scope_workspace_bytes", "tlsan_eval_topk_scoped", "tlsan_similar_topk_scoped",
     "tlsan_lists_workspace_bytes", "tlsan_eval_topk_lists", "tlsan_similar_topk_lists",
     "tlsan_cluster_workspace_bytes", "tlsan_cluster_assign", "tlsan_cluster_means", "tlsan_cluster_probe",
+    "tlsan_dense_topk_workspace_bytes", "tlsan_dense_topk",
     "tlsan_score_candidates", "tlsan_candidate_ranks", "tlsan_sample_negatives", "tlsan_profile_enable", "tlsan_profile_stride",
     "tlsan_profile_collect", "tlsan_debug_stamps", "tlsan_rows_apply_workspace", "tlsan_rows_apply", "tlsan_scan_compact",
     "tlsan_route_plan", "tlsan_shard_gather", "tlsan_shard_summary", "tlsan_shard_apply_workspace", "tlsan_shard_apply",
@@ -269,6 +270,13 @@ def load():
         lib.tlsan_cluster_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.tlsan_cluster_probe.restype = C.c_int
+    if hasattr(lib, "tlsan_dense_topk"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
+        lib.tlsan_dense_topk_workspace_bytes.argtypes = [C.c_int32] * 3
+        lib.tlsan_dense_topk_workspace_bytes.restype = C.c_size_t
+        lib.tlsan_dense_topk.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_size_t, C.c_void_p]
+        lib.tlsan_dense_topk.restype = C.c_int
     lib.tlsan_rerank.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.tlsan_rerank.restype = C.c_int
     if hasattr(lib, "tlsan_list_metrics"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)

@@ -31,7 +31,8 @@ from .dist_comm import (ExchangePlan, KeyRouter, ModPartition, RowExchange, _sta
 from .dist_step import DynamicStep, FlatLayout, StaticStep, fused_params
 from .model import (LAZY_ADAGRAD_OPTIMIZERS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer, candidate_tensor, eval_topk,
                     exclusion_csr, grow_workspace, hits_and_rows, pack_dense, read_checkpoint, sample_negatives, sampled_ranks,
-                    score_candidates, item_vectors, list_metric_inputs, list_metrics, list_metrics_chunks, rerank, rerank_chunk, rerank_pool, batch_rows, last_items, scope_categories, scope_within, scoped_similar_topk, scoped_topk, CategoryIndex, index_categories, indexed_topk, recommend_index, lists_similar_topk, similar_index, similar_queries, similar_topk, topk_merge, ItemScope, unpack_dense, write_checkpoint)
+                    score_candidates, item_vectors, list_metric_inputs, list_metrics, list_metrics_chunks, rerank, rerank_chunk, rerank_pool, batch_rows, last_items, scope_categories, scope_within, scoped_similar_topk, scoped_topk, CategoryIndex, index_categories, indexed_topk, recommend_index, lists_similar_topk, similar_index, similar_queries, similar_topk, topk_merge, ItemScope, unpack_dense, write_checkpoint,
+                    UserVectors, audience_exclusion, audience_queries, batch_list, check_user_vectors, dense_topk, kept_rows)
 
 
 def _ru4(x):
@@ -593,6 +594,65 @@ class ShardedModel:
             cid, csc = topk_merge(self.lib, allgather_rows(cid, self.group).view(self.world, Q, k).transpose(0, 1).contiguous(),
                                   allgather_rows(csc, self.group).view(self.world, Q, k).transpose(0, 1).contiguous(), st)
         return cid, csc
+
+    def user_vectors(self, batches, real=None):
+        """Model.user_vectors for this rank's rows, collective: every rank passes as many batches (a forward is an
+        exchange; a rank without rows passes a placeholder batch with real 0, as the evaluation's shares do) -> this
+        rank's UserVectors.  One all-gather of the row counts fixes row0 and n_total: the global rows are rank 0's rows,
+        then rank 1's, and so on."""
+        batches = batch_list(batches)
+        real = kept_rows(real, len(batches))
+        vec, user = [torch.empty(0, self.d, dtype=torch.float32, device=self.device)], [torch.empty(0, dtype=torch.int32, device=self.device)]
+        for batch, n in zip(batches, real):
+            with self._eval_forward(batch) as (db, _, _, _, ut):
+                vec.append(ut[:n].clone())
+                user.append(db.u[:n].to(torch.int32))
+        vec, user = torch.cat(vec), torch.cat(user)
+        counts = allgather_rows(torch.tensor([int(vec.shape[0])], device=self.device), self.group).tolist()
+        return UserVectors(vec, user, self, self._step, row0=sum(counts[:self.rank]), n_total=sum(counts), group=self.group,
+                           world=self.world)
+
+    def audience(self, items, k, users, exclude=None):
+        """Model.audience, collective: every rank passes the same items, k and exclusion (lists of GLOBAL row numbers,
+        whole; or the same SeenItems) and its own UserVectors, and every rank gets all Q lists, in global row numbers
+        (users.users_of maps them to user ids).  The queries' stored vectors are read on each item shard
+        (tlsan_item_vectors, zeros for the others) and their item_b from the fused shard rows, both all-gathered and each
+        query's SELECTED from the rank that owns it (never a sum: it would turn -0 into +0); each rank scans its own
+        rows with id_add = row0 (a rank without rows contributes -1 / -inf lists); the ranks' lists are all-gathered and
+        folded with tlsan_topk_merge.  Same rows and score bits as Model.audience on the gathered parameters and rows."""
+        qids = audience_queries(items, k, self.I, self.device)
+        check_user_vectors(users, self, self._step, self.d, self.device)
+        if users.n_total < 1:
+            raise ValueError("users: no rows")
+        excl = audience_exclusion(exclude, qids, users)
+        if self._static is not None:   # (plans announced ahead may be running on the side streams)
+            self._static.drain()
+        Q, k, st, W = int(qids.shape[0]), int(k), self._stream(), self.world
+        nloc, ldims, lp = self._item_shard()
+        if nloc > 0:
+            vec, _ = item_vectors(self.lib, ldims, lp, qids, W, self.rank, st)
+        else:
+            vec = torch.zeros(Q, self.d, dtype=torch.float32, device=self.device)
+        mine = (qids % W) == self.rank
+        local = torch.where(mine, torch.div(qids, W, rounding_mode="floor"), torch.zeros_like(qids)).long()
+        bias = torch.where(mine, self.shard[local, self.di], torch.zeros(Q, dtype=torch.float32, device=self.device))
+        if W > 1:
+            owner = (qids % W).long()
+            vec = torch.gather(allgather_rows(vec, self.group).view(W, Q, self.d), 0,
+                               owner[None, :, None].expand(1, Q, self.d))[0].contiguous()
+            bias = torch.gather(allgather_rows(bias, self.group).view(W, Q), 0, owner[None])[0]
+        bias = bias.contiguous()
+        scale = self._P.expand(Q).contiguous() if self.lazy else None
+        if len(users) > 0:
+            rid, rsc = dense_topk(self.lib, vec, users.vec, scale, bias, excl, users.row0, k,
+                                  lambda nbytes: grow_workspace(self, "_tws", nbytes), st)
+        else:
+            rid = torch.full((Q, k), -1, dtype=torch.int32, device=self.device)
+            rsc = torch.full((Q, k), float("-inf"), dtype=torch.float32, device=self.device)
+        if W > 1:
+            rid, rsc = topk_merge(self.lib, allgather_rows(rid, self.group).view(W, Q, k).transpose(0, 1).contiguous(),
+                                  allgather_rows(rsc, self.group).view(W, Q, k).transpose(0, 1).contiguous(), st)
+        return rid, rsc
 
     def _score_owned(self, ut, cand):
         """Scores of this rank's rows' candidates (u_t [B, d], cand [B, C] global ids; every rank calls it with the same

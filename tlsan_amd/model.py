@@ -800,6 +800,161 @@ def topk_merge(lib, cand_ids, cand_scores, stream):
     return ids, scores
 
 
+AUDIENCE_CHUNK = 4096   # queries per tlsan_dense_topk call: bounds the slices' lists in the workspace (Q x slices x K)
+
+
+class UserVectors:
+    """The rows' representations u_t as a reusable object -- what Model.user_vectors / ShardedModel.user_vectors return and
+    audience takes: vec [N, d] float32 and user [N] int32 (the batch's u) on the device.  A row is a SAMPLE: a user at a point of
+    their history.  row0 / n_total: the global number of row 0 and the number of rows over all holders (0 and N on a Model;
+    on a ShardedModel the ranks' rows follow each other in rank order).  A snapshot of the model `owner` at its global
+    step `step`: audience refuses it once the model has trained on, like the indexes it is rebuilt after training."""
+
+    def __init__(self, vec, user, owner, step, row0=0, n_total=None, group=None, world=1):
+        self.vec, self.user = vec.contiguous(), user.to(torch.int32).contiguous()
+        self.owner, self.step = owner, int(step)
+        self.row0, self.n_total = int(row0), int(vec.shape[0] if n_total is None else n_total)
+        self.group, self.world = group, int(world)
+        self._all_users = None
+
+    def __len__(self):
+        return int(self.vec.shape[0])
+
+    def users_of(self, rows):
+        """The user ids of global row numbers (tensor or array of any shape, as audience returns them; -1 stays -1) ->
+        int32 device tensor of that shape.  On a sharded model the call is collective the first time: the ranks' `user`
+        arrays are gathered once and kept."""
+        if self._all_users is None:
+            users = self.user
+            if self.world > 1:
+                from .dist_comm import allgather_rows
+                n = allgather_rows(torch.tensor([len(self)], device=users.device), self.group).tolist()
+                padded = torch.full((max(max(n), 1),), -1, dtype=torch.int32, device=users.device)
+                padded[:len(self)] = users
+                got = allgather_rows(padded, self.group).view(len(n), -1)
+                users = torch.cat([got[r, :n[r]] for r in range(len(n))])
+            self._all_users = users
+        rows = torch.as_tensor(rows).to(self._all_users.device).long()
+        if self._all_users.numel() == 0:
+            return torch.full_like(rows, -1, dtype=torch.int32)
+        return torch.where(rows >= 0, self._all_users[rows.clamp(min=0)], -1).to(torch.int32)
+
+
+def batch_list(batches):
+    """user_vectors' argument -> a list of batches: one batch (a tuple of arrays or a DeviceBatch) or an iterable of them."""
+    if isinstance(batches, DeviceBatch) or (isinstance(batches, tuple) and len(batches) > 0 and not
+                                            isinstance(batches[0], (tuple, DeviceBatch))):
+        return [batches]
+    return list(batches)
+
+
+def kept_rows(real, n):
+    """user_vectors' real= -> how many rows of each of the n batches are kept (None: all of them)."""
+    if real is None:
+        return [None] * n
+    real = [int(r) for r in (real if isinstance(real, (list, tuple, np.ndarray)) else [real])]
+    if len(real) != n or min(real + [0]) < 0:
+        raise ValueError("real: want one non-negative row count per batch (%d batches)" % n)
+    return real
+
+
+def audience_queries(items, k, item_count, device):
+    """Checks audience's items and k -> the ids [Q] as an int32 device tensor."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= L.TOPK_MAX:
+        raise ValueError("k must be an integer in 1..%d, got %r" % (L.TOPK_MAX, k))
+    host = items.detach().cpu().numpy() if isinstance(items, torch.Tensor) else np.asarray(items)
+    if host.ndim != 1 or host.size < 1 or host.dtype.kind not in "iu":
+        raise ValueError("items: want a 1-D sequence of item ids, got shape %s dtype %s" % (host.shape, host.dtype))
+    host = host.astype(np.int64)
+    if host.min() < 0 or host.max() >= item_count:
+        raise ValueError("items: ids must be in [0, %d)" % item_count)
+    return torch.as_tensor(host.astype(np.int32)).to(device)
+
+
+def check_user_vectors(users, owner, step, d, device):
+    """audience's refusals about `users`: anything but a UserVectors of this model at its current global step."""
+    if not isinstance(users, UserVectors):
+        raise ValueError("users: want the UserVectors that user_vectors() returns, got %s" % type(users).__name__)
+    if users.owner is not owner:
+        raise ValueError("users: these UserVectors come from another model")
+    if users.step != step:
+        raise ValueError("users: taken at global step %d, the model is at %d -- rebuild them after training" % (users.step, step))
+    have, device = users.vec.device, torch.device(device)
+    other = have.type != device.type or (have.index is not None and device.index is not None and have.index != device.index)
+    if users.vec.dim() != 2 or users.vec.shape[1] != d or users.vec.dtype != torch.float32 or other:
+        raise ValueError("users: vec must be [N, %d] float32 on %s" % (d, device))
+    if users.user.shape != users.vec.shape[:1]:
+        raise ValueError("users: user must be [N]")
+
+
+def seen_rows_csr(seen_off, seen_ids, user, items, row0=0):
+    """The item -> rows transposition of a seen-items CSR for the query items: (off [Q + 1] int32, rows int32), query q's
+    list the global numbers row0 + n, ascending, of the rows n whose user user[n] has items[q] in their seen list
+    seen_ids[seen_off[u] : seen_off[u + 1]].  A user id outside the CSR has seen nothing; a repeated query item gets
+    its list again.  Torch on the tensors' device (CPU tensors work), one sort of the (query item, row) pairs that hit,
+    no loop over items or rows."""
+    dev = user.device
+    seen_off, seen_ids, items = seen_off.to(dev).long(), seen_ids.to(dev).long(), items.to(dev).long()
+    n_users, N, Q = int(seen_off.shape[0]) - 1, int(user.shape[0]), int(items.shape[0])
+    u = user.long()
+    known = (u >= 0) & (u < n_users)
+    u = torch.where(known, u, torch.zeros_like(u))
+    lo = seen_off[u]
+    n = torch.where(known, seen_off[u + 1] - lo, torch.zeros_like(lo))
+    start = torch.cumsum(n, 0) - n
+    row = torch.repeat_interleave(torch.arange(N, device=dev), n)          # the row of every (row, seen item) pair
+    item = seen_ids[lo[row] + (torch.arange(int(row.shape[0]), device=dev) - start[row])]
+    uq, slot_of = torch.unique(items, return_inverse=True)                # the distinct query items, ascending
+    pos = torch.searchsorted(uq, item).clamp(max=int(uq.shape[0]) - 1)
+    hit = uq[pos] == item
+    key = torch.unique(pos[hit] * max(N, 1) + row[hit])                    # (sorted; a seen list that repeats an item counts once)
+    kslot, krow = torch.div(key, max(N, 1), rounding_mode="floor"), key % max(N, 1)
+    cnt = torch.bincount(kslot, minlength=int(uq.shape[0]))
+    ustart = torch.cumsum(cnt, 0) - cnt
+    qn = cnt[slot_of]                                                      # every query's list, repeats included
+    off = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+    off[1:] = torch.cumsum(qn, 0)
+    qq = torch.repeat_interleave(torch.arange(Q, device=dev), qn)
+    src = ustart[slot_of[qq]] + (torch.arange(int(qq.shape[0]), device=dev) - off[qq])
+    rows = torch.cat([krow[src] + int(row0), torch.zeros(1, dtype=torch.int64, device=dev)])   # (+1: never empty)
+    return off.to(torch.int32), rows.to(torch.int32)
+
+
+def audience_exclusion(exclude, qids, users):
+    """audience's exclude -> the CSR of global row numbers tlsan_dense_topk takes: None -> (None, None); a SeenItems ->
+    seen_rows_csr over these rows (a rank's own rows are all its scan can meet); a sequence of Q sequences of global row
+    numbers -> _csr_of_slots, numbers outside [0, n_total) dropped."""
+    if exclude is None:
+        return None, None
+    if isinstance(exclude, SeenItems):
+        return seen_rows_csr(exclude.off, exclude.ids[:-1], users.user, qids, users.row0)
+    if isinstance(exclude, str):
+        raise ValueError("exclude must be None, a SeenItems or a sequence of per-item arrays of row numbers")
+    pad = np.iinfo(np.int32).max
+    return _csr_of_slots(_listed_items(exclude, int(qids.shape[0]), users.n_total, qids.device, pad), pad)
+
+
+def dense_topk(lib, q, x, scale, bias, excl, id_add, k, workspace, stream):
+    """tlsan_dense_topk over the queries q [Q, d] against the matrix x [N, d], AUDIENCE_CHUNK queries at a time -> (ids
+    [Q, k] int32, scores [Q, k] float32) device tensors.  scale / bias: [Q] float32 device tensors or None."""
+    Q, d, N, k = int(q.shape[0]), int(q.shape[1]), int(x.shape[0]), int(k)
+    ids = torch.empty(Q, k, dtype=torch.int32, device=q.device)
+    scores = torch.empty(Q, k, dtype=torch.float32, device=q.device)
+    off, xid = excl
+    ptr = lambda t, q0=0: None if t is None else t[q0:].data_ptr()
+    for q0 in range(0, Q, AUDIENCE_CHUNK):
+        n = min(AUDIENCE_CHUNK, Q - q0)
+        nws = lib.tlsan_dense_topk_workspace_bytes(n, N, k)
+        if nws == 0:
+            raise L.TlsanError("tlsan_dense_topk_workspace_bytes: %s" % lib.tlsan_last_error().decode())
+        ws = workspace(nws)
+        # (a chunk's queries keep their offsets into the one id array: the offsets are absolute)
+        L.check(lib.tlsan_dense_topk(q[q0:].data_ptr(), n, d, x.data_ptr(), N, ptr(scale, q0), ptr(bias, q0), ptr(off, q0),
+                                     ptr(xid), id_add, k, ids[q0:].data_ptr(), scores[q0:].data_ptr(), ws.data_ptr(),
+                                     ws.numel(), stream), "tlsan_dense_topk")
+    return ids, scores
+
+
 def candidate_tensor(candidates, B, device):
     """[B, C] global item ids (array or tensor, -1 = padding) -> contiguous int32 device tensor."""
     if isinstance(candidates, torch.Tensor):
@@ -1864,6 +2019,47 @@ class Model(object):
         cate = self.item_cate[qids.long()].to(torch.int32).contiguous() if same_category else None
         return scoped_similar_topk(self.lib, self.dims, self.cparams, vec, inv, qids, k, mc, excl, sub, cate, 1, 0,
                                    self._topk_workspace, st)
+
+    def user_vectors(self, batches, real=None):
+        """The rows' u_t as a UserVectors: `batches` is one test-style batch (a tuple or a DeviceBatch, whatever recommend
+        takes) or an iterable of them; each goes through forward(is_test=True, want_u_t=True) and the rows are
+        concatenated in the order given.  A row is a sample -- a user at a point of their history; the test set has one
+        row per user.  real (None, or one count per batch): only a batch's first real rows are kept (a padded launch).
+        A snapshot of the parameters: rebuild it after training."""
+        batches = batch_list(batches)
+        real = kept_rows(real, len(batches))
+        vec, user = [], []
+        for batch, n in zip(batches, real):
+            _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
+            vec.append(ut[:n])
+            user.append(db.u[:n])
+        if not vec:
+            raise ValueError("user_vectors: no batch given")
+        return UserVectors(torch.cat(vec), torch.cat(user), self, self._step)
+
+    def audience(self, items, k, users, exclude=None):
+        """The k best ROWS of `users` (a UserVectors of this model at its current global step) for each item of `items` (a
+        1-D list, array or tensor of global ids, repeats allowed; outside [0, item_count): ValueError): whom to notify
+        about an item.  -> (rows [Q, k] int32, scores [Q, k] float32) device tensors in recommend's order (higher score
+        first, ties -> lower row); users.users_of(rows) gives the user ids; with fewer than k eligible rows a list ends in
+        -1 / -inf.  A row appears with exactly the score the item has in that row's recommend / score_candidates list,
+        bit for bit: tlsan_dense_topk runs recommend's tiles with the item's stored vector in u_t's place, the table
+        scale and the item's item_b applied as recommend applies them; the [N, Q] scores are never materialised.
+        exclude: None; a sequence of Q sequences of global row numbers; or a SeenItems holder -- every row whose user
+        has item q in their seen list stays out of q's list (seen_rows_csr).  The item side is read at call time, as
+        similar_items reads it: an owed lazy-L2 correction lands first, the scale is NOT folded -- parameters, scale and
+        state keep their bits.  k outside 1..256, or users that are not this model's at this step (another model,
+        another d or device, trained since): ValueError before any launch."""
+        qids = audience_queries(items, k, self.config["item_count"], self.device)
+        check_user_vectors(users, self, self._step, self.config["hidden_units"], self.device)
+        if len(users) < 1:
+            raise ValueError("users: no rows")
+        excl = audience_exclusion(exclude, qids, users)
+        self._flush()
+        st = self._stream()
+        vec, _ = item_vectors(self.lib, self.dims, self.cparams, qids, 1, 0, st)
+        return dense_topk(self.lib, vec, users.vec, self._scale_vector(int(qids.shape[0])), self.item_b[qids.long()].contiguous(),
+                          excl, 0, k, self._topk_workspace, st)
 
     def score_candidates(self, batch, candidates):
         """Scores of caller-given items: candidates [B, C] global item ids (array or tensor; -1 = padding, which scores

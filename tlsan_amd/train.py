@@ -113,6 +113,14 @@ def parse(argv=None):
                          "of these lists against the exact ones over the test rows is printed.  0 = off")
     ap.add_argument("--cluster_probes", type=int, default=8, metavar="P",
                     help="with --cluster_index: lists a row probes, 1..64")
+    ap.add_argument("--audience_k", type=int, default=0,
+                    help="at the end of training, write <model_dir>/audience-<K>.npz: for every item of --audience_items the K "
+                         "best test rows (Model.audience over the user vectors of the test set, one row per user): item [Q], "
+                         "users [Q, K], rows [Q, K], scores [Q, K]; 0 = off")
+    ap.add_argument("--audience_items", default="",
+                    help="with --audience_k (required): the global item ids whose audiences are wanted, e.g. 3,7,12")
+    ap.add_argument("--audience_exclude", default="none", choices=["none", "seen"],
+                    help="with --audience_k: 'seen' = a user whose training samples hold the item stays out of its audience")
     ap.add_argument("--eval_negatives", type=int, default=0,
                     help="sampled evaluation at every evaluation point: rank each test label among N sampled negatives "
                          "and report HR@k, NDCG@k (k = 1, 5, 10, 20), MRR and AUC_N; 0 = off")
@@ -142,6 +150,18 @@ def parse(argv=None):
         ap.error("--cluster_index goes without --category_index / --recommend_same_category: a row's lists are chosen by the index")
     if args.cluster_index < 0 or (args.cluster_index and not 1 <= args.cluster_probes <= 64):
         ap.error("--cluster_index wants NLISTS >= 1 and --cluster_probes in 1..64")
+    if args.audience_k < 0 or args.audience_k > 256:
+        ap.error("--audience_k: want K in 1..256 (0 = off)")
+    if args.audience_k and not args.audience_items.strip():
+        ap.error("--audience_k lists the audiences of --audience_items: give --audience_items")
+    if (args.audience_items.strip() or args.audience_exclude != "none") and not args.audience_k:
+        ap.error("--audience_items / --audience_exclude serve --audience_k: give --audience_k")
+    try:
+        args.audience_items = [int(c) for c in args.audience_items.split(",") if c.strip()]
+    except ValueError:
+        ap.error("--audience_items: want item ids separated by commas, e.g. 3,7,12")
+    if any(c < 0 for c in args.audience_items):
+        ap.error("--audience_items: item ids are non-negative")
     try:
         args.recommend_categories = [int(c) for c in args.recommend_categories.split(",") if c.strip()]
     except ValueError:
@@ -173,7 +193,7 @@ def exclude_arg(mode, seen):
 
 def seen_items_for(args, train_set, n_users, device):
     """The seen-items holder when one of the exclusion flags asks for it (built once, from the host train set)."""
-    if "seen" not in (args.recommend_exclude, args.eval_neg_exclude, args.eval_rank_exclude):
+    if "seen" not in (args.recommend_exclude, args.eval_neg_exclude, args.eval_rank_exclude, args.audience_exclude):
         return None
     return SeenItems.from_train_set(train_set, n_users, device)
 
@@ -241,6 +261,27 @@ def write_similar(model, model_dir, k, metric, item_count, write=True, same_cate
         return None
     path = similar_path(model_dir, k)
     np.savez(path, item=np.arange(item_count, dtype=np.int32), ids=np.concatenate(ids), scores=np.concatenate(scores))
+    return path
+
+
+def audience_path(model_dir, k):
+    return os.path.join(model_dir, "audience-%d.npz" % k)
+
+
+def write_audience(model, rows, model_dir, k, items, exclude, write=True):
+    """The k best test rows for each item of `items` (model.user_vectors over this process's test rows, then
+    model.audience; both collective on a sharded model, where only the process with write=True keeps the lists) -> the
+    path of the .npz written: item [Q], users [Q, k] (the rows' user ids, -1 where a list ran out), rows [Q, k] (row
+    numbers in the order of the user vectors: the test set's on one GPU, rank by rank on a sharded model), scores [Q, k]."""
+    launches = list(rows.launches(False))
+    users = model.user_vectors([batch for batch, _, _ in launches], real=[real for _, real, _ in launches])
+    ids, scores = model.audience(items, k, users, exclude=exclude)
+    who = users.users_of(ids)                                          # (collective: every rank)
+    if not write:
+        return None
+    path = audience_path(model_dir, k)
+    np.savez(path, item=np.asarray(items, np.int32), users=who.cpu().numpy().astype(np.int32),
+             rows=ids.cpu().numpy().astype(np.int32), scores=scores.cpu().numpy().astype(np.float32))
     return path
 
 
@@ -629,6 +670,13 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
                              write=rows.rank in (None, 0), same_category=bool(args.similar_same_category), index=whole)
         if path is not None:
             say("Similar items: %s" % path)
+    if args.audience_k:
+        if max(args.audience_items) >= rows.config["item_count"]:
+            raise ValueError("--audience_items: ids must be in [0, %d)" % rows.config["item_count"])
+        path = write_audience(model, rows, args.model_dir, args.audience_k, args.audience_items,
+                              seen if args.audience_exclude == "seen" else None, write=rows.rank in (None, 0))
+        if path is not None:
+            say("Audience: %s" % path)
     model.train_writer.flush()
     model.eval_writer.flush()
     say("Best test_auc:", best_auc)
