@@ -693,6 +693,45 @@ int tlsan_dense_topk(const float* q, int32_t Q, int32_t d, const float* x, int32
                      const int32_t* excl_off, const int32_t* excl_ids, int32_t id_add, int32_t K, int32_t* ids, float* scores,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* bf16 shortlist index: the exact top K over the whole table in two stages, with a per-row CERTIFICATE that the cheap
+ * first stage lost nothing.  With w_n = [item_emb[n] || cate_emb[item_cate[n]]] as stored (d columns, the table scale P
+ * not folded) and row b's u_t:
+ *   tlsan_shortlist_build: the snapshot.  vec [item_count, d] bf16 (uint16 patterns) = w_n rounded to nearest even -- a
+ *     bf16 table's values are copied, not rounded again; *wmax (a device float) = max_n ||w_n||_2 of the STORED fp32
+ *     values, every norm summed in fp32 in one fixed order and the maximum taken on bit patterns: the same table gives
+ *     the same bits, whatever the launch.  Non-finite (+inf) when any element is, or when a sum of squares overflows.
+ *   tlsan_shortlist_topk (stage 1): ids / approx [B, N], 16 <= N <= 256: the N items of highest APPROXIMATE score
+ *       a~(b, n) = fl(fl(acc~ * P) + item_b[n * ld_itemb]),
+ *     acc~ the fp32 accumulation by v_mfma_f32_16x16x32_bf16 of bf16(u_t[b]) . vec[n] (u_t rounded to nearest even; scale
+ *     NULL: P = 1), in tlsan_eval_topk's order on (a~, global id); the exclusion lists and id_mul / id_add are
+ *     tlsan_eval_topk's.  Rows with fewer than N eligible items end in id -1, approx -inf.  A row's result depends on that
+ *     row only.  Workspace: tlsan_shortlist_workspace_bytes(I, B, d, N) (never 0 for sizes the call accepts).
+ *   tlsan_shortlist_select (stage 2): from sl_ids / sl_approx [B, N] (stage 1's) and sl_exact [B, N], the shortlist's scores
+ *     by tlsan_score_candidates -- the exact path's bits -- ids / scores [B, K], 1 <= K < N: the K entries of highest exact
+ *     score in tlsan_eval_topk's order (short rows end in -1 / -inf), and certified [B] int32.  With s_K the K-th best exact
+ *     score of the shortlist, a~_N the approximate score of its N-th entry and
+ *       eps_b = c |P| ||u_t[b]||_2 wmax + 2^-20 (|s_K| + |a~_N|),   c = 2^-7 + 2^-11
+ *     (the norm in fp32 from the fp32 u_t, the rest in double), certified[b] = 1 when the shortlist holds fewer than N
+ *     valid entries (every eligible item is in it), or when s_K, a~_N and eps_b are finite and s_K > a~_N + eps_b, strictly;
+ *     else 0.  certified[b] = 1 means ids / scores [b] ARE tlsan_eval_topk's row, ids and score bits (DESIGN.md section 7
+ *     has the proof); a row with 0 is to be served by tlsan_eval_topk.
+ * vec is 16-byte aligned (both kernels move it 16 bytes at a time); its rows are d bf16 values, densely packed.
+ * No call changes the parameters, P or any state.  Refused before any launch, with the function's name in
+ * tlsan_last_error: a NULL pointer among the required ones, N outside 16..256, K outside 1..N-1, I outside 1..2^30, B outside
+ * 1..2^24, excl_off without excl_ids or the reverse, ld_itemb < 1, an id mapping that leaves int32, d_item / d_cate that are
+ * no multiples of 4 adding up to d, an unknown table_dtype (TLSAN_E_BADARG); d not 64 / 128 / 256, or -- stage 1 and its
+ * workspace call -- B * slices * N at or above 2^31, slices the item slices of the launch (TLSAN_E_UNSUPPORTED); a
+ * workspace that is NULL or too small (TLSAN_E_WORKSPACE).  The four functions are additions: nothing else in the ABI
+ * changed (TLSAN_ABI_VERSION stays 15). */
+int tlsan_shortlist_build(const tlsan_dims* dims, const tlsan_params* p, uint16_t* vec, float* wmax, void* stream);
+size_t tlsan_shortlist_workspace_bytes(int32_t I, int32_t B, int32_t d, int32_t N);
+int tlsan_shortlist_topk(const uint16_t* vec, int32_t I, int32_t d, const float* u_t, int32_t B, const float* scale,
+                         const float* item_b, int32_t ld_itemb, int32_t N, const int32_t* excl_off, const int32_t* excl_ids,
+                         int32_t id_mul, int32_t id_add, int32_t* ids, float* approx, void* ws, size_t ws_bytes, void* stream);
+int tlsan_shortlist_select(const int32_t* sl_ids, const float* sl_exact, const float* sl_approx, const float* u_t,
+                           const float* scale, const float* wmax, int32_t B, int32_t d, int32_t N, int32_t K, int32_t* ids,
+                           float* scores, int32_t* certified, void* stream);
+
 /* Diversified lists: the second stage behind tlsan_eval_topk. From each row's POOL of N entries (1 <= K <= N <= 256, in
  * tlsan_eval_topk's order: higher score first, ties -> lower global id) pick K by greedy maximal marginal relevance
  * under a per-category cap.  Pool entry j of a row has a global id g_j and the model score s_j (pool_ids, pool_scores

@@ -22,6 +22,7 @@ RERANK_MAX = 256  # RERANK_MAX (csrc/tlsan_rerank.h): largest pool of tlsan_rera
 LISTM_MAX = 256   # LISTM_MAX (csrc/tlsan_listm.h): longest list of tlsan_list_metrics
 SIM_DOT, SIM_COSINE = 0, 1   # TLSAN_SIM_DOT / TLSAN_SIM_COSINE (include/tlsan.h): the metrics of tlsan_similar_topk
 CLUSTER_CMAX, CLUSTER_PMAX = 16384, 64   # csrc/tlsan_cluster.h: most centroids of a call, most probes of a row
+SHORTLIST_NMIN, SHORTLIST_NMAX = 16, 256   # csrc/tlsan_shortlist.h: the shortest and the longest shortlist of a row
 NEG_MAX = 1024  # NEG_MAX (csrc/tlsan_cand.h): largest N of tlsan_sample_negatives
 
 EXPORTS = [
@@ -36,6 +37,7 @@ EXPORTS = [
     "tlsan_lists_workspace_bytes", "tlsan_eval_topk_lists", "tlsan_similar_topk_lists",
     "tlsan_cluster_workspace_bytes", "tlsan_cluster_assign", "tlsan_cluster_means", "tlsan_cluster_probe",
     "tlsan_dense_topk_workspace_bytes", "tlsan_dense_topk",
+    "tlsan_shortlist_build", "tlsan_shortlist_workspace_bytes", "tlsan_shortlist_topk", "tlsan_shortlist_select",
     "tlsan_score_candidates", "tlsan_candidate_ranks", "tlsan_sample_negatives", "tlsan_profile_enable", "tlsan_profile_stride",
     "tlsan_profile_collect", "tlsan_debug_stamps", "tlsan_rows_apply_workspace", "tlsan_rows_apply", "tlsan_scan_compact",
     "tlsan_route_plan", "tlsan_shard_gather", "tlsan_shard_summary", "tlsan_shard_apply_workspace", "tlsan_shard_apply",
@@ -277,6 +279,17 @@ def load():
                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_size_t, C.c_void_p]
         lib.tlsan_dense_topk.restype = C.c_int
+    if hasattr(lib, "tlsan_shortlist_topk"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
+        lib.tlsan_shortlist_build.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.tlsan_shortlist_build.restype = C.c_int
+        lib.tlsan_shortlist_workspace_bytes.argtypes = [C.c_int32] * 4
+        lib.tlsan_shortlist_workspace_bytes.restype = C.c_size_t
+        lib.tlsan_shortlist_topk.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.tlsan_shortlist_topk.restype = C.c_int
+        lib.tlsan_shortlist_select.argtypes = [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p] * 4
+        lib.tlsan_shortlist_select.restype = C.c_int
     lib.tlsan_rerank.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.tlsan_rerank.restype = C.c_int
     if hasattr(lib, "tlsan_list_metrics"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)

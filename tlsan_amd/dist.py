@@ -28,6 +28,7 @@ import torch.distributed as dist
 from . import _lib as L
 from .dist_comm import (ExchangePlan, KeyRouter, ModPartition, RowExchange, _staged, a2a, allgather_rows,  # noqa: F401
                         allreduce_sum, torch_scan)
+from .shortlist import ShortlistIndex
 from .dist_step import DynamicStep, FlatLayout, StaticStep, fused_params
 from .model import (LAZY_ADAGRAD_OPTIMIZERS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer, candidate_tensor, eval_topk,
                     exclusion_csr, grow_workspace, hits_and_rows, pack_dense, read_checkpoint, sample_negatives, sampled_ranks,
@@ -422,6 +423,10 @@ class ShardedModel:
         item = last_items(self.device_batch(batch, is_test=True))
         return torch.where(item >= 0, self._item_cate(item.clamp(min=0)), -1).to(torch.int32)
 
+    def shortlist_index(self):
+        """Model.shortlist_index is not built across ranks: per-shard certificates are a follow-up."""
+        raise NotImplementedError("ShardedModel: a ShortlistIndex certifies a row against one table; per-shard certificates are not built")
+
     def cluster_index(self, *args, **kwargs):
         """Model.cluster_index is not built across ranks: a ValueError (train and probe a ClusteredIndex on a Model)."""
         raise ValueError("ShardedModel: a ClusteredIndex is not supported on a row-sharded model (building and probing across ranks)")
@@ -448,6 +453,8 @@ class ShardedModel:
         category arrays are all-gathered with u_t, and the unrestricted rows among them run through the path without
         an index on every rank."""
         refuse_clustered(index, probes)
+        if isinstance(index, ShortlistIndex):
+            raise NotImplementedError("ShardedModel: a ShortlistIndex certifies a row against one table; per-shard certificates are not built")
         N = rerank_pool(k, diversity, per_category, pool)
         want = int(k)
         within = scope_within(within, self.I)

@@ -1868,8 +1868,15 @@ class Model(object):
         from .cluster import fit
         return fit(self, nlists, within=within, iters=iters, seed=seed, train_size=train_size, max_list=max_list)
 
+    def shortlist_index(self):
+        """A ShortlistIndex (shortlist.py) over this model's items: the bf16 snapshot of the item vectors as stored and the
+        largest row norm -- the `index=` behind recommend's two-stage exact lists.  A snapshot of the parameters: rebuild
+        it after training."""
+        from .shortlist import build
+        return build(self)
+
     def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None, index=None,
-                  probes=None):
+                  probes=None, shortlist=None, fallback=True):
         """The k best items over ALL items for each row -- what tf.nn.top_k(eval_logits, k) gives the reference
         (model.py:140) -- without materialising the [B, I] scores.  Takes label_ranks' batches (the label and the
         negative are not used).  -> (ids [B, k] int32, scores [B, k] float32) device tensors, in tf.nn.top_k's
@@ -1909,12 +1916,25 @@ class Model(object):
         groups of 8 probes, merged.  Every returned score is the exact path's bit for bit and the list is the exact top k
         of the probed lists' union minus the exclusions; with P >= the number of non-empty lists it equals recommend()
         without an index.  Recall at fewer probes is not guaranteed (cluster.recall measures it).  category= or within=
-        beside it, probes= without it or outside 1..64, or an index over another item count: ValueError before any launch."""
+        beside it, probes= without it or outside 1..64, or an index over another item count: ValueError before any launch.
+        index (a ShortlistIndex, shortlist_index()) with shortlist=N (default min(256, max(4 n, 64)), n the list length
+        asked of the first stage: k, or the diversity pool; n < N <= 256): the EXACT list over the whole catalogue in two
+        stages -- the N best by bf16 score (tlsan_shortlist_topk), their exact scores (tlsan_score_candidates), the n best
+        of those and, per row, a certificate that no item outside the shortlist can belong to the exact list
+        (tlsan_shortlist_select).  fallback=True: the rows without a certificate (one host read finds them) run through
+        the path without an index as a sub-batch, so every row is recommend()'s without an index, ids and score bits;
+        fallback=False: the shortlist's lists as they are.  index.certified is the call's [B] bool device tensor,
+        index.counts the (rows, certified) of all calls.  exclude= and the second stage compose; within=, category= or
+        probes= beside it, shortlist= without it, n >= N, or an index over another item count or d: ValueError before any
+        launch."""
         from .cluster import clustered_probes, clustered_topk
+        from .shortlist import shortlist_size, shortlist_topk
         N = rerank_pool(k, diversity, per_category, pool)
-        probes = clustered_probes(index, probes, self.config["item_count"], category=category, within=within)
+        short = shortlist_size(index, shortlist, int(k) if N is None else N, self.config["item_count"], self.config["hidden_units"],
+                               category=category, within=within, probes=probes)
+        probes = None if short is not None else clustered_probes(index, probes, self.config["item_count"], category=category, within=within)
         within = scope_within(within, self.config["item_count"])
-        if probes is not None:
+        if probes is not None or short is not None:
             pass
         elif recommend_index(index, within, self.config["item_count"], self.config["cate_count"]) is not None:
             category = index_categories(category, batch_rows(batch), self.config["cate_count"], self.device)
@@ -1922,7 +1942,10 @@ class Model(object):
             category = scope_categories(category, batch_rows(batch), self.config["cate_count"], self.device)
         _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
         excl, st = exclusion_csr(db, exclude, self.config["item_count"]), self._stream()
-        if probes is not None:
+        if short is not None:
+            topk = lambda n: shortlist_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, short, fallback,
+                                            self._topk_workspace, st)
+        elif probes is not None:
             topk = lambda n: clustered_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, probes,
                                             self._scale_vector(index.lists), self._topk_workspace, st)
         elif index is not None:

@@ -113,6 +113,13 @@ def parse(argv=None):
                          "of these lists against the exact ones over the test rows is printed.  0 = off")
     ap.add_argument("--cluster_probes", type=int, default=8, metavar="P",
                     help="with --cluster_index: lists a row probes, 1..64")
+    ap.add_argument("--shortlist_index", type=int, default=0, choices=[0, 1],
+                    help="with --recommend_k: 1 = serve the lists through a bf16 shortlist index (Model.shortlist_index): the same "
+                         "EXACT lists in two stages, rows without a certificate through the full scan; the share of certified "
+                         "rows is printed.  Not with a scope, a category or another index")
+    ap.add_argument("--shortlist", type=int, default=0, metavar="N",
+                    help="with --shortlist_index: entries of a row's shortlist, 16..256 and above the list asked of the first "
+                         "stage (0 = min(256, max(4 n, 64)))")
     ap.add_argument("--audience_k", type=int, default=0,
                     help="at the end of training, write <model_dir>/audience-<K>.npz: for every item of --audience_items the K "
                          "best test rows (Model.audience over the user vectors of the test set, one row per user): item [Q], "
@@ -150,6 +157,22 @@ def parse(argv=None):
         ap.error("--cluster_index goes without --category_index / --recommend_same_category: a row's lists are chosen by the index")
     if args.cluster_index < 0 or (args.cluster_index and not 1 <= args.cluster_probes <= 64):
         ap.error("--cluster_index wants NLISTS >= 1 and --cluster_probes in 1..64")
+    if (args.shortlist_index or args.shortlist) and not args.recommend_k:
+        ap.error("--shortlist_index / --shortlist serve the lists of --recommend_k: give --recommend_k")
+    if args.shortlist and not args.shortlist_index:
+        ap.error("--shortlist is the shortlist index's length: give --shortlist_index 1")
+    if args.shortlist_index and (args.cluster_index or args.category_index or args.recommend_same_category or args.recommend_categories):
+        ap.error("--shortlist_index serves the whole catalogue: it goes without a scope, a category or another index")
+    if args.shortlist and not 16 <= args.shortlist <= 256:
+        ap.error("--shortlist wants N in 16..256")
+    if args.shortlist_index and (args.sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--shortlist_index certifies a row against one table: it is not built for the sharded driver")
+    if args.shortlist_index:      # (the first stage's list -- K, or the second stage's pool -- must be shorter than the shortlist)
+        first = args.recommend_k if not recommend_settings(args) else (args.recommend_pool or min(256, max(4 * args.recommend_k, 32)))
+        short = args.shortlist or min(256, max(4 * first, 64))
+        if not first < short:
+            ap.error("--shortlist_index: the first stage's list of %d entries (--recommend_k, or the pool of the second stage) "
+                     "needs a shortlist longer than that, and the shortlist is %d (--shortlist, at most 256)" % (first, short))
     if args.audience_k < 0 or args.audience_k > 256:
         ap.error("--audience_k: want K in 1..256 (0 = off)")
     if args.audience_k and not args.audience_items.strip():
@@ -510,6 +533,25 @@ class RecallMeasurement:
         return (float(s[0] / s[1]) if s[1] else float("nan")), int(s[1])
 
 
+class CertifiedShare:
+    """The certified share of --shortlist_index: after every launch, how many of its REAL rows the index certified (the rows
+    past `real` only pad a launch); result() -> (rows, certified).  then: the hook to call on as well (None: none)."""
+
+    def __init__(self, index, then=None):
+        self.index, self.then = index, then
+        self.sums = torch.zeros(2, dtype=torch.int64, device=index.device)
+
+    def __call__(self, db, ids, real):
+        self.sums += torch.stack([torch.ones_like(self.index.certified[:real], dtype=torch.int64).sum(),
+                                  self.index.certified[:real].sum()])
+        if self.then is not None:
+            self.then(db, ids, real)
+
+    def result(self):
+        rows, cert = self.sums.tolist()
+        return rows, cert
+
+
 def recommend_test_set(model, rows, k, exclude, on_lists=None, same_category=False, **settings):
     """model.recommend over every test row (settings: its diversity keywords and within=) -> (user, ids, scores) host
     arrays in test-set order; None but on rank 0.  on_lists(device batch, ids, real): called with every launch's device
@@ -653,12 +695,19 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
                 recall_of = RecallMeasurement(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen),
                                               dict(settings, **scope), then=measure)
             scope = dict(index=cindex, probes=args.cluster_probes)
+        share_of = None
+        if args.shortlist_index:
+            scope = dict(index=model.shortlist_index(), shortlist=args.shortlist or None)
+            share_of = CertifiedShare(scope["index"], then=measure)
         rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen),
-                                 on_lists=recall_of or measure, same_category=bool(args.recommend_same_category), **settings, **scope)
+                                 on_lists=share_of or recall_of or measure, same_category=bool(args.recommend_same_category), **settings, **scope)
         list_res = measure.result() if measure is not None else None       # (collective: every rank)
         if recall_of is not None:
             say("Clustered index: recall@%d = %.4f against the exact lists over %d rows (%d probes)"
                 % ((args.recommend_k,) + recall_of.result() + (args.cluster_probes,)))
+        if share_of is not None:
+            n_rows, n_cert = shortlist_share = share_of.result()
+            say("Shortlist index: %d of %d rows certified (%.4f); the others served by the full scan" % (n_cert, n_rows, n_cert / max(n_rows, 1)))
         if rec is not None:                                    # (rank 0 holds the rows)
             path = write_recommendations(args.model_dir, args.recommend_k, *rec, settings=settings)
             say("Recommendations: %s" % path)
@@ -697,6 +746,8 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
         res["full_ranking"] = final_full
     if args.recommend_k and list_res is not None:
         res["list_metrics"] = list_res
+    if args.recommend_k and args.shortlist_index:
+        res["shortlist_certified"] = shortlist_share      # (real test rows, certified ones)
     return res
 
 
