@@ -636,6 +636,40 @@ int tlsan_similar_topk_lists(const tlsan_dims* dims, const tlsan_params* p, cons
                              int32_t max_list, const int32_t* row_lists, int32_t P, int32_t id_mul, int32_t id_add,
                              int32_t* ids, float* scores, void* ws, size_t ws_bytes, void* stream);
 
+/* Boosted lists: tlsan_eval_topk_scoped and tlsan_eval_topk_lists with a per-item score adjustment applied INSIDE the
+ * selection, where a score meets its row's threshold ("promote these items", "bury those", "pay this much for novelty").
+ * An item just outside the unboosted list that the boost lifts in is found; a caller who adjusts the returned list
+ * afterwards can only reorder its prefix.  Both take the unboosted call's arguments, unchanged in meaning, and two more:
+ *   boost: fp32, one value per GLOBAL item id.  The caller guarantees that it covers every global id the id mapping can
+ *     produce, 0 .. (item_count - 1) * id_mul + id_add: it is read at n * id_mul + id_add for the local items n the call
+ *     scores (in the item-sharded form every rank passes the same, replicated vector).  It is not checked.
+ *   row_weight [B] fp32, or NULL: a per-row factor on the boost.
+ * With s(b, g) the model's score of row b and the item of global id g, bit for bit what the unboosted call and
+ * tlsan_score_candidates return, the adjusted score is
+ *     s'(b, g) = fl(s(b, g) + t),   t = boost[g] without row weights, t = fl(row_weight[b] * boost[g]) with them,
+ * in fp32 with separate roundings (no fused multiply-add).  Selection, the thresholds, the merge of slices and the order
+ * all act on s' by tlsan_eval_topk's rules: higher first, equal s' -> lower global id, +0.0 == -0.0 (returned as +0.0),
+ * NaN after everything else.  The scores returned are s'; tlsan_score_candidates on the returned ids gives the raw ones.
+ *   boost[g] = -inf gives s' = -inf, a valid score that ranks after every finite one: it is NOT an exclusion (the item
+ *     still appears when the row has fewer than K finite candidates).  The exclusion lists, sub and the index remove items.
+ *   IEEE rules decide the rest: a NaN boost, or 0 * inf from a zero weight, gives NaN, which ranks last.
+ *   A boost of all +0.0 returns exactly the ids and score bits of the unboosted call.
+ *   A row's result depends on its own inputs only: not on B, the other rows, the launch geometry or the number of ranks.
+ * Neither call changes the parameters, P or any state.  Workspaces: the unboosted calls' (tlsan_scope_workspace_bytes,
+ * tlsan_lists_workspace_bytes).  Everything the unboosted call refuses is refused with the same code, before any launch,
+ * with this function's name in tlsan_last_error; boost NULL is TLSAN_E_BADARG (the unboosted call exists for that).
+ * tlsan_similar_topk*, tlsan_dense_topk and the shortlist index take no boost.  The two functions are additions: nothing
+ * else in the ABI changed (TLSAN_ABI_VERSION stays 15). */
+int tlsan_eval_topk_scoped_boost(const tlsan_dims* dims, const tlsan_params* p, const float* u_t, int32_t B, int32_t K,
+                                 const int32_t* excl_off, const int32_t* excl_ids, const int32_t* sub, int32_t nsub,
+                                 const int32_t* row_cate, int32_t id_mul, int32_t id_add, int32_t* ids, float* scores,
+                                 void* ws, size_t ws_bytes, void* stream, const float* boost, const float* row_weight);
+int tlsan_eval_topk_lists_boost(const tlsan_dims* dims, const tlsan_params* p, const float* u_t, int32_t B, int32_t K,
+                                const int32_t* excl_off, const int32_t* excl_ids, const int32_t* list_off,
+                                const int32_t* list_items, int32_t nlists, int32_t max_list, const int32_t* row_lists,
+                                int32_t P, int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws,
+                                size_t ws_bytes, void* stream, const float* boost, const float* row_weight);
+
 /* Clustered item index: the partition the indexed lists take, LEARNED from the item vectors (k-means over what
  * tlsan_item_vectors writes), and the choice of the lists a query probes.  The three calls take dense fp32 matrices with
  * d = 64, 128 or 256 (16-byte aligned rows), read no table and change no parameter or state; C is the number of

@@ -35,6 +35,7 @@ EXPORTS = [
     "tlsan_item_vectors", "tlsan_similar_workspace_bytes", "tlsan_similar_topk", "tlsan_rerank", "tlsan_list_metrics",
     "tlsan_scope_workspace_bytes", "tlsan_eval_topk_scoped", "tlsan_similar_topk_scoped",
     "tlsan_lists_workspace_bytes", "tlsan_eval_topk_lists", "tlsan_similar_topk_lists",
+    "tlsan_eval_topk_scoped_boost", "tlsan_eval_topk_lists_boost",
     "tlsan_cluster_workspace_bytes", "tlsan_cluster_assign", "tlsan_cluster_means", "tlsan_cluster_probe",
     "tlsan_dense_topk_workspace_bytes", "tlsan_dense_topk",
     "tlsan_shortlist_build", "tlsan_shortlist_workspace_bytes", "tlsan_shortlist_topk", "tlsan_shortlist_select",
@@ -260,6 +261,12 @@ def load():
                                                  C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_size_t, C.c_void_p]
         lib.tlsan_similar_topk_lists.restype = C.c_int
+    if hasattr(lib, "tlsan_eval_topk_scoped_boost"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
+        # the unboosted calls' arguments, then boost and row_weight
+        lib.tlsan_eval_topk_scoped_boost.argtypes = lib.tlsan_eval_topk_scoped.argtypes + [C.c_void_p, C.c_void_p]
+        lib.tlsan_eval_topk_scoped_boost.restype = C.c_int
+        lib.tlsan_eval_topk_lists_boost.argtypes = lib.tlsan_eval_topk_lists.argtypes + [C.c_void_p, C.c_void_p]
+        lib.tlsan_eval_topk_lists_boost.restype = C.c_int
     if hasattr(lib, "tlsan_cluster_probe"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
         lib.tlsan_cluster_workspace_bytes.argtypes = [C.c_int32] * 3
         lib.tlsan_cluster_workspace_bytes.restype = C.c_size_t

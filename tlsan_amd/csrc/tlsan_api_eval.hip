@@ -8,6 +8,7 @@
 #include "tlsan_topk.h"
 #include "tlsan_similar.h"
 #include "tlsan_scope.h"
+#include "tlsan_scope_host.h"
 #include "tlsan_rerank.h"
 #include "tlsan_cand.h"
 
@@ -19,20 +20,6 @@ struct ExclOut { const int32_t* off; const int32_t* ids; int32_t* ahead; int32_t
 // The one place that says which counting kernel ranks a table: the one that reads the dense item matrix when the
 // workspace holds one (carve: up to EVAL_DENSE_MAX bytes), else the gathering one.  k_excl_ahead follows it.
 static bool eval_rank_dense(const EvalArgs& e) { return e.all_emb != nullptr; }
-
-// what every scoring kernel reads: the tables, the rows of u_t and the id mapping of this table; the rest zero
-static EvalArgs eval_args(const tlsan_dims* d, const tlsan_params* p, const float* u_t, int32_t B, int32_t id_mul, int32_t id_add) {
-  EvalArgs e;
-  memset(&e, 0, sizeof(e));
-  e.p = norm_params(p, d); e.u_t = u_t; e.B = B; e.I = d->item_count; e.di = d->d_item; e.dc = d->d_cate;
-  e.id_mul = id_mul; e.id_add = id_add;
-  return e;
-}
-
-// global ids n * id_mul + id_add of the table's items must be non-negative int32 (d NULL: left to shape_of's refusal)
-static bool eval_ids_ok(const tlsan_dims* d, int32_t id_mul, int32_t id_add) {
-  return id_mul >= 1 && id_add >= 0 && (!d || (long long)(d->item_count - 1) * id_mul + id_add < (1LL << 31));
-}
 
 static void launch_all_emb(const EvalArgs& e, int D, hipStream_t hs) {
   const int nae = (e.I * (D / 4) + 255) / 256;
@@ -198,18 +185,12 @@ int tlsan_topk_merge(const int32_t* cand_ids, const float* cand_scores, int32_t 
 }
 
 // ---- similar-items lists (tlsan_similar.h) ----
-// a refusal of shape_of / check_params, with the entry point's name in front of its message
-static int sim_named(const char* fn, int rc) {
-  char m[384];
-  snprintf(m, sizeof(m), "%s", tlsan_last_error());
-  return fail(rc, "%s: %s", fn, m);
-}
-
+// (tlsan_scope_host.h: named_refusal, a refusal of shape_of / check_params with the entry point's name in front)
 int tlsan_item_vectors(const tlsan_dims* d, const tlsan_params* p, const int32_t* ids, int32_t Q, int32_t id_mul,
                        int32_t id_add, float* vec, float* inv_norm, void* stream) {
   Shape s;
   int rc = shape_of(d, &s);
-  if (rc || (rc = check_params(p))) return sim_named("tlsan_item_vectors", rc);
+  if (rc || (rc = check_params(p))) return named_refusal("tlsan_item_vectors", rc);
   if (!ids || !vec) return fail(TLSAN_E_BADARG, "tlsan_item_vectors: NULL argument");
   if (Q < 1) return fail(TLSAN_E_BADARG, "tlsan_item_vectors: Q must be >= 1 (got %d)", Q);
   if (!eval_ids_ok(d, id_mul, id_add))
@@ -238,7 +219,7 @@ static void carve_similar(const tlsan_dims* d, int D, int Q, int K, char* base, 
 size_t tlsan_similar_workspace_bytes(const tlsan_dims* d, int32_t Q, int32_t K) {
   Shape s;
   const int rc = shape_of(d, &s);
-  if (rc) { sim_named("tlsan_similar_workspace_bytes", rc); return 0; }
+  if (rc) { named_refusal("tlsan_similar_workspace_bytes", rc); return 0; }
   if (K < 1 || K > TOPK_MAX) { fail(TLSAN_E_BADARG, "tlsan_similar_workspace_bytes: K must be in 1..%d (got %d)", TOPK_MAX, K); return 0; }
   if (Q < 1) { fail(TLSAN_E_BADARG, "tlsan_similar_workspace_bytes: Q must be >= 1 (got %d)", Q); return 0; }
   SimWs w;
@@ -251,7 +232,7 @@ int tlsan_similar_topk(const tlsan_dims* d, const tlsan_params* p, const float* 
                        int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws, size_t ws_bytes, void* stream) {
   Shape s;
   int rc = shape_of(d, &s);
-  if (rc || (rc = check_params(p))) return sim_named("tlsan_similar_topk", rc);
+  if (rc || (rc = check_params(p))) return named_refusal("tlsan_similar_topk", rc);
   if (metric != SIM_DOT && metric != SIM_COSINE)
     return fail(TLSAN_E_BADARG, "tlsan_similar_topk: metric must be TLSAN_SIM_DOT or TLSAN_SIM_COSINE (got %d)", metric);
   if (!qvec || !qids || !ids || !scores || (metric == SIM_COSINE && !qinv))
@@ -289,51 +270,12 @@ int tlsan_similar_topk(const tlsan_dims* d, const tlsan_params* p, const float* 
 }
 
 // ---- scoped lists (tlsan_scope.h) ----
-struct ScopeWs {
-  int32_t* ids;        // [B, nsl, K] the slices' lists (nsl > 1)
-  float* scores;
-  float* inv;          // [I] inv of the scope's items, by local item (the cosine form)
-  size_t bytes;
-  int nsl;
-};
-
-// positions of a scope: nsub, or the whole table (nsub < 0)
-static int scope_count(const tlsan_dims* d, int32_t nsub) { return nsub < 0 ? d->item_count : nsub; }
-
-static void carve_scope(const tlsan_dims* d, int B, int K, int32_t nsub, char* base, ScopeWs* w) {
-  size_t o = 0;
-  auto take = [&](size_t n) { char* p = base ? base + o : nullptr; o += al(n); return p; };
-  const int nsl = w->nsl = eval_slices((B + 15) / 16, ((scope_count(d, nsub) + 63) / 64 + 3) / 4);
-  const size_t nc = nsl > 1 ? (size_t)B * nsl * K : 0;
-  w->ids = (int32_t*)take(4 * nc);
-  w->scores = (float*)take(4 * nc);
-  w->inv = (float*)take(sizeof(float) * (size_t)d->item_count);
-  w->bytes = o;
-}
-
-// what both scoped entry points refuse about (B or Q, K, the exclusion lists, the id mapping, the scope, the workspace)
-static int scope_check(const char* fn, const tlsan_dims* d, int32_t B, int32_t K, const int32_t* excl_off,
-                       const int32_t* excl_ids, const int32_t* sub, int32_t nsub, int32_t id_mul, int32_t id_add, void* ws,
-                       size_t ws_bytes, ScopeWs* w) {
-  if (K < 1 || K > TOPK_MAX) return fail(TLSAN_E_BADARG, "%s: K must be in 1..%d (got %d)", fn, TOPK_MAX, K);
-  if (!excl_off != !excl_ids) return fail(TLSAN_E_BADARG, "%s: excl_off and excl_ids go together", fn);
-  if (!eval_ids_ok(d, id_mul, id_add))
-    return fail(TLSAN_E_BADARG, "%s: global ids n * id_mul + id_add must be non-negative int32", fn);
-  if (!sub != (nsub < 0))
-    return fail(TLSAN_E_BADARG, "%s: sub and nsub go together (sub NULL with nsub < 0: the whole table; got nsub %d)", fn, nsub);
-  if (nsub > d->item_count)
-    return fail(TLSAN_E_BADARG, "%s: nsub %d exceeds the table's %d items (sub holds distinct indices)", fn, nsub, d->item_count);
-  if (!ws) return fail(TLSAN_E_WORKSPACE, "%s: ws is NULL", fn);
-  carve_scope(d, B, K, nsub, (char*)ws, w);
-  if (w->bytes > ws_bytes) return fail(TLSAN_E_WORKSPACE, "%s: workspace too small: need %zu have %zu", fn, w->bytes, ws_bytes);
-  return TLSAN_OK;
-}
-
+// (tlsan_scope_host.h: ScopeWs, carve_scope, scope_check -- shared with the boosted call of tlsan_boost.hip)
 size_t tlsan_scope_workspace_bytes(const tlsan_dims* d, int32_t B, int32_t K, int32_t nsub) {
   static const char* fn = "tlsan_scope_workspace_bytes";
   Shape s;
   const int rc = shape_of(d, &s);
-  if (rc) { sim_named(fn, rc); return 0; }
+  if (rc) { named_refusal(fn, rc); return 0; }
   if (K < 1 || K > TOPK_MAX) { fail(TLSAN_E_BADARG, "%s: K must be in 1..%d (got %d)", fn, TOPK_MAX, K); return 0; }
   if (B < 1) { fail(TLSAN_E_BADARG, "%s: B must be >= 1 (got %d)", fn, B); return 0; }
   if (nsub > d->item_count) { fail(TLSAN_E_BADARG, "%s: nsub %d exceeds the table's %d items", fn, nsub, d->item_count); return 0; }
@@ -349,7 +291,7 @@ int tlsan_eval_topk_scoped(const tlsan_dims* d, const tlsan_params* p, const flo
   static const char* fn = "tlsan_eval_topk_scoped";
   Shape s;
   int rc = shape_of(d, &s);
-  if (rc || (rc = check_params(p))) return sim_named(fn, rc);
+  if (rc || (rc = check_params(p))) return named_refusal(fn, rc);
   if (!u_t || !ids || !scores || B < 1) return fail(TLSAN_E_BADARG, "%s: bad arguments", fn);
   ScopeWs w;
   if ((rc = scope_check(fn, d, B, K, excl_off, excl_ids, sub, nsub, id_mul, id_add, ws, ws_bytes, &w))) return rc;
@@ -377,7 +319,7 @@ int tlsan_similar_topk_scoped(const tlsan_dims* d, const tlsan_params* p, const 
   static const char* fn = "tlsan_similar_topk_scoped";
   Shape s;
   int rc = shape_of(d, &s);
-  if (rc || (rc = check_params(p))) return sim_named(fn, rc);
+  if (rc || (rc = check_params(p))) return named_refusal(fn, rc);
   if (metric != SIM_DOT && metric != SIM_COSINE)
     return fail(TLSAN_E_BADARG, "%s: metric must be TLSAN_SIM_DOT or TLSAN_SIM_COSINE (got %d)", fn, metric);
   if (!qvec || !qids || !ids || !scores || (metric == SIM_COSINE && !qinv)) return fail(TLSAN_E_BADARG, "%s: NULL argument", fn);

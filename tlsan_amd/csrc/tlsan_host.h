@@ -15,6 +15,7 @@ struct CandArgs; struct NegArgs; struct ExclArgs;  // tlsan_cand.h
 struct EvalArgs;                                   // tlsan_eval.h
 struct SimArgs; struct VecArgs;                    // tlsan_similar.h
 struct ScopeArgs; struct ScopedTopkArgs; struct ScopedSimArgs;   // tlsan_scope.h
+struct ListsArgs;                                  // tlsan_lists.h
 
 #pragma GCC visibility push(hidden)
 
@@ -94,6 +95,8 @@ hipError_t tlsan_launch_item_vectors(const VecArgs& a, int D, hipStream_t hs);
 hipError_t tlsan_launch_scoped_topk(const ScopedTopkArgs& a, int D, int nslices, hipStream_t hs);
 hipError_t tlsan_launch_scoped_similar(const ScopedSimArgs& a, int D, int nslices, hipStream_t hs);
 hipError_t tlsan_launch_scope_inv(const EvalArgs& e, const ScopeArgs& s, int count, int D, float* inv, hipStream_t hs);
+// ---- indexed lists (tlsan_lists.hip): the grouping of the valid (row, probe) pairs by list, in the caller's workspace
+hipError_t tlsan_launch_lists_group(const ListsArgs& l, hipStream_t hs);
 // ---- candidate scoring, candidate ranks, negative sampling (tlsan_cand.hip)
 hipError_t tlsan_launch_score_cand(const CandArgs& a, int D, hipStream_t hs);
 hipError_t tlsan_launch_cand_ranks(const int32_t* cand, const float* scores, int B, int C, int32_t* ranks, hipStream_t hs);

@@ -6,7 +6,8 @@
 //
 // A (row, probe) PAIR t = b * P + p is valid when 0 <= row_lists[t] < nlists, no earlier probe of the row names the
 // same list (a repeat counts once, so a row's lists stay disjoint for the merge) and the list is not empty.  The call
-// groups the valid pairs by list, on the device, into GROUPS of up to 16 pairs that share a list:
+// groups the valid pairs by list, on the device, into GROUPS of up to 16 pairs that share a list (the three kernels are
+// tlsan_lists.hip's, behind tlsan_launch_lists_group):
 //   k_lists_count   rank[t] = the pair's arrival number among its list's pairs (an atomic counter per list), or -1
 //   k_lists_groups  gbase[c] = exclusive sum of ceil(cnt[c] / 16) over the lists (one workgroup), *ngroups = the total
 //   k_lists_place   pair t sits in group gbase[c] + rank / 16 at slot rank % 16; slot 0 names the group's list
@@ -45,51 +46,6 @@ struct ListsArgs {
 
 struct ListsTopkArgs { TopkArgs t; ListsArgs l; };
 struct ListsSimArgs { SimArgs m; ListsArgs l; };
-
-__global__ __launch_bounds__(256) void k_lists_count(ListsArgs l) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= l.N) return;
-  const int b0 = t - t % l.P;
-  const int c = l.row_lists[t];
-  bool ok = (unsigned)c < (unsigned)l.nlists;          // (a list id past the index is no probe: list_off is not addressed)
-  for (int j = b0; j < t; ++j) ok = ok && l.row_lists[j] != c;
-  if (ok) ok = l.list_off[c + 1] > l.list_off[c];
-  l.rank[t] = ok ? atomicAdd(&l.cnt[c], 1) : -1;
-}
-
-__global__ __launch_bounds__(1024) void k_lists_groups(ListsArgs l) {
-  __shared__ int part[1024];
-  const int t = threadIdx.x;
-  const int per = (l.nlists + 1023) / 1024;
-  const int lo = min(t * per, l.nlists), hi = min(lo + per, l.nlists);
-  int s = 0;
-  for (int c = lo; c < hi; ++c) s += (l.cnt[c] + 15) >> 4;
-  part[t] = s;
-  __syncthreads();
-  for (int d = 1; d < 1024; d <<= 1) {
-    const int v = t >= d ? part[t - d] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int base = part[t] - s;
-  for (int c = lo; c < hi; ++c) {
-    l.gbase[c] = base;
-    base += (l.cnt[c] + 15) >> 4;
-  }
-  if (t == 1023) l.ngroups[0] = part[1023];
-}
-
-__global__ __launch_bounds__(256) void k_lists_place(ListsArgs l) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= l.N) return;
-  const int rk = l.rank[t];
-  if (rk < 0) return;
-  const int c = l.row_lists[t];
-  const int g = l.gbase[c] + (rk >> 4);
-  l.gpair[(size_t)g * 16 + (rk & 15)] = t;
-  if ((rk & 15) == 0) l.glist[g] = c;
-}
 
 // topk_scan's item mapping of one list (ScopeMap with a base and a count of the workgroup's own)
 struct ListMap {

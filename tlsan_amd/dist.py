@@ -32,7 +32,7 @@ from .shortlist import ShortlistIndex
 from .dist_step import DynamicStep, FlatLayout, StaticStep, fused_params
 from .model import (LAZY_ADAGRAD_OPTIMIZERS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer, candidate_tensor, eval_topk,
                     exclusion_csr, grow_workspace, hits_and_rows, pack_dense, read_checkpoint, sample_negatives, sampled_ranks,
-                    score_candidates, item_vectors, list_metric_inputs, list_metrics, list_metrics_chunks, rerank, rerank_chunk, rerank_pool, batch_rows, last_items, scope_categories, scope_within, scoped_similar_topk, scoped_topk, CategoryIndex, index_categories, indexed_topk, recommend_index, lists_similar_topk, similar_index, similar_queries, similar_topk, topk_merge, ItemScope, unpack_dense, write_checkpoint,
+                    score_candidates, item_vectors, list_metric_inputs, list_metrics, list_metrics_chunks, rerank, rerank_chunk, rerank_pool, batch_rows, last_items, scope_categories, scope_within, scoped_similar_topk, scoped_topk, CategoryIndex, index_categories, indexed_topk, recommend_index, lists_similar_topk, similar_index, similar_queries, similar_topk, topk_merge, ItemScope, boost_of, item_boost_for, unpack_dense, write_checkpoint,
                     UserVectors, audience_exclusion, audience_queries, batch_list, check_user_vectors, dense_topk, kept_rows)
 
 
@@ -418,6 +418,11 @@ class ShardedModel:
         icl = None if categories is None else self._item_cate(torch.arange(self.I, device=self.device))
         return ItemScope(self.I, self.device, items=items, mask=mask, categories=categories, item_cate=icl)
 
+    def item_boost(self, values=None, items=None, categories=None, base=0.0):
+        """Model.item_boost: an ItemBoost over the model's items (every rank builds the same one, replicated)."""
+        return item_boost_for(self.I, self.device, lambda: self._item_cate(torch.arange(self.I, device=self.device)), values, items,
+                              categories, base)
+
     def last_item_categories(self, batch):
         """Model.last_item_categories for this rank's rows (no collective: the map is replicated)."""
         item = last_items(self.device_batch(batch, is_test=True))
@@ -437,7 +442,7 @@ class ShardedModel:
                              within=scope_within(within, self.I))
 
     def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None, index=None,
-                  probes=None):
+                  probes=None, boost=None, boost_weight=None):
         """Model.recommend for this rank's rows (every rank calls it, with the same k, exclusion mode and diversity
         settings): u_t and the exclusion lists are all-gathered, every rank selects the k best of ITS item shard for all
         rows (tlsan_eval_topk, global ids n * world + rank), each row's lists go to the rank that owns the row (one
@@ -451,10 +456,15 @@ class ShardedModel:
         index (Model.recommend's; every rank passes the same index and the same P): each rank scans the lists of ITS
         item shard, index.local(world, rank, its count), for all gathered rows (tlsan_eval_topk_lists); the rows'
         category arrays are all-gathered with u_t, and the unrestricted rows among them run through the path without
-        an index on every rank."""
+        an index on every rank.
+        boost / boost_weight (Model.recommend's; every rank passes the same boost, replicated and indexed by GLOBAL id,
+        and its own rows' weights): the weights are all-gathered with u_t and every rank calls the boosted entry point
+        (tlsan_eval_topk_scoped_boost / tlsan_eval_topk_lists_boost) with (id_mul, id_add) = (world, rank), so a column
+        reads the boost of its global id.  The all-to-all, the merge and _rerank are unchanged: they see boosted scores."""
         refuse_clustered(index, probes)
         if isinstance(index, ShortlistIndex):
             raise NotImplementedError("ShardedModel: a ShortlistIndex certifies a row against one table; per-shard certificates are not built")
+        boost = boost_of(boost, boost_weight, batch_rows(batch), self.I, self.device)
         N = rerank_pool(k, diversity, per_category, pool)
         want = int(k)
         within = scope_within(within, self.I)
@@ -469,14 +479,16 @@ class ShardedModel:
             off, xid = self._gather_excl(*exclusion_csr(db, exclude, self.I), B)
             nloc, ldims, lp = self._item_shard()
             tws = lambda nbytes: grow_workspace(self, "_tws", nbytes)
+            if boost is not None and boost[1] is not None:
+                boost = (boost[0], allgather_rows(boost[1], self.group))
             if nloc > 0 and index is not None:
                 cid, csc = indexed_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), index, allgather_rows(category, self.group),
-                                        self.world, self.rank, nloc, tws, st)
-            elif nloc > 0 and (within is not None or category is not None):
+                                        self.world, self.rank, nloc, tws, st, boost=boost)
+            elif nloc > 0 and (within is not None or category is not None or boost is not None):
                 sub = None if within is None else within.sub(self.world, self.rank, nloc)
                 cat_all = None if category is None else allgather_rows(category, self.group)
                 cid, csc = scoped_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), sub, cat_all, self.world, self.rank,
-                                       tws, st)
+                                       tws, st, boost=boost)
             elif nloc > 0:
                 cid, csc = eval_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), self.world, self.rank, tws, st)
             else:

@@ -301,6 +301,98 @@ class ItemScope:
         return self._local[key]
 
 
+class ItemBoost:
+    """A per-item score adjustment held on the device: fp32 [item_count], one value per GLOBAL item id -- the `boost=` of
+    recommend, single and sharded, reusable across calls.  A row's score of item g becomes fl(s + boost[g]), or
+    fl(s + fl(boost_weight[b] * boost[g])) with row weights, INSIDE the selection (tlsan_eval_topk_scoped_boost /
+    tlsan_eval_topk_lists_boost), so an item just outside the unboosted list that the boost lifts in is found.  -inf buries
+    an item behind every finite score without removing it (exclude= / within= remove items); NaN ranks last.
+    Built from an array or tensor of item_count values, or by of_items (a few ids against a base value) / of_categories
+    (a value per category, gathered through the item -> category map); a + b adds two holders over the same items in fp32.
+    device None: the tensor's own, "cpu" for an array; device "cpu" works for building and adding."""
+
+    def __init__(self, values, device=None):
+        t = values if isinstance(values, torch.Tensor) else torch.as_tensor(np.asarray(values))
+        if t.dim() != 1 or t.numel() < 1 or not (t.dtype.is_floating_point or t.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)):
+            raise ValueError("ItemBoost: want a 1-D array of item_count numbers, got shape %s dtype %s" % (tuple(t.shape), t.dtype))
+        self.values = t.detach().to(device=t.device if device is None else device, dtype=torch.float32).contiguous()
+        self.item_count, self.device = int(t.numel()), self.values.device
+
+    @classmethod
+    def of_items(cls, item_count, ids, values, base=0.0, device="cpu"):
+        """boost[ids[j]] = values[j] (values: one number for all, or one per id; an id named twice keeps its last value),
+        `base` everywhere else.  An id outside [0, item_count) or a wrong shape is a ValueError."""
+        host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        I, ids = int(item_count), host(ids)
+        if I < 1 or ids.ndim != 1 or (ids.size and ids.dtype.kind not in "iu"):
+            raise ValueError("ItemBoost.of_items: want item_count >= 1 and a 1-D sequence of item ids")
+        if ids.size and (ids.min() < 0 or ids.max() >= I):
+            raise ValueError("ItemBoost.of_items: item ids must be in [0, %d)" % I)
+        vals = host(values).astype(np.float32)
+        if vals.ndim != 0 and vals.shape != ids.shape:
+            raise ValueError("ItemBoost.of_items: values must be one number or one per id, got shape %s for %d ids" % (vals.shape, ids.size))
+        out = np.full(I, base, np.float32)
+        out[ids.astype(np.int64)] = vals
+        return cls(out, device=device)
+
+    @classmethod
+    def of_categories(cls, cate_values, item_cate, device=None):
+        """boost[i] = cate_values[item_cate[i]]: a gather on item_cate's device (device None) or on `device`.  A category
+        id outside [0, len(cate_values)) or a wrong shape is a ValueError."""
+        ic = item_cate if isinstance(item_cate, torch.Tensor) else torch.as_tensor(np.asarray(item_cate))
+        cv = cate_values if isinstance(cate_values, torch.Tensor) else torch.as_tensor(np.asarray(cate_values))
+        if ic.dim() != 1 or ic.numel() < 1 or ic.dtype.is_floating_point or ic.dtype == torch.bool or cv.dim() != 1 or cv.numel() < 1:
+            raise ValueError("ItemBoost.of_categories: want cate_values [cate_count] and item_cate [item_count] category ids")
+        if int(ic.min()) < 0 or int(ic.max()) >= cv.numel():
+            raise ValueError("ItemBoost.of_categories: category ids must be in [0, %d)" % cv.numel())
+        dev = ic.device if device is None else device
+        return cls(cv.to(device=dev, dtype=torch.float32)[ic.to(dev).long()], device=dev)
+
+    def __add__(self, other):
+        if not isinstance(other, ItemBoost):
+            return NotImplemented
+        if other.item_count != self.item_count:
+            raise ValueError("ItemBoost: adding boosts over %d and %d items" % (self.item_count, other.item_count))
+        return ItemBoost(self.values + other.values.to(self.device))
+
+
+def item_boost_for(item_count, device, item_cate, values, items, categories, base):
+    """Model.item_boost / ShardedModel.item_boost: fills in the count and the device (item_cate: a callable giving the
+    item -> category map on the device)."""
+    if (values is not None) + (items is not None) + (categories is not None) != 1:
+        raise ValueError("item_boost: give exactly one of values, items=(ids, values) and categories=")
+    if values is not None:
+        boost = ItemBoost(values, device=device)
+        if boost.item_count != item_count:
+            raise ValueError("item_boost: want %d values, got %d" % (item_count, boost.item_count))
+        return boost
+    if items is not None:
+        ids, vals = items
+        return ItemBoost.of_items(item_count, ids, vals, base=base, device=device)
+    return ItemBoost.of_categories(categories, item_cate(), device=device)
+
+
+def boost_of(boost, boost_weight, B, item_count, device):
+    """Checks recommend's `boost=` (an ItemBoost, or an array or tensor that is wrapped) and `boost_weight=` ([B] numbers,
+    array or tensor) -> None without a boost, else (values [item_count] float32, weights [B] float32 or None) on `device`.
+    A weight without a boost, a boost over another item count or a weight of the wrong length is a ValueError."""
+    if boost is None:
+        if boost_weight is not None:
+            raise ValueError("boost_weight= weighs boost=: give boost=")
+        return None
+    if not isinstance(boost, ItemBoost):
+        boost = ItemBoost(boost, device=device)
+    if boost.item_count != item_count:
+        raise ValueError("boost must cover the model's %d items, got %d" % (item_count, boost.item_count))
+    w = None
+    if boost_weight is not None:
+        w = boost_weight if isinstance(boost_weight, torch.Tensor) else torch.as_tensor(np.asarray(boost_weight))
+        if tuple(w.shape) != (B,) or w.dtype == torch.bool or w.dtype.is_complex:
+            raise ValueError("boost_weight: want [%d] numbers, got shape %s dtype %s" % (B, tuple(w.shape), w.dtype))
+        w = w.detach().to(device=device, dtype=torch.float32).contiguous()
+    return boost.values.to(device), w
+
+
 class CategoryIndex:
     """The items by category: a partition of the GLOBAL item ids -- of all item_count of them, or of an ItemScope's when
     within= is given -- into one list per category, held on the device: list_off [cate_count + 1] int32 and list_items
@@ -393,9 +485,10 @@ def index_categories(category, B, cate_count, device):
     return cat.to(device).clamp(min=-1).to(torch.int32).contiguous()
 
 
-def lists_topk(lib, dims, cparams, ut, B, k, excl, lists, row_lists, id_mul, id_add, workspace, stream):
+def lists_topk(lib, dims, cparams, ut, B, k, excl, lists, row_lists, id_mul, id_add, workspace, stream, boost=None):
     """tlsan_eval_topk_lists on u_t [B, d]: the k best of the union of the lists row_lists [B, P] int32 names, of the index
-    `lists` (CategoryIndex.local's triple) -> (ids [B, k] int32, scores [B, k] float32)."""
+    `lists` (CategoryIndex.local's triple) -> (ids [B, k] int32, scores [B, k] float32).  boost: boost_of's pair (values by
+    GLOBAL id, the B rows' weights or None) -> tlsan_eval_topk_lists_boost, the scores adjusted inside the selection."""
     k, P = int(k), int(row_lists.shape[1])
     off, items, max_list = lists
     nl = int(off.shape[0]) - 1
@@ -407,9 +500,12 @@ def lists_topk(lib, dims, cparams, ut, B, k, excl, lists, row_lists, id_mul, id_
     scores = torch.empty(B, k, dtype=torch.float32, device=ut.device)
     xoff, xid = excl
     ptr = lambda t: None if t is None else t.data_ptr()
-    L.check(lib.tlsan_eval_topk_lists(C.byref(dims), C.byref(cparams), ut.data_ptr(), B, k, ptr(xoff), ptr(xid), off.data_ptr(),
-                                      items.data_ptr(), nl, max_list, row_lists.data_ptr(), P, id_mul, id_add, ids.data_ptr(),
-                                      scores.data_ptr(), ws.data_ptr(), ws.numel(), stream), "tlsan_eval_topk_lists")
+    args = (C.byref(dims), C.byref(cparams), ut.data_ptr(), B, k, ptr(xoff), ptr(xid), off.data_ptr(), items.data_ptr(), nl,
+            max_list, row_lists.data_ptr(), P, id_mul, id_add, ids.data_ptr(), scores.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+    if boost is None:
+        L.check(lib.tlsan_eval_topk_lists(*args), "tlsan_eval_topk_lists")
+    else:
+        L.check(lib.tlsan_eval_topk_lists_boost(*args, boost[0].data_ptr(), ptr(boost[1])), "tlsan_eval_topk_lists_boost")
     return ids, scores
 
 
@@ -448,20 +544,23 @@ def excl_rows(excl, rows, B):
     return torch.arange(0, (vals.shape[0] + 1) * w, w, dtype=torch.int32, device=xid.device), vals.view(-1)
 
 
-def indexed_topk(lib, dims, cparams, ut, B, k, excl, index, row_lists, id_mul, id_add, n_local, workspace, stream):
+def indexed_topk(lib, dims, cparams, ut, B, k, excl, index, row_lists, id_mul, id_add, n_local, workspace, stream, boost=None):
     """recommend's lists with an index on u_t [B, d]: the rows that probe a list go through lists_topk; the rows whose
     entries are all negative are unrestricted -- they run through the path without an index (scoped_topk over the index's
-    scope, eval_topk without one) as a sub-batch and are scattered back.  One host read says whether there are any."""
+    scope, eval_topk without one) as a sub-batch and are scattered back.  One host read says whether there are any.
+    boost (boost_of's pair): the sub-batch carries the boost and its rows' slice of the weights."""
     ids, scores = lists_topk(lib, dims, cparams, ut, B, k, excl, index.local(id_mul, id_add, n_local), row_lists, id_mul, id_add,
-                             workspace, stream)
+                             workspace, stream, boost=boost)
     free = torch.nonzero((row_lists < 0).all(1))[:, 0]
     if free.numel():
         sub_ut, sub_excl, n = ut[free].contiguous(), excl_rows(excl, free, B), int(free.numel())
-        if index.within is None:
+        sub_boost = None if boost is None else (boost[0], None if boost[1] is None else boost[1][free].contiguous())
+        if index.within is None and boost is None:
             fid, fsc = eval_topk(lib, dims, cparams, sub_ut, n, k, sub_excl, id_mul, id_add, workspace, stream)
         else:
-            fid, fsc = scoped_topk(lib, dims, cparams, sub_ut, n, k, sub_excl, index.within.sub(id_mul, id_add, n_local), None,
-                                   id_mul, id_add, workspace, stream)
+            sub = None if index.within is None else index.within.sub(id_mul, id_add, n_local)
+            fid, fsc = scoped_topk(lib, dims, cparams, sub_ut, n, k, sub_excl, sub, None, id_mul, id_add, workspace, stream,
+                                   boost=sub_boost)
         ids[free], scores[free] = fid, fsc
     return ids, scores
 
@@ -511,9 +610,11 @@ def scope_categories(category, B, cate_count, device):
     return cat.to(device).clamp(min=-1).to(torch.int32).contiguous()
 
 
-def scoped_topk(lib, dims, cparams, ut, B, k, excl, sub, row_cate, id_mul, id_add, workspace, stream):
+def scoped_topk(lib, dims, cparams, ut, B, k, excl, sub, row_cate, id_mul, id_add, workspace, stream, boost=None):
     """tlsan_eval_topk_scoped on u_t [B, d]: eval_topk over the local items sub (ItemScope.sub's pair; None: every item)
-    with the rows' wanted categories row_cate ([B] int32 or None) -> (ids [B, k] int32, scores [B, k] float32)."""
+    with the rows' wanted categories row_cate ([B] int32 or None) -> (ids [B, k] int32, scores [B, k] float32).  boost:
+    boost_of's pair (values by GLOBAL id, the B rows' weights or None) -> tlsan_eval_topk_scoped_boost, the scores adjusted
+    inside the selection."""
     k = int(k)
     sub, nsub = (None, -1) if sub is None else sub
     nws = lib.tlsan_scope_workspace_bytes(C.byref(dims), B, k, nsub)
@@ -524,9 +625,12 @@ def scoped_topk(lib, dims, cparams, ut, B, k, excl, sub, row_cate, id_mul, id_ad
     scores = torch.empty(B, k, dtype=torch.float32, device=ut.device)
     off, xid = excl
     ptr = lambda t: None if t is None else t.data_ptr()
-    L.check(lib.tlsan_eval_topk_scoped(C.byref(dims), C.byref(cparams), ut.data_ptr(), B, k, ptr(off), ptr(xid), ptr(sub), nsub,
-                                       ptr(row_cate), id_mul, id_add, ids.data_ptr(), scores.data_ptr(), ws.data_ptr(),
-                                       ws.numel(), stream), "tlsan_eval_topk_scoped")
+    args = (C.byref(dims), C.byref(cparams), ut.data_ptr(), B, k, ptr(off), ptr(xid), ptr(sub), nsub, ptr(row_cate), id_mul, id_add,
+            ids.data_ptr(), scores.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+    if boost is None:
+        L.check(lib.tlsan_eval_topk_scoped(*args), "tlsan_eval_topk_scoped")
+    else:
+        L.check(lib.tlsan_eval_topk_scoped_boost(*args, boost[0].data_ptr(), ptr(boost[1])), "tlsan_eval_topk_scoped_boost")
     return ids, scores
 
 
@@ -1852,6 +1956,12 @@ class Model(object):
         return ItemScope(self.config["item_count"], self.device, items=items, mask=mask, categories=categories,
                          item_cate=None if categories is None else self.item_cate)
 
+    def item_boost(self, values=None, items=None, categories=None, base=0.0):
+        """An ItemBoost over this model's items, on its device: from values ([item_count] numbers), from items=(ids,
+        values) against `base` (ItemBoost.of_items), or from categories=[cate_count] values through the model's item_cate
+        (ItemBoost.of_categories).  Exactly one of the three."""
+        return item_boost_for(self.config["item_count"], self.device, lambda: self.item_cate, values, items, categories, base)
+
     def last_item_categories(self, batch):
         """last_item_categories of a batch (tuple or DeviceBatch) with this model's item -> category map."""
         return last_item_categories(self.device_batch(batch, is_test=True), self.item_cate)
@@ -1876,7 +1986,7 @@ class Model(object):
         return build(self)
 
     def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None, index=None,
-                  probes=None, shortlist=None, fallback=True):
+                  probes=None, shortlist=None, fallback=True, boost=None, boost_weight=None):
         """The k best items over ALL items for each row -- what tf.nn.top_k(eval_logits, k) gives the reference
         (model.py:140) -- without materialising the [B, I] scores.  Takes label_ranks' batches (the label and the
         negative are not used).  -> (ids [B, k] int32, scores [B, k] float32) device tensors, in tf.nn.top_k's
@@ -1926,7 +2036,20 @@ class Model(object):
         fallback=False: the shortlist's lists as they are.  index.certified is the call's [B] bool device tensor,
         index.counts the (rows, certified) of all calls.  exclude= and the second stage compose; within=, category= or
         probes= beside it, shortlist= without it, n >= N, or an index over another item count or d: ValueError before any
-        launch."""
+        launch.
+        boost (an ItemBoost, item_boost(); or an array or tensor of item_count values, wrapped) / boost_weight ([B]
+        numbers, array or tensor): every score becomes s' = fl(s + boost[g]), or fl(s + fl(boost_weight[b] * boost[g]))
+        with weights (fp32, separate roundings), INSIDE the selection -- tlsan_eval_topk_scoped_boost /
+        tlsan_eval_topk_lists_boost -- so a promoted item just outside the unboosted list is found.  Selection, ties
+        (lower id), zeros and NaN (last) follow s'; the scores returned are s' (score_candidates on the ids gives the raw
+        ones).  -inf buries an item behind every finite score but does not remove it: exclude= / within= remove items.  An
+        all-zero boost, or a weight of 0, gives the unboosted row, ids and bits.  It composes with exclude=, within=,
+        category=, a CategoryIndex (the unrestricted sub-batch carries the boost and its rows' weights), a ClusteredIndex
+        (probing still picks the lists by the UNBOOSTED centroid scores; probing every non-empty list is the boosted
+        exact result) and the second stage (the pool is the boosted list and the relevance is formed from s').  With both
+        None nothing changes: the same launches and bits.  boost_weight without boost, a boost over another item count,
+        a weight of the wrong length, or boost= beside a ShortlistIndex (its certificate bounds the model's score, not
+        s'): ValueError before any launch.  similar_items, audience and label_ranks take no boost."""
         from .cluster import clustered_probes, clustered_topk
         from .shortlist import shortlist_size, shortlist_topk
         N = rerank_pool(k, diversity, per_category, pool)
@@ -1934,6 +2057,9 @@ class Model(object):
                                category=category, within=within, probes=probes)
         probes = None if short is not None else clustered_probes(index, probes, self.config["item_count"], category=category, within=within)
         within = scope_within(within, self.config["item_count"])
+        boost = boost_of(boost, boost_weight, batch_rows(batch), self.config["item_count"], self.device)
+        if boost is not None and short is not None:
+            raise ValueError("boost= beside a ShortlistIndex: its certificate bounds the model's score, not the boosted one")
         if probes is not None or short is not None:
             pass
         elif recommend_index(index, within, self.config["item_count"], self.config["cate_count"]) is not None:
@@ -1947,16 +2073,16 @@ class Model(object):
                                             self._topk_workspace, st)
         elif probes is not None:
             topk = lambda n: clustered_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, probes,
-                                            self._scale_vector(index.lists), self._topk_workspace, st)
+                                            self._scale_vector(index.lists), self._topk_workspace, st, boost=boost)
         elif index is not None:
             topk = lambda n: indexed_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, category, 1, 0,
-                                          self.config["item_count"], self._topk_workspace, st)
-        elif within is None and category is None:
+                                          self.config["item_count"], self._topk_workspace, st, boost=boost)
+        elif within is None and category is None and boost is None:
             topk = lambda n: eval_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, 1, 0, self._topk_workspace, st)
         else:
             sub = None if within is None else within.sub(1, 0, self.config["item_count"])
             topk = lambda n: scoped_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, sub, category, 1, 0,
-                                         self._topk_workspace, st)
+                                         self._topk_workspace, st, boost=boost)
         if N is None:
             return topk(k)
         # (forward has landed an owed lazy-L2 correction; the vectors are read as stored, the scale not folded)

@@ -89,6 +89,15 @@ def parse(argv=None):
                          "the largest per-category count, HR / NDCG / MRR of the test positives, novelty by the training "
                          "set's self-information, catalogue coverage and the Gini coefficient of the exposure), print them "
                          "and write <model_dir>/recommend_top<K>_metrics.json")
+    ap.add_argument("--recommend_boost", default="", metavar="PATH.npy",
+                    help="with --recommend_k: a per-item score adjustment, fp32 [item_count] (np.save): every score becomes "
+                         "score + boost[item] inside the selection (Model.recommend's boost=).  -inf buries an item, it does "
+                         "not remove it")
+    ap.add_argument("--recommend_novelty", type=float, default=0.0, metavar="ALPHA",
+                    help="with --recommend_k: boost = ALPHA x the items' self-information over the training set "
+                         "(input.item_self_information, the novelty weight of --recommend_metrics): ALPHA > 0 pays for rare "
+                         "items, ALPHA < 0 for popular ones.  Summed with --recommend_boost when both are given; with "
+                         "--recommend_metrics 1 the metrics are those of the lists as served")
     ap.add_argument("--recommend_categories", default="",
                     help="with --recommend_k: recommend within the items of these categories only, e.g. 3,7,12 (an ItemScope: "
                          "only those items are scored)")
@@ -163,6 +172,10 @@ def parse(argv=None):
         ap.error("--shortlist is the shortlist index's length: give --shortlist_index 1")
     if args.shortlist_index and (args.cluster_index or args.category_index or args.recommend_same_category or args.recommend_categories):
         ap.error("--shortlist_index serves the whole catalogue: it goes without a scope, a category or another index")
+    if (args.recommend_boost or args.recommend_novelty) and not args.recommend_k:
+        ap.error("--recommend_boost / --recommend_novelty adjust the lists of --recommend_k: give --recommend_k")
+    if (args.recommend_boost or args.recommend_novelty) and args.shortlist_index:
+        ap.error("--shortlist_index certifies the model's score, not a boosted one: it goes without --recommend_boost / --recommend_novelty")
     if args.shortlist and not 16 <= args.shortlist <= 256:
         ap.error("--shortlist wants N in 16..256")
     if args.shortlist_index and (args.sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1):
@@ -257,6 +270,22 @@ def recommend_settings(args):
         return {}
     return dict(diversity=args.recommend_diversity, per_category=args.recommend_per_category,
                 pool=args.recommend_pool or None)
+
+
+def recommend_boost_vector(args, train_set, item_count):
+    """The boost of --recommend_boost / --recommend_novelty -> float32 [item_count] host array, or None when neither is
+    given: the file's values, ALPHA x item_self_information(train_set, item_count) formed in float32, or their float32
+    sum.  A file of another shape or dtype kind is a ValueError."""
+    boost = None
+    if args.recommend_boost:
+        boost = np.load(args.recommend_boost)
+        if boost.shape != (item_count,) or boost.dtype.kind not in "fiu":
+            raise ValueError("--recommend_boost: want [%d] numbers, got shape %s dtype %s" % (item_count, boost.shape, boost.dtype))
+        boost = boost.astype(np.float32)
+    if args.recommend_novelty:
+        novelty = np.float32(args.recommend_novelty) * item_self_information(train_set, item_count)
+        boost = novelty if boost is None else boost + novelty
+    return boost
 
 
 def similar_path(model_dir, k):
@@ -683,6 +712,9 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
         # (a DevicePackedSet keeps the host set it was made from: the novelty weights are counted on the host)
         measure = ListMeasurement(model, rows, args.recommend_k, getattr(train_set, "ps", train_set)) \
             if args.recommend_metrics else None
+        boost = recommend_boost_vector(args, getattr(train_set, "ps", train_set), rows.config["item_count"])
+        # (one holder for every launch; every rank builds the same)
+        served = settings if boost is None else dict(settings, boost=model.item_boost(boost))
         scope = dict(within=model.item_scope(categories=args.recommend_categories)) if args.recommend_categories else {}
         if args.category_index and args.recommend_same_category:   # (the scope belongs to the index)
             scope = dict(index=model.category_index(**scope) if scope else whole)
@@ -693,14 +725,14 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
                 % (cindex.lists, cindex.count, cindex.max_list, cindex.mean_list, len(cindex.objective)))
             if args.recommend_metrics:
                 recall_of = RecallMeasurement(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen),
-                                              dict(settings, **scope), then=measure)
+                                              dict(served, **scope), then=measure)
             scope = dict(index=cindex, probes=args.cluster_probes)
         share_of = None
         if args.shortlist_index:
             scope = dict(index=model.shortlist_index(), shortlist=args.shortlist or None)
             share_of = CertifiedShare(scope["index"], then=measure)
         rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen),
-                                 on_lists=share_of or recall_of or measure, same_category=bool(args.recommend_same_category), **settings, **scope)
+                                 on_lists=share_of or recall_of or measure, same_category=bool(args.recommend_same_category), **served, **scope)
         list_res = measure.result() if measure is not None else None       # (collective: every rank)
         if recall_of is not None:
             say("Clustered index: recall@%d = %.4f against the exact lists over %d rows (%d probes)"
