@@ -636,6 +636,48 @@ int tlsan_similar_topk_lists(const tlsan_dims* dims, const tlsan_params* p, cons
                              int32_t max_list, const int32_t* row_lists, int32_t P, int32_t id_mul, int32_t id_add,
                              int32_t* ids, float* scores, void* ws, size_t ws_bytes, void* stream);
 
+/* Category shelves: for each row the S lists of an index (the indexed lists' list_off / list_items, above) whose own
+ * m-lists rank highest, with those m-lists -- a page of departments and what goes on each shelf -- in one scan of the
+ * index.  No [B, item_count] score array and no [B, nlists, m] array is ever built.
+ *   L(b, c): the m best items of list c for row b minus the row's exclusion list, in tlsan_eval_topk's order: exactly
+ *     row b of tlsan_eval_topk_lists with K = m and row_lists[b] = c, ids and score bits.  n(b, c): its valid entries.
+ *   List c is a CANDIDATE of row b when no entry of skip[b, 0 .. X) names it (skip [B, X] list ids, 0 <= X <= 8, NULL
+ *     with X = 0; a negative entry names nothing) and n(b, c) >= min_items, 1 <= min_items <= m.  Its rank key is entry
+ *     rank_at of L(b, c), 0 <= rank_at < min_items: (score, global id) in tlsan_eval_topk's order, so NaN ranks last and
+ *     +0.0 == -0.0; no arithmetic is done on scores.  Row b's page is its S candidates of highest rank key, in that order;
+ *     equal rank keys (possible only when two lists hold the same item) go to the lower list id.
+ *   cats [B, S], ids [B, S, m], scores [B, S, m]: shelf j of row b is list cats[b, j] with L(b, cats[b, j]).  A row with
+ *     fewer than S candidates ends in cats -1, ids -1, scores -inf; entries of a shelf past n(b, c) are -1 / -inf.
+ *   1 <= S <= 32, 1 <= m <= 64, S * m <= 256 (a page flattened to [B, S * m] is a list tlsan_list_metrics takes).
+ *   The PLAN, built by the host from the lists' lengths, says how the scan walks the index; every list with items appears
+ *     in it exactly once:
+ *       seg_off [nseg + 1], seg_lists [nsmall]: segment s is the lists seg_lists[seg_off[s] .. seg_off[s + 1]); one
+ *         workgroup per 16 rows walks a segment's lists one after another;
+ *       big_off [nbig + 1], big_slices [nbs, 3] = (list, lo, hi): big list j is cut into the slices big_off[j] ..
+ *         big_off[j + 1], at most 16, slice t the positions lo .. hi of its list; one workgroup per 16 rows and slice.
+ *     The result does not depend on the plan: not on which lists share a segment, which are big or where they are cut.  A
+ *     list id outside [0, nlists) or positions outside the list are passed over, never used as addresses; a list the plan
+ *     leaves out is no candidate.  max_list is the longest list's length as the host knows it (>= 0; it sizes nothing).
+ *   A row's result depends on its own inputs only: not on B, the other rows, a repeated call or the launch geometry.
+ *   id_mul / id_add: the table's id mapping, as everywhere (the returned ids and the exclusion lists are global ids).
+ * Two launches on `stream`, no host synchronisation; no grid is sized by a device value.  The call changes no parameter
+ * and no state.  Workspace: tlsan_shelves_workspace_bytes(dims, B, S, m, nseg, nbig, nbs), never less for a larger
+ * argument; 0, with tlsan_last_error set, on a refusal.  Refused before any launch, with the function's name in
+ * tlsan_last_error: bad dims or parameters (tlsan_eval_topk_lists' codes); B or nlists outside 1..2^24, S outside 1..32,
+ * m outside 1..64, S * m > 256, min_items outside 1..m, rank_at outside 0..min_items - 1, nseg or nbig outside 0..32767,
+ * nbs outside nbig..min(32767, 16 nbig), nsmall < 0 (or 0 with segments), max_list < 0, X outside 0..8 or skip not going
+ * with it, a NULL pointer (the plan's arrays may be NULL where their count is 0), excl_off without excl_ids, an id
+ * mapping that leaves int32 (TLSAN_E_BADARG); a workspace that is NULL or too small (TLSAN_E_WORKSPACE).
+ * The two functions are additions: nothing else in the ABI changed (TLSAN_ABI_VERSION stays 15). */
+size_t tlsan_shelves_workspace_bytes(const tlsan_dims* dims, int32_t B, int32_t S, int32_t m, int32_t nseg, int32_t nbig,
+                                     int32_t nbs);
+int tlsan_eval_shelves(const tlsan_dims* dims, const tlsan_params* p, const float* u_t, int32_t B, int32_t S, int32_t m,
+                       int32_t min_items, int32_t rank_at, const int32_t* excl_off, const int32_t* excl_ids,
+                       const int32_t* list_off, const int32_t* list_items, int32_t nlists, int32_t max_list,
+                       const int32_t* seg_off, const int32_t* seg_lists, int32_t nseg, int32_t nsmall, const int32_t* big_off,
+                       const int32_t* big_slices, int32_t nbig, int32_t nbs, const int32_t* skip, int32_t X, int32_t id_mul,
+                       int32_t id_add, int32_t* cats, int32_t* ids, float* scores, void* ws, size_t ws_bytes, void* stream);
+
 /* Boosted lists: tlsan_eval_topk_scoped and tlsan_eval_topk_lists with a per-item score adjustment applied INSIDE the
  * selection, where a score meets its row's threshold ("promote these items", "bury those", "pay this much for novelty").
  * An item just outside the unboosted list that the boost lifts in is found; a caller who adjusts the returned list

@@ -36,6 +36,7 @@ EXPORTS = [
     "tlsan_scope_workspace_bytes", "tlsan_eval_topk_scoped", "tlsan_similar_topk_scoped",
     "tlsan_lists_workspace_bytes", "tlsan_eval_topk_lists", "tlsan_similar_topk_lists",
     "tlsan_eval_topk_scoped_boost", "tlsan_eval_topk_lists_boost",
+    "tlsan_shelves_workspace_bytes", "tlsan_eval_shelves",
     "tlsan_cluster_workspace_bytes", "tlsan_cluster_assign", "tlsan_cluster_means", "tlsan_cluster_probe",
     "tlsan_dense_topk_workspace_bytes", "tlsan_dense_topk",
     "tlsan_shortlist_build", "tlsan_shortlist_workspace_bytes", "tlsan_shortlist_topk", "tlsan_shortlist_select",
@@ -267,6 +268,15 @@ def load():
         lib.tlsan_eval_topk_scoped_boost.restype = C.c_int
         lib.tlsan_eval_topk_lists_boost.argtypes = lib.tlsan_eval_topk_lists.argtypes + [C.c_void_p, C.c_void_p]
         lib.tlsan_eval_topk_lists_boost.restype = C.c_int
+    if hasattr(lib, "tlsan_eval_shelves"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
+        lib.tlsan_shelves_workspace_bytes.argtypes = [P(Dims)] + [C.c_int32] * 6
+        lib.tlsan_shelves_workspace_bytes.restype = C.c_size_t
+        # (dims, params, u_t, B, S, m, min_items, rank_at, the exclusion pair, the index and its two counts, the plan's
+        #  segments and big lists with their counts, skip, X, the id mapping, the three outputs, the workspace, the stream)
+        lib.tlsan_eval_shelves.argtypes = [P(Dims), P(Params), C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 4 + [C.c_int32] * 2 + \
+                                          [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] * 2 + [C.c_void_p] + [C.c_int32] * 3 + \
+                                          [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
+        lib.tlsan_eval_shelves.restype = C.c_int
     if hasattr(lib, "tlsan_cluster_probe"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
         lib.tlsan_cluster_workspace_bytes.argtypes = [C.c_int32] * 3
         lib.tlsan_cluster_workspace_bytes.restype = C.c_size_t

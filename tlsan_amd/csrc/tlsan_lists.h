@@ -26,6 +26,7 @@
 // leaves at once), hold an empty list.  The slice count comes from the host's max_list: no device value sizes a grid.
 // Scores: ListScore is ScopedScore and SimScore is ScopedSim without the category test (membership of the list
 // replaces it), on score_tiles4's gather form: the bits of tlsan_eval_topk_scoped / tlsan_similar_topk_scoped.
+// (tlsan_shelves.h holds one more copy of this loop, inside a loop over lists: a fix to either goes into both.)
 #pragma once
 #include "tlsan_similar.h"
 
@@ -63,6 +64,7 @@ struct ListScore {
   float bias;
   f32x4 acc;
   __device__ __forceinline__ explicit ListScore(const ListsTopkArgs& s) : a(s.t.e), P(eval_scale(s.t.e)) {}
+  __device__ __forceinline__ explicit ListScore(const EvalArgs& e) : a(e), P(eval_scale(e)) {}   // (tlsan_shelves.h)
   __device__ __forceinline__ bool row(int, int u) { return u < a.B; }
   __device__ __forceinline__ void col(const f32x4& tile, int item) {
     acc = tile;

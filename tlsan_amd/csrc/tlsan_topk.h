@@ -190,7 +190,8 @@ __device__ __forceinline__ void topk_offer(TopkSmem<KP, BUF>& sm, const topk_key
 // SimScore).  k_eval_topk itself keeps its own text: on this loop with a policy of its own (built in the kernel or
 // inside the loop), and with only score_tiles4 or only topk_offer put into its text, it measured 1-2 % slower with an
 // exclusion list or at K > 64 (profiles/eval_scan.md).  So a fix to the scan's prologue, tile loop or offer loop goes
-// into both; the push, the phases, the reselection and the finish are shared functions.
+// into both; the push, the phases, the reselection and the finish are shared functions.  (Two more copies of the loop
+// exist for forms it cannot take: lists_scan, tlsan_lists.h, and shelves_scan, tlsan_shelves.h -- a fix goes into all four.)
 // A workgroup of grid (ceil(B/16), slices): wavefront w of slice y scores items n0 .. n0 + 63,
 // n0 = (round * slices + y) * 256 + 64 w, as 4 tiles of 16 rows x 16 items (score_tiles4: DENSE from all_emb, the chains
 // of k_eval_rank_dense; else through all_emb4, k_eval_rank's), and offers the eligible scores that beat their row's

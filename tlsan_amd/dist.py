@@ -432,6 +432,11 @@ class ShardedModel:
         """Model.shortlist_index is not built across ranks: per-shard certificates are a follow-up."""
         raise NotImplementedError("ShardedModel: a ShortlistIndex certifies a row against one table; per-shard certificates are not built")
 
+    def shelves(self, *args, **kwargs):
+        """Model.shelves is not built across ranks: a category's items are spread over the ranks."""
+        raise NotImplementedError("ShardedModel: a category's items are spread over the ranks, so a rank cannot rank categories "
+                                  "alone; the sharded form of shelves is not built")
+
     def cluster_index(self, *args, **kwargs):
         """Model.cluster_index is not built across ranks: a ValueError (train and probe a ClusteredIndex on a Model)."""
         raise ValueError("ShardedModel: a ClusteredIndex is not supported on a row-sharded model (building and probing across ranks)")

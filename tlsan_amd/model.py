@@ -423,6 +423,7 @@ class CategoryIndex:
         self.list_off = torch.as_tensor(off.astype(np.int32)).to(device)
         self.list_items = torch.as_tensor(self._items.astype(np.int32)).to(device)
         self._local = {}
+        self._lens, self._plans = {}, {}    # per table: the lists' lengths (host); per (table, thresholds): the shelves' plan
 
     def local(self, id_mul, id_add, n_local):
         """The index of a table of n_local items whose local item n is global id n * id_mul + id_add (a whole table:
@@ -435,9 +436,20 @@ class CategoryIndex:
             keep = (rel >= 0) & (rel % key[0] == 0) & (rel // key[0] < key[2])
             off = np.concatenate([[0], np.cumsum(np.bincount(self._cats[keep], minlength=self.cate_count))])
             items = np.concatenate([rel[keep] // key[0], [0]])
+            self._lens[key] = np.diff(off)
             self._local[key] = (torch.as_tensor(off.astype(np.int32)).to(self.device),
                                 torch.as_tensor(items.astype(np.int32)).to(self.device), int(np.diff(off).max()))
         return self._local[key]
+
+    def shelf_plan(self, id_mul, id_add, n_local, seg_items, big_items):
+        """The ShelfPlan of local()'s index of that table under the two thresholds (shelves_plan), built from the host copy
+        of the lists' lengths; cached per (table, thresholds)."""
+        key = (int(id_mul), int(id_add), int(n_local))
+        self.local(*key)
+        pk = key + (int(seg_items), int(big_items))
+        if pk not in self._plans:
+            self._plans[pk] = ShelfPlan(self._lens[key], seg_items, big_items, self.device)
+        return self._plans[pk]
 
 
 def index_of(index, item_count, cate_count):
@@ -563,6 +575,141 @@ def indexed_topk(lib, dims, cparams, ut, B, k, excl, index, row_lists, id_mul, i
                                    boost=sub_boost)
         ids[free], scores[free] = fid, fsc
     return ids, scores
+
+
+SHELF_SMAX, SHELF_MMAX, SHELF_SKIP_MAX, SHELF_SLICES_MAX = 32, 64, 8, 16   # csrc/tlsan_shelves.h
+
+
+def shelves_plan(lens, seg_items, big_items):
+    """The plan tlsan_eval_shelves takes, from the lists' lengths lens [nlists] (host): the lists with items, in list
+    order, either packed into segments of about seg_items items (a list goes into the open segment while the segment
+    stays within seg_items; a segment holds at least one list) or, when longer than big_items, cut into at most
+    SHELF_SLICES_MAX slices of max(seg_items, 256) positions or more (a multiple of 256).  big_items = 0: every list is big.
+    -> (seg_off [nseg + 1], seg_lists [nsmall], big_off [nbig + 1], big_slices [nbs, 3]) int32 arrays.  Which plan is used
+    changes the launch geometry, never the result."""
+    lens = np.asarray(lens, np.int64)
+    seg_items, big_items = int(seg_items), int(big_items)
+    if seg_items < 1 or big_items < 0:
+        raise ValueError("shelves: seg_items must be >= 1 and big_items >= 0, got %d and %d" % (seg_items, big_items))
+    seg_off, seg_lists, big_off, big_slices, fill = [0], [], [0], [], 0
+    for c in np.flatnonzero(lens > 0):
+        n = int(lens[c])
+        if n > big_items:
+            sl = max(seg_items, 256, -(-n // SHELF_SLICES_MAX))
+            sl = -(-sl // 256) * 256
+            big_slices += [(c, lo, min(n, lo + sl)) for lo in range(0, n, sl)]
+            big_off.append(len(big_slices))
+            continue
+        if fill and fill + n > seg_items:
+            seg_off.append(len(seg_lists))
+            fill = 0
+        seg_lists.append(c)
+        fill += n
+    if fill:
+        seg_off.append(len(seg_lists))
+    i32 = lambda x, shape: np.asarray(x, np.int32).reshape(shape)
+    return i32(seg_off, -1), i32(seg_lists, -1), i32(big_off, -1), i32(big_slices, (-1, 3))
+
+
+def shelves_thresholds(total, B):
+    """The production (seg_items, big_items) of an index of `total` items for B rows (profiles/shelves.md): about
+    2048 / ceil(B / 16) units, a power of two in 32..1024, so that the grid (row tiles, units) fills the device a few
+    times over while the [B, units, S, m] workspace stays small; a list is big from four segments' worth."""
+    tiles = (int(B) + 15) // 16
+    units = 1 << int(np.log2(min(1024, max(32, 2048 // tiles))))
+    seg = -(-max(1024, -(-int(total) // units)) // 256) * 256
+    return seg, 4 * seg
+
+
+class ShelfPlan:
+    """shelves_plan's arrays on the device (each one element longer than its content, so that an empty one still has an
+    address) with their host counts."""
+
+    def __init__(self, lens, seg_items, big_items, device):
+        so, sl, bo, bs = shelves_plan(lens, seg_items, big_items)
+        self.nseg, self.nsmall, self.nbig, self.nbs = len(so) - 1, len(sl), len(bo) - 1, len(bs)
+        dev = lambda x: torch.as_tensor(np.concatenate([x.reshape(-1), [0]]).astype(np.int32)).to(device)
+        self.seg_off, self.seg_lists, self.big_off, self.big_slices = dev(so), dev(sl), dev(bo), dev(bs)
+
+
+def shelves_sizes(S, m, min_items, rank_at):
+    """Checks the four sizes of a page of shelves -> them as ints.  1 <= S <= 32, 1 <= m <= 64, S * m <= 256 (TOPK_MAX, the
+    width list_metrics takes), 1 <= min_items <= m, 0 <= rank_at < min_items; anything else is a ValueError."""
+    vals = []
+    for name, v in (("shelves", S), ("k", m), ("min_items", min_items), ("rank_at", rank_at)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("shelves: %s must be an integer, got %r" % (name, v))
+        vals.append(int(v))
+    S, m, min_items, rank_at = vals
+    if not 1 <= S <= SHELF_SMAX:
+        raise ValueError("shelves: shelves must be in 1..%d, got %d" % (SHELF_SMAX, S))
+    if not 1 <= m <= SHELF_MMAX:
+        raise ValueError("shelves: k must be in 1..%d, got %d" % (SHELF_MMAX, m))
+    if S * m > L.TOPK_MAX:
+        raise ValueError("shelves: shelves * k must be at most %d, got %d * %d" % (L.TOPK_MAX, S, m))
+    if not 1 <= min_items <= m:
+        raise ValueError("shelves: min_items must be in 1..k = %d, got %d" % (m, min_items))
+    if not 0 <= rank_at < min_items:
+        raise ValueError("shelves: rank_at must be in 0..min_items - 1 = %d, got %d" % (min_items - 1, rank_at))
+    return S, m, min_items, rank_at
+
+
+def shelves_index(index, item_count, cate_count):
+    """Checks shelves' `index=` -> it: a CategoryIndex over the model's items and categories, required."""
+    if not isinstance(index, CategoryIndex) or index.item_count != item_count or index.cate_count != cate_count:
+        raise ValueError("shelves: index must be a CategoryIndex over the model's %d items in %d categories (category_index())"
+                         % (item_count, cate_count))
+    return index
+
+
+def shelves_skip(skip, B, cate_count, device):
+    """Checks shelves' `skip=` (None, [B] or [B, X] category ids, X <= 8, array or tensor; negative: nothing) ->
+    contiguous int32 [B, X] device tensor, or None.  An id >= cate_count or a wrong shape is a ValueError."""
+    if skip is None:
+        return None
+    sk = skip if isinstance(skip, torch.Tensor) else torch.as_tensor(np.asarray(skip))
+    shape = tuple(sk.shape)
+    if shape == (B,):
+        sk = sk.reshape(B, 1)
+    elif len(shape) != 2 or shape[0] != B or not 1 <= shape[1] <= SHELF_SKIP_MAX:
+        raise ValueError("shelves: skip must be [%d] or [%d, X] category ids, X in 1..%d, got shape %s" % (B, B, SHELF_SKIP_MAX, shape))
+    if sk.dtype.is_floating_point or sk.dtype == torch.bool or sk.dtype.is_complex:
+        raise ValueError("shelves: skip must hold category ids, got dtype %s" % sk.dtype)
+    if int(sk.max()) >= cate_count:
+        raise ValueError("shelves: skip ids must be below %d (negative: nothing is skipped)" % cate_count)
+    return sk.to(device).clamp(min=-1).to(torch.int32).contiguous()
+
+
+def shelves_topk(lib, dims, cparams, ut, B, S, m, min_items, rank_at, excl, lists, skip, id_mul, id_add, workspace, stream,
+                 seg_items=None, big_items=None, plan=None):
+    """tlsan_eval_shelves on u_t [B, d]: each row's S best lists of the index `lists` (CategoryIndex.local's triple; any
+    lists of local items serve) with their m best items -> (cats [B, S] int32, ids [B, S, m] int32, scores [B, S, m]
+    float32).  skip: shelves_skip's tensor or None.  plan: a ShelfPlan of the index (CategoryIndex.shelf_plan caches them);
+    None: built here from the offsets, which are read back from the device -- for callers with lists of their own.
+    seg_items / big_items: the plan's thresholds, None: shelves_thresholds' production values; they decide the launch
+    geometry and never the result."""
+    off, items, max_list = lists
+    nl = int(off.shape[0]) - 1
+    if plan is None:
+        lens = np.diff(off.detach().cpu().numpy().astype(np.int64))
+        dflt = shelves_thresholds(int(lens.clip(min=0).sum()), B)
+        plan = ShelfPlan(lens, dflt[0] if seg_items is None else seg_items, dflt[1] if big_items is None else big_items, ut.device)
+    nws = lib.tlsan_shelves_workspace_bytes(C.byref(dims), B, S, m, plan.nseg, plan.nbig, plan.nbs)
+    if nws == 0:
+        raise L.TlsanError("tlsan_shelves_workspace_bytes: %s" % lib.tlsan_last_error().decode())
+    ws = workspace(nws)
+    cats = torch.empty(B, S, dtype=torch.int32, device=ut.device)
+    ids = torch.empty(B, S, m, dtype=torch.int32, device=ut.device)
+    scores = torch.empty(B, S, m, dtype=torch.float32, device=ut.device)
+    xoff, xid = excl
+    ptr = lambda t: None if t is None else t.data_ptr()
+    L.check(lib.tlsan_eval_shelves(C.byref(dims), C.byref(cparams), ut.data_ptr(), B, S, m, min_items, rank_at, ptr(xoff), ptr(xid),
+                                   off.data_ptr(), items.data_ptr(), nl, max_list, plan.seg_off.data_ptr(),
+                                   plan.seg_lists.data_ptr(), plan.nseg, plan.nsmall, plan.big_off.data_ptr(),
+                                   plan.big_slices.data_ptr(), plan.nbig, plan.nbs, ptr(skip), 0 if skip is None else int(skip.shape[1]),
+                                   id_mul, id_add, cats.data_ptr(), ids.data_ptr(), scores.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   stream), "tlsan_eval_shelves")
+    return cats, ids, scores
 
 
 def last_items(db):
@@ -2097,6 +2244,42 @@ class Model(object):
             rerank(self.lib, pid[r0:r0 + rows], psc[r0:r0 + rows], vec, inv, cate, k, diversity, per_category,
                    ids[r0:r0 + rows], scores[r0:r0 + rows], st)
         return ids, scores
+
+    def shelves(self, batch, shelves, k, index=None, exclude=None, min_items=1, rank_at=0, skip=None, seg_items=None,
+                big_items=None):
+        """A page of category shelves for each row: its S = shelves best categories and the m = k best items of each, in
+        one scan of the index -> (cats [B, S] int32, ids [B, S, m] int32, scores [B, S, m] float32) device tensors
+        (tlsan_eval_shelves).  Takes recommend's batches.
+        index (a CategoryIndex, category_index()) is required; its scope is the page's: category_index(within=scope)
+        removes items, and a category the scope empties is never a shelf.  exclude is recommend's: None, "history", B id
+        lists or a SeenItems.  skip: None, [B] or [B, X] category ids, X <= 8 (array or tensor; negative: nothing) that are
+        not offered as shelves for that row -- last_item_categories gives "not the department the row is already in".
+        For row b and category c, L(b, c) is row b of recommend(batch, m, exclude=exclude, category=np.full(B, c),
+        index=index), ids and score bits, and n(b, c) its valid entries.  Category c is a candidate of row b when it is
+        not skipped and n(b, c) >= min_items (1 <= min_items <= m); its rank key is entry rank_at of L(b, c) (0 <= rank_at
+        < min_items, so the entry exists): rank_at=0 ranks a department by its best item, rank_at=min_items-1 by the
+        weakest item it is sure to show.  No arithmetic is done on scores: the order of shelves is recommend's order of
+        those entries (higher score first, equal scores -> lower item id, NaN last).  The page is the S candidates of
+        highest rank key in that order; a row with fewer ends in cats -1, ids -1, scores -inf, and a shelf's entries past
+        n(b, c) are -1 / -inf.  ids.view(B, S * m) is a list list_metrics takes.
+        Limits: 1 <= S <= 32, 1 <= m <= 64, S * m <= 256.  A breach, rank_at >= min_items, min_items > m, a missing index
+        or one over another item or category count, a skip of the wrong shape or with an id >= cate_count: ValueError
+        before any launch.  Out of scope, and not arguments: boost=, diversity / per_category, within= (the scope belongs
+        to the index) and category= (skip= says which categories not to offer).
+        seg_items / big_items: the thresholds of the scan's plan (shelves_plan; None: shelves_thresholds' production
+        values).  They decide the launch geometry, never the result; the plan is cached on the index.  The result is a
+        function of (row, index, arguments): not of the batch, the row order or a repeated call.  Nothing in the model
+        changes; every other call keeps its launches and bits."""
+        I, Cn = self.config["item_count"], self.config["cate_count"]
+        S, m, min_items, rank_at = shelves_sizes(shelves, k, min_items, rank_at)
+        index = shelves_index(index, I, Cn)
+        skip = shelves_skip(skip, batch_rows(batch), Cn, self.device)
+        _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
+        excl, st = exclusion_csr(db, exclude, I), self._stream()
+        dflt = shelves_thresholds(index.count, db.B)
+        plan = index.shelf_plan(1, 0, I, dflt[0] if seg_items is None else seg_items, dflt[1] if big_items is None else big_items)
+        return shelves_topk(self.lib, self.dims, self.cparams, ut, db.B, S, m, min_items, rank_at, excl, index.local(1, 0, I), skip,
+                            1, 0, self._topk_workspace, st, plan=plan)
 
     def list_metrics(self, ids, labels=None, item_weight=None, exposure=None):
         """What the lists ids [B, K] (tensor or array of global item ids, -1 = no entry, anywhere; 1 <= K <= 256; for

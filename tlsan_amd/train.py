@@ -115,6 +115,17 @@ def parse(argv=None):
                     help="1 = build a per-category item index (Model.category_index; over the items of --recommend_categories "
                          "when given) and pass it wherever --recommend_same_category / --similar_same_category apply: a row "
                          "scores its category's items only.  The files written are the same")
+    ap.add_argument("--shelves", type=int, default=0, metavar="S",
+                    help="at the end of training, write <model_dir>/shelves_<S>x<M>.npz: for every test row its S best "
+                         "categories and the M best items of each (Model.shelves over the per-category index: users [N], cats "
+                         "[N, S], ids [N, S, M], scores [N, S, M]); needs --category_index 1 and --shelf_items; --recommend_exclude "
+                         "applies as it does to the lists; 0 = off")
+    ap.add_argument("--shelf_items", type=int, default=0, metavar="M",
+                    help="with --shelves: items of a shelf, 1..64 with S x M <= 256")
+    ap.add_argument("--shelf_min_items", type=int, default=1, metavar="N",
+                    help="with --shelves: a category is a shelf only when it has N items left for the row, 1..M")
+    ap.add_argument("--shelf_skip_last", type=int, default=0, choices=[0, 1],
+                    help="with --shelves: 1 = the category of the last item of a row's input is not offered to that row")
     ap.add_argument("--cluster_index", type=int, default=0, metavar="NLISTS",
                     help="with --recommend_k: build a clustered item index of NLISTS lists (Model.cluster_index: k-means over "
                          "the item vectors; over the items of --recommend_categories when given) and write APPROXIMATE lists: "
@@ -157,9 +168,20 @@ def parse(argv=None):
         ap.error("--recommend_categories / --recommend_same_category narrow the lists of --recommend_k: give --recommend_k")
     if args.similar_same_category and not args.similar_k:
         ap.error("--similar_same_category narrows the lists of --similar_k: give --similar_k")
-    if args.category_index and not (args.recommend_categories or args.recommend_same_category or args.similar_same_category):
+    if (args.shelves or args.shelf_items or args.shelf_min_items != 1 or args.shelf_skip_last) and not (args.shelves and args.shelf_items):
+        ap.error("--shelves S and --shelf_items M go together; --shelf_min_items / --shelf_skip_last serve them")
+    if args.shelves and not args.category_index:
+        ap.error("--shelves scans the per-category index: give --category_index 1")
+    if args.shelves and not (1 <= args.shelves <= 32 and 1 <= args.shelf_items <= 64 and args.shelves * args.shelf_items <= 256
+                             and 1 <= args.shelf_min_items <= args.shelf_items):
+        ap.error("--shelves wants S in 1..32, --shelf_items M in 1..64 with S x M <= 256, --shelf_min_items in 1..M")
+    if args.shelves and (args.sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--shelves: a category's items are spread over the ranks, so a rank cannot rank categories alone: it is "
+                 "not built for the sharded driver")
+    if args.category_index and not (args.recommend_categories or args.recommend_same_category or args.similar_same_category
+                                    or args.shelves):
         ap.error("--category_index serves --recommend_same_category / --similar_same_category (and --recommend_categories "
-                 "with them): give one of them")
+                 "with them) and --shelves: give one of them")
     if args.cluster_index and not args.recommend_k:
         ap.error("--cluster_index serves the lists of --recommend_k: give --recommend_k")
     if args.cluster_index and (args.category_index or args.recommend_same_category):
@@ -318,6 +340,26 @@ def write_similar(model, model_dir, k, metric, item_count, write=True, same_cate
 
 def audience_path(model_dir, k):
     return os.path.join(model_dir, "audience-%d.npz" % k)
+
+
+def shelves_path(model_dir, S, M):
+    return os.path.join(model_dir, "shelves_%dx%d.npz" % (S, M))
+
+
+def write_shelves(model, rows, model_dir, S, M, index, exclude, min_items=1, skip_last=False):
+    """model.shelves over every test row (the single-GPU driver's) -> the path of the .npz written: users [N], cats
+    [N, S], ids [N, S, M], scores [N, S, M] in test-set order.  skip_last: a row is not offered the category of the last
+    item of its input (last_item_categories)."""
+    parts = []
+    for batch, real, _ in rows.launches(True):
+        db = model.device_batch(batch, is_test=True)
+        skip = model.last_item_categories(db) if skip_last else None
+        cats, ids, scores = model.shelves(db, S, M, index=index, exclude=exclude, min_items=min_items, skip=skip)
+        parts.append([t[:real].cpu().numpy() for t in (db.u, cats, ids, scores)])
+    users, cats, ids, scores = (np.concatenate(x) for x in zip(*parts))
+    path = shelves_path(model_dir, S, M)
+    np.savez(path, users=users.astype(np.int64), cats=cats.astype(np.int32), ids=ids.astype(np.int32), scores=scores.astype(np.float32))
+    return path
 
 
 def write_audience(model, rows, model_dir, k, items, exclude, write=True):
@@ -751,6 +793,10 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
                              write=rows.rank in (None, 0), same_category=bool(args.similar_same_category), index=whole)
         if path is not None:
             say("Similar items: %s" % path)
+    if args.shelves:
+        path = write_shelves(model, rows, args.model_dir, args.shelves, args.shelf_items, whole or model.category_index(),
+                             exclude_arg(args.recommend_exclude, seen), args.shelf_min_items, bool(args.shelf_skip_last))
+        say("Shelves: %s" % path)
     if args.audience_k:
         if max(args.audience_items) >= rows.config["item_count"]:
             raise ValueError("--audience_items: ids must be in [0, %d)" % rows.config["item_count"])
