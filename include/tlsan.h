@@ -678,6 +678,53 @@ int tlsan_eval_shelves(const tlsan_dims* dims, const tlsan_params* p, const floa
                        const int32_t* big_slices, int32_t nbig, int32_t nbs, const int32_t* skip, int32_t X, int32_t id_mul,
                        int32_t id_add, int32_t* cats, int32_t* ids, float* scores, void* ws, size_t ws_bytes, void* stream);
 
+/* Explanations: the exact parts of a listed score, per source ("because you viewed X").  TLSAN's logit is linear in
+ * everything behind its two softmaxes, so with the attention weights taken as given (att0 / att1 exactly as
+ * tlsan_forward_att writes them, row h * B + b) the score of row b for item g splits, with no gradient and no approximation,
+ * into (true parameters: the four regularised tables are P * stored; names of oracle/tlsan_oracle.py::forward)
+ *   score(b, g) = b_g                                               bias               column 0
+ *               + sum_c  u_emb[b,c] w_g[c]                          user               column 1
+ *               + sum_c  a1[b,0,c] k0[c] w_g[c]                     bridge offset      column 2
+ *               + sum_l sum_c' a0[b,l,c'] h[b,l,c'] v_bg[c']        long-term position l   columns 3 .. 3 + Ls - 1
+ *               + sum_j sum_c  a1[b,1+j,c] h_new[b,j,c] w_g[c]      session position j     columns 3 + Ls .. R - 1
+ *   w_g = item_emb[g] || cate_emb[item_cate[g]],  v_bg = K (a1[b,0,:] o w_g),  h[b,l,:] = e_long[b,l,:] gamma usert[u_b,l] hist_t[b,l],
+ *   R = 3 + Ls + Sn.
+ * items [B, Kc]: the ids to explain, typically a row's recommendation list; a negative id is padding; an id >= item_count is
+ *   TLSAN_E_BADARG before any launch (the call copies `items` to the host for that check and waits for `stream`; it
+ *   cannot be captured into a graph).  b->i, b->j and b->y are not read.
+ * parts [B, Kc, R] fp32, or NULL.  A position at or past sl[b] (long-term) or sl_new[b] (session) is exactly 0.0f, decided by
+ *   the lengths and not by the attention value (a row with sl[b] == 0 has att0 of 0.1 or 0, see tlsan_forward_att: its
+ *   long-term columns are 0 either way); every column of a padding item is 0.0f.
+ * top_src, top_item [B, Kc, r] int32 and top_val [B, Kc, r] fp32, 1 <= r <= 16, or NULL together: the r strongest history
+ *   sources of each (row, item), selected in the same launch.  Columns 0 .. 2 never compete.
+ *   by     TLSAN_EXPLAIN_BY_POSITION: every valid position is a source (src = its column, item = the id it holds);
+ *          TLSAN_EXPLAIN_BY_ITEM: the valid positions of a row that hold the same item id, in the long window or the
+ *          session, are ONE source: its value is the fp32 sum of its positions' parts in ascending column order (one
+ *          rounding per addition), its src the lowest of its columns.
+ *   order  TLSAN_EXPLAIN_POSITIVE: larger value first;  TLSAN_EXPLAIN_ABS: larger magnitude first, the value keeps its sign.
+ *   Equal keys (+0.0 == -0.0) go to the lower src; a NaN comes after every number.  A (row, item) with fewer than r
+ *   sources, and every padding item, ends in src = item = -1, val = 0.
+ *   The selection runs over the fp32 parts the call writes (or would write): with parts == NULL the same top_* come back bit
+ *   for bit, and no [B, Kc, R] array is allocated or written anywhere -- a tile's parts live in LDS.
+ * Arithmetic: fp32 throughout; bf16 tables are widened exactly; the K product runs on v_mfma_f32_16x16x4_f32.
+ *   p->matrix_dtype is not looked at: with bf16 matrix products the parts decompose the fp32 model's score for the given
+ *   attention weights, not the bf16 logit.
+ * One launch: a workgroup takes one row and a tile of up to 64 items (LDS holds the tile's w and v rows), so any Kc >= 1.
+ * All six (d, heads) pairs, Ls <= 96, Ls + Sn <= 192 (the longest window and session the training step takes;
+ * TLSAN_E_UNSUPPORTED beyond: grouping a row's positions by item and ranking an item's sources compare every position
+ * with every other, so the cost is quadratic in Ls + Sn).  Row strides and p->scale are honoured as in tlsan_score_candidates.  ws is not
+ * used and may be NULL.  Refusals (NULL pointers, B or Kc < 1, B * Kc * R >= 2^31, r outside 1..16 with top_*, an unknown by
+ * or order, nothing asked for) come before any launch.  An addition: nothing else in the ABI changed (TLSAN_ABI_VERSION
+ * stays 15). */
+#define TLSAN_EXPLAIN_BY_POSITION 0
+#define TLSAN_EXPLAIN_BY_ITEM 1
+#define TLSAN_EXPLAIN_POSITIVE 0
+#define TLSAN_EXPLAIN_ABS 1
+#define TLSAN_EXPLAIN_RMAX 16
+int tlsan_explain(const tlsan_dims* dims, const tlsan_params* p, const tlsan_batch* b, const float* att0, const float* att1,
+                  const int32_t* items, int32_t Kc, int32_t r, int32_t by, int32_t order, float* parts, int32_t* top_src,
+                  int32_t* top_item, float* top_val, void* ws, size_t ws_bytes, void* stream);
+
 /* Boosted lists: tlsan_eval_topk_scoped and tlsan_eval_topk_lists with a per-item score adjustment applied INSIDE the
  * selection, where a score meets its row's threshold ("promote these items", "bury those", "pay this much for novelty").
  * An item just outside the unboosted list that the boost lifts in is found; a caller who adjusts the returned list

@@ -23,6 +23,9 @@ LISTM_MAX = 256   # LISTM_MAX (csrc/tlsan_listm.h): longest list of tlsan_list_m
 SIM_DOT, SIM_COSINE = 0, 1   # TLSAN_SIM_DOT / TLSAN_SIM_COSINE (include/tlsan.h): the metrics of tlsan_similar_topk
 CLUSTER_CMAX, CLUSTER_PMAX = 16384, 64   # csrc/tlsan_cluster.h: most centroids of a call, most probes of a row
 SHORTLIST_NMIN, SHORTLIST_NMAX = 16, 256   # csrc/tlsan_shortlist.h: the shortest and the longest shortlist of a row
+EXPLAIN_BY_POSITION, EXPLAIN_BY_ITEM = 0, 1   # TLSAN_EXPLAIN_BY_* (include/tlsan.h): what a source of tlsan_explain is
+EXPLAIN_POSITIVE, EXPLAIN_ABS = 0, 1       # TLSAN_EXPLAIN_POSITIVE / _ABS: the order of its sources
+EXPLAIN_RMAX = 16   # TLSAN_EXPLAIN_RMAX: most sources of a (row, item)
 NEG_MAX = 1024  # NEG_MAX (csrc/tlsan_cand.h): largest N of tlsan_sample_negatives
 
 EXPORTS = [
@@ -36,7 +39,7 @@ EXPORTS = [
     "tlsan_scope_workspace_bytes", "tlsan_eval_topk_scoped", "tlsan_similar_topk_scoped",
     "tlsan_lists_workspace_bytes", "tlsan_eval_topk_lists", "tlsan_similar_topk_lists",
     "tlsan_eval_topk_scoped_boost", "tlsan_eval_topk_lists_boost",
-    "tlsan_shelves_workspace_bytes", "tlsan_eval_shelves",
+    "tlsan_shelves_workspace_bytes", "tlsan_eval_shelves", "tlsan_explain",
     "tlsan_cluster_workspace_bytes", "tlsan_cluster_assign", "tlsan_cluster_means", "tlsan_cluster_probe",
     "tlsan_dense_topk_workspace_bytes", "tlsan_dense_topk",
     "tlsan_shortlist_build", "tlsan_shortlist_workspace_bytes", "tlsan_shortlist_topk", "tlsan_shortlist_select",
@@ -277,6 +280,11 @@ def load():
                                           [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] * 2 + [C.c_void_p] + [C.c_int32] * 3 + \
                                           [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
         lib.tlsan_eval_shelves.restype = C.c_int
+    if hasattr(lib, "tlsan_explain"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
+        # (dims, params, batch, att0, att1, items, Kc, r, by, order, parts, top_src, top_item, top_val, the workspace, the stream)
+        lib.tlsan_explain.argtypes = [P(Dims), P(Params), P(Batch)] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 5 + \
+                                     [C.c_size_t, C.c_void_p]
+        lib.tlsan_explain.restype = C.c_int
     if hasattr(lib, "tlsan_cluster_probe"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
         lib.tlsan_cluster_workspace_bytes.argtypes = [C.c_int32] * 3
         lib.tlsan_cluster_workspace_bytes.restype = C.c_size_t

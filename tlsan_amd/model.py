@@ -1206,6 +1206,54 @@ def dense_topk(lib, q, x, scale, bias, excl, id_add, k, workspace, stream):
     return ids, scores
 
 
+EXPLAIN_BY = {"position": L.EXPLAIN_BY_POSITION, "item": L.EXPLAIN_BY_ITEM}
+EXPLAIN_ORDER = {"positive": L.EXPLAIN_POSITIVE, "abs": L.EXPLAIN_ABS}
+
+
+def explain_args(top, by, order):
+    """Checks explain's switches -> (r, by, order) as tlsan_explain takes them.  top: an integer in 1..16; by: "item" or
+    "position"; order: "positive" or "abs"."""
+    if isinstance(top, bool) or not isinstance(top, (int, np.integer)) or not 1 <= int(top) <= L.EXPLAIN_RMAX:
+        raise ValueError("explain: top must be an integer in 1..%d, got %r" % (L.EXPLAIN_RMAX, top))
+    if by not in EXPLAIN_BY:
+        raise ValueError("explain: by must be 'item' or 'position', got %r" % (by,))
+    if order not in EXPLAIN_ORDER:
+        raise ValueError("explain: order must be 'positive' or 'abs', got %r" % (order,))
+    return int(top), EXPLAIN_BY[by], EXPLAIN_ORDER[order]
+
+
+class Explanation:
+    """What Model.explain returns, device tensors: parts [B, Kc, R] float32 or None (R = 3 + Ls + Sn, the columns that
+    columns() names); src, item [B, Kc, top] int32 and value [B, Kc, top] float32, the strongest history sources of every
+    (row, item) -- src the column of parts the source starts at, item the id it holds; -1 / -1 / 0 where a row has fewer
+    sources and for padding items; kind: 0 where src is in the long window, 1 in the session, -1 where src is -1."""
+
+    def __init__(self, parts, src, item, value, Ls):
+        self.parts, self.src, self.item, self.value, self.Ls = parts, src, item, value, Ls
+        self.kind = torch.where(src < 0, torch.full_like(src, -1), (src >= 3 + Ls).to(torch.int32))
+
+    @staticmethod
+    def columns(Ls, Sn):
+        """The names of the R = 3 + Ls + Sn columns of parts."""
+        return ["bias", "user", "bridge"] + ["long[%d]" % l for l in range(Ls)] + ["session[%d]" % j for j in range(Sn)]
+
+
+def explain(lib, dims, cparams, db, att0, att1, items, r, by, order, want_parts, stream):
+    """tlsan_explain on a device batch, the attention tensors of its forward and items [B, Kc] int32 -> Explanation."""
+    if not hasattr(lib, "tlsan_explain"):
+        raise L.TlsanError("this build of the library has no tlsan_explain")
+    B, Kc = items.shape
+    R = 3 + dims.Ls + db.Sn
+    parts = torch.empty(B, Kc, R, dtype=torch.float32, device=items.device) if want_parts else None
+    src = torch.empty(B, Kc, r, dtype=torch.int32, device=items.device)
+    item = torch.empty_like(src)
+    val = torch.empty(B, Kc, r, dtype=torch.float32, device=items.device)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    L.check(lib.tlsan_explain(C.byref(dims), C.byref(cparams), C.byref(db.c), att0.data_ptr(), att1.data_ptr(), items.data_ptr(),
+                              Kc, r, by, order, ptr(parts), ptr(src), ptr(item), ptr(val), None, 0, stream), "tlsan_explain")
+    return Explanation(parts, src, item, val, dims.Ls)
+
+
 def candidate_tensor(candidates, B, device):
     """[B, C] global item ids (array or tensor, -1 = padding) -> contiguous int32 device tensor."""
     if isinstance(candidates, torch.Tensor):
@@ -2400,6 +2448,29 @@ class Model(object):
         _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
         cand = candidate_tensor(candidates, db.B, self.device)
         return score_candidates(self.lib, self.dims, self.cparams, ut, cand, 1, 0, self._stream())
+
+    def explain(self, batch, items, top=3, by="item", order="positive", parts=False):
+        """Why these items: the exact parts of the score of every (row, item) of items [B, Kc] (array or device tensor of
+        global ids, typically recommend's ids; a negative id -- recommend's -1 tail -- is padding) -> Explanation.  Takes
+        recommend's batches.  The score is linear in everything behind the two softmaxes, so with the attention weights
+        of the row's forward (forward(want_att=True): att0 / att1 stay on the model) it splits exactly into a bias, a
+        user part, the bridge's offset and one part per position of the long window and of the session
+        (tlsan_explain, include/tlsan.h); the parts of a row add up to score_candidates' score up to
+        fp32 rounding.
+        top (1..16): the strongest history sources of every (row, item), selected in the kernel -- Explanation.src /
+        .item / .value / .kind.  by="item": the positions of a row that hold the same item id are one source (their
+        parts summed), "position": every valid position is one.  order="positive": the largest part first ("because you
+        viewed X"), "abs": the largest magnitude first.  Ties go to the earlier column, NaN last.
+        parts=True: also the [B, Kc, 3 + Ls + Sn] parts themselves (Explanation.columns names them); without it no such
+        array exists anywhere and the selection is the same bit for bit.
+        The parts decompose the fp32 model: with matrix_dtype="bf16" they are those of the fp32 score under the bf16
+        forward's attention weights.  A wrong shape, top outside 1..16, an unknown by or order: ValueError before any
+        launch; an id >= item_count, and a batch of more than 192
+        positions per row (Ls + Sn: the selection is quadratic in them), is refused by the library before its launch.  Nothing in the model changes."""
+        r, cby, corder = explain_args(top, by, order)
+        cand = candidate_tensor(items, batch_rows(batch), self.device)
+        _, _, _, db = self.forward(batch, is_test=True, want_att=True)
+        return explain(self.lib, self.dims, self.cparams, db, self.att0, self.att1, cand, r, cby, corder, bool(parts), self._stream())
 
     def sample_negatives(self, batch, n, seed=1234, row0=0, exclude="history"):
         """n distinct negatives per row -> [B, n] int32 device tensor (-1 where fewer are found): the first n eligible

@@ -115,6 +115,10 @@ def parse(argv=None):
                     help="1 = build a per-category item index (Model.category_index; over the items of --recommend_categories "
                          "when given) and pass it wherever --recommend_same_category / --similar_same_category apply: a row "
                          "scores its category's items only.  The files written are the same")
+    ap.add_argument("--recommend_explain", type=int, default=0, metavar="R",
+                    help="with --recommend_k: the R strongest history sources of every listed item, 1..16 (Model.explain, by item, "
+                         "larger part first): the lists' file gains why_item, why_value and why_kind, each [rows, K, R] (-1 / 0 / "
+                         "-1 where a row has fewer sources; kind 0 = the long window, 1 = the session); single GPU")
     ap.add_argument("--shelves", type=int, default=0, metavar="S",
                     help="at the end of training, write <model_dir>/shelves_<S>x<M>.npz: for every test row its S best "
                          "categories and the M best items of each (Model.shelves over the per-category index: users [N], cats "
@@ -168,6 +172,12 @@ def parse(argv=None):
         ap.error("--recommend_categories / --recommend_same_category narrow the lists of --recommend_k: give --recommend_k")
     if args.similar_same_category and not args.similar_k:
         ap.error("--similar_same_category narrows the lists of --similar_k: give --similar_k")
+    if args.recommend_explain and not args.recommend_k:
+        ap.error("--recommend_explain explains the lists of --recommend_k: give --recommend_k")
+    if args.recommend_explain and not 1 <= args.recommend_explain <= 16:
+        ap.error("--recommend_explain wants R in 1..16")
+    if args.recommend_explain and (args.sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--recommend_explain: Model.explain is single GPU; the sharded form is not built")
     if (args.shelves or args.shelf_items or args.shelf_min_items != 1 or args.shelf_skip_last) and not (args.shelves and args.shelf_items):
         ap.error("--shelves S and --shelf_items M go together; --shelf_min_items / --shelf_skip_last serve them")
     if args.shelves and not args.category_index:
@@ -260,12 +270,16 @@ def recommend_path(model_dir, k):
     return os.path.join(model_dir, "recommend_top%d.npz" % k)
 
 
-def write_recommendations(model_dir, k, user, ids, scores, settings=None):
-    """settings: the diversity keywords of recommend (recommend_settings), recorded beside the lists when any is set."""
+def write_recommendations(model_dir, k, user, ids, scores, settings=None, *, why_item=None, why_value=None, why_kind=None):
+    """settings: the diversity keywords of recommend (recommend_settings), recorded beside the lists when any is set.
+    why_*: the [rows, k, R] explanations of --recommend_explain; without them the file and its keys are unchanged."""
     path = recommend_path(model_dir, k)
     extra = {} if not settings else dict(diversity=np.float64(settings["diversity"]),
                                          per_category=np.int64(settings["per_category"]),
                                          pool=np.int64(settings["pool"] or 0))
+    if why_item is not None:
+        extra.update(why_item=np.asarray(why_item, np.int32), why_value=np.asarray(why_value, np.float32),
+                     why_kind=np.asarray(why_kind, np.int32))
     np.savez(path, user=np.asarray(user, np.int64), ids=np.asarray(ids, np.int32), scores=np.asarray(scores, np.float32),
              **extra)
     return path
@@ -623,9 +637,10 @@ class CertifiedShare:
         return rows, cert
 
 
-def recommend_test_set(model, rows, k, exclude, on_lists=None, same_category=False, **settings):
+def recommend_test_set(model, rows, k, exclude, on_lists=None, same_category=False, explain=0, **settings):
     """model.recommend over every test row (settings: its diversity keywords and within=) -> (user, ids, scores) host
-    arrays in test-set order; None but on rank 0.  on_lists(device batch, ids, real): called with every launch's device
+    arrays in test-set order; None but on rank 0.  explain=R > 0: also (why_item, why_value, why_kind), [rows, k, R], the R
+    strongest history sources of every listed item (model.explain on each launch's lists).  on_lists(device batch, ids, real): called with every launch's device
     lists [rows, k] before they leave the device (ListMeasurement).  same_category: every launch's rows get
     category=model.last_item_categories(their batch)."""
     parts = []
@@ -636,7 +651,11 @@ def recommend_test_set(model, rows, k, exclude, on_lists=None, same_category=Fal
         ids, scores = model.recommend(db, k, exclude=exclude, **settings)
         if on_lists is not None:
             on_lists(db, ids, real)
-        parts.append(rows.gather((db.u, ids, scores), real))
+        out = (db.u, ids, scores)
+        if explain:
+            why = model.explain(db, ids, top=explain)
+            out += (why.item, why.value, why.kind)
+        parts.append(rows.gather(out, real))
     if parts[0] is not None:
         return tuple(torch.cat(x).cpu().numpy() for x in zip(*parts))
 
@@ -774,7 +793,8 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
             scope = dict(index=model.shortlist_index(), shortlist=args.shortlist or None)
             share_of = CertifiedShare(scope["index"], then=measure)
         rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen),
-                                 on_lists=share_of or recall_of or measure, same_category=bool(args.recommend_same_category), **served, **scope)
+                                 on_lists=share_of or recall_of or measure, same_category=bool(args.recommend_same_category),
+                                 explain=args.recommend_explain, **served, **scope)
         list_res = measure.result() if measure is not None else None       # (collective: every rank)
         if recall_of is not None:
             say("Clustered index: recall@%d = %.4f against the exact lists over %d rows (%d probes)"
@@ -783,7 +803,8 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
             n_rows, n_cert = shortlist_share = share_of.result()
             say("Shortlist index: %d of %d rows certified (%.4f); the others served by the full scan" % (n_cert, n_rows, n_cert / max(n_rows, 1)))
         if rec is not None:                                    # (rank 0 holds the rows)
-            path = write_recommendations(args.model_dir, args.recommend_k, *rec, settings=settings)
+            path = write_recommendations(args.model_dir, args.recommend_k, *rec[:3], settings=settings,
+                                         **dict(zip(("why_item", "why_value", "why_kind"), rec[3:])))
             say("Recommendations: %s" % path)
             if list_res is not None:
                 say(list_metrics_line(list_res))
