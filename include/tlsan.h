@@ -816,6 +816,50 @@ int tlsan_dense_topk(const float* q, int32_t Q, int32_t d, const float* x, int32
                      const int32_t* excl_off, const int32_t* excl_ids, int32_t id_add, int32_t K, int32_t* ids, float* scores,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* List cursors: tlsan_eval_topk_scoped(_boost), tlsan_eval_topk_lists(_boost) and tlsan_dense_topk continued behind a
+ * position of their own ranking, so that pages of K entries tile the exact list at any depth (K itself stays 1..256) for
+ * one scan per page; nothing of the earlier pages is kept but one (id, score) pair per row.  The three calls take their
+ * twin's arguments, unchanged in meaning, and two more: after_ids [B] int32 and after_scores [B] fp32 (per query, [Q], in
+ * global row ids id_add + n, for the dense call).  With key(s, g) the 64-bit order of every list call (higher score first,
+ * equal scores -> lower global id, +0.0 == -0.0, NaN after everything else; larger key = earlier) and s'(b, g) the score
+ * the call would return for the pair (the model's, or the boosted one):
+ *   after_ids[b] >= 0: row b may select item g only when key(s'(b, g), g) < key(after_scores[b], after_ids[b]).  Everything
+ *     else about the call is unchanged -- eligibility (exclusion lists, sub, row_cate, the lists), order, padding with
+ *     -1 / -inf, the score bits -- so the page is the K best of what the same call without a cursor ranks strictly behind
+ *     the cursor.  The cursor is a position in the order, not an item: it need not be in the table, in the scope or
+ *     eligible, and its zero's sign and NaN payload do not matter (the key drops both).
+ *   after_ids[b] == TLSAN_AFTER_START (-2): no cursor; the row is the twin's, ids and bits.
+ *   any other negative id (in particular -1, what the last entry of a short row holds): the row is exhausted; its page is
+ *     all -1 / -inf.
+ * So with the cursor of a page its last column (ids[:, K - 1], scores[:, K - 1]), pages 1 .. P concatenated are the first
+ * P * K entries of the exact ranking; the page after a short page is empty and stays empty; rows of one call may sit at
+ * different depths; and a row's page depends on its own inputs only, not on B, the other rows, the launch geometry or the
+ * number of ranks (in the item-sharded form every rank applies the same cursor, in global ids; tlsan_topk_merge is
+ * unchanged).  Pages tile only while the parameters, the boost, the scope and the exclusions stay the same: a cursor is a
+ * snapshot, and nothing detects a change.
+ * boost may be NULL here (no adjustment: t = 0, the unboosted score bits); row_weight may be NULL (1) and needs boost.
+ * Workspaces: the twins' (tlsan_scope_workspace_bytes, tlsan_lists_workspace_bytes, tlsan_dense_topk_workspace_bytes).
+ * Everything the twin refuses is refused with the same code, before any launch, with this function's name in
+ * tlsan_last_error; a NULL after_ids or after_scores, and row_weight without boost, are TLSAN_E_BADARG.
+ * tlsan_eval_topk itself, tlsan_similar_topk*, tlsan_eval_shelves, the shortlist index and tlsan_rerank take no cursor.
+ * The three functions and the constant are additions: nothing else in the ABI changed (TLSAN_ABI_VERSION stays 15). */
+#define TLSAN_AFTER_START (-2)
+int tlsan_eval_topk_scoped_after(const tlsan_dims* dims, const tlsan_params* p, const float* u_t, int32_t B, int32_t K,
+                                 const int32_t* excl_off, const int32_t* excl_ids, const int32_t* sub, int32_t nsub,
+                                 const int32_t* row_cate, int32_t id_mul, int32_t id_add, int32_t* ids, float* scores,
+                                 void* ws, size_t ws_bytes, void* stream, const float* boost, const float* row_weight,
+                                 const int32_t* after_ids, const float* after_scores);
+int tlsan_eval_topk_lists_after(const tlsan_dims* dims, const tlsan_params* p, const float* u_t, int32_t B, int32_t K,
+                                const int32_t* excl_off, const int32_t* excl_ids, const int32_t* list_off,
+                                const int32_t* list_items, int32_t nlists, int32_t max_list, const int32_t* row_lists,
+                                int32_t P, int32_t id_mul, int32_t id_add, int32_t* ids, float* scores, void* ws,
+                                size_t ws_bytes, void* stream, const float* boost, const float* row_weight,
+                                const int32_t* after_ids, const float* after_scores);
+int tlsan_dense_topk_after(const float* q, int32_t Q, int32_t d, const float* x, int32_t N, const float* q_scale,
+                           const float* q_bias, const int32_t* excl_off, const int32_t* excl_ids, int32_t id_add, int32_t K,
+                           int32_t* ids, float* scores, void* ws, size_t ws_bytes, void* stream, const int32_t* after_ids,
+                           const float* after_scores);
+
 /* bf16 shortlist index: the exact top K over the whole table in two stages, with a per-row CERTIFICATE that the cheap
  * first stage lost nothing.  With w_n = [item_emb[n] || cate_emb[item_cate[n]]] as stored (d columns, the table scale P
  * not folded) and row b's u_t:

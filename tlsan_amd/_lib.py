@@ -26,6 +26,7 @@ SHORTLIST_NMIN, SHORTLIST_NMAX = 16, 256   # csrc/tlsan_shortlist.h: the shortes
 EXPLAIN_BY_POSITION, EXPLAIN_BY_ITEM = 0, 1   # TLSAN_EXPLAIN_BY_* (include/tlsan.h): what a source of tlsan_explain is
 EXPLAIN_POSITIVE, EXPLAIN_ABS = 0, 1       # TLSAN_EXPLAIN_POSITIVE / _ABS: the order of its sources
 EXPLAIN_RMAX = 16   # TLSAN_EXPLAIN_RMAX: most sources of a (row, item)
+AFTER_START = -2   # TLSAN_AFTER_START (include/tlsan.h): the cursor id of a row that has no cursor
 NEG_MAX = 1024  # NEG_MAX (csrc/tlsan_cand.h): largest N of tlsan_sample_negatives
 
 EXPORTS = [
@@ -42,6 +43,7 @@ EXPORTS = [
     "tlsan_shelves_workspace_bytes", "tlsan_eval_shelves", "tlsan_explain",
     "tlsan_cluster_workspace_bytes", "tlsan_cluster_assign", "tlsan_cluster_means", "tlsan_cluster_probe",
     "tlsan_dense_topk_workspace_bytes", "tlsan_dense_topk",
+    "tlsan_eval_topk_scoped_after", "tlsan_eval_topk_lists_after", "tlsan_dense_topk_after",
     "tlsan_shortlist_build", "tlsan_shortlist_workspace_bytes", "tlsan_shortlist_topk", "tlsan_shortlist_select",
     "tlsan_score_candidates", "tlsan_candidate_ranks", "tlsan_sample_negatives", "tlsan_profile_enable", "tlsan_profile_stride",
     "tlsan_profile_collect", "tlsan_debug_stamps", "tlsan_rows_apply_workspace", "tlsan_rows_apply", "tlsan_scan_compact",
@@ -304,6 +306,14 @@ def load():
                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_size_t, C.c_void_p]
         lib.tlsan_dense_topk.restype = C.c_int
+    if hasattr(lib, "tlsan_dense_topk_after"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
+        # the boosted calls' / the dense call's arguments, then after_ids and after_scores
+        lib.tlsan_eval_topk_scoped_after.argtypes = lib.tlsan_eval_topk_scoped_boost.argtypes + [C.c_void_p, C.c_void_p]
+        lib.tlsan_eval_topk_scoped_after.restype = C.c_int
+        lib.tlsan_eval_topk_lists_after.argtypes = lib.tlsan_eval_topk_lists_boost.argtypes + [C.c_void_p, C.c_void_p]
+        lib.tlsan_eval_topk_lists_after.restype = C.c_int
+        lib.tlsan_dense_topk_after.argtypes = lib.tlsan_dense_topk.argtypes + [C.c_void_p, C.c_void_p]
+        lib.tlsan_dense_topk_after.restype = C.c_int
     if hasattr(lib, "tlsan_shortlist_topk"):   # (an older build of the same ABI, loaded through TLSAN_LIB_PATH for an A/B, has none)
         lib.tlsan_shortlist_build.argtypes = [P(Dims), P(Params), C.c_void_p, C.c_void_p, C.c_void_p]
         lib.tlsan_shortlist_build.restype = C.c_int

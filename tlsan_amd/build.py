@@ -1,7 +1,7 @@
-"""Build libtlsan_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: thirty-one translation units compiled in parallel,
+"""Build libtlsan_hip.so (gfx950) in-tree with hipcc.  No torch, no cmake: thirty-two translation units compiled in parallel,
 one link -- four host units of the C ABI by subsystem (tlsan_api.hip core, training and state, with every kernel of the step
 but the fused one and the dense finalize -- tlsan_index.h, tlsan_apply.h, tlsan_update_lazy.h, tlsan_update_adagrad.h; tlsan_api_plan.hip the plans of a step's front and tail; tlsan_api_eval.hip evaluation;
-tlsan_api_shard.hip rows and the sharded step), the top-K selection, the similar-items lists, the scoped lists, the indexed lists (with their entry points), the category shelves (with their entry points), the explanations of listed scores (with their entry point), the boosted scoped and indexed lists (with their entry points), the clustered index (k-means and the probe, with their entry points), the dense top-K call behind the audience lists (with its entry points), the bf16 shortlist index (with its entry points), the re-ranking of diversified lists, the list metrics (with their entry point), the candidate kernels, and per (d, heads) pair k_fwd_bwd
+tlsan_api_shard.hip rows and the sharded step), the top-K selection, the similar-items lists, the scoped lists, the indexed lists (with their entry points), the category shelves (with their entry points), the explanations of listed scores (with their entry point), the boosted scoped and indexed lists (with their entry points), the lists behind a cursor (with their entry points), the clustered index (k-means and the probe, with their entry points), the dense top-K call behind the audience lists (with its entry points), the bf16 shortlist index (with its entry points), the re-ranking of diversified lists, the list metrics (with their entry point), the candidate kernels, and per (d, heads) pair k_fwd_bwd
 (d = 128 / 8 also as 8-sample workgroups, d = 256 with the window in registers and streamed) and the dense finalize kernels.
 A unit is recompiled when a file named in the compiler's depfile of its last compile is newer than its object.
 `python -m tlsan_amd.build` or `build()`."""
@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libtlsan_hip.so")
-SOURCES = ["tlsan_api.hip", "tlsan_api_plan.hip", "tlsan_api_eval.hip", "tlsan_api_shard.hip", "tlsan_topk.hip", "tlsan_similar.hip", "tlsan_scope.hip", "tlsan_lists.hip", "tlsan_shelves.hip", "tlsan_explain.hip", "tlsan_boost.hip", "tlsan_cluster.hip", "tlsan_dense.hip", "tlsan_shortlist.hip", "tlsan_rerank.hip", "tlsan_listm.hip", "tlsan_cand.hip",
+SOURCES = ["tlsan_api.hip", "tlsan_api_plan.hip", "tlsan_api_eval.hip", "tlsan_api_shard.hip", "tlsan_topk.hip", "tlsan_similar.hip", "tlsan_scope.hip", "tlsan_lists.hip", "tlsan_shelves.hip", "tlsan_explain.hip", "tlsan_boost.hip", "tlsan_after.hip", "tlsan_cluster.hip", "tlsan_dense.hip", "tlsan_shortlist.hip", "tlsan_rerank.hip", "tlsan_listm.hip", "tlsan_cand.hip",
            "tlsan_attn_d64.hip", "tlsan_attn_d128.hip", "tlsan_attn_d128w4.hip", "tlsan_attn_d256.hip", "tlsan_attn_d256s.hip",
            "tlsan_attn_d64h4.hip", "tlsan_attn_d128h16.hip", "tlsan_attn_d128h4.hip",
            "tlsan_update_d64.hip", "tlsan_update_d128.hip", "tlsan_update_d256.hip",

@@ -245,14 +245,16 @@ def _grouped(index, rows, run, lib, stream):
     return topk_merge(lib, torch.stack([o[0] for o in outs], 1), torch.stack([o[1] for o in outs], 1), stream)
 
 
-def clustered_topk(lib, dims, cparams, ut, B, k, excl, index, probes, scale, workspace, stream, boost=None):
+def clustered_topk(lib, dims, cparams, ut, B, k, excl, index, probes, scale, workspace, stream, boost=None, after=None):
     """recommend's lists with a clustered index on u_t [B, d]: probe (scale: the table scale as [L], or None; bias: the
     lists' mean item_b), then lists_topk per group of 8 probes, then the merge.  boost (model.boost_of's pair): the lists
-    are still chosen by the unboosted centroid scores; the scores selected and merged are the boosted ones."""
+    are still chosen by the unboosted centroid scores; the scores selected and merged are the boosted ones.  after (the
+    rows' model.ListCursor): the probe sees u_t alone, so every page probes the same lists; each group's list is already
+    behind the cursor and the merge is unchanged."""
     rows = index.probe(ut, probes, scale=scale, bias=index.list_bias)
     lists = index.partition.local(1, 0, index.item_count)
     return _grouped(index, rows, lambda rl: lists_topk(lib, dims, cparams, ut, B, k, excl, lists, rl, 1, 0, workspace, stream,
-                                                            boost=boost), lib, stream)
+                                                            boost=boost, after=after), lib, stream)
 
 
 def clustered_similar_topk(lib, dims, cparams, vec, inv, qids, k, metric, excl, index, probes, workspace, stream):

@@ -26,6 +26,8 @@ struct BoostArgs {
 struct BoostedScopedArgs { ScopedTopkArgs s; BoostArgs b; };
 struct BoostedListsArgs { ListsTopkArgs l; BoostArgs b; };
 
+// (tlsan_after.h's MaybeBoosted<Base> is this policy with the boost optional, a text of its own so that the kernels here keep
+//  their code: a change to row(), col() or score() goes into both.)
 template <class Base>
 struct Boosted {
   Base base;

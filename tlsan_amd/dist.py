@@ -33,7 +33,8 @@ from .dist_step import DynamicStep, FlatLayout, StaticStep, fused_params
 from .model import (LAZY_ADAGRAD_OPTIMIZERS, LAZY_OPTIMIZERS, OPTIMIZERS, DeviceBatch, Model, TopKCounters, _Var, _Writer, candidate_tensor, eval_topk,
                     exclusion_csr, grow_workspace, hits_and_rows, pack_dense, read_checkpoint, sample_negatives, sampled_ranks,
                     score_candidates, item_vectors, list_metric_inputs, list_metrics, list_metrics_chunks, rerank, rerank_chunk, rerank_pool, batch_rows, last_items, scope_categories, scope_within, scoped_similar_topk, scoped_topk, CategoryIndex, index_categories, indexed_topk, recommend_index, lists_similar_topk, similar_index, similar_queries, similar_topk, topk_merge, ItemScope, boost_of, item_boost_for, unpack_dense, write_checkpoint,
-                    UserVectors, audience_exclusion, audience_queries, batch_list, check_user_vectors, dense_topk, kept_rows)
+                    UserVectors, audience_exclusion, audience_queries, batch_list, check_user_vectors, dense_topk, kept_rows,
+                    ListCursor, check_deep, cursor_of, deep_pages)
 
 
 def _ru4(x):
@@ -447,7 +448,7 @@ class ShardedModel:
                              within=scope_within(within, self.I))
 
     def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None, index=None,
-                  probes=None, boost=None, boost_weight=None):
+                  probes=None, boost=None, boost_weight=None, after=None):
         """Model.recommend for this rank's rows (every rank calls it, with the same k, exclusion mode and diversity
         settings): u_t and the exclusion lists are all-gathered, every rank selects the k best of ITS item shard for all
         rows (tlsan_eval_topk, global ids n * world + rank), each row's lists go to the rank that owns the row (one
@@ -465,20 +466,51 @@ class ShardedModel:
         boost / boost_weight (Model.recommend's; every rank passes the same boost, replicated and indexed by GLOBAL id,
         and its own rows' weights): the weights are all-gathered with u_t and every rank calls the boosted entry point
         (tlsan_eval_topk_scoped_boost / tlsan_eval_topk_lists_boost) with (id_mul, id_add) = (world, rank), so a column
-        reads the boost of its global id.  The all-to-all, the merge and _rerank are unchanged: they see boosted scores."""
+        reads the boost of its global id.  The all-to-all, the merge and _rerank are unchanged: they see boosted scores.
+        after (Model.recommend's; this rank's rows' ListCursor, every rank passes one or none does): the cursors are
+        all-gathered with u_t and every rank calls the entry point behind a cursor (tlsan_eval_topk_scoped_after /
+        tlsan_eval_topk_lists_after) on its shard with (world, rank): the cursor is in global ids, so every shard's list is
+        behind the same position; the all-to-all and the merge are unchanged.  Same ids and score bits as
+        Model.recommend(after=) on the gathered parameters."""
+        after = None if after is None else cursor_of(after, batch_rows(batch), self.device)
+        N = rerank_pool(k, diversity, per_category, pool)
+        with self._recommend_lists(batch, after is not None, exclude, N, within, category, index, probes, boost, boost_weight) as topk:
+            cid, csc = topk(int(k) if N is None else N, after)
+            if N is not None:
+                cid, csc = self._rerank(cid, csc, int(k), diversity, per_category)
+        return cid, csc
+
+    def recommend_deep(self, batch, n, page=256, **kw):
+        """Model.recommend_deep for this rank's rows (collective: every rank calls it with the same n, page and forms):
+        one forward, ceil(n / page) pages of ShardedModel.recommend(after=) chained on the device."""
+        n, page = check_deep(n, page)
+        after = kw.pop("after", None)
+        after = None if after is None else cursor_of(after, batch_rows(batch), self.device)
+        N = rerank_pool(page, kw.pop("diversity", 0.0), kw.pop("per_category", 0), kw.pop("pool", None))
+        with self._recommend_lists(batch, True, kw.pop("exclude", None), N, kw.pop("within", None), kw.pop("category", None),
+                                   kw.pop("index", None), kw.pop("probes", None), kw.pop("boost", None),
+                                   kw.pop("boost_weight", None), **kw) as topk:
+            return deep_pages(topk, n, page, after)
+
+    @contextlib.contextmanager
+    def _recommend_lists(self, batch, paged, exclude, N, within, category, index, probes, boost, boost_weight):
+        """What recommend and recommend_deep share: recommend's argument checks (paged: the call takes a cursor, so the
+        second stage is refused), one forward, the gathers of u_t, exclusion lists, categories and weights -> topk(n, after),
+        valid inside the block: this rank's rows' merged lists of n entries behind the ListCursor `after` (None: the
+        entry points without a cursor, as ever)."""
         refuse_clustered(index, probes)
         if isinstance(index, ShortlistIndex):
             raise NotImplementedError("ShardedModel: a ShortlistIndex certifies a row against one table; per-shard certificates are not built")
+        if paged and N is not None:
+            raise ValueError("after= beside diversity / per_category / pool: the greedy second stage is not a prefix order")
         boost = boost_of(boost, boost_weight, batch_rows(batch), self.I, self.device)
-        N = rerank_pool(k, diversity, per_category, pool)
-        want = int(k)
         within = scope_within(within, self.I)
         if recommend_index(index, within, self.I, self.C) is not None:
             category = index_categories(category, batch_rows(batch), self.C, self.device)
         else:
             category = scope_categories(category, batch_rows(batch), self.C, self.device)
         with self._eval_forward(batch) as (db, _, _, _, ut):
-            B, k, st = db.B, want if N is None else N, self._stream()
+            B, st = db.B, self._stream()
             ut_all = allgather_rows(ut, self.group)
             Bt = int(ut_all.shape[0])
             off, xid = self._gather_excl(*exclusion_csr(db, exclude, self.I), B)
@@ -486,29 +518,33 @@ class ShardedModel:
             tws = lambda nbytes: grow_workspace(self, "_tws", nbytes)
             if boost is not None and boost[1] is not None:
                 boost = (boost[0], allgather_rows(boost[1], self.group))
-            if nloc > 0 and index is not None:
-                cid, csc = indexed_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), index, allgather_rows(category, self.group),
-                                        self.world, self.rank, nloc, tws, st, boost=boost)
-            elif nloc > 0 and (within is not None or category is not None or boost is not None):
-                sub = None if within is None else within.sub(self.world, self.rank, nloc)
-                cat_all = None if category is None else allgather_rows(category, self.group)
-                cid, csc = scoped_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), sub, cat_all, self.world, self.rank,
-                                       tws, st, boost=boost)
-            elif nloc > 0:
-                cid, csc = eval_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), self.world, self.rank, tws, st)
-            else:
-                cid = torch.full((Bt, k), -1, dtype=torch.int32, device=self.device)
-                csc = torch.full((Bt, k), float("-inf"), dtype=torch.float32, device=self.device)
-            if self.world > 1:
-                # rows [r B, (r + 1) B) belong to rank r: block s of what arrives is rank s's list of this rank's rows
-                rid, rsc = torch.empty_like(cid), torch.empty_like(csc)
-                a2a(rid, cid, None, None, self.group)
-                a2a(rsc, csc, None, None, self.group)
-                cid, csc = topk_merge(self.lib, rid.view(self.world, B, k).transpose(0, 1).contiguous(),
-                                      rsc.view(self.world, B, k).transpose(0, 1).contiguous(), st)
-            if N is not None:
-                cid, csc = self._rerank(cid, csc, want, diversity, per_category)
-        return cid, csc
+            cat_all = None if category is None else allgather_rows(category, self.group)
+            sub = None if within is None or nloc == 0 else within.sub(self.world, self.rank, nloc)
+            found = {}      # (the unrestricted rows of an indexed call: read from the device once, by the first page)
+
+            def topk(k, after):
+                if after is not None:
+                    after = ListCursor(allgather_rows(after.ids, self.group), allgather_rows(after.scores, self.group))
+                if nloc > 0 and index is not None:
+                    cid, csc = indexed_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), index, cat_all,
+                                            self.world, self.rank, nloc, tws, st, boost=boost, after=after, found=found)
+                elif nloc > 0 and (within is not None or category is not None or boost is not None or after is not None):
+                    cid, csc = scoped_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), sub, cat_all, self.world, self.rank,
+                                           tws, st, boost=boost, after=after)
+                elif nloc > 0:
+                    cid, csc = eval_topk(self.lib, ldims, lp, ut_all, Bt, k, (off, xid), self.world, self.rank, tws, st)
+                else:
+                    cid = torch.full((Bt, k), -1, dtype=torch.int32, device=self.device)
+                    csc = torch.full((Bt, k), float("-inf"), dtype=torch.float32, device=self.device)
+                if self.world > 1:
+                    # rows [r B, (r + 1) B) belong to rank r: block s of what arrives is rank s's list of this rank's rows
+                    rid, rsc = torch.empty_like(cid), torch.empty_like(csc)
+                    a2a(rid, cid, None, None, self.group)
+                    a2a(rsc, csc, None, None, self.group)
+                    cid, csc = topk_merge(self.lib, rid.view(self.world, B, k).transpose(0, 1).contiguous(),
+                                          rsc.view(self.world, B, k).transpose(0, 1).contiguous(), st)
+                return cid, csc
+            yield topk
 
     def _rerank(self, pid, psc, k, diversity, per_category):
         """The second stage of a diversified recommend on this rank's merged pools [B, N] (collective; B, N the same on
@@ -636,22 +672,39 @@ class ShardedModel:
         return UserVectors(vec, user, self, self._step, row0=sum(counts[:self.rank]), n_total=sum(counts), group=self.group,
                            world=self.world)
 
-    def audience(self, items, k, users, exclude=None):
+    def audience(self, items, k, users, exclude=None, after=None):
         """Model.audience, collective: every rank passes the same items, k and exclusion (lists of GLOBAL row numbers,
         whole; or the same SeenItems) and its own UserVectors, and every rank gets all Q lists, in global row numbers
         (users.users_of maps them to user ids).  The queries' stored vectors are read on each item shard
         (tlsan_item_vectors, zeros for the others) and their item_b from the fused shard rows, both all-gathered and each
         query's SELECTED from the rank that owns it (never a sum: it would turn -0 into +0); each rank scans its own
         rows with id_add = row0 (a rank without rows contributes -1 / -inf lists); the ranks' lists are all-gathered and
-        folded with tlsan_topk_merge.  Same rows and score bits as Model.audience on the gathered parameters and rows."""
+        folded with tlsan_topk_merge.  Same rows and score bits as Model.audience on the gathered parameters and rows.
+        after (Model.audience's; every rank passes the same cursors, in global row numbers): each rank scans its own rows
+        behind them (tlsan_dense_topk_after, id_add = row0); the merge is unchanged."""
+        topk, after = self._audience_lists(items, k, users, exclude, after)
+        return topk(int(k), after)
+
+    def audience_deep(self, items, n, users, page=256, exclude=None, after=None):
+        """Model.audience_deep, collective (every rank passes the same items, n, page, exclusion and cursors): one read of
+        the items' vectors, ceil(n / page) pages of ShardedModel.audience(after=) chained on the device."""
+        n, page = check_deep(n, page)
+        topk, after = self._audience_lists(items, page, users, exclude, after)
+        return deep_pages(topk, n, page, after)
+
+    def _audience_lists(self, items, k, users, exclude, after):
+        """What audience and audience_deep share: the checks, the exclusion lists and the gather of the queries' vectors and
+        biases -> (topk, the checked cursor): topk(k, after) every query's merged list of k rows behind the ListCursor
+        `after` (None: tlsan_dense_topk, as ever)."""
         qids = audience_queries(items, k, self.I, self.device)
+        after = cursor_of(after, int(qids.shape[0]), self.device)
         check_user_vectors(users, self, self._step, self.d, self.device)
         if users.n_total < 1:
             raise ValueError("users: no rows")
         excl = audience_exclusion(exclude, qids, users)
         if self._static is not None:   # (plans announced ahead may be running on the side streams)
             self._static.drain()
-        Q, k, st, W = int(qids.shape[0]), int(k), self._stream(), self.world
+        Q, st, W = int(qids.shape[0]), self._stream(), self.world
         nloc, ldims, lp = self._item_shard()
         if nloc > 0:
             vec, _ = item_vectors(self.lib, ldims, lp, qids, W, self.rank, st)
@@ -667,16 +720,19 @@ class ShardedModel:
             bias = torch.gather(allgather_rows(bias, self.group).view(W, Q), 0, owner[None])[0]
         bias = bias.contiguous()
         scale = self._P.expand(Q).contiguous() if self.lazy else None
-        if len(users) > 0:
-            rid, rsc = dense_topk(self.lib, vec, users.vec, scale, bias, excl, users.row0, k,
-                                  lambda nbytes: grow_workspace(self, "_tws", nbytes), st)
-        else:
-            rid = torch.full((Q, k), -1, dtype=torch.int32, device=self.device)
-            rsc = torch.full((Q, k), float("-inf"), dtype=torch.float32, device=self.device)
-        if W > 1:
-            rid, rsc = topk_merge(self.lib, allgather_rows(rid, self.group).view(W, Q, k).transpose(0, 1).contiguous(),
-                                  allgather_rows(rsc, self.group).view(W, Q, k).transpose(0, 1).contiguous(), st)
-        return rid, rsc
+
+        def topk(k, after):
+            if len(users) > 0:
+                rid, rsc = dense_topk(self.lib, vec, users.vec, scale, bias, excl, users.row0, k,
+                                      lambda nbytes: grow_workspace(self, "_tws", nbytes), st, after=after)
+            else:
+                rid = torch.full((Q, k), -1, dtype=torch.int32, device=self.device)
+                rsc = torch.full((Q, k), float("-inf"), dtype=torch.float32, device=self.device)
+            if W > 1:
+                rid, rsc = topk_merge(self.lib, allgather_rows(rid, self.group).view(W, Q, k).transpose(0, 1).contiguous(),
+                                      allgather_rows(rsc, self.group).view(W, Q, k).transpose(0, 1).contiguous(), st)
+            return rid, rsc
+        return topk, after
 
     def _score_owned(self, ut, cand):
         """Scores of this rank's rows' candidates (u_t [B, d], cand [B, C] global ids; every rank calls it with the same

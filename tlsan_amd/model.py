@@ -393,6 +393,108 @@ def boost_of(boost, boost_weight, B, item_count, device):
     return boost.values.to(device), w
 
 
+class ListCursor:
+    """A position in each row's ranking, held on the device: ids [B] int32 and scores [B] float32 -- the `after=` of
+    recommend and audience, single and sharded.  A row with ids[b] >= 0 gets the next entries of the same call's ranking
+    strictly behind (scores[b], ids[b]) in the lists' order (higher score first, equal -> lower id, +0 == -0, NaN last);
+    ids[b] == ListCursor.START (-2) is no cursor: the row is the call's without after=; any other negative id (-1: what a
+    short page ends in) is an exhausted row, whose page is all -1 / -inf.  ListCursor.of(ids, scores) is the cursor behind
+    a page (its last column, cloned), so pages chained through it tile the exact ranking at any depth, one scan a page.
+    The cursor is a position, not an item: it need not be in the table, the scope or eligible.  It is a SNAPSHOT, like
+    UserVectors: pages tile only while the parameters, boost, scope and exclusions stay the same; nothing detects a
+    change.  device None: the tensors' own, "cpu" for arrays; device "cpu" works for building."""
+
+    START = L.AFTER_START
+
+    def __init__(self, ids, scores, device=None):
+        i = ids if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids))
+        s = scores if isinstance(scores, torch.Tensor) else torch.as_tensor(np.asarray(scores))
+        ints = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+        if i.dim() != 1 or i.numel() < 1 or i.dtype not in ints:
+            raise ValueError("ListCursor: ids must be a 1-D array of integers, got shape %s dtype %s" % (tuple(i.shape), i.dtype))
+        if s.shape != i.shape or not (s.dtype.is_floating_point or s.dtype in ints):
+            raise ValueError("ListCursor: scores must be [%d] numbers, got shape %s dtype %s" % (i.numel(), tuple(s.shape), s.dtype))
+        if i.dtype == torch.int64 and (int(i.min()) < -(1 << 31) or int(i.max()) >= (1 << 31)):
+            raise ValueError("ListCursor: ids must fit int32")
+        dev = i.device if device is None else device
+        self.ids = i.detach().to(device=dev, dtype=torch.int32).contiguous()
+        self.scores = s.detach().to(device=dev, dtype=torch.float32).contiguous()
+        self.device = self.ids.device
+
+    @classmethod
+    def of(cls, ids, scores):
+        """The cursor behind a page (ids, scores) [B, K], as a list call returned it: its last column, cloned."""
+        if not isinstance(ids, torch.Tensor) or not isinstance(scores, torch.Tensor) or ids.dim() != 2 or ids.shape != scores.shape \
+                or ids.shape[1] < 1:
+            raise ValueError("ListCursor.of: want a page (ids, scores) of [B, K] tensors")
+        return cls(ids[:, -1].clone(), scores[:, -1].clone())
+
+    @classmethod
+    def start(cls, B, device="cpu"):
+        """B rows without a cursor: after=ListCursor.start(B, device) is the call without after=, ids and bits."""
+        if int(B) < 1:
+            raise ValueError("ListCursor.start: want B >= 1")
+        return cls(torch.full((int(B),), cls.START, dtype=torch.int32, device=device),
+                   torch.zeros(int(B), dtype=torch.float32, device=device))
+
+    def __len__(self):
+        return int(self.ids.shape[0])
+
+    @property
+    def done(self):
+        """[B] bool: the rows whose last page ended short (their next page is empty)."""
+        return self.ids == -1
+
+    def rows(self, rows):
+        """The cursor of the rows `rows` (an index tensor) alone."""
+        return ListCursor(self.ids[rows], self.scores[rows])
+
+
+def cursor_of(after, B, device):
+    """Checks an `after=` argument (a ListCursor, or an (ids, scores) pair of arrays or tensors that is wrapped) -> None
+    without one, else the ListCursor on `device`.  Anything else, or a cursor of another length than the call's B rows, is
+    a ValueError."""
+    if after is None:
+        return None
+    if not isinstance(after, ListCursor):
+        if not isinstance(after, (tuple, list)) or len(after) != 2:
+            raise ValueError("after: want a ListCursor or an (ids, scores) pair, got %s" % type(after).__name__)
+        try:
+            after = ListCursor(after[0], after[1])
+        except (TypeError, RuntimeError) as e:
+            raise ValueError("after: %s" % e)
+    if len(after) != B:
+        raise ValueError("after: a cursor of %d rows for %d rows" % (len(after), B))
+    try:
+        return ListCursor(after.ids, after.scores, device=device)
+    except RuntimeError as e:
+        raise ValueError("after: cannot be moved to %s: %s" % (device, e))
+
+
+def check_deep(n, page):
+    """Checks the n and page of recommend_deep / audience_deep -> them as ints: n >= 1, page in 1..256."""
+    for name, v in (("n", n), ("page", page)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+    if int(n) < 1 or not 1 <= int(page) <= L.TOPK_MAX:
+        raise ValueError("want n >= 1 and page in 1..%d, got n %d, page %d" % (L.TOPK_MAX, n, page))
+    return int(n), int(page)
+
+
+def deep_pages(topk, n, page, after=None):
+    """The first n entries of a ranking in ceil(n / page) pages: topk(k, cursor) gives the k entries behind a ListCursor
+    (None: the head of the list), and every page's cursor is the last column of the page before, taken on the device --
+    no host read between the pages (a CategoryIndex call reads its unrestricted rows once, on the first page).  The last page asks only for what is left of n.  -> (ids [B, n], scores [B, n])."""
+    ids, scores = [], []
+    for p0 in range(0, n, page):
+        pid, psc = topk(min(page, n - p0), after)
+        ids.append(pid)
+        scores.append(psc)
+        if p0 + page < n:
+            after = ListCursor.of(pid, psc)
+    return (ids[0], scores[0]) if len(ids) == 1 else (torch.cat(ids, 1), torch.cat(scores, 1))
+
+
 class CategoryIndex:
     """The items by category: a partition of the GLOBAL item ids -- of all item_count of them, or of an ItemScope's when
     within= is given -- into one list per category, held on the device: list_off [cate_count + 1] int32 and list_items
@@ -497,10 +599,11 @@ def index_categories(category, B, cate_count, device):
     return cat.to(device).clamp(min=-1).to(torch.int32).contiguous()
 
 
-def lists_topk(lib, dims, cparams, ut, B, k, excl, lists, row_lists, id_mul, id_add, workspace, stream, boost=None):
+def lists_topk(lib, dims, cparams, ut, B, k, excl, lists, row_lists, id_mul, id_add, workspace, stream, boost=None, after=None):
     """tlsan_eval_topk_lists on u_t [B, d]: the k best of the union of the lists row_lists [B, P] int32 names, of the index
     `lists` (CategoryIndex.local's triple) -> (ids [B, k] int32, scores [B, k] float32).  boost: boost_of's pair (values by
-    GLOBAL id, the B rows' weights or None) -> tlsan_eval_topk_lists_boost, the scores adjusted inside the selection."""
+    GLOBAL id, the B rows' weights or None) -> tlsan_eval_topk_lists_boost, the scores adjusted inside the selection.
+    after: the B rows' ListCursor -> tlsan_eval_topk_lists_after, with the boost or without."""
     k, P = int(k), int(row_lists.shape[1])
     off, items, max_list = lists
     nl = int(off.shape[0]) - 1
@@ -514,7 +617,10 @@ def lists_topk(lib, dims, cparams, ut, B, k, excl, lists, row_lists, id_mul, id_
     ptr = lambda t: None if t is None else t.data_ptr()
     args = (C.byref(dims), C.byref(cparams), ut.data_ptr(), B, k, ptr(xoff), ptr(xid), off.data_ptr(), items.data_ptr(), nl,
             max_list, row_lists.data_ptr(), P, id_mul, id_add, ids.data_ptr(), scores.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-    if boost is None:
+    if after is not None:
+        bp = (None, None) if boost is None else (boost[0].data_ptr(), ptr(boost[1]))
+        L.check(lib.tlsan_eval_topk_lists_after(*args, *bp, after.ids.data_ptr(), after.scores.data_ptr()), "tlsan_eval_topk_lists_after")
+    elif boost is None:
         L.check(lib.tlsan_eval_topk_lists(*args), "tlsan_eval_topk_lists")
     else:
         L.check(lib.tlsan_eval_topk_lists_boost(*args, boost[0].data_ptr(), ptr(boost[1])), "tlsan_eval_topk_lists_boost")
@@ -556,23 +662,31 @@ def excl_rows(excl, rows, B):
     return torch.arange(0, (vals.shape[0] + 1) * w, w, dtype=torch.int32, device=xid.device), vals.view(-1)
 
 
-def indexed_topk(lib, dims, cparams, ut, B, k, excl, index, row_lists, id_mul, id_add, n_local, workspace, stream, boost=None):
+def indexed_topk(lib, dims, cparams, ut, B, k, excl, index, row_lists, id_mul, id_add, n_local, workspace, stream, boost=None,
+                 after=None, found=None):
     """recommend's lists with an index on u_t [B, d]: the rows that probe a list go through lists_topk; the rows whose
     entries are all negative are unrestricted -- they run through the path without an index (scoped_topk over the index's
     scope, eval_topk without one) as a sub-batch and are scattered back.  One host read says whether there are any.
-    boost (boost_of's pair): the sub-batch carries the boost and its rows' slice of the weights."""
+    boost (boost_of's pair): the sub-batch carries the boost and its rows' slice of the weights.  after (the B rows'
+    ListCursor): the sub-batch carries its rows' cursors the same way, through scoped_topk.  found: a dict kept by a caller
+    that pages (recommend_deep): the unrestricted rows are the same on every page, so the first call leaves them in it and
+    the later ones read nothing from the device."""
     ids, scores = lists_topk(lib, dims, cparams, ut, B, k, excl, index.local(id_mul, id_add, n_local), row_lists, id_mul, id_add,
-                             workspace, stream, boost=boost)
-    free = torch.nonzero((row_lists < 0).all(1))[:, 0]
+                             workspace, stream, boost=boost, after=after)
+    if found is None or "free" not in found:
+        free = torch.nonzero((row_lists < 0).all(1))[:, 0]
+        if found is not None:
+            found["free"] = free
+    free = free if found is None else found["free"]
     if free.numel():
         sub_ut, sub_excl, n = ut[free].contiguous(), excl_rows(excl, free, B), int(free.numel())
         sub_boost = None if boost is None else (boost[0], None if boost[1] is None else boost[1][free].contiguous())
-        if index.within is None and boost is None:
+        if index.within is None and boost is None and after is None:
             fid, fsc = eval_topk(lib, dims, cparams, sub_ut, n, k, sub_excl, id_mul, id_add, workspace, stream)
         else:
             sub = None if index.within is None else index.within.sub(id_mul, id_add, n_local)
             fid, fsc = scoped_topk(lib, dims, cparams, sub_ut, n, k, sub_excl, sub, None, id_mul, id_add, workspace, stream,
-                                   boost=sub_boost)
+                                   boost=sub_boost, after=None if after is None else after.rows(free))
         ids[free], scores[free] = fid, fsc
     return ids, scores
 
@@ -757,11 +871,11 @@ def scope_categories(category, B, cate_count, device):
     return cat.to(device).clamp(min=-1).to(torch.int32).contiguous()
 
 
-def scoped_topk(lib, dims, cparams, ut, B, k, excl, sub, row_cate, id_mul, id_add, workspace, stream, boost=None):
+def scoped_topk(lib, dims, cparams, ut, B, k, excl, sub, row_cate, id_mul, id_add, workspace, stream, boost=None, after=None):
     """tlsan_eval_topk_scoped on u_t [B, d]: eval_topk over the local items sub (ItemScope.sub's pair; None: every item)
     with the rows' wanted categories row_cate ([B] int32 or None) -> (ids [B, k] int32, scores [B, k] float32).  boost:
     boost_of's pair (values by GLOBAL id, the B rows' weights or None) -> tlsan_eval_topk_scoped_boost, the scores adjusted
-    inside the selection."""
+    inside the selection.  after: the B rows' ListCursor -> tlsan_eval_topk_scoped_after, with the boost or without."""
     k = int(k)
     sub, nsub = (None, -1) if sub is None else sub
     nws = lib.tlsan_scope_workspace_bytes(C.byref(dims), B, k, nsub)
@@ -774,7 +888,10 @@ def scoped_topk(lib, dims, cparams, ut, B, k, excl, sub, row_cate, id_mul, id_ad
     ptr = lambda t: None if t is None else t.data_ptr()
     args = (C.byref(dims), C.byref(cparams), ut.data_ptr(), B, k, ptr(off), ptr(xid), ptr(sub), nsub, ptr(row_cate), id_mul, id_add,
             ids.data_ptr(), scores.data_ptr(), ws.data_ptr(), ws.numel(), stream)
-    if boost is None:
+    if after is not None:
+        bp = (None, None) if boost is None else (boost[0].data_ptr(), ptr(boost[1]))
+        L.check(lib.tlsan_eval_topk_scoped_after(*args, *bp, after.ids.data_ptr(), after.scores.data_ptr()), "tlsan_eval_topk_scoped_after")
+    elif boost is None:
         L.check(lib.tlsan_eval_topk_scoped(*args), "tlsan_eval_topk_scoped")
     else:
         L.check(lib.tlsan_eval_topk_scoped_boost(*args, boost[0].data_ptr(), ptr(boost[1])), "tlsan_eval_topk_scoped_boost")
@@ -1185,9 +1302,10 @@ def audience_exclusion(exclude, qids, users):
     return _csr_of_slots(_listed_items(exclude, int(qids.shape[0]), users.n_total, qids.device, pad), pad)
 
 
-def dense_topk(lib, q, x, scale, bias, excl, id_add, k, workspace, stream):
+def dense_topk(lib, q, x, scale, bias, excl, id_add, k, workspace, stream, after=None):
     """tlsan_dense_topk over the queries q [Q, d] against the matrix x [N, d], AUDIENCE_CHUNK queries at a time -> (ids
-    [Q, k] int32, scores [Q, k] float32) device tensors.  scale / bias: [Q] float32 device tensors or None."""
+    [Q, k] int32, scores [Q, k] float32) device tensors.  scale / bias: [Q] float32 device tensors or None.  after: the Q
+    queries' ListCursor, in global row ids -> tlsan_dense_topk_after."""
     Q, d, N, k = int(q.shape[0]), int(q.shape[1]), int(x.shape[0]), int(k)
     ids = torch.empty(Q, k, dtype=torch.int32, device=q.device)
     scores = torch.empty(Q, k, dtype=torch.float32, device=q.device)
@@ -1200,9 +1318,12 @@ def dense_topk(lib, q, x, scale, bias, excl, id_add, k, workspace, stream):
             raise L.TlsanError("tlsan_dense_topk_workspace_bytes: %s" % lib.tlsan_last_error().decode())
         ws = workspace(nws)
         # (a chunk's queries keep their offsets into the one id array: the offsets are absolute)
-        L.check(lib.tlsan_dense_topk(q[q0:].data_ptr(), n, d, x.data_ptr(), N, ptr(scale, q0), ptr(bias, q0), ptr(off, q0),
-                                     ptr(xid), id_add, k, ids[q0:].data_ptr(), scores[q0:].data_ptr(), ws.data_ptr(),
-                                     ws.numel(), stream), "tlsan_dense_topk")
+        args = (q[q0:].data_ptr(), n, d, x.data_ptr(), N, ptr(scale, q0), ptr(bias, q0), ptr(off, q0), ptr(xid), id_add, k,
+                ids[q0:].data_ptr(), scores[q0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        if after is None:
+            L.check(lib.tlsan_dense_topk(*args), "tlsan_dense_topk")
+        else:
+            L.check(lib.tlsan_dense_topk_after(*args, after.ids[q0:].data_ptr(), after.scores[q0:].data_ptr()), "tlsan_dense_topk_after")
     return ids, scores
 
 
@@ -2181,7 +2302,7 @@ class Model(object):
         return build(self)
 
     def recommend(self, batch, k, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None, index=None,
-                  probes=None, shortlist=None, fallback=True, boost=None, boost_weight=None):
+                  probes=None, shortlist=None, fallback=True, boost=None, boost_weight=None, after=None):
         """The k best items over ALL items for each row -- what tf.nn.top_k(eval_logits, k) gives the reference
         (model.py:140) -- without materialising the [B, I] scores.  Takes label_ranks' batches (the label and the
         negative are not used).  -> (ids [B, k] int32, scores [B, k] float32) device tensors, in tf.nn.top_k's
@@ -2244,10 +2365,70 @@ class Model(object):
         exact result) and the second stage (the pool is the boosted list and the relevance is formed from s').  With both
         None nothing changes: the same launches and bits.  boost_weight without boost, a boost over another item count,
         a weight of the wrong length, or boost= beside a ShortlistIndex (its certificate bounds the model's score, not
-        s'): ValueError before any launch.  similar_items, audience and label_ranks take no boost."""
+        s'): ValueError before any launch.  similar_items, audience and label_ranks take no boost.
+        after (a ListCursor, ListCursor.of(ids, scores) of the page before; or an (ids, scores) pair of [B] arrays or
+        tensors, wrapped): the NEXT k entries of the same call's ranking -- a row selects only what the call without
+        after= ranks strictly behind its cursor (by s' when boosted), so pages chained through their last columns tile
+        the exact ranking, ids and score bits, at any depth and for one scan a page: k stays 1..256, the depth does not.
+        Rows may sit at different depths: ListCursor.START (-2) is no cursor, the page after a short page is empty and
+        stays empty (cursor.done).  The cursor is a position, not an item: it need not be in the scope or eligible.  It
+        composes with exclude=, within=, category=, boost= / boost_weight= (tlsan_eval_topk_scoped_after), a
+        CategoryIndex (the unrestricted sub-batch carries its rows' cursors) and a ClusteredIndex (the probe sees u_t
+        alone, so every page probes the same lists and the pages tile the ranking of the probed union) --
+        tlsan_eval_topk_lists_after.  A cursor is a snapshot: pages tile only while parameters, boost, scope and
+        exclusions stay the same; nothing detects a change.  With None nothing changes: the same launches and bits.
+        after= beside diversity / per_category / pool (the greedy second stage is not a prefix order) or a
+        ShortlistIndex (its first stage ranks by bf16 score and its certificate is about the head of the list), a
+        cursor of another length than the batch, or one that cannot be converted: ValueError before any launch.
+        recommend_deep chains the pages on the device.  shelves, similar_items, label_ranks and explain take none."""
+        after = None if after is None else cursor_of(after, batch_rows(batch), self.device)
+        topk, N, db = self._recommend_lists(batch, k, after is not None, exclude=exclude, diversity=diversity,
+                                            per_category=per_category, pool=pool, within=within, category=category, index=index,
+                                            probes=probes, shortlist=shortlist, fallback=fallback, boost=boost,
+                                            boost_weight=boost_weight)
+        if N is None:
+            return topk(k, after)
+        # (forward has landed an owed lazy-L2 correction; the vectors are read as stored, the scale not folded)
+        st = self._stream()
+        pid, psc = topk(N, None)
+        ids = torch.empty(db.B, int(k), dtype=torch.int32, device=self.device)
+        scores = torch.empty(db.B, int(k), dtype=torch.float32, device=self.device)
+        rows = rerank_chunk(N, self.config["hidden_units"])
+        for r0 in range(0, db.B, rows):
+            flat = pid[r0:r0 + rows].reshape(-1)
+            vec, inv = item_vectors(self.lib, self.dims, self.cparams, flat, 1, 0, st)
+            cate = self.item_cate[flat.clamp(min=0).long()]
+            rerank(self.lib, pid[r0:r0 + rows], psc[r0:r0 + rows], vec, inv, cate, k, diversity, per_category,
+                   ids[r0:r0 + rows], scores[r0:r0 + rows], st)
+        return ids, scores
+
+    def recommend_deep(self, batch, n, page=256, **kw):
+        """The n best items of each row for ANY n >= 1 -- recommend(batch, n, **kw) without its limit of 256 -- in
+        ceil(n / page) scans of `page` entries (1..256) behind ONE forward: the pages' cursors are chained on the device
+        (ListCursor.of's columns), no host read between them.  -> (ids [B, n] int32, scores [B, n] float32), the exact
+        ranking, ids and score bits; rows with fewer than n eligible items end in -1 / -inf.  kw: recommend's exclude=,
+        within=, category=, index= (a CategoryIndex or a ClusteredIndex with probes=), boost=, boost_weight= and after= (a
+        cursor to start behind); what recommend refuses beside after= is refused here."""
+        n, page = check_deep(n, page)
+        after = kw.pop("after", None)
+        after = None if after is None else cursor_of(after, batch_rows(batch), self.device)
+        topk, _, _ = self._recommend_lists(batch, page, True, **kw)
+        return deep_pages(topk, n, page, after)
+
+    def _recommend_lists(self, batch, k, paged, exclude=None, diversity=0.0, per_category=0, pool=None, within=None, category=None,
+                         index=None, probes=None, shortlist=None, fallback=True, boost=None, boost_weight=None):
+        """What recommend and recommend_deep share: recommend's argument checks (paged: the call takes a cursor, so the
+        second stage and a ShortlistIndex are refused), one forward and the exclusion lists -> (topk, N, db) with
+        topk(n, after) the call's lists of n entries behind the ListCursor `after` (None: the entry points without a
+        cursor, as ever) and N the second stage's pool size or None."""
         from .cluster import clustered_probes, clustered_topk
-        from .shortlist import shortlist_size, shortlist_topk
+        from .shortlist import ShortlistIndex, shortlist_size, shortlist_topk
         N = rerank_pool(k, diversity, per_category, pool)
+        if paged and N is not None:
+            raise ValueError("after= beside diversity / per_category / pool: the greedy second stage is not a prefix order")
+        if paged and isinstance(index, ShortlistIndex):
+            raise ValueError("after= beside a ShortlistIndex: its first stage ranks by bf16 score and its certificate is about the "
+                             "head of the list")
         short = shortlist_size(index, shortlist, int(k) if N is None else N, self.config["item_count"], self.config["hidden_units"],
                                category=category, within=within, probes=probes)
         probes = None if short is not None else clustered_probes(index, probes, self.config["item_count"], category=category, within=within)
@@ -2264,34 +2445,27 @@ class Model(object):
         _, _, ut, db = self.forward(batch, is_test=True, want_u_t=True)
         excl, st = exclusion_csr(db, exclude, self.config["item_count"]), self._stream()
         if short is not None:
-            topk = lambda n: shortlist_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, short, fallback,
+            topk = lambda n, after: shortlist_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, short, fallback,
                                             self._topk_workspace, st)
         elif probes is not None:
-            topk = lambda n: clustered_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, probes,
-                                            self._scale_vector(index.lists), self._topk_workspace, st, boost=boost)
+            topk = lambda n, after: clustered_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, probes,
+                                                   self._scale_vector(index.lists), self._topk_workspace, st, boost=boost, after=after)
         elif index is not None:
-            topk = lambda n: indexed_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, category, 1, 0,
-                                          self.config["item_count"], self._topk_workspace, st, boost=boost)
+            found = {}      # (the unrestricted rows: read from the device once, by the first page)
+            topk = lambda n, after: indexed_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, index, category, 1, 0,
+                                                 self.config["item_count"], self._topk_workspace, st, boost=boost, after=after,
+                                                 found=found)
         elif within is None and category is None and boost is None:
-            topk = lambda n: eval_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, 1, 0, self._topk_workspace, st)
+            # (the plain path keeps tlsan_eval_topk; behind a cursor it is the scoped call over the whole table)
+            topk = lambda n, after: (eval_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, 1, 0, self._topk_workspace, st)
+                                     if after is None else
+                                     scoped_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, None, None, 1, 0,
+                                                 self._topk_workspace, st, after=after))
         else:
             sub = None if within is None else within.sub(1, 0, self.config["item_count"])
-            topk = lambda n: scoped_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, sub, category, 1, 0,
-                                         self._topk_workspace, st, boost=boost)
-        if N is None:
-            return topk(k)
-        # (forward has landed an owed lazy-L2 correction; the vectors are read as stored, the scale not folded)
-        pid, psc = topk(N)
-        ids = torch.empty(db.B, int(k), dtype=torch.int32, device=self.device)
-        scores = torch.empty(db.B, int(k), dtype=torch.float32, device=self.device)
-        rows = rerank_chunk(N, self.config["hidden_units"])
-        for r0 in range(0, db.B, rows):
-            flat = pid[r0:r0 + rows].reshape(-1)
-            vec, inv = item_vectors(self.lib, self.dims, self.cparams, flat, 1, 0, st)
-            cate = self.item_cate[flat.clamp(min=0).long()]
-            rerank(self.lib, pid[r0:r0 + rows], psc[r0:r0 + rows], vec, inv, cate, k, diversity, per_category,
-                   ids[r0:r0 + rows], scores[r0:r0 + rows], st)
-        return ids, scores
+            topk = lambda n, after: scoped_topk(self.lib, self.dims, self.cparams, ut, db.B, n, excl, sub, category, 1, 0,
+                                                self._topk_workspace, st, boost=boost, after=after)
+        return topk, N, db
 
     def shelves(self, batch, shelves, k, index=None, exclude=None, min_items=1, rank_at=0, skip=None, seg_items=None,
                 big_items=None):
@@ -2417,7 +2591,7 @@ class Model(object):
             raise ValueError("user_vectors: no batch given")
         return UserVectors(torch.cat(vec), torch.cat(user), self, self._step)
 
-    def audience(self, items, k, users, exclude=None):
+    def audience(self, items, k, users, exclude=None, after=None):
         """The k best ROWS of `users` (a UserVectors of this model at its current global step) for each item of `items` (a
         1-D list, array or tensor of global ids, repeats allowed; outside [0, item_count): ValueError): whom to notify
         about an item.  -> (rows [Q, k] int32, scores [Q, k] float32) device tensors in recommend's order (higher score
@@ -2429,8 +2603,30 @@ class Model(object):
         has item q in their seen list stays out of q's list (seen_rows_csr).  The item side is read at call time, as
         similar_items reads it: an owed lazy-L2 correction lands first, the scale is NOT folded -- parameters, scale and
         state keep their bits.  k outside 1..256, or users that are not this model's at this step (another model,
-        another d or device, trained since): ValueError before any launch."""
+        another d or device, trained since): ValueError before any launch.
+        after (a ListCursor over the Q query items, in global ROW numbers; or an (ids, scores) pair, wrapped): the next k
+        rows of each item's audience, strictly behind its cursor -- recommend's after=, on tlsan_dense_topk_after: pages
+        chained through ListCursor.of tile the exact audience at any depth (a notification batch of thousands), ids and
+        score bits; ListCursor.START is no cursor, the page after a short page is empty.  A snapshot, as `users` is.  A
+        cursor of another length than items: ValueError before any launch.  audience_deep chains the pages."""
+        topk, after = self._audience_lists(items, k, users, exclude, after)
+        return topk(k, after)
+
+    def audience_deep(self, items, n, users, page=256, exclude=None, after=None):
+        """The n best rows of `users` for each item for ANY n >= 1 -- audience(items, n, users) without its limit of 256
+        -- in ceil(n / page) scans of `page` rows (1..256) behind ONE read of the items' vectors; the pages' cursors are
+        chained on the device, no host read between them.  -> (rows [Q, n] int32, scores [Q, n] float32), the exact
+        ranking, ids and score bits; exclude= and after= are audience's."""
+        n, page = check_deep(n, page)
+        topk, after = self._audience_lists(items, page, users, exclude, after)
+        return deep_pages(topk, n, page, after)
+
+    def _audience_lists(self, items, k, users, exclude, after):
+        """What audience and audience_deep share: the checks, the exclusion lists and one tlsan_item_vectors -> (topk, the
+        checked cursor): topk(k, after) the queries' lists of k rows behind the ListCursor `after` (None: tlsan_dense_topk,
+        as ever)."""
         qids = audience_queries(items, k, self.config["item_count"], self.device)
+        after = cursor_of(after, int(qids.shape[0]), self.device)
         check_user_vectors(users, self, self._step, self.config["hidden_units"], self.device)
         if len(users) < 1:
             raise ValueError("users: no rows")
@@ -2438,8 +2634,8 @@ class Model(object):
         self._flush()
         st = self._stream()
         vec, _ = item_vectors(self.lib, self.dims, self.cparams, qids, 1, 0, st)
-        return dense_topk(self.lib, vec, users.vec, self._scale_vector(int(qids.shape[0])), self.item_b[qids.long()].contiguous(),
-                          excl, 0, k, self._topk_workspace, st)
+        scale, bias = self._scale_vector(int(qids.shape[0])), self.item_b[qids.long()].contiguous()
+        return (lambda k, after: dense_topk(self.lib, vec, users.vec, scale, bias, excl, 0, k, self._topk_workspace, st, after=after)), after
 
     def score_candidates(self, batch, candidates):
         """Scores of caller-given items: candidates [B, C] global item ids (array or tensor; -1 = padding, which scores

@@ -76,6 +76,11 @@ def parse(argv=None):
                     help="items kept out of the recommendations: 'history' = the items the test row's input holds (its "
                          "last Ls items and its current session -- what the batch carries), 'none' = nothing, 'seen' = "
                          "every item of the user's training samples and the row's input")
+    ap.add_argument("--recommend_pages", type=int, default=1, metavar="P",
+                    help="with --recommend_k: lists of P x K entries -- P pages of K chained through list cursors "
+                         "(Model.recommend_deep: one forward, one scan a page, the exact ranking at any depth); the file is "
+                         "recommend_top<P x K>.npz.  It goes without the diversity flags, --shortlist_index, --recommend_metrics "
+                         "and --recommend_explain")
     ap.add_argument("--recommend_diversity", type=float, default=0.0,
                     help="with --recommend_k: re-rank each row's pool by maximal marginal relevance, theta in [0, 1] "
                          "(0 = relevance only, 1 = novelty only after the first pick; Model.recommend's diversity)")
@@ -148,6 +153,10 @@ def parse(argv=None):
                     help="at the end of training, write <model_dir>/audience-<K>.npz: for every item of --audience_items the K "
                          "best test rows (Model.audience over the user vectors of the test set, one row per user): item [Q], "
                          "users [Q, K], rows [Q, K], scores [Q, K]; 0 = off")
+    ap.add_argument("--audience_pages", type=int, default=1, metavar="P",
+                    help="with --audience_k: audiences of P x K rows -- P pages of K chained through list cursors "
+                         "(Model.audience_deep: one scan a page, any depth); the file is audience-<P x K>.npz; --audience_k itself "
+                         "stays 1..256")
     ap.add_argument("--audience_items", default="",
                     help="with --audience_k (required): the global item ids whose audiences are wanted, e.g. 3,7,12")
     ap.add_argument("--audience_exclude", default="none", choices=["none", "seen"],
@@ -218,6 +227,20 @@ def parse(argv=None):
         if not first < short:
             ap.error("--shortlist_index: the first stage's list of %d entries (--recommend_k, or the pool of the second stage) "
                      "needs a shortlist longer than that, and the shortlist is %d (--shortlist, at most 256)" % (first, short))
+    if args.recommend_pages < 1 or args.audience_pages < 1:
+        ap.error("--recommend_pages / --audience_pages: want P >= 1")
+    if args.recommend_pages > 1 and not args.recommend_k:
+        ap.error("--recommend_pages pages the lists of --recommend_k: give --recommend_k")
+    if args.recommend_pages > 1 and recommend_settings(args):
+        ap.error("--recommend_pages: the greedy second stage is not a prefix order: it goes without --recommend_diversity / "
+                 "--recommend_per_category / --recommend_pool")
+    if args.recommend_pages > 1 and args.shortlist_index:
+        ap.error("--shortlist_index certifies the head of the list: it goes without --recommend_pages")
+    if args.recommend_pages > 1 and (args.recommend_metrics or args.recommend_explain):
+        ap.error("--recommend_metrics / --recommend_explain measure and explain lists of --recommend_k entries: they go without "
+                 "--recommend_pages")
+    if args.audience_pages > 1 and not args.audience_k:
+        ap.error("--audience_pages pages the audiences of --audience_k: give --audience_k")
     if args.audience_k < 0 or args.audience_k > 256:
         ap.error("--audience_k: want K in 1..256 (0 = off)")
     if args.audience_k and not args.audience_items.strip():
@@ -376,18 +399,22 @@ def write_shelves(model, rows, model_dir, S, M, index, exclude, min_items=1, ski
     return path
 
 
-def write_audience(model, rows, model_dir, k, items, exclude, write=True):
+def write_audience(model, rows, model_dir, k, items, exclude, write=True, pages=1):
     """The k best test rows for each item of `items` (model.user_vectors over this process's test rows, then
     model.audience; both collective on a sharded model, where only the process with write=True keeps the lists) -> the
     path of the .npz written: item [Q], users [Q, k] (the rows' user ids, -1 where a list ran out), rows [Q, k] (row
-    numbers in the order of the user vectors: the test set's on one GPU, rank by rank on a sharded model), scores [Q, k]."""
+    numbers in the order of the user vectors: the test set's on one GPU, rank by rank on a sharded model), scores [Q, k].
+    pages=P > 1: audiences of P x k rows, P pages of k (model.audience_deep); the file is named by P x k."""
     launches = list(rows.launches(False))
     users = model.user_vectors([batch for batch, _, _ in launches], real=[real for _, real, _ in launches])
-    ids, scores = model.audience(items, k, users, exclude=exclude)
+    if pages > 1:
+        ids, scores = model.audience_deep(items, k * pages, users, page=k, exclude=exclude)
+    else:
+        ids, scores = model.audience(items, k, users, exclude=exclude)
     who = users.users_of(ids)                                          # (collective: every rank)
     if not write:
         return None
-    path = audience_path(model_dir, k)
+    path = audience_path(model_dir, k * pages)
     np.savez(path, item=np.asarray(items, np.int32), users=who.cpu().numpy().astype(np.int32),
              rows=ids.cpu().numpy().astype(np.int32), scores=scores.cpu().numpy().astype(np.float32))
     return path
@@ -637,18 +664,22 @@ class CertifiedShare:
         return rows, cert
 
 
-def recommend_test_set(model, rows, k, exclude, on_lists=None, same_category=False, explain=0, **settings):
+def recommend_test_set(model, rows, k, exclude, on_lists=None, same_category=False, explain=0, pages=1, **settings):
     """model.recommend over every test row (settings: its diversity keywords and within=) -> (user, ids, scores) host
     arrays in test-set order; None but on rank 0.  explain=R > 0: also (why_item, why_value, why_kind), [rows, k, R], the R
     strongest history sources of every listed item (model.explain on each launch's lists).  on_lists(device batch, ids, real): called with every launch's device
     lists [rows, k] before they leave the device (ListMeasurement).  same_category: every launch's rows get
-    category=model.last_item_categories(their batch)."""
+    category=model.last_item_categories(their batch).  pages=P > 1: lists of P x k entries, P pages of k behind one
+    forward (model.recommend_deep)."""
     parts = []
     for batch, real, _ in rows.launches(True):
         db = model.device_batch(batch, is_test=True)
         if same_category:
             settings["category"] = model.last_item_categories(db)
-        ids, scores = model.recommend(db, k, exclude=exclude, **settings)
+        if pages > 1:
+            ids, scores = model.recommend_deep(db, k * pages, page=k, exclude=exclude, **settings)
+        else:
+            ids, scores = model.recommend(db, k, exclude=exclude, **settings)
         if on_lists is not None:
             on_lists(db, ids, real)
         out = (db.u, ids, scores)
@@ -794,7 +825,7 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
             share_of = CertifiedShare(scope["index"], then=measure)
         rec = recommend_test_set(model, rows, args.recommend_k, exclude_arg(args.recommend_exclude, seen),
                                  on_lists=share_of or recall_of or measure, same_category=bool(args.recommend_same_category),
-                                 explain=args.recommend_explain, **served, **scope)
+                                 explain=args.recommend_explain, pages=args.recommend_pages, **served, **scope)
         list_res = measure.result() if measure is not None else None       # (collective: every rank)
         if recall_of is not None:
             say("Clustered index: recall@%d = %.4f against the exact lists over %d rows (%d probes)"
@@ -803,7 +834,7 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
             n_rows, n_cert = shortlist_share = share_of.result()
             say("Shortlist index: %d of %d rows certified (%.4f); the others served by the full scan" % (n_cert, n_rows, n_cert / max(n_rows, 1)))
         if rec is not None:                                    # (rank 0 holds the rows)
-            path = write_recommendations(args.model_dir, args.recommend_k, *rec[:3], settings=settings,
+            path = write_recommendations(args.model_dir, args.recommend_k * args.recommend_pages, *rec[:3], settings=settings,
                                          **dict(zip(("why_item", "why_value", "why_kind"), rec[3:])))
             say("Recommendations: %s" % path)
             if list_res is not None:
@@ -822,7 +853,8 @@ def _run(args, say, model, train_set, rows, seen, triples, issue, topk_report, *
         if max(args.audience_items) >= rows.config["item_count"]:
             raise ValueError("--audience_items: ids must be in [0, %d)" % rows.config["item_count"])
         path = write_audience(model, rows, args.model_dir, args.audience_k, args.audience_items,
-                              seen if args.audience_exclude == "seen" else None, write=rows.rank in (None, 0))
+                              seen if args.audience_exclude == "seen" else None, write=rows.rank in (None, 0),
+                              pages=args.audience_pages)
         if path is not None:
             say("Audience: %s" % path)
     model.train_writer.flush()
